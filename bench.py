@@ -11,9 +11,14 @@ dense optimizer (mindrec_amd/wide_deep.py; reference models/wide_deep/src/wide_a
 Workload = BASELINE.json configs[1]: vocab 200 M, dim 80, batch 16384 per GPU, 26 categorical slots,
 fp32 tables.  Rank 0 prints ONE JSON line.
 
-Timing: W untimed warmup steps, then R (--repeats, default 5) blocks of EXACTLY K steps, each bracketed by a
-barrier + synchronize on both sides and reduced with MAX over the ranks; `ms_per_step` / `value` are the MEDIAN
-block, min / max are reported beside it.
+Timing: W untimed warmup steps, then EXACTLY K timed steps, bracketed by a barrier + synchronize on both sides and
+reduced with MAX over the ranks; `ms_per_step` / `value` come from them.  --repeats R times R such blocks instead
+(R x K timed steps) and reports the MEDIAN block, min / max beside it.
+
+A plain run does only that.  --full adds everything else behind the timed steps: the roofline figures of the
+embedding kernels (kernel stamps, per-phase HIP events, the device copy ceiling), the Criteo-like Zipf x 39 line
+and the CPU baseline.  --dump-outputs DIR writes what the last timed step handed its caller (loss, dense net,
+seeded samples of the tables) as .npy files; the inputs are the same on every run with the same arguments.
 """
 import argparse
 import json
@@ -31,7 +36,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--full", action="store_true", help="behind the timed steps, also measure the roofline figures, the Zipf x 39 "
+                    "line and the CPU baseline (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (loss, dense "
+                    "parameters and moments, seeded row samples of the tables) to DIR/<name>.npy")
     ap.add_argument("--prime-steps", type=int, default=300, help="untimed steps of setup in front of --warmup (graphs captured, clocks settled)")
     ap.add_argument("--vocab", type=int, default=200_000_000)
     ap.add_argument("--emb-dim", type=int, default=80)
@@ -46,7 +55,7 @@ def parse():
                     "train_and_eval.py:98-101, train_and_eval_distribute.py:115-116); with the whole-step graph a sink is ONE graph launch "
                     "(sinks of 1 / 2 / 3 / 5 / 6 / 10 / 15 / 30 steps measured on one box, round 5: 0.636 / 0.636 / 0.631 / 0.631-0.636 / 0.633 / "
                     "0.639 / 0.642 / 0.640 ms per step -- the host enqueues the next sink while this one runs; longer graphs are no faster)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="budget of each cpu_baseline leg")
     ap.add_argument("--n-batches", type=int, default=4, help="distinct resident batches cycled through")
     ap.add_argument("--split-state", action="store_true", help="p, m, v as three separate arrays (default: fused rows)")
@@ -71,9 +80,9 @@ def parse():
     ap.add_argument("--stamps", default="roofline", choices=["roofline", "always", "never"],
                     help="the kernels' own wall-clock stamps (they cost the step ~6 us, profiles/r05_stamps_ab.txt): 'roofline' (default) = off in "
                     "the timed blocks `value` comes from, on in --stamp-blocks extra blocks of the same steps right behind them, which the "
-                    "roofline figures come from; 'always' = on throughout (what the runs under rocprofv3 that calibrate the clock offsets use)")
+                    "roofline figures come from (--full only); 'always' = on throughout (what the runs under rocprofv3 that calibrate the clock offsets use)")
     ap.add_argument("--stamp-blocks", type=int, default=2)
-    ap.add_argument("--no-zipf39", action="store_true", help="skip the secondary Criteo-like measurement (Zipf ids, 39 fields) behind the timed region")
+    ap.add_argument("--no-zipf39", action="store_true", help="--full without the secondary Criteo-like measurement (Zipf ids, 39 fields) behind the timed region")
     args = ap.parse_args()
     if args.capacity_factor is None:
         args.capacity_factor = 1.05 if args.dist == "uniform" else 1.25
@@ -274,6 +283,47 @@ def zipf39_line(args, eng, dev, peak, clock_off=None):
             "timing": f"in-graph kernel stamps over {len(st)} steps behind the timed region" + (" + the dispatch overhead by rocprofv3's clock" if clock_off else "")}
 
 
+DUMP_BYTES = 64_000_000           # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, eng, batch, loss):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (float32; row numbers float64).
+      loss                       the step's loss
+      dense, dense_m, dense_v    the dense net's flat parameters (Wide_b included) and their Adam moments
+      rows                       row numbers of the table sample: seeded positions of the step's batch (the rows it updated) and
+                                 seeded rows anywhere in this rank's table
+      deep, deep_m, deep_v, wide, wide_accum, wide_linear    those rows of the tables and their optimizer state
+    Arrays too large for the budget are a fixed, seeded sample of their elements."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20251015)
+    out = {}
+    if isinstance(loss, (list, tuple)):
+        loss = loss[-1]
+    out["loss"] = loss.detach().float().reshape(-1)[-1:].cpu().numpy()
+    for name in ("dense", "dense_m", "dense_v"):
+        t = (eng.dense_flat if name == "dense" else getattr(eng, name)).detach().reshape(-1)
+        if t.numel() > 3_500_000:
+            t = t[torch.from_numpy(np.sort(rng.choice(t.numel(), 3_500_000, replace=False))).to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    R, D = eng.local_rows, eng.cfg.emb_dim
+    n = max(64, min(8192, (16 << 20) // ((3 * D + 3) * 4)))             # at most 16 MiB of rows
+    rows = rng.integers(0, R, size=min(R, n // 4))
+    if eng.world == 1 and eng.index is None and eng.hb is None:          # (ids are this table's row numbers)
+        ids = batch[0].reshape(-1).cpu().numpy()
+        rows = np.concatenate([rows, ids[rng.integers(0, ids.size, size=n - rows.size)]])
+    rows = np.unique(rows)
+    out["rows"] = rows.astype(np.float64)
+    for name in ("deep", "deep_m", "deep_v", "wide", "wide_accum", "wide_linear"):
+        t = getattr(eng, name)
+        out[name] = t.index_select(0, torch.from_numpy(rows).to(t.device)).float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes over the {DUMP_BYTES}-byte budget"
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -361,17 +411,19 @@ def _measure(args, world, rank, dev):
     S = max(1, args.sink_size)            # (a sink is ONE graph of whole steps wherever the step has a graph: one GPU, or a shard over RCCL)
 
     def run_steps(n, timers=None):
-        """n training steps over the resident batches, S per host call where S > 1 (a remainder step by step)."""
-        i = 0
+        """n training steps over the resident batches, S per host call where S > 1 (a remainder step by step); returns what the
+        last host call returned (the loss of a step, or the losses of a sink)."""
+        i, loss = 0, None
         while i < n:
             if S > 1 and n - i >= S and eng._step_graph is not None:       # (a sink is a graph of whole steps: where the step has one)
-                eng.train_steps([batches[(i + j) % len(batches)] for j in range(S)])
+                loss = eng.train_steps([batches[(i + j) % len(batches)] for j in range(S)])
                 i += S
             else:
                 if timers is not None:
                     eng.deep_apply_timer = timers[i]      # armed by the engine right before the deep-table LazyAdam launch
-                eng.train_step(*batches[i % len(batches)])
+                loss = eng.train_step(*batches[i % len(batches)])
                 i += 1
+        return loss
 
     # Priming (setup, whatever --warmup says): workspaces and the HIP graphs come into being in the engine's first steps.
     for i in range(5):
@@ -385,17 +437,19 @@ def _measure(args, world, rank, dev):
     barrier()
     ss_ = getattr(eng, "_step_state", None)
     # (one GPU only: with ranks, a rank whose capture failed would run a different number of steps -- and collectives -- than its peers)
-    stamps_split = bool(args.stamps == "roofline" and ss_ is not None and eng._step_graph is not None and world == 1)
-    if ss_ is not None and (stamps_split or args.stamps == "never"):
+    stamps_off = bool(args.stamps == "roofline" and ss_ is not None and eng._step_graph is not None and world == 1)
+    stamps_split = stamps_off and args.full          # (--full: stamped blocks behind the timed ones, for the roofline figures)
+    if ss_ is not None and (stamps_off or args.stamps == "never"):
         ss_.set_stamps(False)
     run_steps(args.warmup)
     barrier()
-    block_s, kmain = [], []
+    block_s, kmain, loss = [], [], None
     for r in range(max(1, args.repeats)):
-        ktimers = [ops.KernelTimer() for _ in range(args.steps)]     # HIP events around k_apply_main only
+        # (--full: HIP events around k_apply_main only, read where the step runs kernel by kernel)
+        ktimers = [ops.KernelTimer() for _ in range(args.steps)] if args.full else None
         barrier()
         t0 = time.perf_counter()
-        run_steps(args.steps, ktimers)
+        loss = run_steps(args.steps, ktimers)
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -403,8 +457,91 @@ def _measure(args, world, rank, dev):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         block_s.append(dt)
-        if eng._step_graph is None:
+        if ktimers is not None and eng._step_graph is None:
             kmain += [t.ms() for t in ktimers]
+    if args.dump_outputs and rank == 0:
+        # (the step with index steps - 1 of the block ran on this batch: run_steps starts every block at batch 0)
+        dump_outputs(args.dump_outputs, eng, batches[(args.steps - 1) % len(batches)], loss)
+    dt = median(block_s)
+    graphs_used = {"step": eng._step_graph is not None, "front": eng._front_graph is not None, "mlp": eng._mlp_graph is not None,
+                   "sink_size": S if (any(k[0] == S and v for k, v in eng._sink_graphs.items()) and args.steps >= S) else 1}
+    U, n_apply = eng.last_plan.U, eng.last_plan.n
+    dt_name = {"bf16": "bf16", "fp16": "f16", "fp32": "f32"}[args.mlp_dtype]
+    out = {
+        "metric": "samples/sec Wide&Deep Criteo batch16384",
+        "value": round(args.batch * world * args.steps / dt, 1),
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "repeats": len(block_s),
+        "ms_per_step_min": round(min(block_s) / args.steps * 1e3, 4),
+        "ms_per_step_max": round(max(block_s) / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": dt_name,
+        "data": "synthetic",
+        "config": {"workload": f"Wide&Deep Criteo (BASELINE configs[1]): vocab {args.vocab}, dim {args.emb_dim}, "
+                               f"batch {args.batch}/GPU, {args.fields} fields, fp32 tables and fp32 optimizer state ({'split' if args.split_state else 'fused-row'} "
+                               f"layout), {args.dist} ids{', hash tables keyed by id (dynamic_embedding)' if args.dynamic_embedding else ''}"
+                               f"{f', tables in host DRAM behind a {args.host_cache_rows}-row device cache' if args.host_cache_rows else ''}, "
+                               f"MLP {cfg.field_size * cfg.emb_dim}-1024-512-256-128-1 in {args.mlp_dtype} "
+                               f"({'hand-written MFMA kernels' if eng._mfma else (f'hand-written fp32 DenseLayers, MatMuls: {cfg.fp32_matmul}' if getattr(eng, '_f32net', False) else 'torch GEMMs')}; looked-up rows and row gradients in {dt_name})"
+                               f"{f', {S} steps per host call (sink_size)' if graphs_used.get('sink_size', 1) > 1 else ''}"
+                               f"{', Dropout(0.5) on every DenseLayer input' if args.dropout else ''}",
+                   "kernel_stamps": "off in the timed blocks" if stamps_off else args.stamps,
+                   "global_batch": args.batch * world, "id_dist": args.dist, "hip_graphs": graphs_used, "unique_frac": round(U / max(n_apply, 1), 4),
+                   "parallelism": ("1 GPU" + (", row-shard protocol over RCCL with itself" if args.shard_protocol else "")) if world == 1 else f"tables row-sharded x{world} (RCCL all-to-all), MLP dp{world}"},
+    }
+    if args.full:
+        _full_extras(args, world, rank, dev, eng, batches, run_steps, barrier, ss_, stamps_split, block_s, kmain, out)
+    if world > 1 or args.shard_protocol:
+        # what a first multi-GPU run needs in order to be diagnosable from its one line
+        uq = float(args.shard_uniques)
+        N_ = args.batch * args.fields
+        ns = eng.k.shard_capacity(max(int(N_ * uq), 1) if uq > 0 else N_, world, args.capacity_factor) * world
+        W = eng.k.shard_msg_words(args.emb_dim, torch.float32 if uq > 0 else eng._act)[1]
+        off = (world - 1) / world                  # a rank's own chunk never moves
+        id_b = 8 if batches[0][0].dtype == torch.int32 else 16
+
+        def model(nw, uqf, act):                   # bytes a rank puts on xGMI per step and direction at nw ranks (its own chunk stays)
+            slots = eng.k.shard_capacity(max(int(N_ * uqf), 1) if uqf > 0 else N_, nw, args.capacity_factor) * nw
+            Wm = eng.k.shard_msg_words(args.emb_dim, torch.float32 if uqf > 0 else act)[1]
+            o_ = (nw - 1) / nw
+            return {"slots_per_rank": slots, "request": int(slots * id_b * o_), "answer": int(slots * Wm * 4 * o_), "gradient": int(slots * Wm * 4 * o_)}
+        out["rccl"] = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(),
+                       "own_chunk_bypass": bool(eng._bypass),          # did _exchange_selftest keep the per-peer-list exchange?
+                       "whole_step_graph": eng._step_graph is not None,
+                       "slots_per_rank": ns, "capacity_factor": args.capacity_factor,
+                       "a2a_bytes_per_rank_per_step": {"request": int(ns * id_b * off), "answer": int(ns * W * 4 * off),
+                                                       "gradient": int(ns * W * 4 * off)},
+                       "exchange": "unique ids (fp32 rows / summed gradient rows)" if uq > 0 else "positions (16-bit rows)", "unique_factor": uq,
+                       # the byte model of an 8-rank node, whatever this run's world size (at world 1 nothing moves): today's
+                       # per-position exchange against the unique-level one at this run's unique ids per position
+                       "a2a_bytes_model_n8": {"positions": model(8, 0.0, eng._act),
+                                              "uniques": model(8, uq if uq > 0 else min(1.0, round(U / max(n_apply, 1), 4)), eng._act),
+                                              "unique_ids_per_position": uq if uq > 0 else round(U / max(n_apply, 1), 4)},
+                       "allreduce_bytes_per_step": int(eng.dense_grad_full.numel() * 4),
+                       "kernels_ms_keys": ["route", "a2a_rows", "unroute", "a2a_grads", "allreduce_dense"]}
+        # dropped positions: the count every rank holds is the SUM over all ranks (it rides the dense all-reduce), so all ranks
+        # take the same branch here -- nobody is left inside a barrier
+        eng.check_shard_overflow()
+        out["config"]["shard_capacity"] = {"factor": args.capacity_factor, "dropped_positions": 0}
+    eng.check_cache()           # host_cache_rows: a batch that did not fit the device cache is latched on the device
+    if world > 1 or args.shard_protocol:
+        dist.barrier()
+    return out
+
+
+def _full_extras(args, world, rank, dev, eng, batches, run_steps, barrier, ss_, stamps_split, block_s, kmain, out):
+    """--full: everything behind the timed steps that `value` does not need -- the roofline figures (kernel stamps in extra blocks,
+    per-phase HIP events in eager extra steps, the device copy ceiling, the committed profiles), the Zipf x 39 line and the CPU
+    baseline -- added to `out`."""
+    import torch
+    from mindrec_amd import ops
+    from mindrec_amd.wide_deep import embedding_bytes
     embed_stamps = []
     apply_timing = ("HIP events around k_apply_main on its launch stream (mrec_profile_next_apply), "
                     "averaged over the {n} timed steps")
@@ -435,9 +572,9 @@ def _measure(args, world, rank, dev):
                         "is one HIP graph, whose event nodes cannot be timed), averaged over the last {n} timed steps"
                         + (f" -- of {n_stamped_blocks} extra blocks of the same steps run right behind the blocks `value` comes from, with the "
                            f"stamps switched on ({stamped_ms_per_step} ms per step there); `value`'s blocks run without them" if stamps_split else ""))
-    dt = median(block_s)
-    graphs_used = {"step": eng._step_graph is not None, "front": eng._front_graph is not None, "mlp": eng._mlp_graph is not None,
-                   "sink_size": S if (any(k[0] == S and v for k, v in eng._sink_graphs.items()) and args.steps >= S) else 1}
+    if stamps_split:
+        out["config"]["kernel_stamps"] = ("off in the timed blocks; on in %d extra blocks of the same steps behind them (%s ms per step), which "
+                                          "the roofline figures are read from" % (n_stamped_blocks, stamped_ms_per_step))
 
     # Per-phase device times (informational "kernels_ms"): HIP events around every phase, recorded in a few
     # EXTRA steps after the timed region -- two dozen timing events per step serialise the queue and cost
@@ -530,34 +667,7 @@ def _measure(args, world, rank, dev):
 
     lookup_ms, wide_ms, wapply_ms = med_ms("gather_deep"), med_ms("wide_sum"), med_ms("apply_wide")
     dt_name = {"bf16": "bf16", "fp16": "f16", "fp32": "f32"}[args.mlp_dtype]
-    out = {
-        "metric": "samples/sec Wide&Deep Criteo batch16384",
-        "value": round(args.batch * world * args.steps / dt, 1),
-        "unit": "samples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "repeats": len(block_s),
-        "ms_per_step_min": round(min(block_s) / args.steps * 1e3, 4),
-        "ms_per_step_max": round(max(block_s) / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": dt_name,
-        "data": "synthetic",
-        "config": {"workload": f"Wide&Deep Criteo (BASELINE configs[1]): vocab {args.vocab}, dim {args.emb_dim}, "
-                               f"batch {args.batch}/GPU, {args.fields} fields, fp32 tables and fp32 optimizer state ({'split' if args.split_state else 'fused-row'} "
-                               f"layout), {args.dist} ids{', hash tables keyed by id (dynamic_embedding)' if args.dynamic_embedding else ''}"
-                               f"{f', tables in host DRAM behind a {args.host_cache_rows}-row device cache' if args.host_cache_rows else ''}, "
-                               f"MLP {cfg.field_size * cfg.emb_dim}-1024-512-256-128-1 in {args.mlp_dtype} "
-                               f"({'hand-written MFMA kernels' if eng._mfma else (f'hand-written fp32 DenseLayers, MatMuls: {cfg.fp32_matmul}' if getattr(eng, '_f32net', False) else 'torch GEMMs')}; looked-up rows and row gradients in {dt_name})"
-                               f"{f', {S} steps per host call (sink_size)' if graphs_used.get('sink_size', 1) > 1 else ''}"
-                               f"{', Dropout(0.5) on every DenseLayer input' if args.dropout else ''}",
-                   "kernel_stamps": ("off in the timed blocks; on in %d extra blocks of the same steps behind them (%s ms per step), which the roofline "
-                                     "figures are read from" % (n_stamped_blocks, stamped_ms_per_step)) if stamps_split else args.stamps,
-                   "global_batch": args.batch * world, "id_dist": args.dist, "hip_graphs": graphs_used, "unique_frac": round(U / max(n_apply, 1), 4),
-                   "parallelism": ("1 GPU" + (", row-shard protocol over RCCL with itself" if args.shard_protocol else "")) if world == 1 else f"tables row-sharded x{world} (RCCL all-to-all), MLP dp{world}"},
+    out.update({
         "roofline": {"bound": "hbm",
                      "kernel": ("k_apply_main<4,int,UpdAdam,%s,WIDE> (segment-sum + LazyAdam row update + FTRL on the row's wide record)" if fold else
                                 "k_apply_main<4,int,UpdAdam,%s> (fused segment-sum + LazyAdam row update)") % (dt_name + "_t" if io16 else "float"),
@@ -573,7 +683,7 @@ def _measure(args, world, rank, dev):
         # medians over n eager extra steps behind the timed region (HIP events around each phase on the main stream: a phase that only
         # ENQUEUES work on the side stream -- the plan -- is not listed; one cold outlier does not move a median)
         "kernels_ms": {k: {"median": round(median(v), 5), "n": len(v)} for k, v in sorted(kern_ms.items()) if v and k != "plan"},
-    }
+    })
     lookup_timing = "torch events around the gather in eager extra steps after the timed region"
     apply_all_ms = None
     lookup_ms_stamps = apply_all_stamps = None
@@ -656,47 +766,11 @@ def _measure(args, world, rank, dev):
             out["roofline_zipf39"] = zipf39_line(args, eng, dev, peak, clock_off if clock_src else None)
         except Exception as e:       # noqa: BLE001  (a secondary measurement must not take the line down)
             out["roofline_zipf39"] = {"error": f"{type(e).__name__}: {e}"[:200]}
-    if world > 1 or args.shard_protocol:
-        # what a first multi-GPU run needs in order to be diagnosable from its one line
-        uq = float(args.shard_uniques)
-        N_ = args.batch * args.fields
-        ns = eng.k.shard_capacity(max(int(N_ * uq), 1) if uq > 0 else N_, world, args.capacity_factor) * world
-        W = eng.k.shard_msg_words(args.emb_dim, torch.float32 if uq > 0 else eng._act)[1]
-        off = (world - 1) / world                  # a rank's own chunk never moves
-        id_b = 8 if batches[0][0].dtype == torch.int32 else 16
-
-        def model(nw, uqf, act):                   # bytes a rank puts on xGMI per step and direction at nw ranks (its own chunk stays)
-            slots = eng.k.shard_capacity(max(int(N_ * uqf), 1) if uqf > 0 else N_, nw, args.capacity_factor) * nw
-            Wm = eng.k.shard_msg_words(args.emb_dim, torch.float32 if uqf > 0 else act)[1]
-            o_ = (nw - 1) / nw
-            return {"slots_per_rank": slots, "request": int(slots * id_b * o_), "answer": int(slots * Wm * 4 * o_), "gradient": int(slots * Wm * 4 * o_)}
-        out["rccl"] = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(),
-                       "own_chunk_bypass": bool(eng._bypass),          # did _exchange_selftest keep the per-peer-list exchange?
-                       "whole_step_graph": eng._step_graph is not None,
-                       "slots_per_rank": ns, "capacity_factor": args.capacity_factor,
-                       "a2a_bytes_per_rank_per_step": {"request": int(ns * id_b * off), "answer": int(ns * W * 4 * off),
-                                                       "gradient": int(ns * W * 4 * off)},
-                       "exchange": "unique ids (fp32 rows / summed gradient rows)" if uq > 0 else "positions (16-bit rows)", "unique_factor": uq,
-                       # the byte model of an 8-rank node, whatever this run's world size (at world 1 nothing moves): today's
-                       # per-position exchange against the unique-level one at this run's unique ids per position
-                       "a2a_bytes_model_n8": {"positions": model(8, 0.0, eng._act),
-                                              "uniques": model(8, uq if uq > 0 else min(1.0, round(U / max(n_apply, 1), 4)), eng._act),
-                                              "unique_ids_per_position": uq if uq > 0 else round(U / max(n_apply, 1), 4)},
-                       "allreduce_bytes_per_step": int(eng.dense_grad_full.numel() * 4),
-                       "kernels_ms_keys": ["route", "a2a_rows", "unroute", "a2a_grads", "allreduce_dense"]}
-        # dropped positions: the count every rank holds is the SUM over all ranks (it rides the dense all-reduce), so all ranks
-        # take the same branch here -- nobody is left inside a barrier
-        eng.check_shard_overflow()
-        out["config"]["shard_capacity"] = {"factor": args.capacity_factor, "dropped_positions": 0}
-    eng.check_cache()           # host_cache_rows: a batch that did not fit the device cache is latched on the device
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
-    if world > 1 or args.shard_protocol:
-        dist.barrier()
-    return out
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""The committed bench line of the current round (profiles/r05_bench_line.json, produced by `python bench.py` on the GPU box) carries every
+"""The committed bench line of the current round (profiles/r05_bench_line.json, produced by `python bench.py --full` on the GPU box) carries every
 field of the driver's contract: metric/value/unit/n_gpus/steps/warmup/ms_per_step/higher_is_better/scaling/vs_baseline/
 dtype/data/config.workload plus the roofline and cpu_baseline objects."""
 import json

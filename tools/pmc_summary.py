@@ -4,8 +4,8 @@
 128-B read requests at 64 B, so read bytes = 2 * FETCH_SIZE KiB; WRITE_SIZE is exact.
 
 The correction is checked in the same runs on two launches whose traffic is known exactly:
-  * the 1-GiB device-to-device copy bench.py times for `measured_copy_gbps` (reads 1 GiB, writes 1 GiB);
-  * k_dense_adam4_slabs, from the byte counts bench.py prints in `dense_adam_bytes` (pass that JSON line as 4th argument).
+  * the 1-GiB device-to-device copy `bench.py --full` times for `measured_copy_gbps` (reads 1 GiB, writes 1 GiB);
+  * k_dense_adam4_slabs, from the byte counts `bench.py --full` prints in `dense_adam_bytes` (pass that JSON line as 4th argument).
 
 usage: pmc_summary.py FETCH_DIR WRITE_DIR [OUT_JSON [BENCH_LINE_JSON]]"""
 import collections
