@@ -151,6 +151,31 @@ int mrec_gather_rows_wide_ex(const float* table, int64_t V, int64_t ld, int32_t 
                              int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw, const struct mrec_dropout* drop,
                              int32_t fields, uint32_t flags, void* step_state, void* stream);
 
+/* max_norm (nn.ClipByNorm over every looked-up row: HashEmbeddingLookup / nn.EmbeddingLookup(max_norm=c), mindspore_rec/ops/
+ * embedding.py:156-161,202-205).  The _clip lookups are the entries above with one argument more (the `_ex` style): each row x,
+ * as an fp32 row, becomes x * (c / n) where n = sqrt(sum of x_d^2) > c and stays x exactly otherwise -- a tie is not clipped, nor
+ * is a zero row (ids outside [0, V)) -- and is then multiplied by row_scale, rounded and dropped out as without the clip.  The
+ * sum of squares is added in an order that depends on the column index only (the same order the sparse apply's Jacobian uses,
+ * so the lookup and the apply of one step take one clip decision per row; mrec_sparse_apply_next_max_norm below).  out: float*
+ * for the f32 entries, uint16_t* for bf16 / f16.  max_norm not finite or <= 0: MREC_EINVAL; D % 4 != 0, D > 256 (the wide form:
+ * D > 252), or rows that are not 16-byte aligned: MREC_EUNSUPPORTED -- all before any launch.  The wide word is not clipped. */
+int mrec_gather_rows_clip_f32_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, int64_t n,
+                                  const float* row_scale, void* out, float max_norm, void* stream);
+int mrec_gather_rows_clip_f32_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids, int64_t n,
+                                  const float* row_scale, void* out, float max_norm, void* stream);
+int mrec_gather_rows_clip_bf16_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, int64_t n,
+                                   const float* row_scale, void* out, float max_norm, void* stream);
+int mrec_gather_rows_clip_bf16_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids, int64_t n,
+                                   const float* row_scale, void* out, float max_norm, void* stream);
+int mrec_gather_rows_clip_f16_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, int64_t n,
+                                  const float* row_scale, void* out, float max_norm, void* stream);
+int mrec_gather_rows_clip_f16_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids, int64_t n,
+                                  const float* row_scale, void* out, float max_norm, void* stream);
+int mrec_gather_rows_wide_clip(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
+                               int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out, int32_t out_kind,
+                               int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw, const struct mrec_dropout* drop,
+                               int32_t fields, uint32_t flags, void* step_state, float max_norm, void* stream);
+
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row
  * stride ldw floats: 1 for a dense column, 4 when it lives in a fused w|accum|linear|pad record). */
@@ -379,6 +404,16 @@ int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int64_t V, in
 #define MREC_CONST_COLS_STATE_BYTES 2592
 int mrec_const_cols_detect(const void* ids, int32_t id_bytes, int64_t B, int32_t F, int64_t V, int64_t min_count, void* state, void* stream);
 int mrec_sparse_apply_next_const_cols(const void* state, const void* ids, int32_t id_bytes, int64_t B);
+/* max_norm on the backward side.  The lookup's clip y = x * (c / n) (n = |x| > c) has the Jacobian J(x) = (c / n)(I - x x^T / n^2),
+ * and J is linear, so the sum of a row's gradients over the step goes through it once: mrec_sparse_apply_next_max_norm(c) ARMS the
+ * NEXT LazyAdam apply of this host thread (mrec_sparse_lazy_adam_{f32,bf16g,f16g}_{i32,i64}, mrec_sparse_lazy_adam_wide(_defer);
+ * the "arm the next call" precedent of mrec_sparse_apply_next_const_cols, so that no existing entry changes), which replaces each
+ * touched row's completed gradient sum G by J(x) G where the row x it loads -- the row the step's lookup read -- has n > c, and
+ * leaves G alone otherwise (n from the lookup's order of additions: the same decision).  Window partial sums stay unclipped; the
+ * wide record's FTRL is not touched; the call runs the plain windows (no hot columns).  The armed call returns MREC_EUNSUPPORTED
+ * for D % 4 != 0, D > 256, D > 252 with the wide record, or rows that are not 16-byte aligned, before any launch; it disarms
+ * either way.  max_norm not finite or <= 0: MREC_EINVAL (nothing is armed). */
+int mrec_sparse_apply_next_max_norm(float max_norm);
 int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, const float* g, void* shadow16, int shadow_kind, int64_t n,
                                      int32_t nseg, const float* const* slabs, const int64_t* starts, const int64_t* lens,
                                      const int32_t* splits, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,

@@ -72,6 +72,15 @@ _SIGS = {
     "mrec_sparse_apply_workspace_bytes": [_i64, _i32, _szp],
     "mrec_const_cols_detect": [_vp, _i32, _i64, _i32, _i64, _i64, _vp, _vp],
     "mrec_sparse_apply_next_const_cols": [_vp, _vp, _i32, _i64],
+    "mrec_sparse_apply_next_max_norm": [_f32],
+    "mrec_gather_rows_clip_f32_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
+    "mrec_gather_rows_clip_f32_i64": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
+    "mrec_gather_rows_clip_bf16_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
+    "mrec_gather_rows_clip_bf16_i64": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
+    "mrec_gather_rows_clip_f16_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
+    "mrec_gather_rows_clip_f16_i64": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
+    "mrec_gather_rows_wide_clip": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _i32,
+                                   C.c_uint32, _vp, _f32, _vp],
     "mrec_sparse_apply_window": [_i32, _int],
     "mrec_segment_sum_f32": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _i32, _vp, _vp, _sz, _vp],
     "mrec_segment_sum_g16": [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _f32, _i32, _vp, _vp, _sz, _vp],

@@ -29,6 +29,7 @@
 // each, partials in order, and the long ones with a whole 256-thread block in a fixed tree order.
 // Both passes are bitwise reproducible.
 #include <type_traits>
+#include <cstddef>
 
 #include "mrec_common.h"
 #include "mrec_optim.h"
@@ -273,6 +274,7 @@ MREC_GTOUCH16(f16_t)
 struct UpdAdam {
     static constexpr int NS = 3;
     static constexpr bool kLoad = true;
+    static constexpr bool kClip = false;
     float* s[3];
     AdamH h;
     __device__ __forceinline__ void elem(float* st, float g) const { adam_elem(st[0], st[1], st[2], g, h); }
@@ -280,6 +282,7 @@ struct UpdAdam {
 struct UpdFtrl {
     static constexpr int NS = 3;
     static constexpr bool kLoad = true;
+    static constexpr bool kClip = false;
     float* s[3];
     FtrlH h;
     __device__ __forceinline__ void elem(float* st, float g) const { ftrl_elem(st[0], st[1], st[2], g, h); }
@@ -287,9 +290,40 @@ struct UpdFtrl {
 struct UpdStore {  // UnsortedSegmentSum: out[u,:] = sum
     static constexpr int NS = 1;
     static constexpr bool kLoad = false;
+    static constexpr bool kClip = false;
     float* s[1];
     __device__ __forceinline__ void elem(float* st, float g) const { st[0] = g; }
 };
+
+// LazyAdam behind max_norm (mrec_sparse_apply_next_max_norm): the row's completed gradient sum G goes through the clip's Jacobian,
+// G' = (c / n) (G - (x.G / n^2) x) where n = |x| > c, x = the pre-update row p the update loads anyway (= what the step's lookup
+// read: one row, one decision -- n^2 in mrec_row_sumsq's order, as in the lookup).  Its own type: the plain LazyAdam kernels are
+// not touched.
+struct UpdAdamClip : UpdAdam {
+    static constexpr bool kClip = true;
+    float clip;
+};
+template <class U> struct IsAdam : std::is_same<U, UpdAdam> {};
+template <> struct IsAdam<UpdAdamClip> : std::true_type {};
+
+// lanes ds = 0 .. nd - 1 of the lane-group (lane0 = hardware lane of ds 0) hold row x (= p) and the sum g; every one of them calls
+template <class Upd>
+__device__ __forceinline__ void clip_grad(const Upd& u, Vf<4>& g, const Vf<4>& x, int ds, int nd, int lane0) {
+    const float n2 = mrec_row_sumsq(x.v, ds, nd, lane0);
+    float d = x.v.x * g.v.x;
+    d = d + x.v.y * g.v.y;
+    d = d + x.v.z * g.v.z;
+    d = d + x.v.w * g.v.w;
+    d = mrec_group_sum(d, ds, nd, lane0);
+    float s;
+    if (mrec_clip_scale(n2, u.clip, &s)) {
+        const float t = d / n2;
+        g.v.x = s * (g.v.x - t * x.v.x);
+        g.v.y = s * (g.v.y - t * x.v.y);
+        g.v.z = s * (g.v.z - t * x.v.z);
+        g.v.w = s * (g.v.w - t * x.v.w);
+    }
+}
 
 template <class Upd>
 __device__ __forceinline__ void upd_apply(const Upd& u, Vf<4> (&st)[Upd::NS], const Vf<4>& g) {
@@ -649,8 +683,15 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
                     if ((openm >> q) & 1u) {
                         if (!head_pair) vstore<false>(carry_head + sw * gm.D + ccol, acc);
                     } else if (upd_ok[k]) {
-                        if (WIDE && wl) wide_apply(st[k][0], acc, wa.h);
-                        else upd_apply<Upd>(upd, st[k], acc);
+                        if (WIDE && wl) {
+                            wide_apply(st[k][0], acc, wa.h);
+                        } else if constexpr (Upd::kClip && VEC == 4) {      // (all deep lanes of the group are here: endm, upd_ok are the group's)
+                            Vf<VEC> gc = acc;
+                            clip_grad(upd, gc, st[k][0], sub, gm.lpr - (WIDE ? 1 : 0), lane - sub);
+                            upd_apply<Upd>(upd, st[k], gc);
+                        } else {
+                            upd_apply<Upd>(upd, st[k], acc);
+                        }
 #pragma unroll
                         for (int i = 0; i < Upd::NS; ++i)
                             if (!(WIDE && wl && i > 0)) vstore<NT>(upd.s[i] + roff[k], st[k][i]);
@@ -683,6 +724,7 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
 template <class Upd>
 __device__ __forceinline__ void resolve_step(Upd&, const StepState*) {}
 __device__ __forceinline__ void resolve_step(UpdAdam& u, const StepState* ss) { if (ss) u.h.lr_t = ss->lr_t; }
+__device__ __forceinline__ void resolve_step(UpdAdamClip& u, const StepState* ss) { if (ss) u.h.lr_t = ss->lr_t; }
 
 template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false>
 __global__ __launch_bounds__(256, WIDE ? MREC_WPS4 : 1) void k_apply_main(Upd upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
@@ -821,6 +863,7 @@ __device__ __forceinline__ void apply_long_body(Upd upd, int64_t V, int64_t ld, 
                     wide_apply(st[0], acc, wa.h);
                     vstore<false>(upd.s[0] + roff, st[0]);
                 } else {
+                    if constexpr (Upd::kClip && VEC == 4) clip_grad(upd, acc, st[0], sub, gm.lpr - (WIDE ? 1 : 0), lane - sub);
                     upd_apply<Upd>(upd, st, acc);
 #pragma unroll
                     for (int i = 0; i < Upd::NS; ++i) vstore<false>(upd.s[i] + roff, st[i]);
@@ -894,6 +937,7 @@ __device__ __forceinline__ void apply_long_body(Upd upd, int64_t V, int64_t ld, 
 #pragma unroll
                             for (int i = 0; i < Upd::NS; ++i) vload<false>(st[i], upd.s[i] + roff);
                         }
+                        if constexpr (Upd::kClip && VEC == 4) clip_grad(upd, acc, st[0], sub, gm.lpr - (WIDE ? 1 : 0), lane - sub);
                         upd_apply<Upd>(upd, st, acc);
 #pragma unroll
                         for (int i = 0; i < Upd::NS; ++i) vstore<false>(upd.s[i] + roff, st[i]);
@@ -1014,7 +1058,9 @@ struct ApplyFinish {
     const float* carry_head; const float* carry_tail; const int* owners; int nsw; WideArgs wa; const StepState* ss;
     const int64_t* nv; unsigned lblocks; unsigned magic;
     ConstCols cc; unsigned cfin;            // cfin: workgroups of the constant columns' finishing pass (kConstMax, or 0: no such pass)
+    float clip;                             // max_norm of the apply (0: none); sits in what was the record's tail padding
 };
+static_assert(offsetof(ApplyFinish, clip) + sizeof(float) == sizeof(ApplyFinish), "ApplyFinish: clip in the tail padding");
 static_assert(sizeof(ApplyFinish) <= sizeof(mrec_apply_finish_t), "mrec_apply_finish_t too small");
 constexpr unsigned kFinishMagic = 0x4D524543u;
 
@@ -1033,12 +1079,28 @@ __global__ __launch_bounds__(256) void k_finish_dense_adam(ApplyFinish f, DenseA
     dense_adam4_slabs_body<SHK>(a.p, a.m, a.v, a.g, a.n4, a.h, a.shadow, sg, a.ss, a.f1,
                                 (int64_t)(blockIdx.x - front) * 256 + threadIdx.x, (int64_t)(gridDim.x - front) * 256);
 }
+// ... the same behind max_norm (f.clip > 0): the finishing pass applies the clip's Jacobian (no constant columns there: cfin == 0)
+template <class K, int SHK>
+__global__ __launch_bounds__(256) void k_finish_dense_adam_clip(ApplyFinish f, DenseAdamSlabArgs a, SlabSegs sg) {
+    if (blockIdx.x < f.lblocks) {
+        UpdAdamClip u;
+        static_cast<UpdAdam&>(u) = f.upd;
+        u.clip = f.clip;
+        apply_long_body<4, K, UpdAdamClip, true>(u, f.V, f.ld, (const K*)f.uniq, f.sseg, f.seg_offsets, f.n, f.gm, f.carry_head,
+                                                 f.carry_tail, f.owners, f.nsw, f.wa, f.ss, f.nv, (int)blockIdx.x, (int)f.lblocks);
+        return;
+    }
+    const unsigned front = f.lblocks;
+    dense_adam4_slabs_body<SHK>(a.p, a.m, a.v, a.g, a.n4, a.h, a.shadow, sg, a.ss, a.f1,
+                                (int64_t)(blockIdx.x - front) * 256 + threadIdx.x, (int64_t)(gridDim.x - front) * 256);
+}
 
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 thread_local hipEvent_t t_prof_start = nullptr, t_prof_stop = nullptr;
 thread_local ApplyFinish* t_defer = nullptr;        // set by mrec_sparse_lazy_adam_wide_defer: the finishing pass is handed back, not launched
 thread_local ConstCols t_const = ConstCols{};       // set by mrec_sparse_apply_next_const_cols: the next wide apply takes constant columns out of its windows
+thread_local float t_max_norm = 0.0f;               // set by mrec_sparse_apply_next_max_norm: the next LazyAdam apply clips (0: none)
 
 struct ApplyWs { float* carry_head; float* carry_tail; int* owners; int* n_owners; float* dummy; float* cpart; };
 
@@ -1089,10 +1151,10 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
         cc.cblocks = (unsigned)mrec_cdiv((int64_t)cc.nlg * kConstMax, (int64_t)4 * gm.G);      // (room for kConstMax columns: how many there are is known on the device)
     }
     if (vec == 4 && wide) {
-      if constexpr (!std::is_same<Upd, UpdAdam>::value) {
+      if constexpr (!IsAdam<Upd>::value) {
         return MREC_EUNSUPPORTED;                  // (the wide lane rides LazyAdam only: no such instantiation of the other updaters)
       } else {
-        if constexpr (sizeof(K) == 4) {
+        if constexpr (sizeof(K) == 4 && std::is_same<Upd, UpdAdam>::value) {      // (no HOT variant behind max_norm: cc is empty there)
             if (cc.mask)
                 k_apply_main<4, K, Upd, GT, true, true><<<blocks + cc.cblocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale,
                                                              gscale, gm, w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss, nv, cc);
@@ -1102,12 +1164,13 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
                                                              w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss, nv, cc);
         if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
         if (t_defer) {
-            if constexpr (std::is_same<Upd, UpdAdam>::value) {
+            if constexpr (IsAdam<Upd>::value) {
                 ApplyFinish* f = t_defer;
                 f->upd = upd; f->V = V; f->ld = ld; f->uniq = uniq; f->key_bytes = (int)sizeof(K); f->sseg = sseg; f->seg_offsets = seg_offsets;
                 f->n = (int)n; f->gm = gm; f->carry_head = w.carry_head; f->carry_tail = w.carry_tail; f->owners = w.owners; f->nsw = (int)nsw;
                 f->wa = wa; f->ss = ss; f->nv = nv; f->lblocks = lblocks; f->magic = kFinishMagic;
                 f->cc = cc; f->cfin = cc.mask ? (unsigned)kConstMax : 0u;
+                if constexpr (Upd::kClip) f->clip = upd.clip; else f->clip = 0.0f;
             } else {
                 return MREC_EUNSUPPORTED;
             }
@@ -1125,6 +1188,8 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
         if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
         k_apply_long<4, K, Upd><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
                                                         w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss);
+    } else if constexpr (Upd::kClip) {
+        return MREC_EUNSUPPORTED;                  // (max_norm: float4 rows only, refused by apply_impl before any launch)
     } else if (vec == 2) {
         k_apply_main<2, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,
                                                        w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);
@@ -1174,6 +1239,7 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
     // 16-byte lanes when rows allow it, else 8-byte lanes (D = 30 of the DCN table), else scalar
     const int vec = (aligned && D % 4 == 0) ? 4 : ((aligned8 && D % 2 == 0) ? 2 : 1);
     if (wide && (vec != 4 || D > 252 || wide->wcol != D || D + 4 > ld || wide->F <= 0 || !wide->gw)) return MREC_EUNSUPPORTED;
+    if (Upd::kClip && (vec != 4 || D > 256)) return MREC_EUNSUPPORTED;         // (one column block: a row's norm is one lane-group's)
     const int CB = 64 * vec;  // columns per launch
     for (int c0 = 0; c0 < D; c0 += CB) {
         const int Dc = (D - c0 < CB) ? D - c0 : CB;
@@ -1191,12 +1257,22 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
                    int64_t ldg, const float* rscale, float lr, float b1, float b2, float eps, float b1_pow,
                    float b2_pow, float gscale, int nesterov, void* ws, size_t ws_bytes, void* stream,
                    const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr) {
+    const float clip = t_max_norm;                 // (armed for this call only)
+    t_max_norm = 0.0f;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdAdam u;
     u.s[0] = p; u.s[1] = m; u.s[2] = v;
     u.h.lr_t = lr * sqrtf(1.0f - b2_pow) / (1.0f - b1_pow);
     u.h.b1 = b1; u.h.b2 = b2; u.h.omb1 = 1.0f - b1; u.h.omb2 = 1.0f - b2; u.h.eps = eps; u.h.gscale = gscale;
     u.h.nesterov = nesterov;
+    if (clip > 0.0f) {
+        if (D % 4 || D > (wide ? 252 : 256)) return MREC_EUNSUPPORTED;
+        UpdAdamClip uc;
+        static_cast<UpdAdam&>(uc) = u;
+        uc.clip = clip;
+        return apply_impl<K, UpdAdamClip, GT>(uc, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
+                                              stream, wide, ss, nv);
+    }
     return apply_impl<K, UpdAdam, GT>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
                                   stream, wide, ss, nv);
 }
@@ -1414,6 +1490,13 @@ MREC_API int mrec_sparse_apply_next_const_cols(const void* state, const void* id
     return MREC_OK;
 }
 
+MREC_API int mrec_sparse_apply_next_max_norm(float max_norm) {
+    t_max_norm = 0.0f;
+    if (!(max_norm > 0.0f) || !(max_norm <= 3.402823466e38f)) return MREC_EINVAL;
+    t_max_norm = max_norm;
+    return MREC_OK;
+}
+
 MREC_API int mrec_step_state_init(void* state, float beta1_power, float beta2_power, int64_t step, void* stream) {
     if (!state || step < 0) return MREC_EINVAL;
     k_step_init<<<1, 256, 0, (hipStream_t)stream>>>((StepState*)state, beta1_power, beta2_power, (long long)step);
@@ -1564,7 +1647,7 @@ MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V,
                                         float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F,
                                         int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                         size_t ws_bytes, void* step_state, const int64_t* n_valid_dev, void* stream) {
-    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) return MREC_EINVAL;
+    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; return MREC_EINVAL; }
     WideArgs wa;
     wa.gw = gw; wa.F = F; wa.wcol = wide_col; wa.magic = 0; wa.dummy = nullptr; wa.gws = (unsigned)gw_stride;
     wa.h = FtrlH{ftrl_lr, l1, l2, lr_power, grad_scale};
@@ -1592,10 +1675,11 @@ MREC_API int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int6
                                               int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                               size_t ws_bytes, void* step_state, const int64_t* n_valid_dev,
                                               mrec_apply_finish_t* finish_out, void* stream) {
-    if (!finish_out) return MREC_EINVAL;
-    if (D > 252) return MREC_EUNSUPPORTED;            // (one column block: one finishing pass)
+    if (!finish_out) { t_max_norm = 0.0f; return MREC_EINVAL; }
+    if (D > 252) { t_max_norm = 0.0f; return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
     ApplyFinish* f = (ApplyFinish*)finish_out;
     f->magic = 0u;
+    f->clip = 0.0f;
     t_defer = f;
     const int rc = mrec_sparse_lazy_adam_wide(p, m, v, V, ld, D, uniq, uniq_bytes, sorted_pos, sorted_seg, seg_offsets, n, g, g_kind, ldg,
                                               row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, gw, gw_stride, F, wide_col,
@@ -1650,7 +1734,11 @@ MREC_API int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, cons
     hipStream_t st = (hipStream_t)stream;
 #define MREC_FIN(KT)                                                                                      \
     do {                                                                                                   \
-        if (shadow_kind == 1) k_finish_dense_adam<KT, 1><<<grid, 256, 0, st>>>(*fp, a, sg);                \
+        if (fp->clip > 0.0f) {                                                                             \
+            if (shadow_kind == 1) k_finish_dense_adam_clip<KT, 1><<<grid, 256, 0, st>>>(*fp, a, sg);       \
+            else if (shadow_kind == 2) k_finish_dense_adam_clip<KT, 2><<<grid, 256, 0, st>>>(*fp, a, sg);  \
+            else k_finish_dense_adam_clip<KT, 0><<<grid, 256, 0, st>>>(*fp, a, sg);                        \
+        } else if (shadow_kind == 1) k_finish_dense_adam<KT, 1><<<grid, 256, 0, st>>>(*fp, a, sg);         \
         else if (shadow_kind == 2) k_finish_dense_adam<KT, 2><<<grid, 256, 0, st>>>(*fp, a, sg);           \
         else k_finish_dense_adam<KT, 0><<<grid, 256, 0, st>>>(*fp, a, sg);                                 \
     } while (0)

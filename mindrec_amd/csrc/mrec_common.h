@@ -94,3 +94,36 @@ __device__ __forceinline__ int block_excl_scan_256(int x, int* smem, int* total)
     *total = tot;
     return base + incl - x;
 }
+
+// ---- max_norm (nn.ClipByNorm over a looked-up row) ----------------------------------------------------------------------
+// A row of D = 4 nd columns sits in nd consecutive lanes of a lane-group, four columns each; `lane0` is the hardware lane of deep
+// lane 0 and `ds` this lane's deep lane number (the wide lane, where a group has one, passes any ds and ignores the result; it is
+// never read).  mrec_group_sum adds one value per deep lane in an order fixed by the deep lane numbers alone -- a butterfly over
+// ds: at distance m a block of m deep lanes adds the sum of its partner block (read from any of that block's lanes: they all hold
+// the same bits), a + b and b + a being the same float -- so every deep lane of the group ends with the same bits, and the lookup
+// (k_gather_rows*, whose odd lane-groups of the w16 form put the wide lane first) and the sparse apply (wide lane last) get the
+// same sum of squares for the same row: the clip decision of the forward and of the backward is one decision.
+__device__ __forceinline__ float mrec_group_sum(float v, int ds, int nd, int lane0) {
+    for (int m = 1; m < nd; m <<= 1) {
+        const int p = ds ^ m;
+        const bool has = (p & ~(m - 1)) < nd;                       // the partner block holds at least one deep lane
+        const int src = lane0 + (p < nd ? p : nd - 1);              // (its last one where p lies past the row)
+        const float o = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v)));
+        if (has) v = v + o;
+    }
+    return v;
+}
+// sum of squares of the row: the lane's four columns in column order, then mrec_group_sum
+__device__ __forceinline__ float mrec_row_sumsq(const float4& x, int ds, int nd, int lane0) {
+    float s = x.x * x.x;
+    s = s + x.y * x.y;
+    s = s + x.z * x.z;
+    s = s + x.w * x.w;
+    return mrec_group_sum(s, ds, nd, lane0);
+}
+// the clip decision: n = sqrt(n2) > c (a tie is not clipped; a zero row never is); *scale = c / n where it is
+__device__ __forceinline__ bool mrec_clip_scale(float n2, float c, float* scale) {
+    const float n = sqrtf(n2);
+    *scale = c / n;
+    return n > c;
+}

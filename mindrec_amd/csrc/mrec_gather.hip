@@ -95,14 +95,19 @@ __device__ __forceinline__ uint2 drop16(uint2 u, const GatherDrop& gd, uint64_t 
     return pack16((const OT*)nullptr, make_float4(v[0], v[1], v[2], v[3]));
 }
 
-template <int VEC, class K, class OT = float>
+// max_norm (the clip instantiations: Clip = float, the one trailing argument c > 0; nn.ClipByNorm of every looked-up row,
+// embedding.py:156-161,202-205): the row x the lane-group holds becomes x * (c / ||x||) where ||x|| > c, before row_scale -- one
+// lane-group sum of squares (mrec_row_sumsq, the order the sparse apply's Jacobian uses too) and a multiply; no byte more moves.
+// D % 4 == 0 (VEC 4).  Without it (an empty pack) the kernel is, instruction for instruction, the one before the clip existed.
+template <int VEC, class K, class OT = float, class... Clip>
 __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ table, int64_t V, int64_t ld,
                                                      const K* __restrict__ ids, int64_t n,
                                                      const float* __restrict__ row_scale,
                                                      OT* __restrict__ out, int D, RowGeom gm,
                                                      float* __restrict__ wprod = nullptr, int64_t ldo = 0, int64_t ldw = 2,
                                                      GatherDrop gd = GatherDrop{}, int ids_stride = 1, int rs_stride = 1,
-                                                     bool skip_invalid = false, StepState* ss = nullptr) {
+                                                     bool skip_invalid = false, StepState* ss = nullptr, Clip... clip) {
+    static_assert(sizeof...(Clip) == 0 || (sizeof...(Clip) == 1 && VEC == 4), "max_norm: one float, float4 rows");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
     // Stamps (measurement only; ss == nullptr: none): workgroup 0 stores the begin, the last wave of each of the LAST-dispatched
@@ -154,6 +159,13 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ t
     for (int k = 0; k < GB; ++k) {
         vtouch(x[k]);
         if (!okr[k]) x[k] = vzero((Vf<VEC>*)nullptr);
+    }
+    if constexpr (sizeof...(Clip) > 0) {
+#pragma unroll
+        for (int k = 0; k < GB; ++k) {
+            float s;
+            if (mrec_clip_scale(mrec_row_sumsq(x[k].v, sub, D >> 2, lane - sub), (clip + ...), &s) && !wl) x[k] = vscale(x[k], s);
+        }
     }
 #pragma unroll
     for (int k = 0; k < GB; ++k) {
@@ -216,11 +228,11 @@ template <> struct Ids4<int64_t> {
     __device__ __forceinline__ int64_t at(int k) const { return k == 0 ? a.x : k == 1 ? a.y : k == 2 ? b.x : b.y; }
 };
 
-template <class K, class OT>
+template <class K, class OT, class... Clip>
 __global__ __launch_bounds__(256) void k_gather_rows_w16(const float* __restrict__ table, int64_t V, int64_t ld,
                                                          const K* __restrict__ ids, int64_t n, const float* __restrict__ row_scale,
                                                          OT* __restrict__ out, int D, RowGeom gm, float* __restrict__ wprod,
-                                                         int64_t ldo, GatherDrop gd, StepState* ss) {
+                                                         int64_t ldo, GatherDrop gd, StepState* ss, Clip... clip) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
     __shared__ int waves_done;
@@ -259,6 +271,14 @@ __global__ __launch_bounds__(256) void k_gather_rows_w16(const float* __restrict
         for (int k = 0; k < 4; ++k) {
             vtouch(x[k]);
             if (!okr[k]) x[k] = vzero((Vf<4>*)nullptr);
+        }
+        if constexpr (sizeof...(Clip) > 0) {                        // (as k_gather_rows; deep lane 0 sits behind a leading wide lane)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float s;
+                if (mrec_clip_scale(mrec_row_sumsq(x[k].v, ds < 0 ? 0 : ds, D >> 2, lane - sub + (wfirst ? 1 : 0)), (clip + ...), &s) && !wl)
+                    x[k] = vscale(x[k], s);
+            }
         }
         const float sc[4] = {scv.x, scv.y, scv.z, scv.w};
         uint2 pk[4];
@@ -688,7 +708,7 @@ template <class K, class OT = bf16o_t>
 int gather_bf16_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t n,
                      const float* row_scale, uint16_t* out, void* stream, int wcol = 0, float* wprod = nullptr, int64_t ldo = 0,
                      int64_t ldw = 2, GatherDrop gd = GatherDrop{}, int ids_stride = 1, int rs_stride = 1, bool skip_invalid = false,
-                     StepState* ss = nullptr) {
+                     StepState* ss = nullptr, float clip = 0.0f) {
     constexpr int ob = (int)sizeof(OT);                    // bytes per output element (2: bf16 / f16, 4: fp32 rows + the wide lane)
     const int oa = ob == 2 ? 7 : 15;                       // alignment of an output row's 4-element quad
     if ((ldo != 0 && (ldo < D || ldo % 4)) || (wprod && (ldw < 2 || ldw % 2)) || ids_stride < 1 || rs_stride < 1) return MREC_EINVAL;
@@ -706,13 +726,23 @@ int gather_bf16_impl(const float* table, int64_t V, int64_t ld, int32_t D, const
     const bool w16 = vec && ob == 2 && D % 8 == 0 && n % 4 == 0 && n >= 4 && ids_stride == 1 && rs_stride == 1 && !skip_invalid && ldw == 2 &&
                      ldo_e % 8 == 0 && al16(out) && (!wprod || al16(wprod)) && al16(ids) && (!row_scale || al16(row_scale)) &&
                      !no_w16;
+    if (clip > 0.0f && !vec) return MREC_EUNSUPPORTED;
     if (w16) {
         if constexpr (ob == 2) {
             const int lpr = D / 4 + (wprod ? 1 : 0);
             RowGeom gm{lpr, 64 / lpr};
-            k_gather_rows_w16<K, OT><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * 4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, (OT*)out, D, gm,
-                                                                                                 wprod, ldo_e, gd, ss);
+            if (clip > 0.0f)
+                k_gather_rows_w16<K, OT, float><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * 4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, (OT*)out,
+                                                                                                          D, gm, wprod, ldo_e, gd, ss, clip);
+            else
+                k_gather_rows_w16<K, OT><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * 4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, (OT*)out,
+                                                                                                     D, gm, wprod, ldo_e, gd, ss);
         }
+    } else if (vec && clip > 0.0f) {
+        const int lpr = D / 4 + (wprod ? 1 : 0);
+        RowGeom gm{lpr, 64 / lpr};
+        k_gather_rows<4, K, OT, float><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * GB), 256, 0, st>>>(
+            table, V, ld, ids, n, row_scale, (OT*)out, D, gm, wprod, ldo, ldw, gd, ids_stride, rs_stride, skip_invalid, ss, clip);
     } else if (vec) {
         const int lpr = D / 4 + (wprod ? 1 : 0);
         RowGeom gm{lpr, 64 / lpr};
@@ -731,14 +761,19 @@ int gather_bf16_impl(const float* table, int64_t V, int64_t ld, int32_t D, const
 
 template <class K>
 int gather_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t n,
-                const float* row_scale, float* out, void* stream, bool skip_invalid = false) {
+                const float* row_scale, float* out, void* stream, bool skip_invalid = false, float clip = 0.0f) {
     hipStream_t st = (hipStream_t)stream;
     if (n < 0 || D <= 0 || V < 0 || ld < D) return MREC_EINVAL;
     if (n == 0) return MREC_OK;
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!table || !ids || !out) return MREC_EINVAL;
     const bool vec = (D % 4 == 0) && (D <= 256) && (ld % 4 == 0) && al16(table) && al16(out);
-    if (vec) {
+    if (clip > 0.0f) {
+        if (!vec) return MREC_EUNSUPPORTED;
+        RowGeom gm{D / 4, 64 / (D / 4)};
+        k_gather_rows<4, K, float, float><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * GB), 256, 0, st>>>(
+            table, V, ld, ids, n, row_scale, out, D, gm, nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, clip);
+    } else if (vec) {
         RowGeom gm{D / 4, 64 / (D / 4)};
         const int64_t rows_per_block = (int64_t)4 * gm.G * GB;
         k_gather_rows<4, K><<<(unsigned)mrec_cdiv(n, rows_per_block), 256, 0, st>>>(table, V, ld, ids, n, row_scale,
@@ -887,11 +922,60 @@ MREC_API int mrec_gather_rows_f16_i64(const float* table, int64_t V, int64_t ld,
     return gather_bf16_impl<int64_t, f16o_t>(table, V, ld, D, ids, n, row_scale, out, stream);
 }
 
+/* max_norm: finite and > 0 (else MREC_EINVAL); D % 4 == 0 and D <= max_d (else MREC_EUNSUPPORTED) -- checked before any launch */
+static int clip_check(float max_norm, int32_t D, int32_t max_d) {
+    if (!(max_norm > 0.0f) || !(max_norm <= 3.402823466e38f)) return MREC_EINVAL;
+    if (D <= 0) return MREC_EINVAL;
+    if (D % 4 || D > max_d) return MREC_EUNSUPPORTED;
+    return MREC_OK;
+}
+#define MREC_GATHER_CLIP(NAME, KT, IMPL_CALL)                                                                                      \
+    MREC_API int NAME(const float* table, int64_t V, int64_t ld, int32_t D, const KT* ids, int64_t n, const float* row_scale,      \
+                      void* out, float max_norm, void* stream) {                                                                  \
+        const int rc = clip_check(max_norm, D, 256);                                                                              \
+        if (rc != MREC_OK) return rc;                                                                                             \
+        return IMPL_CALL;                                                                                                         \
+    }
+MREC_GATHER_CLIP(mrec_gather_rows_clip_f32_i32, int32_t, (gather_impl<int32_t>(table, V, ld, D, ids, n, row_scale, (float*)out, stream, false, max_norm)))
+MREC_GATHER_CLIP(mrec_gather_rows_clip_f32_i64, int64_t, (gather_impl<int64_t>(table, V, ld, D, ids, n, row_scale, (float*)out, stream, false, max_norm)))
+MREC_GATHER_CLIP(mrec_gather_rows_clip_bf16_i32, int32_t, (gather_bf16_impl<int32_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream, 0,
+                                                                                    nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
+MREC_GATHER_CLIP(mrec_gather_rows_clip_bf16_i64, int64_t, (gather_bf16_impl<int64_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream, 0,
+                                                                                    nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
+MREC_GATHER_CLIP(mrec_gather_rows_clip_f16_i32, int32_t, (gather_bf16_impl<int32_t, f16o_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream,
+                                                                                           0, nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
+MREC_GATHER_CLIP(mrec_gather_rows_clip_f16_i64, int64_t, (gather_bf16_impl<int64_t, f16o_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream,
+                                                                                           0, nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
+#undef MREC_GATHER_CLIP
+
+static int gather_wide_ex_impl(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
+                               int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out,
+                               int32_t out_kind, int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw,
+                               const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, void* stream, float clip);
+
 /* Gather + the wide branch's products in one pass (see include/mrec.h): out_kind 0 = fp32, 1 = bf16, 2 = f16 rows. */
 MREC_API int mrec_gather_rows_wide_ex(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
                                       int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out,
                                       int32_t out_kind, int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw,
                                       const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, void* stream) {
+    return gather_wide_ex_impl(table, V, ld, D, ids, id_bytes, id_stride, n, row_scale, scale_stride, out, out_kind, ldo, wide_col, wide_prod,
+                               ldw, drop, fields, flags, step_state, stream, 0.0f);
+}
+/* ... with max_norm on the deep columns (the wide word is not clipped) */
+MREC_API int mrec_gather_rows_wide_clip(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
+                                        int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out,
+                                        int32_t out_kind, int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw,
+                                        const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, float max_norm,
+                                        void* stream) {
+    const int rc = clip_check(max_norm, D, 252);
+    if (rc != MREC_OK) return rc;
+    return gather_wide_ex_impl(table, V, ld, D, ids, id_bytes, id_stride, n, row_scale, scale_stride, out, out_kind, ldo, wide_col, wide_prod,
+                               ldw, drop, fields, flags, step_state, stream, max_norm);
+}
+static int gather_wide_ex_impl(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
+                                      int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out,
+                                      int32_t out_kind, int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw,
+                                      const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, void* stream, float clip) {
     if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || id_stride < 1 || id_stride > (1 << 20) || scale_stride < 1 ||
         scale_stride > (1 << 20))
         return MREC_EINVAL;
@@ -905,7 +989,7 @@ MREC_API int mrec_gather_rows_wide_ex(const float* table, int64_t V, int64_t ld,
     const int is = (int)id_stride, rs = (int)scale_stride;
     const bool skip = (flags & MREC_GATHER_SKIP_INVALID) != 0;
 #define MREC_GW(KT, OT) return gather_bf16_impl<KT, OT>(table, V, ld, D, (const KT*)ids, n, row_scale, (uint16_t*)out, stream, wide_col, \
-                                                        wide_prod, ldo, ldw, gd, is, rs, skip, (StepState*)step_state)
+                                                        wide_prod, ldo, ldw, gd, is, rs, skip, (StepState*)step_state, clip)
     if (id_bytes == 4) {
         if (out_kind == 0) { MREC_GW(int32_t, float); }
         if (out_kind == 1) { MREC_GW(int32_t, bf16o_t); }

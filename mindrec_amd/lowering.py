@@ -73,6 +73,21 @@ def _lookup_table(c):
     return t, ("sparse" if sparse else "dense")
 
 
+def _max_norm_of(c):
+    """The max_norm of an embedding-lookup cell as a float (None: no clip) -- a float on nn.EmbeddingLookup, a Tensor on
+    HashEmbeddingLookup (embedding.py:156-161)."""
+    mn = getattr(c, "max_norm", None)
+    if mn is None:
+        return None
+    return float(mn.item()) if isinstance(mn, torch.Tensor) else float(mn)
+
+
+def _refuse_max_norm(owner, what):
+    """No lowering drops a lookup's max_norm: the engines other than Wide&Deep's have no clip."""
+    if any(_lookup_table(x) and _max_norm_of(x) is not None for x in owner.cells()):
+        raise LoweringRefused(f"max_norm on an embedding lookup of a {what} model: no engine mode clips its rows")
+
+
 def _chain(layers, width_in):
     """Orders DenseLayer-shaped cells into a chain width_in -> ... by their weight shapes; None if they do not form one."""
     if layers and layers[0].weight.shape[0] == width_in and all(a.weight.shape[1] == b.weight.shape[0] for a, b in zip(layers, layers[1:])):
@@ -434,6 +449,9 @@ def _lower_wide_deep(cell, plan):
     (deep_t, deep_kind), (wide_t, wide_kind) = _lookup_table(deep_l[0]), _lookup_table(wide_l[0])
     if deep_kind != wide_kind:
         raise LoweringRefused("the two tables are looked up differently")
+    if _max_norm_of(wide_l[0]) is not None:
+        raise LoweringRefused("max_norm on the wide lookup (scalar rows) has no engine mode")
+    max_norm = _max_norm_of(deep_l[0])
     hashed = deep_kind == "hash"
     if hashed:
         (sig_d, seed_d, kd, cap_d), (sig_w, seed_w, kw_, cap_w) = _hash_spec(deep_t), _hash_spec(wide_t)
@@ -481,6 +499,13 @@ def _lower_wide_deep(cell, plan):
         raise LoweringRefused("weight decay / Nesterov are not lowered")
     if abs(float(getattr(ftrl, "lr_power", -0.5)) + 0.5) > 1e-9:
         raise LoweringRefused(f"FTRL lr_power {ftrl.lr_power} is not lowered (the engine computes lr_power = -0.5)")
+    if max_norm is not None:
+        if plan.shard:
+            raise LoweringRefused("max_norm on a distributed train cell (row shards) has no engine mode")
+        if deep_kind != "sparse":
+            raise LoweringRefused("max_norm with dense table gradients (sparse=False) has no engine mode")
+        if D % 4 or D > 252:
+            raise LoweringRefused(f"max_norm needs an embedding size that is a multiple of 4 and at most 252 (got {D})")
     if plan.shard and deep_kind == "dense":
         raise LoweringRefused("distributed train cell with dense table gradients (sparse=False: every rank all-reduces [V, D]): no "
                               "engine mode -- the step runs primitive by primitive with its all-reduce")
@@ -489,6 +514,7 @@ def _lower_wide_deep(cell, plan):
                          ftrl_l2=ftrl.l2, ftrl_initial_accum=ftrl.initial_accum, mlp_dtype="fp16" if half else "fp32",
                          sparse=deep_kind == "sparse", l2_coef=l2 if not no_l2 else 0.0, dropout_flag=drop, dropout_keep_prob=keep,
                          id_dtype="int64" if hashed and kd == torch.int64 else "int32", wide_b_optimizer="ftrl" if in_ftrl else "adam",
+                         max_norm=max_norm,
                          **(dict(dynamic_embedding=True, hash_capacity=V, init_sigma=sig_d, seed=seed_d) if hashed else {}))
     if not cfg.sparse and no_l2:
         cfg.l2_coef = 0.0
@@ -709,6 +735,7 @@ def _lower_deep_cross(cell, plan):
             break
     if owner is None:
         return None
+    _refuse_max_norm(owner, "Deep&Cross")
     if plan.shard:
         raise LoweringRefused("distributed train cell (Deep&Cross under DistributedGradReducer, models/deep_and_cross/train.py:57-62): "
                               "DeepCrossEngine is a one-rank engine -- the step runs primitive by primitive with its all-reduce")
@@ -784,6 +811,7 @@ def _lower_deepfm(cell, plan):
             break
     if owner is None:
         return None
+    _refuse_max_norm(owner, "DeepFM")
     if plan.shard:
         raise LoweringRefused("distributed train cell (DeepFM under DistributedGradReducer): DeepFMEngine is a one-rank engine -- the "
                               "step runs primitive by primitive with its all-reduce")

@@ -5,6 +5,7 @@ Each function names the MindSpore primitive it stands in for and the reference c
 only: no arithmetic on the hot path is done by torch here.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -169,10 +170,36 @@ def sparse_plan(ids, skip_negative=False):
     return SparsePlan(Dedup(flat, uniq, inv, n_uniq), sorted_pos, sorted_seg, seg_offsets, n_uniq2[1:] if skip_negative else None)
 
 
-def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32):
+def _max_norm(max_norm):
+    """max_norm as the C entry points take it: a finite float > 0 (None: no clip)."""
+    c = float(max_norm)
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"max_norm must be a finite number > 0, got {max_norm!r}")
+    return c
+
+
+def _call_clipped(max_norm, name, *args):
+    """_lib.call(name, *args) -- a LazyAdam apply -- armed with max_norm (mrec_sparse_apply_next_max_norm: the NEXT apply of this host
+    thread clips).  Everything is evaluated before the arm, and an exception between the arm and the apply (ctypes refusing an
+    argument) disarms again, so that no later apply of another table is clipped by mistake."""
+    if max_norm is None:
+        _lib.call(name, *args)
+        return
+    c = _max_norm(max_norm)
+    _lib.call("mrec_sparse_apply_next_max_norm", c)
+    try:
+        _lib.call(name, *args)
+    except BaseException:
+        _lib.lib().mrec_sparse_apply_next_max_norm(0.0)      # (EINVAL: leaves nothing armed; the C side disarms on its own refusals)
+        raise
+
+
+def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32, max_norm=None):
     """ops.Gather / SparseGatherV2 / EmbeddingLookup (embedding.py:150,194; deep_and_cross.py:199),
     optionally fused with the mask multiply of wide_and_deep.py:303,308.  out_dtype=torch.bfloat16
-    also fuses the half-precision cast in front of the MLP (wide_and_deep.py:122)."""
+    also fuses the half-precision cast in front of the MLP (wide_and_deep.py:122).  max_norm=c: every row x is clipped to
+    x * (c / |x|) where |x| > c before the mask multiply (ClipByNorm of HashEmbeddingLookup / nn.EmbeddingLookup(max_norm),
+    embedding.py:156-161,202-205); D % 4 == 0, D <= 256."""
     _need_cuda(table, ids, row_scale)
     V, D, ld = _table(table)
     sfx = _suffix(ids)
@@ -188,18 +215,24 @@ def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32):
         out = torch.empty((n, D), dtype=out_dtype, device=table.device)
     fn = {torch.float32: "mrec_gather_rows_f32_", torch.bfloat16: "mrec_gather_rows_bf16_",
           torch.float16: "mrec_gather_rows_f16_"}[out.dtype]
+    if max_norm is not None:
+        _lib.call(fn.replace("mrec_gather_rows_", "mrec_gather_rows_clip_") + sfx, _ptr(table), V, ld, D, _ptr(flat), n, _ptr(row_scale),
+                  _ptr(out), _max_norm(max_norm), _stream())
+        return out.view(tuple(ids.shape) + (D,))
     _lib.call(fn + sfx, _ptr(table), V, ld, D, _ptr(flat), n, _ptr(row_scale), _ptr(out), _stream())
     return out.view(tuple(ids.shape) + (D,))
 
 
-def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None):
+def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
+                     max_norm=None):
     """Both lookups of WideDeepModel.construct (wide_and_deep.py:300-302) in one pass over fused rows: returns
     (rows [.., D] in out_dtype, wide_prod [.., 2] with [.., 0] = table_row[wide_col] * row_scale and [.., 1] = 0).  `table` is the [V, D] view of the deep
     columns; wide_col is the column (relative to it, >= D) of the wide weight in the same rows.
     packed_words=W (>= D/2 + 2, multiple of 4): ONE float32 [n, W] result whose row is [D 16-bit values | product, 0 | pad] --
     a shard's answer message (one collective for both tables).  drop (Dropout; ids [B, F]): the looked-up rows are the
     [F * D] input of the DenseLayer the descriptor names and leave the kernel dropped out.  step_state (StepState): the kernel
-    leaves its begin / end stamps there (StepState.lookup_ms)."""
+    leaves its begin / end stamps there (StepState.lookup_ms).  max_norm (as gather_rows): the deep columns are clipped, the wide word
+    is not; D <= 252."""
     _need_cuda(table, ids, row_scale, out)
     V, D, ld = _table(table)
     flat = ids.reshape(-1).contiguous()
@@ -212,6 +245,8 @@ def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.
         raise TypeError("gather_rows_wide writes bfloat16 or float16 rows")
     kind = 1 if out_dtype == torch.bfloat16 else 2
     if packed_words:
+        if max_norm is not None:
+            raise ValueError("max_norm: not on a shard's packed answer message")
         W = int(packed_words)
         if D % 2 or W < D // 2 + 2 or W % 4:
             raise ValueError("packed_words must be a multiple of 4 that holds D / 2 + 2 words")
@@ -222,9 +257,13 @@ def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.
     if out is None:
         out = torch.empty((n, D), dtype=out_dtype, device=table.device)
     wprod = torch.empty((max(n, 1), 2), dtype=torch.float32, device=table.device)[:n]      # (product, pad) pairs
-    _lib.call("mrec_gather_rows_wide_ex", _ptr(table), V, ld, D, _ptr(flat), flat.element_size(), 1, n, _ptr(row_scale), 1, _ptr(out),
-              1 if out.dtype == torch.bfloat16 else 2, D, int(wide_col), _ptr(wprod), 2, _drop_ref(drop),
-              ids.shape[-1] if drop is not None else 0, 0, _ptr(step_state.buf) if step_state is not None else None, _stream())
+    args = (_ptr(table), V, ld, D, _ptr(flat), flat.element_size(), 1, n, _ptr(row_scale), 1, _ptr(out),
+            1 if out.dtype == torch.bfloat16 else 2, D, int(wide_col), _ptr(wprod), 2, _drop_ref(drop),
+            ids.shape[-1] if drop is not None else 0, 0, _ptr(step_state.buf) if step_state is not None else None)
+    if max_norm is not None:
+        _lib.call("mrec_gather_rows_wide_clip", *args, _max_norm(max_norm), _stream())
+    else:
+        _lib.call("mrec_gather_rows_wide_ex", *args, _stream())
     return out.view(tuple(ids.shape) + (D,)), wprod.view(tuple(ids.shape) + (2,))
 
 
@@ -350,8 +389,10 @@ def segment_sum(plan, g, row_scale=None, grad_scale=1.0):
 
 
 def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_power=0.9,
-                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False):
-    """nn.LazyAdam on a RowTensor gradient (wide_and_deep.py:420-422): in place on p, m, v."""
+                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False, max_norm=None):
+    """nn.LazyAdam on a RowTensor gradient (wide_and_deep.py:420-422): in place on p, m, v.  max_norm=c: the gradients are those
+    of rows the lookup clipped to c (gather_rows(..., max_norm=c) of the same p): each touched row's summed gradient G becomes
+    (c / n)(G - (p.G / n^2) p) where n = |p| > c (mrec_sparse_apply_next_max_norm); D % 4 == 0, D <= 256."""
     _need_cuda(p, m, v, g, row_scale)
     V, D, ld = _table(p)
     for t in (m, v):
@@ -363,9 +404,10 @@ def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, be
     sfx = _suffix(plan.uniq_buf)
     fn = {torch.float32: "mrec_sparse_lazy_adam_f32_", torch.bfloat16: "mrec_sparse_lazy_adam_bf16g_",
           torch.float16: "mrec_sparse_lazy_adam_f16g_"}[g2.dtype]
-    _lib.call(fn + sfx, _ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf),
-              _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr,
-              beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(ws), ws.numel(), _stream())
+    args = (_ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets),
+            plan.n, _ptr(g2), ldg, _ptr(rs), lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(ws),
+            ws.numel(), _stream())
+    _call_clipped(max_norm, fn + sfx, *args)
 
 
 class ApplyFinish(C.Structure):      # mrec_apply_finish_t
@@ -416,12 +458,13 @@ def const_cols_ids(state):
 
 def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                            beta1_power=0.9, beta2_power=0.999, grad_scale=1.0, use_nesterov=False, ftrl_lr=5e-2, l1=1e-8, l2=1e-8,
-                           lr_power=-0.5, step_state=None, defer=False, const_cols=None):
+                           lr_power=-0.5, step_state=None, defer=False, const_cols=None, max_norm=None):
     """LazyAdam on the deep columns and FTRL on the wide record of the same fused rows in ONE pass (wide_and_deep.py:420-430):
     gw [n / F] is the wide branch's gradient per sample (the head's dlogit); position i contributes gw[i // F] * row_scale[i].
     step_state (StepState): the Adam step size comes from device memory (beta powers ignored) and the main kernel stamps its
     begin / end there.  const_cols = (const_cols_detect(ids, V), ids): the batch's constant columns are summed sample by sample
-    by the same launch instead of through the index (a different, fixed order of additions for those rows)."""
+    by the same launch instead of through the index (a different, fixed order of additions for those rows).  max_norm: as
+    sparse_lazy_adam_ for the deep columns (the wide record's FTRL is not clipped; D <= 252); not with const_cols."""
     _need_cuda(p, m, v, g, row_scale, gw)
     V, D, ld = _table(p)
     for t in (m, v):
@@ -446,6 +489,8 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
             ftrl_lr, l1, l2, lr_power, _ptr(ws), ws.numel(), _ptr(step_state.buf) if step_state is not None else None,
             _ptr(getattr(plan, "n_valid_dev", None)))
     keep_cc = None
+    if max_norm is not None and const_cols is not None and const_cols[0] is not None:
+        raise ValueError("max_norm: the hot-column apply has no clip (const_cols=None)")
     if const_cols is not None and const_cols[0] is not None:
         bad, ids = const_cols
         _need_cuda(bad, ids)
@@ -460,9 +505,9 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
         # the tables: run the finish before any of them is reused.
         fin = ApplyFinish()
         fin.keep = (ws, plan, p, g2, rs, gw, keep_cc)
-        _lib.call("mrec_sparse_lazy_adam_wide_defer", *args, C.cast(C.pointer(fin), C.c_void_p), _stream())
+        _call_clipped(max_norm, "mrec_sparse_lazy_adam_wide_defer", *args, C.cast(C.pointer(fin), C.c_void_p), _stream())
         return fin
-    _lib.call("mrec_sparse_lazy_adam_wide", *args, _stream())
+    _call_clipped(max_norm, "mrec_sparse_lazy_adam_wide", *args, _stream())
     return None
 
 

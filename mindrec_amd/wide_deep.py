@@ -25,9 +25,10 @@ data-parallel with one flat all-reduce(mean) (gradients_mean=True,
 train_and_eval_distribute.py:135-138).
 """
 import contextlib
+import math
 import os
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -100,6 +101,12 @@ class WideDeepConfig:
                                    # one-GPU apply instead of through the inverted index (WideDeepEngine._plan; include/mrec.h,
                                    # mrec_const_cols_detect): same products, another fixed order of additions for those rows -- False
                                    # where two engines must agree bit for bit across code paths (hash tables, row shards)
+    max_norm: Optional[float] = None   # HashEmbeddingLookup / nn.EmbeddingLookup(max_norm=c) of the DEEP table (embedding.py:156-161,
+                                       # 202-205): every looked-up row x is clipped to x * (c / |x|) where |x| > c before the mask
+                                       # multiply, in training and in predict(); the sparse apply takes the gradient through the clip
+                                       # (include/mrec.h, mrec_sparse_apply_next_max_norm).  One GPU, sparse, resident tables (dense or
+                                       # dynamic_embedding), emb_dim % 4 == 0 and <= 252.  Hot-column detection is off under it (the
+                                       # hot-column apply has no clip).  The wide table is never clipped.
 
 
 _GRAPH_LEVEL = {"none": 0, "mlp": 1, "front": 2, "step": 3}
@@ -245,6 +252,20 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             raise ValueError(f"graphs must be one of {sorted(_GRAPH_LEVEL)}")
         self._graph_level = _GRAPH_LEVEL[cfg.graphs]      # lowered when a capture is refused
         V, D = cfg.vocab_size, cfg.emb_dim
+        self._max_norm = None
+        if cfg.max_norm is not None:
+            c = float(cfg.max_norm)
+            if not (math.isfinite(c) and c > 0.0):
+                raise ValueError(f"max_norm must be a finite number > 0, got {cfg.max_norm!r}")
+            if self._sharded:
+                raise ValueError("max_norm is not supported with row shards (world > 1)")
+            if cfg.host_cache_rows > 0:
+                raise ValueError("max_norm is not supported with the host cache (host_cache_rows > 0)")
+            if not cfg.sparse:
+                raise ValueError("max_norm is not supported with dense gradients (sparse=False)")
+            if D % 4 or D > 252:
+                raise ValueError(f"max_norm needs emb_dim % 4 == 0 and emb_dim <= 252 (emb_dim={D})")
+            self._max_norm = c
         self.local_rows = (V - rank + world - 1) // world          # rows r with r*world + rank < V
         self.index = None
         self.hb = None
@@ -350,7 +371,8 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
         self._side = torch.cuda.Stream(device=self.device) if self._gpu else None
         import os
         self._fuse_finish = True      # the apply's finishing pass inside the dense Adam launch (see _choose_finish)
-        self._const_cols = bool(getattr(cfg, "const_columns", True)) and os.environ.get("MREC_CONST_COLS", "1") != "0"      # (see _plan)
+        self._const_cols = (bool(getattr(cfg, "const_columns", True)) and os.environ.get("MREC_CONST_COLS", "1") != "0"      # (see _plan)
+                            and self._max_norm is None)
         self._col_bad, self._cc = None, None
         self._hot_seen = False          # the stream's first batches held hot columns (looked at in the eager steps, see _plan)
         # a field's DOMINANT id (not in every sample, but in at least max(MREC_HOT_MIN, B / 8) of them) can take the same path; 0 (the
@@ -406,14 +428,14 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             d0 = self._drop(0, B)                  # Dropout on the first layer's input rides the lookup (train_step only)
             self._emb_dropped = d0 is not None
             emb, wprod = self.k.gather_rows_wide(self.deep, ids, wts, cfg.emb_dim, out=self._emb_out(B * Fd, cfg.emb_dim, self._amp), drop=d0,
-                                                 out_dtype=self._amp, step_state=self._step_state if self._dyn else None)
+                                                 out_dtype=self._amp, step_state=self._step_state if self._dyn else None, **self._clip_kw())
             self._tock(ev)
             return emb.view(B, Fd * cfg.emb_dim), _WideProd(wprod), None
         if self._mfma and torch.is_grad_enabled():
             emb = self.k.gather_rows(self.deep, ids, wts, out=self._emb_out(B * Fd, cfg.emb_dim, self._amp),
-                                     out_dtype=self._amp).view(B, Fd * cfg.emb_dim)
+                                     out_dtype=self._amp, **self._clip_kw()).view(B, Fd * cfg.emb_dim)
         else:
-            emb = self.k.gather_rows(self.deep, ids, wts).view(B, Fd * cfg.emb_dim)
+            emb = self.k.gather_rows(self.deep, ids, wts, **self._clip_kw()).view(B, Fd * cfg.emb_dim)
         self._tock(ev)
         if defer_wide:
             return emb, (lambda: self.k.wide_sum(self.wide, ids, wts, self.wide_b)), None
@@ -421,6 +443,12 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
         wide = self.k.wide_sum(self.wide, ids, wts, self.wide_b)
         self._tock(ev)
         return emb, wide, None
+
+    def _clip_kw(self):
+        """{"max_norm": c} for the deep table's lookup and apply when cfg.max_norm is set, {} otherwise (the calls are then exactly
+        the ones without the clip -- stand-in kernel modules need not know the keyword)."""
+        c = getattr(self, "_max_norm", None)
+        return {} if c is None else {"max_norm": c}
 
     def predict(self, ids, wts):
         if self._sharded:
@@ -968,12 +996,13 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
                                                    lr=cfg.adam_lr, beta1=float(self.beta1), beta2=float(self.beta2), eps=cfg.adam_eps,
                                                    beta1_power=float(self.beta1_power), beta2_power=float(self.beta2_power),
                                                    grad_scale=inv_sens, ftrl_lr=cfg.ftrl_lr, l1=cfg.ftrl_l1, l2=cfg.ftrl_l2,
-                                                   step_state=state, defer=self._fuse_finish, const_cols=getattr(self, "_cc", None))
+                                                   step_state=state, defer=self._fuse_finish, const_cols=getattr(self, "_cc", None),
+                                                   **self._clip_kw())
         else:
             self.k.sparse_lazy_adam_(self.deep, self.deep_m, self.deep_v, plan, g_emb.view(B * Fd, D), wts, lr=cfg.adam_lr,
                                      beta1=float(self.beta1), beta2=float(self.beta2), eps=cfg.adam_eps,
                                      beta1_power=float(self.beta1_power), beta2_power=float(self.beta2_power),
-                                     grad_scale=inv_sens)
+                                     grad_scale=inv_sens, **self._clip_kw())
         self._tock(ev)
         if not wide_done:
             ev = self._tick("apply_wide")
