@@ -4,11 +4,17 @@ same in every sample -- what the reference's Criteo pipeline gives the 13 dense 
 a numpy restatement (ragged cases: a column equal in all but one sample, an id that also occurs in another field, an id outside the
 table), and the apply against the oracle's LazyAdam / FTRL restatements and against the same call without the constant-column path
 (every other row bit-identical; the constant columns' rows equal to rounding: a different fixed order of additions)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _apply_order as A  # noqa: E402
 
 
 def _ids(rng, B, F, V, nconst, dtype):
@@ -98,6 +104,8 @@ def test_apply_with_constant_columns(dev, oracle, defer, idt, gdt, B, nconst, do
         st = torch.from_numpy(st0.copy()).to(dev)
         plan = ops.sparse_plan(tid)
         const = (ops.const_cols_detect(tid, V, min_count=B // 8 if dom else None), tid) if cc else None
+        if cc:
+            found.update(ops.const_cols_ids(const[0]))
         fin = ops.sparse_lazy_adam_wide_(st[:, :D], st[:, D + 4:2 * D + 4], st[:, 2 * D + 4:3 * D + 4], plan, tg, twt, tgw, F, D, defer=defer,
                                          const_cols=const, **kw)
         if defer:
@@ -106,6 +114,7 @@ def test_apply_with_constant_columns(dev, oracle, defer, idt, gdt, B, nconst, do
         torch.cuda.synchronize()
         return st.cpu().numpy()
 
+    found = {}
     a, b = run(True), run(False)
     crows = np.concatenate([np.arange(nconst) + 7, np.arange(dom) + 30]).astype(np.int64)       # the rows that take the new path
     other = np.ones(V, bool)
@@ -126,6 +135,16 @@ def test_apply_with_constant_columns(dev, oracle, defer, idt, gdt, B, nconst, do
         assert close(got[crows, D + 4:2 * D + 4], rm[crows]) and close(got[crows, 2 * D + 4:3 * D + 4], rv[crows])
         assert close(got[crows, D], rw[crows, 0], 1e-4) and close(got[crows, D + 1], rwa[crows, 0]) and close(got[crows, D + 2], rwl[crows, 0], 1e-4)
     assert (a[:, D + 3] == st0[:, D + 3]).all() and (a[:, 3 * D + 4:] == st0[:, 3 * D + 4:]).all()      # pad words untouched
+    # both runs bit for bit what their fixed orders (windows and tree of partials; hot columns in chunks), restated, give
+    idx = A.Index(ids)
+    x, xw = A.contributions(g16, wts.reshape(-1), 1 / 1024), A.contributions(np.repeat(gw, F), wts.reshape(-1), 1 / 1024)
+    hot = found if idt == torch.int32 else None       # (the hot-column kernel exists for 32-bit keys only: apply_cols)
+    for got, h in ((a, hot), (b, None)):
+        G = A.sums(idx, x, D, 4, ops.apply_window(D, True), xw=xw, hot=h, ids2d=ids if h else None)
+        ref = st0.copy()
+        A.lazy_adam(ref[:, :D], ref[:, D + 4:2 * D + 4], ref[:, 2 * D + 4:3 * D + 4], idx.uniq, G, lr=3.5e-4, b1_pow=0.9, b2_pow=0.999)
+        A.wide_ftrl(ref[:, D:D + 4], idx.uniq, G)
+        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
 
 
 def test_apply_without_constant_columns_is_unchanged(dev):

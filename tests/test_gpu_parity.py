@@ -3,11 +3,17 @@
 Bars (BASELINE.json north_star): bit-exact for ids / dedup / index work; fp32 rows within 1e-5
 relative -- and bit-exact where the summation order provably matches the oracle's.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _apply_order as A  # noqa: E402
 
 RTOL = 1e-5
 
@@ -67,6 +73,20 @@ def check_rows(got, ref, rows_exact, rows_close, tol=RTOL):
             err = np.abs(a[rows_close].astype(np.float64) - b[rows_close]).max()
             assert err <= tol * np.abs(b).max(), (err, np.abs(b).max())
     assert len(rows_exact) > 0 or len(rows_close) > 0
+
+
+def restated_sums(ids, g, row_scale, grad_scale, D):
+    """the kernels' fixed tree of window partials restated on the host (tests/_apply_order.py) for a contiguous [V, D] table:
+    (unique ids, their gradient sums G as the apply forms them)"""
+    from mindrec_amd import ops
+    vec = A.lane_width(D, D, D, [0], 0, 4)
+    idx = A.Index(ids)
+    return idx.uniq, A.sums(idx, A.contributions(g, row_scale, grad_scale), D, vec, ops.apply_window(D, vec == 4))
+
+
+def assert_bits(got, ref):
+    for a, b in zip(got, ref):
+        assert np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))
 
 
 def rel_err(a, b):
@@ -188,6 +208,7 @@ def _adam_case(dev, oracle, kind, n, D, V, dtype, use_scale, nesterov=False, ste
     p = (rng.standard_normal((V, D)) * 0.01).astype(np.float32)
     m = np.zeros((V, D), np.float32); v = np.zeros((V, D), np.float32)
     tp, tm, tv = T(p, dev), T(m, dev), T(v, dev)
+    tree = (p.copy(), m.copy(), v.copy())          # the same steps with the kernels' summation tree restated
     b1p, b2p = np.float32(1.0), np.float32(1.0)
     cross_rows = set()
     for step in range(steps):
@@ -197,20 +218,22 @@ def _adam_case(dev, oracle, kind, n, D, V, dtype, use_scale, nesterov=False, ste
         b1p = np.float32(b1p * np.float32(0.9)); b2p = np.float32(b2p * np.float32(0.999))
         oracle.sparse_lazy_adam(p, m, v, ids, g, sc, lr=3.5e-4, eps=1e-8, b1_pow=float(b1p), b2_pow=float(b2p),
                                 grad_scale=1.0 / 1024, nesterov=nesterov)
+        u, G = restated_sums(ids, g, sc, 1.0 / 1024, D)
+        A.lazy_adam(*tree, u, G, lr=3.5e-4, eps=1e-8, b1_pow=float(b1p), b2_pow=float(b2p), nesterov=nesterov)
         plan = ops.sparse_plan(T(ids, dev))
         ops.sparse_lazy_adam_(tp, tm, tv, plan, T(g, dev), T(sc, dev) if use_scale else None, lr=3.5e-4, eps=1e-8,
                               beta1_power=float(b1p), beta2_power=float(b2p), grad_scale=1.0 / 1024,
                               use_nesterov=nesterov)
         cross_rows.update(plan.uniq.cpu().numpy()[crossing(plan, D)].tolist())
     cross_rows = np.array(sorted(r for r in cross_rows if 0 <= r < V), dtype=np.int64)
-    return (tp.cpu().numpy(), tm.cpu().numpy(), tv.cpu().numpy()), (p, m, v), cross_rows
+    return (tp.cpu().numpy(), tm.cpu().numpy(), tv.cpu().numpy()), (p, m, v), cross_rows, tree
 
 
 @pytest.mark.parametrize("D", [80, 16, 128, 1, 30])
 @pytest.mark.parametrize("dtype", [np.int32, np.int64])
 def test_lazy_adam_unique_ids_bitexact(dev, oracle, D, dtype):
     """No duplicate spans a window -> summation order equals the oracle's -> bit-exact."""
-    got, ref, cross = _adam_case(dev, oracle, "uniform", 3000, D, 1_000_000, dtype, use_scale=True)
+    got, ref, cross, _ = _adam_case(dev, oracle, "uniform", 3000, D, 1_000_000, dtype, use_scale=True)
     # 3000 ids over 1 M rows: at most a few duplicate PAIRS, and a + b does not depend on the order
     for a, b in zip(got, ref):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
@@ -219,16 +242,19 @@ def test_lazy_adam_unique_ids_bitexact(dev, oracle, D, dtype):
 @pytest.mark.parametrize("kind", ["dups", "zipf", "hot", "same"])
 @pytest.mark.parametrize("D", [80, 16, 1, 30])
 def test_lazy_adam_duplicates(dev, oracle, kind, D):
-    got, ref, cross = _adam_case(dev, oracle, kind, 20000, D, 50000, np.int32, use_scale=True)
+    got, ref, cross, tree = _adam_case(dev, oracle, kind, 20000, D, 50000, np.int32, use_scale=True)
     # ids whose run stays inside one window: bit-exact.  ids whose run crosses windows are summed as
     # a fixed tree of window partials: rows within 1e-5 relative of the sequential oracle (1e-4 for
-    # the 20000-copies-of-one-id case, where the oracle's own fp32 chain is ~1e-5 from exact).
+    # the 20000-copies-of-one-id case, where the oracle's own fp32 chain is ~1e-5 from exact) ...
     check_rows(got, ref, rows_exact=[0], rows_close=cross, tol=1e-4 if kind == "same" else RTOL)
+    # ... and every row bit for bit what that tree, restated on the host, gives
+    assert_bits(got, tree)
 
 
 def test_lazy_adam_nesterov_and_noscale(dev, oracle):
-    got, ref, cross = _adam_case(dev, oracle, "dups", 5000, 80, 20000, np.int32, use_scale=False, nesterov=True)
+    got, ref, cross, tree = _adam_case(dev, oracle, "dups", 5000, 80, 20000, np.int32, use_scale=False, nesterov=True)
     check_rows(got, ref, rows_exact=[0], rows_close=cross)
+    assert_bits(got, tree)
 
 
 def test_lazy_adam_out_of_range_ids_skipped(dev, oracle):
@@ -253,11 +279,14 @@ def test_sparse_ftrl(dev, oracle, kind, D):
     var = (rng.standard_normal((V, D)) * 0.01).astype(np.float32)
     acc = np.ones((V, D), np.float32); lin = np.zeros((V, D), np.float32)
     tv, ta, tl = T(var, dev), T(acc, dev), T(lin, dev)
+    tree = (var.copy(), acc.copy(), lin.copy())
     cross = set()
     for step in range(3):
         ids = ids_case(kind, n, V, rng, np.int32)
         g = (rng.standard_normal((n, D)) * 1024).astype(np.float32)
         oracle.sparse_ftrl(var, acc, lin, ids, g, None, lr=5e-2, l1=1e-8, l2=1e-8, grad_scale=1.0 / 1024)
+        u, G = restated_sums(ids, g, None, 1.0 / 1024, D)
+        A.ftrl(*tree, u, G, lr=5e-2, l1=1e-8, l2=1e-8)
         plan = ops.sparse_plan(T(ids, dev))
         ops.sparse_ftrl_(tv, ta, tl, plan, T(g, dev), None, lr=5e-2, l1=1e-8, l2=1e-8, grad_scale=1.0 / 1024)
         cross.update(plan.uniq.cpu().numpy()[crossing(plan, D)].tolist())
@@ -266,6 +295,7 @@ def test_sparse_ftrl(dev, oracle, kind, D):
     # FTRL's weight is a ratio of cancelling sums; for ids with thousands of copies per step the
     # sequential fp32 oracle is itself ~1e-4 from exact, so those rows get the looser bound.
     check_rows(got, (var, acc, lin), rows_exact=[0], rows_close=cross, tol=5e-5 if kind == "uniform" else 2e-3)
+    assert_bits(got, tree)
 
 
 def test_ftrl_general_lr_power(dev, oracle):
@@ -303,6 +333,7 @@ def test_segment_sum(dev, oracle, kind, D):
     bound = np.maximum(cnt - 1, 1) * 2.0 ** -23 * absum
     assert (np.abs(out - exact) <= bound).all()
     assert (np.abs(ref - exact) <= bound).all()        # the oracle obeys the same bound
+    assert_bits([out], [restated_sums(ids, g, None, 1.0, D)[1]])     # and every row is the kernels' tree, bit for bit
 
 
 def test_dense_optimizers(dev, oracle):
