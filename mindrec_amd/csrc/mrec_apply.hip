@@ -426,11 +426,14 @@ __device__ __forceinline__ void const_part_body(const ConstCols& cc, unsigned lo
     const long long hid = cc.hid[f];
     const int b0 = chunk * cc.rr, b1 = (b0 + cc.rr < cc.B) ? b0 + cc.rr : cc.B;
     unsigned long long mm = 0ull;                        // bit i: sample b0 + i holds the hot id
+    // (lpr == 64 at D = 252: a 64-bit shift by 64 is undefined, and the hardware's count modulo 64 would leave an empty mask.  The
+    // other two shifts stay below 64: grp * lpr <= lane <= 63 for live and spare lanes alike, r * lpr < rr = 64)
+    const unsigned long long gmask = gm.lpr >= 64 ? ~0ull : (1ull << gm.lpr) - 1ull;
     for (int r = 0; r * gm.lpr < cc.rr; ++r) {
         const int i = r * gm.lpr + sub;
         const bool pred = live && i < cc.rr && b0 + i < b1 && (long long)((const K*)cc.ids0)[(int64_t)(b0 + i) * wa.F + f] == hid;
         const unsigned long long bal = __ballot(pred);    // (every lane of the wave arrives here: no early return above)
-        mm |= ((bal >> (grp * gm.lpr)) & ((1ull << gm.lpr) - 1ull)) << (r * gm.lpr);
+        mm |= ((bal >> (grp * gm.lpr)) & gmask) << (r * gm.lpr);
     }
     if (!live) return;
     const bool wl = sub == gm.lpr - 1;

@@ -182,3 +182,59 @@ def test_standard_layouts_hit_their_targets(aw):
     keys[2::3] += 2 ** 31 + 10
     c = A.census(A.Index(A.layout_ids(s, keys, rng)), 16, 4, aw, V=len(s))
     assert c["oob_crossing"] > 50
+
+
+# the widths the wide-folded path is swept over (tests/test_wide_widths_gpu.py): D -> (lpr, G, NG, floats of the engine's fused row)
+_WIDE_WIDTHS = {4: (2, 32, 128, 32), 12: (4, 16, 64, 64), 60: (16, 4, 16, 192), 84: (22, 2, 8, 256), 124: (32, 2, 8, 384),
+                128: (33, 1, 4, 416), 172: (44, 1, 4, 544), 248: (63, 1, 4, 768), 252: (64, 1, 4, 768)}
+
+
+def test_wide_geometry_of_the_swept_widths():
+    import test_wide_widths_gpu as W
+    assert W.W == list(_WIDE_WIDTHS) and set(W.EDGE) <= set(W.W)
+    for D, (lpr, G, NG, ld) in _WIDE_WIDTHS.items():
+        assert A.col_blocks(D, 4, wide=True) == [(0, D, G, NG)]
+        assert lpr == D // 4 + 1 and G == 64 // lpr and G * lpr <= 64 and NG == 4 * G
+        assert W._fused_ld(D) == ld and ld % 32 == 0 and 0 <= ld - (3 * D + 4) < 32
+        assert NG * (D + 4) <= 1024                      # (const_finish_body's shared rows: NG lane-groups of D + 4 floats)
+
+
+@pytest.mark.parametrize("B,nconst,dom", [(1024, 13, 0), (777, 5, 3), (65, 2, 0)])
+def test_hot_sums_at_252_obey_the_bound_of_their_own_order(B, nconst, dom):
+    """A.sums(..., hot=...) at D = 252 (G = 1, NG = 4) against a plain float64 sum of the same contributions.  The allowed difference
+    comes from the data: depth * 2^-24 * sum |x| per element, depth the additions on the longest path of the restated order (63 inside a
+    chunk of 64 samples, per - 1 over a lane-group's chunks, the lane-groups' sums - 1)."""
+    rng = np.random.default_rng(B + nconst + dom)
+    D, F, V, aw = 252, 39, 5000, 8
+    ids = np.minimum(rng.zipf(1.1, size=(B, F)) + 64, V - 1).astype(np.int32)
+    ids[:, :nconst] = np.arange(nconst, dtype=np.int32)[None, :] + 7
+    for d in range(dom):
+        ids[rng.random(B) < 0.4 + 0.1 * d, 20 + d] = 30 + d
+    hot = {f: f + 7 for f in range(nconst)}
+    hot.update({20 + d: 30 + d for d in range(dom)})
+    n = B * F
+    g = O.round16(rng.standard_normal((n, D)).astype(np.float32), "bf16")
+    rs = (rng.random(n) + 0.25).astype(np.float32)
+    gw = rng.standard_normal(B).astype(np.float32)
+    x, xw = A.contributions(g, rs, 0.37), A.contributions(np.repeat(gw, F), rs, 0.37)
+    idx = A.Index(ids)
+    G = A.sums(idx, x, D, 4, aw, xw=xw, hot=hot, ids2d=ids)
+    Gw = A.sums(idx, x, D, 4, aw, xw=xw)                                     # the same ids through the windows
+    (_, _, _, NG), = A.col_blocks(D, 4, True)
+    nlg = (B + 63) // 64
+    per = (nlg + NG - 1) // NG
+    depth = 63 + (per - 1) + ((nlg + per - 1) // per - 1)
+    xa = np.concatenate([x, xw[:, None]], axis=1).astype(np.float64).reshape(B, F, D + 1)
+    where = {int(k): u for u, k in enumerate(idx.uniq.tolist())}
+    hrows = np.array([where[h] for h in hot.values()])
+    for f, h in hot.items():
+        sel = ids[:, f] == h
+        assert sel.sum() >= B // 8 and not (np.delete(ids, f, axis=1) == h).any()
+        exact, absum = xa[sel, f].sum(axis=0), np.abs(xa[sel, f]).sum(axis=0)
+        err = np.abs(G[where[h]] - exact)
+        assert (err <= depth * 2.0 ** -24 * absum).all(), (f, float((err / absum).max() / 2.0 ** -24), depth)
+        assert np.abs(G[where[h]]).min() > 0
+    other = np.ones(idx.U, bool)
+    other[hrows] = False
+    assert np.array_equal(G[other].view(np.uint32), Gw[other].view(np.uint32))        # only the hot ids' sums take the other order
+    assert not np.array_equal(G[hrows], Gw[hrows])

@@ -199,11 +199,12 @@ def test_segment_sum_bitwise(dev, D, gdt, layout):
 _WKW = dict(lr=3.5e-4, grad_scale=0.37)
 
 
-def _wide_case(dev, rng, ids, F, gdt, V, defer, skip_negative=False, const=None, max_norm=None, p0=None):
-    """one step of sparse_lazy_adam_wide_ on fused [p | w accum linear pad | m | v | pad] rows (ld 256) and its restatement; returns
-    (device rows, restated rows, device dense buffers, restated dense buffers, the index, the hot columns found)"""
+def _wide_case(dev, rng, ids, F, gdt, V, defer, skip_negative=False, const=None, max_norm=None, p0=None, D=80):
+    """one step of sparse_lazy_adam_wide_ on fused [p | w accum linear pad | m | v | pad] rows (the engine's 128-byte padded stride: ld 256
+    at D = 80) and its restatement; returns (device rows, restated rows, device dense buffers, restated dense buffers, the index, the hot
+    columns found)"""
     from mindrec_amd import ops
-    D, ld = 80, 256
+    ld = -(-(3 * D + 4) // 32) * 32
     n = ids.size
     buf = _state(rng, V, ld, "adam")[0]
     if p0 is not None:

@@ -79,10 +79,21 @@ def test_detection_matches_the_restatement(dev, idt):
                                                  (torch.int32, torch.float16, 2000, 18, 3), (torch.int32, torch.float32, 96, 1, 0),
                                                  (torch.int32, torch.bfloat16, 777, 0, 5)])
 def test_apply_with_constant_columns(dev, oracle, defer, idt, gdt, B, nconst, dom):
+    _apply_with_constant_columns(dev, oracle, defer, idt, gdt, B, nconst, dom)
+
+
+@pytest.mark.parametrize("defer", [False, True])
+def test_apply_with_constant_columns_d252(dev, oracle, defer):
+    """the same at D = 252: 63 data lanes + the wide lane fill the wave (the sample mask of const_part_body covers all 64 bits); a
+    batch whose last chunk of 64 samples is partial"""
+    _apply_with_constant_columns(dev, oracle, defer, torch.int32, torch.bfloat16, 515, 13, 0, D=252)
+
+
+def _apply_with_constant_columns(dev, oracle, defer, idt, gdt, B, nconst, dom, D=80):
     from mindrec_amd import ops
     rng = np.random.default_rng(B + nconst)
-    V, D, F = 5000, 80, 39
-    ld = 256
+    V, F = 5000, 39
+    ld = -(-(3 * D + 4) // 32) * 32                                  # (256 at D = 80)
     ids = _ids(rng, B, F, V, nconst, np.int64)
     for d in range(dom):                                              # `dom` more fields with a dominant id (40-90 % of the samples, ids 30 ..)
         ids[rng.random(B) < 0.4 + 0.1 * d, 20 + d] = 30 + d
