@@ -176,6 +176,23 @@ int mrec_gather_rows_wide_clip(const float* table, int64_t V, int64_t ld, int32_
                                int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw, const struct mrec_dropout* drop,
                                int32_t fields, uint32_t flags, void* step_state, float max_norm, void* stream);
 
+/* ---- multi-hot fields: Gather -> Mul(mask) -> ReduceMean / ReduceSum over a bag of L ids per sample ----------------
+ * models/wide_and_deep_multitable/src/wide_and_deep.py:301-346 (six fields over the 20 900 x 64 table `emb64_multi`, ReduceMean over
+ * axis 1) and :377-418 (the wide side, ReduceSum).
+ *   out[b, 0:D] = table[ids[b,0], :] * mask[b,0] + table[ids[b,1], :] * mask[b,1] + ...      (mode 0: sum; slot order, fp32)
+ *               = (that sum) / (float)L                                                      (mode 1: mean, IEEE division)
+ * The mean divides by L, not by the number of unmasked slots: ReduceMean over the bag axis counts every slot.  ids [B, L] contiguous
+ * (id_bytes 4 / 8), mask float [B, L] (nullable: all ones), table rows ld apart, out rows ldo ELEMENTS apart (0: D) -- a column
+ * block of the DenseLayer input where the reference concatenates its pooled fields (:348-352); out_kind 0 = fp32, 1 = bf16,
+ * 2 = IEEE half (rounded once, at the end, to nearest even).  An id outside [0, V) contributes a +0.0 row, multiplied and added
+ * like any other.  Product then add, no fma, ascending slot order: bit-reproducible on the host; L = 1, mode 0 is
+ * mrec_gather_rows.  1 <= L <= MREC_POOL_MAX_BAG (longer: MREC_EUNSUPPORTED); any D (float4 lanes for D % 4 == 0 with 16-byte aligned
+ * rows and output quads, one column per lane otherwise).  Argument errors are reported before any HIP call; no allocation, no
+ * synchronisation: capturable.  One entry with id_bytes / out_kind (the style of mrec_gather_rows_wide) rather than six names. */
+#define MREC_POOL_MAX_BAG 4096
+int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B, int32_t L,
+                     const float* mask, int32_t mode, void* out, int32_t out_kind, int64_t ldo, void* stream);
+
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row
  * stride ldw floats: 1 for a dense column, 4 when it lives in a fused w|accum|linear|pad record). */
@@ -414,6 +431,19 @@ int mrec_sparse_apply_next_const_cols(const void* state, const void* ids, int32_
  * for D % 4 != 0, D > 256, D > 252 with the wide record, or rows that are not 16-byte aligned, before any launch; it disarms
  * either way.  max_norm not finite or <= 0: MREC_EINVAL (nothing is armed). */
 int mrec_sparse_apply_next_max_norm(float max_norm);
+/* The pooled form of the sparse apply: the bprop of the multi-hot pattern above (wide_and_deep_multitable/src/wide_and_deep.py:
+ * 301-346,377-418) gives position i = b * L + l the gradient row dy[b, :] * mask[b, l] (times 1 / L for the mean), so
+ * mrec_sparse_apply_next_pool(L) ARMS the NEXT apply of this host thread (mrec_segment_sum_f32 / _g16,
+ * mrec_sparse_lazy_adam_{f32,bf16g,f16g}_{i32,i64}, mrec_sparse_ftrl_f32_{i32,i64}; the precedent of
+ * mrec_sparse_apply_next_max_norm) to read position i's gradient row from g[i / L]: g is then [ceil(n / L), D], ldg its row
+ * stride; contribution i stays (g[i / L] * row_scale[i]) * grad_scale with row_scale by POSITION (the mask, 1 / L folded in by the
+ * caller or into grad_scale), and the windows, the tree of partials and so the order of additions are those of the plain apply
+ * on the L-fold expanded gradient -- which is never materialised.  Armed for one call, disarmed by that call whether it runs or
+ * refuses; L == 1 is the plain apply (and disarms).  The armed call launches kernels of its own (k_apply_main_pool); not armed, a
+ * call launches what it launched before this existed.  MREC_EUNSUPPORTED before any launch, and disarmed, for the folded wide
+ * forms (mrec_sparse_lazy_adam_wide(_defer)), with constant columns armed (they are disarmed too), with max_norm, and for
+ * n * L >= 2^32 (i / L is a 32-bit multiply-high).  L < 1: MREC_EINVAL, nothing is armed. */
+int mrec_sparse_apply_next_pool(int32_t L);
 int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, const float* g, void* shadow16, int shadow_kind, int64_t n,
                                      int32_t nseg, const float* const* slabs, const int64_t* starts, const int64_t* lens,
                                      const int32_t* splits, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,

@@ -475,7 +475,10 @@ __device__ __forceinline__ void const_part_body(const ConstCols& cc, unsigned lo
 }
 
 // (WIDE: MREC_WPS4 waves per SIMD asked of the register allocator)
-template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false>
+// (POOL: the pooled form, mrec_sparse_apply_next_pool -- position i's gradient row is g[i / L], i / L by multiply-high with pool_magic
+// as the wide lane's gw[i / F]; only that address differs, so the windows, the partial sums and their order are the plain apply's.  A
+// template argument: the instantiations without it are the code they were)
+template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false, bool POOL = false>
 __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
                                                     const int* __restrict__ spos, const int* __restrict__ sseg,
                                                     int n, const GT* __restrict__ g, int64_t ldg,
@@ -483,7 +486,8 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
                                                     float* __restrict__ carry_head, float* __restrict__ carry_tail,
                                                     int* __restrict__ owners, const int* __restrict__ seg_offsets,
                                                     const WideArgs& wa, const unsigned long long cmask = 0ull, const unsigned bid0 = 0u,
-                                                    const int* s_hid = nullptr) {
+                                                    const int* s_hid = nullptr, const unsigned pool_magic = 0u) {
+    static_assert(!POOL || (!WIDE && !HOT), "POOL: the plain windows only");
     constexpr int AW = ACfg<VEC>::AW, AB = ACfg<VEC>::AB, GP = ACfg<VEC>::GP;
     constexpr bool NT = ACfg<VEC>::NT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -639,7 +643,8 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
             const int pos = posw[jb + q];
             gwq[q] = 0.0f;
             if (WIDE) gwq[q] = wa.gw[(wa.F == 1 ? (unsigned)pos : __umulhi((unsigned)pos, wa.magic)) * wa.gws];
-            gload<NT>(gb[q], g + (int64_t)pos * ldg + (WIDE && wl ? 0 : col));       // (the wide lane's own gradient is gwq)
+            const int64_t grow = POOL ? (int64_t)__umulhi((unsigned)pos, pool_magic) : (int64_t)pos;      // (POOL: the bag's row, pos / L)
+            gload<NT>(gb[q], g + grow * ldg + (WIDE && wl ? 0 : col));               // (the wide lane's own gradient is gwq)
             rsv[q] = rscale ? rscale[pos] : 1.0f;
         }
 #pragma unroll
@@ -775,6 +780,20 @@ __global__ __launch_bounds__(256, WIDE ? MREC_WPS4 : 1) void k_apply_main(Upd up
         ss->ends[(unsigned)ss->step % kStampRing][blockIdx.x & 63u] = (unsigned long long)wall_clock64();
 }
 
+// The pooled apply's windows (mrec_sparse_apply_next_pool): apply_main_body with POOL, a kernel of its own so that k_apply_main's
+// instantiations keep their code and their names.  No step state, no stamps: the plain (not folded) entries have neither.
+template <int VEC, class K, class Upd, class GT>
+__global__ __launch_bounds__(256) void k_apply_main_pool(Upd upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
+                                                         const int* __restrict__ spos, const int* __restrict__ sseg,
+                                                         int n, const GT* __restrict__ g, int64_t ldg,
+                                                         const float* __restrict__ rscale, float gscale, ApplyGeom gm,
+                                                         float* __restrict__ carry_head, float* __restrict__ carry_tail,
+                                                         int* __restrict__ owners, const int* __restrict__ seg_offsets,
+                                                         unsigned pool_magic) {
+    const WideArgs wa{};
+    apply_main_body<VEC, K, Upd, GT, false, false, true>(upd, V, ld, uniq, spos, sseg, n, g, ldg, rscale, gscale, gm, carry_head, carry_tail,
+                                                         owners, seg_offsets, wa, 0ull, 0u, nullptr, pool_magic);
+}
 
 // Finishes the runs that cross windows.  Partial 0 is the owner's tail, partials 1..k the heads of the
 // following k windows.
@@ -1104,6 +1123,17 @@ thread_local hipEvent_t t_prof_start = nullptr, t_prof_stop = nullptr;
 thread_local ApplyFinish* t_defer = nullptr;        // set by mrec_sparse_lazy_adam_wide_defer: the finishing pass is handed back, not launched
 thread_local ConstCols t_const = ConstCols{};       // set by mrec_sparse_apply_next_const_cols: the next wide apply takes constant columns out of its windows
 thread_local float t_max_norm = 0.0f;               // set by mrec_sparse_apply_next_max_norm: the next LazyAdam apply clips (0: none)
+thread_local int t_pool = 1;                        // set by mrec_sparse_apply_next_pool: the next apply reads position i's gradient row from g[i / L] (1: plain)
+// (armed for one call: every entry that can be the "next apply" takes it first thing, whether it then runs or refuses)
+inline int take_pool() { const int L = t_pool; t_pool = 1; return L; }
+// The pooled form is refused, before anything else is looked at, for the folded wide apply (its wide lane and its hot columns address
+// gradient rows by position themselves), behind max_norm, and with constant columns armed -- which are disarmed with it.
+inline bool pool_refused(int pool, bool wide, bool clip) {
+    if (pool <= 1) return false;
+    const bool cc_armed = t_const.mask != nullptr;
+    t_const = ConstCols{};
+    return wide || clip || cc_armed;
+}
 
 struct ApplyWs { float* carry_head; float* carry_tail; int* owners; int* n_owners; float* dummy; float* cpart; };
 
@@ -1120,7 +1150,7 @@ template <class K, class Upd, class GT>
 int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, const int* sseg,
                const int* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale, float gscale,
                int Dc, int vec, const ApplyWs& w, hipStream_t st, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr) {
+               const int64_t* nv = nullptr, int pool = 1) {
     ApplyGeom gm;
     gm.D = Dc + (wide ? 4 : 0);
     gm.lpr = Dc / vec + (wide ? 1 : 0);
@@ -1138,6 +1168,22 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
     const unsigned lblocks = (unsigned)mrec_cdiv(nsw, (int64_t)(16 * gm.G < 256 ? 16 * gm.G : 256));      // k_apply_long: 4 windows per lane-group, 4 G lane-groups, 256 at most
     const hipEvent_t ev0 = t_prof_start, ev1 = t_prof_stop;
     t_prof_start = t_prof_stop = nullptr;
+    const unsigned pmagic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(pool > 1 ? pool : 1) + 1);      // pos / L = umulhi(pos, pmagic) while pos * L < 2^32 (apply_impl)
+    // the pooled windows (pool > 1; refused before this for the folded wide forms and max_norm): k_apply_main_pool, else k_apply_main
+#define MREC_APPLY_MAIN(VECN)                                                                                                          \
+    do {                                                                                                                               \
+        bool pooled = false;                                                                                                           \
+        if constexpr (!Upd::kClip) {                                                                                                   \
+            if (pool > 1) {                                                                                                            \
+                k_apply_main_pool<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm, \
+                                                                           w.carry_head, w.carry_tail, w.owners, seg_offsets, pmagic);  \
+                pooled = true;                                                                                                         \
+            }                                                                                                                          \
+        }                                                                                                                              \
+        if (!pooled)                                                                                                                   \
+            k_apply_main<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,      \
+                                                                  w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);          \
+    } while (0)
     if (ev0) MREC_HIP_CHECK(hipEventRecord(ev0, st));
     if (nv && !(vec == 4 && wide)) return MREC_EUNSUPPORTED;
     // constant columns (armed for this call by mrec_sparse_apply_next_const_cols): the batch is B = n / F samples of F fields, ids of
@@ -1186,26 +1232,24 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
         }
       }
     } else if (vec == 4) {
-        k_apply_main<4, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,
-                                                       w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);
+        MREC_APPLY_MAIN(4);
         if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
         k_apply_long<4, K, Upd><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
                                                         w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss);
     } else if constexpr (Upd::kClip) {
         return MREC_EUNSUPPORTED;                  // (max_norm: float4 rows only, refused by apply_impl before any launch)
     } else if (vec == 2) {
-        k_apply_main<2, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,
-                                                       w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);
+        MREC_APPLY_MAIN(2);
         if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
         k_apply_long<2, K, Upd><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
                                                         w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss);
     } else {
-        k_apply_main<1, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,
-                                                       w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);
+        MREC_APPLY_MAIN(1);
         if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
         k_apply_long<1, K, Upd><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
                                                         w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss);
     }
+#undef MREC_APPLY_MAIN
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
@@ -1214,10 +1258,12 @@ template <class K, class Upd, class GT = float>
 int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const int32_t* spos, const int32_t* sseg,
                const int32_t* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale,
                float gscale, void* ws, size_t ws_bytes, void* stream, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr) {
+               const int64_t* nv = nullptr, int pool = 1) {
     hipStream_t st = (hipStream_t)stream;
+    if (pool > 1 && (wide || Upd::kClip)) return MREC_EUNSUPPORTED;      // (refused by the entries already: pool_refused)
     if (n < 0 || D <= 0 || V < 0 || ld < D || ldg < D) return MREC_EINVAL;
     if (n == 0) return MREC_OK;
+    if (pool > 1 && (uint64_t)n * (uint64_t)pool >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;      // pos / L by a 32-bit multiply-high
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!spos || !sseg || !seg_offsets || !g || !ws) return MREC_EINVAL;
     for (int i = 0; i < Upd::NS; ++i) if (!upd.s[i]) return MREC_EINVAL;
@@ -1248,7 +1294,7 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
         const int Dc = (D - c0 < CB) ? D - c0 : CB;
         Upd u2 = upd;
         for (int i = 0; i < Upd::NS; ++i) u2.s[i] = upd.s[i] + c0;
-        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, wide, ss, nv);
+        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, wide, ss, nv, pool);
         if (rc != MREC_OK) return rc;
     }
     return MREC_OK;
@@ -1262,6 +1308,8 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
                    const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr) {
     const float clip = t_max_norm;                 // (armed for this call only)
     t_max_norm = 0.0f;
+    const int pool = take_pool();
+    if (pool_refused(pool, wide != nullptr, clip > 0.0f)) return MREC_EUNSUPPORTED;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdAdam u;
     u.s[0] = p; u.s[1] = m; u.s[2] = v;
@@ -1274,10 +1322,10 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
         static_cast<UpdAdam&>(uc) = u;
         uc.clip = clip;
         return apply_impl<K, UpdAdamClip, GT>(uc, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                              stream, wide, ss, nv);
+                                              stream, wide, ss, nv, pool);
     }
     return apply_impl<K, UpdAdam, GT>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, wide, ss, nv);
+                                  stream, wide, ss, nv, pool);
 }
 
 template <class K>
@@ -1285,12 +1333,14 @@ int ftrl_impl(float* var, float* accum, float* linear, int64_t V, int64_t ld, in
               const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const float* g,
               int64_t ldg, const float* rscale, float lr, float l1, float l2, float lr_power, float gscale, void* ws,
               size_t ws_bytes, void* stream) {
+    const int pool = take_pool();
+    if (pool_refused(pool, false, false)) return MREC_EUNSUPPORTED;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdFtrl u;
     u.s[0] = var; u.s[1] = accum; u.s[2] = linear;
     u.h = FtrlH{lr, l1, l2, lr_power, gscale};
     return apply_impl<K, UpdFtrl>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream);
+                                  stream, nullptr, nullptr, nullptr, pool);
 }
 
 }  // namespace
@@ -1500,6 +1550,13 @@ MREC_API int mrec_sparse_apply_next_max_norm(float max_norm) {
     return MREC_OK;
 }
 
+MREC_API int mrec_sparse_apply_next_pool(int32_t L) {
+    t_pool = 1;
+    if (L < 1) return MREC_EINVAL;
+    t_pool = L;
+    return MREC_OK;
+}
+
 MREC_API int mrec_step_state_init(void* state, float beta1_power, float beta2_power, int64_t step, void* stream) {
     if (!state || step < 0) return MREC_EINVAL;
     k_step_init<<<1, 256, 0, (hipStream_t)stream>>>((StepState*)state, beta1_power, beta2_power, (long long)step);
@@ -1560,9 +1617,11 @@ MREC_API int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sort
                                   int32_t D, float* out, void* ws, size_t ws_bytes, void* stream) {
     UpdStore u;
     u.s[0] = out;
+    const int pool = take_pool();
+    if (pool_refused(pool, false, false)) return MREC_EUNSUPPORTED;
     // rows are group numbers; there are at most n groups
     return apply_impl<int32_t, UpdStore>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, g,
-                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream);
+                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool);
 }
 
 /* ... over 16-bit row gradients (g_kind 1: bf16, 2: IEEE half), widened exactly and summed in fp32: what a rank of a row-sharded
@@ -1572,12 +1631,14 @@ MREC_API int mrec_segment_sum_g16(const int32_t* sorted_pos, const int32_t* sort
                                   int32_t D, float* out, void* ws, size_t ws_bytes, void* stream) {
     UpdStore u;
     u.s[0] = out;
+    const int pool = take_pool();
+    if (pool_refused(pool, false, false)) return MREC_EUNSUPPORTED;
     if (g_kind == 1)
         return apply_impl<int32_t, UpdStore, bf16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const bf16_t*)g,
-                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream);
+                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool);
     if (g_kind == 2)
         return apply_impl<int32_t, UpdStore, f16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const f16_t*)g,
-                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream);
+                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool);
     return MREC_EINVAL;
 }
 
@@ -1650,7 +1711,7 @@ MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V,
                                         float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F,
                                         int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                         size_t ws_bytes, void* step_state, const int64_t* n_valid_dev, void* stream) {
-    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; return MREC_EINVAL; }
+    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; t_pool = 1; return MREC_EINVAL; }
     WideArgs wa;
     wa.gw = gw; wa.F = F; wa.wcol = wide_col; wa.magic = 0; wa.dummy = nullptr; wa.gws = (unsigned)gw_stride;
     wa.h = FtrlH{ftrl_lr, l1, l2, lr_power, grad_scale};
@@ -1678,8 +1739,8 @@ MREC_API int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int6
                                               int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                               size_t ws_bytes, void* step_state, const int64_t* n_valid_dev,
                                               mrec_apply_finish_t* finish_out, void* stream) {
-    if (!finish_out) { t_max_norm = 0.0f; return MREC_EINVAL; }
-    if (D > 252) { t_max_norm = 0.0f; return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
+    if (!finish_out) { t_max_norm = 0.0f; t_pool = 1; return MREC_EINVAL; }
+    if (D > 252) { t_max_norm = 0.0f; t_pool = 1; return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
     ApplyFinish* f = (ApplyFinish*)finish_out;
     f->magic = 0u;
     f->clip = 0.0f;

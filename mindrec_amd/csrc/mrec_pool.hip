@@ -1,0 +1,174 @@
+// mrec_pool.hip -- the multi-hot lookup: a bag of L ids per sample, looked up, multiplied by a mask and reduced over the bag
+// (Gather -> Mul(mask) -> ReduceMean / ReduceSum), for gfx950.
+//
+// Reference call sites: models/wide_and_deep_multitable/src/wide_and_deep.py:301-346 (six fields over the 20 900 x 64 table
+// `emb64_multi`: Gather -> Mul(mask) -> ReduceMean(axis 1)) and :377-418 (the wide side: Gather -> Mul(mask) -> ReduceSum).
+//
+//   out[b, 0:D] = reduce_{l = 0 .. L-1, ascending}  table[ids[b, l], :] * mask[b, l]        (mode 0: sum)
+//               = (that sum) / (float)L                                                     (mode 1: mean)
+//
+// The mean divides by L, NOT by the number of unmasked slots: that is what ReduceMean over axis 1 does in the reference (the mask
+// zeroes a slot's row, it does not take the slot out of the count).  The division is IEEE (correctly rounded).
+// An id outside [0, V) contributes a +0.0 row, multiplied and added like any other (the rule of mrec_gather_rows).  fp32
+// accumulation: slot 0's product starts the sum, every later slot is product then add (no fma: -ffp-contract=off), strictly in
+// ascending slot order; 16-bit outputs are rounded once, at the end.  Every output is therefore bit-reproducible on the host
+// (tests/_pool_ref.py), and L = 1 / mode 0 is mrec_gather_rows bit for bit.
+//
+// ONE entry, mrec_gather_pool, with id_bytes / out_kind arguments (the style of mrec_gather_rows_wide) instead of six names: the
+// six instantiations differ in two template arguments, and a caller that holds a tensor holds its element size.
+//
+// Shape of the kernel: k_gather_rows' (mrec_gather.hip).  lpr = D / 4 lanes per bag on the float4 path (D % 4 == 0, 16-byte
+// aligned rows), G = 64 / lpr bags per wave; a lane-group keeps PB row loads in flight: the PB ids and mask values of a batch of
+// slots, then the PB rows, all requested unconditionally (a slot past the bag's end reads the bag's last id, an id out of range
+// reads row 0, a bag past the end reads the last bag; the values are dropped by selects) and needed in straight-line code, then the
+// adds in slot order.  The one store comes last.  Everything else (D % 4 != 0, misaligned rows or outputs, D == 1: the wide
+// weights) takes the same kernel at one column per lane.  Rows wider than a wave (D > 256 on the float4 path, D > 64 on the scalar
+// one) are walked in column blocks by the same lane-group.
+#include "mrec_common.h"
+#include "mrec_optim.h"
+#include "mrec_dense_adam.h"
+
+namespace {
+
+template <int VEC> struct Vf;
+template <> struct Vf<4> { float4 v; };
+template <> struct Vf<1> { float v; };
+
+__device__ __forceinline__ Vf<4> vload(const float* p, Vf<4>*) { Vf<4> r; r.v = *(const float4*)p; return r; }
+__device__ __forceinline__ Vf<1> vload(const float* p, Vf<1>*) { Vf<1> r; r.v = *p; return r; }
+__device__ __forceinline__ Vf<4> vscale(Vf<4> x, float s) { x.v.x *= s; x.v.y *= s; x.v.z *= s; x.v.w *= s; return x; }
+__device__ __forceinline__ Vf<1> vscale(Vf<1> x, float s) { x.v *= s; return x; }
+__device__ __forceinline__ Vf<4> vadd(Vf<4> a, const Vf<4>& b) {
+    a.v.x = a.v.x + b.v.x; a.v.y = a.v.y + b.v.y; a.v.z = a.v.z + b.v.z; a.v.w = a.v.w + b.v.w;
+    return a;
+}
+__device__ __forceinline__ Vf<1> vadd(Vf<1> a, const Vf<1>& b) { a.v = a.v + b.v; return a; }
+__device__ __forceinline__ Vf<4> vdiv(Vf<4> x, float d) { x.v.x = x.v.x / d; x.v.y = x.v.y / d; x.v.z = x.v.z / d; x.v.w = x.v.w / d; return x; }
+__device__ __forceinline__ Vf<1> vdiv(Vf<1> x, float d) { x.v = x.v / d; return x; }
+// "this value is needed here" (see k_gather_rows, mrec_gather.hip)
+__device__ __forceinline__ void vtouch(Vf<4>& r) { asm volatile("" : "+v"(r.v.x), "+v"(r.v.y), "+v"(r.v.z), "+v"(r.v.w)); }
+__device__ __forceinline__ void vtouch(Vf<1>& r) { asm volatile("" : "+v"(r.v)); }
+__device__ __forceinline__ Vf<4> vzero(Vf<4>*) { Vf<4> r; r.v = make_float4(0.f, 0.f, 0.f, 0.f); return r; }
+__device__ __forceinline__ Vf<1> vzero(Vf<1>*) { Vf<1> r; r.v = 0.f; return r; }
+
+// output rows: fp32, bf16 or IEEE half (round-to-nearest-even, once), as the lookup's (mrec_gather.hip)
+struct bf16o_t { uint16_t v; };
+struct f16o_t { uint16_t v; };
+__device__ __forceinline__ unsigned f2h2(float lo, float hi) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 v = {(_Float16)lo, (_Float16)hi};
+    return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ void vstore(float* p, const Vf<4>& x) { *(float4*)p = x.v; }
+__device__ __forceinline__ void vstore(float* p, const Vf<1>& x) { *p = x.v; }
+__device__ __forceinline__ void vstore(bf16o_t* p, const Vf<4>& x) {
+    uint2 u;
+    u.x = (unsigned)f2bf(x.v.x) | ((unsigned)f2bf(x.v.y) << 16);
+    u.y = (unsigned)f2bf(x.v.z) | ((unsigned)f2bf(x.v.w) << 16);
+    *(uint2*)p = u;
+}
+__device__ __forceinline__ void vstore(bf16o_t* p, const Vf<1>& x) { p->v = f2bf(x.v); }
+__device__ __forceinline__ void vstore(f16o_t* p, const Vf<4>& x) { *(uint2*)p = make_uint2(f2h2(x.v.x, x.v.y), f2h2(x.v.z, x.v.w)); }
+__device__ __forceinline__ void vstore(f16o_t* p, const Vf<1>& x) { p->v = __builtin_bit_cast(uint16_t, (_Float16)x.v); }
+
+struct PoolGeom { int lpr; int G; };      // lanes per bag, bags per wave
+
+// PB: slots in flight per lane-group (2 for bags of one or two slots, 8 for longer ones: 8 float4 rows = 32 registers)
+template <int VEC, int PB, class K, class OT>
+__global__ __launch_bounds__(256) void k_gather_pool(const float* __restrict__ table, int64_t V, int64_t ld, const K* __restrict__ ids,
+                                                     const float* __restrict__ mask, int64_t B, int L, int mode, OT* __restrict__ out,
+                                                     int64_t ldo, int D, PoolGeom gm) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;                                      // spare lanes; this kernel has no barriers
+    const int64_t b = ((int64_t)blockIdx.x * 4 + wave) * gm.G + grp;
+    const int64_t bc = b < B ? b : B - 1;
+    const K* __restrict__ idb = ids + bc * L;
+    const float* __restrict__ mb = mask ? mask + bc * L : nullptr;
+    const int llast = L - 1;
+    const float fl = (float)L;
+    for (int col = sub * VEC; col < D; col += gm.lpr * VEC) {
+        Vf<VEC> acc = vzero((Vf<VEC>*)nullptr);
+        for (int l0 = 0; l0 < L; l0 += PB) {                      // (L is the launch's: every lane-group walks the same batches)
+            int64_t row[PB];
+            float mk[PB];
+            Vf<VEC> x[PB];
+            bool okr[PB];
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                const int lc = l0 + k < L ? l0 + k : llast;
+                row[k] = (int64_t)idb[lc];
+                mk[k] = mb ? mb[lc] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                okr[k] = row[k] >= 0 && row[k] < V;
+                x[k] = vload(table + (okr[k] ? row[k] : 0) * ld + col, (Vf<VEC>*)nullptr);
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                vtouch(x[k]);
+                if (!okr[k]) x[k] = vzero((Vf<VEC>*)nullptr);
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                if (l0 + k < L) {
+                    const Vf<VEC> p = mb ? vscale(x[k], mk[k]) : x[k];
+                    acc = (l0 + k == 0) ? p : vadd(acc, p);       // slot 0 starts the sum (L = 1: the lookup's product, bit for bit)
+                }
+            }
+        }
+        if (mode == 1) acc = vdiv(acc, fl);
+        if (b < B) vstore(out + b * ldo + col, acc);
+    }
+}
+
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+template <class K, class OT>
+int pool_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t B, int32_t L, const float* mask, int32_t mode,
+              OT* out, int64_t ldo, hipStream_t st) {
+    // float4 lanes where the rows, and the 4-element quads of the output rows, are aligned; else one column per lane
+    const uintptr_t oa = sizeof(OT) == 2 ? 7 : 15;
+    const bool vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
+    const int cols = vec ? D / 4 : D;
+    PoolGeom gm;
+    gm.lpr = cols < 64 ? cols : 64;
+    gm.G = 64 / gm.lpr;
+    const unsigned blocks = (unsigned)mrec_cdiv(B, (int64_t)4 * gm.G);
+#define MREC_POOL_LAUNCH(VECN, PBN) \
+    k_gather_pool<VECN, PBN, K, OT><<<blocks, 256, 0, st>>>(table, V, ld, ids, mask, B, (int)L, (int)mode, out, ldo, (int)D, gm)
+    if (vec) {
+        if (L <= 2) MREC_POOL_LAUNCH(4, 2); else MREC_POOL_LAUNCH(4, 8);
+    } else {
+        if (L <= 2) MREC_POOL_LAUNCH(1, 2); else MREC_POOL_LAUNCH(1, 8);
+    }
+#undef MREC_POOL_LAUNCH
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+}  // namespace
+
+MREC_API int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B, int32_t L,
+                              const float* mask, int32_t mode, void* out, int32_t out_kind, int64_t ldo, void* stream) {
+    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || (mode != 0 && mode != 1)) return MREC_EINVAL;
+    if (B < 0 || L < 1 || D <= 0 || V < 0 || ld < D) return MREC_EINVAL;
+    if (ldo == 0) ldo = D;
+    if (ldo < D) return MREC_EINVAL;
+    if (L > MREC_POOL_MAX_BAG || B > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;
+    if (B == 0) return MREC_OK;
+    if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
+    if (!table || !ids || !out) return MREC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+#define MREC_POOL(KT, OT) return pool_impl<KT, OT>(table, V, ld, D, (const KT*)ids, B, L, mask, mode, (OT*)out, ldo, st)
+    if (id_bytes == 4) {
+        if (out_kind == 0) { MREC_POOL(int32_t, float); }
+        if (out_kind == 1) { MREC_POOL(int32_t, bf16o_t); }
+        MREC_POOL(int32_t, f16o_t);
+    }
+    if (out_kind == 0) { MREC_POOL(int64_t, float); }
+    if (out_kind == 1) { MREC_POOL(int64_t, bf16o_t); }
+    MREC_POOL(int64_t, f16o_t);
+#undef MREC_POOL
+}

@@ -1,0 +1,115 @@
+"""MultiHotEmbedding: one embedding table looked up by BAGS of ids -- the multi-hot fields of the reference's multitable Wide&Deep
+(models/wide_and_deep_multitable/src/wide_and_deep.py:301-346: Gather -> Mul(mask) -> ReduceMean(axis 1), six fields over the
+20 900 x 64 table `emb64_multi`; :377-418, the wide side: Gather -> Mul(mask) -> ReduceSum over [V, 1] weights) -- with its sparse
+gradient applied in place.
+
+    emb = MultiHotEmbedding(vocab=20900, dim=64, bag=8, mode="mean", optimizer="lazy_adam")
+    x = emb.lookup(ids, mask)          # ids [B, L] -> [B, dim];  ids [B, F, L] (F fields of the one table) -> [B, F * dim]
+    ...                                # the model's forward and backward produce dy, the gradient of x
+    emb.apply_(dy)                     # one plan of the looked-up ids, one pooled apply
+
+Forward: ops.gather_pool (mrec_gather_pool: no [B * L, dim] intermediate).  Backward: position (b, l) of a bag contributes
+(dy[b] * mask[b, l]) * gs to row ids[b, l], gs = grad_scale for mode "sum" and fp32(grad_scale / L) for "mean" (ReduceMean's bprop
+divides by the bag's length); ops.sparse_plan over the ids and the pooled sparse apply (pool=L: the gradient rows are read as
+dy[i // L], the L-fold expanded gradient is never written).  Optimizers:
+  "lazy_adam"  nn.LazyAdam on the touched rows (ops.sparse_lazy_adam_);
+  "ftrl"       nn.FTRL on the touched rows (ops.sparse_ftrl_): the wide weights, dim = 1, mode "sum";
+  "adam"       dense nn.Adam over the whole table, the reference's choice for this model (wide_and_deep.py:532-535): ops.segment_sum
+               (pool=L) + ops.dense_adam_rows_l2_ with l2_scaled = 0, which gives every row outside the plan a zero gradient -- so an
+               untouched row's m and v decay and the row keeps moving on its momentum, exactly as under the dense optimizer.  32-bit
+               ids only (that entry numbers rows in 32 bits).
+Neither method synchronises with the host, so lookup + apply_ capture into one HIP graph on one stream.  The Adam bias-correction
+powers advance on the host with every apply_: a captured graph holds the powers of the steps it captured (replaying K captured
+steps repeats those K steps; it does not continue the count).  No torch arithmetic on the step."""
+import numpy as np
+import torch
+
+from . import ops
+
+_OPTIMIZERS = ("lazy_adam", "ftrl", "adam")
+
+
+class MultiHotEmbedding:
+    def __init__(self, vocab, dim, bag, mode="mean", optimizer="lazy_adam", device="cuda:0", seed=0, sigma=0.01, lr=None, beta1=0.9,
+                 beta2=0.999, eps=1e-8, use_nesterov=False, l1=1e-8, l2=1e-8, lr_power=-0.5, initial_accum=1.0,
+                 out_dtype=torch.float32):
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
+        if optimizer not in _OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {_OPTIMIZERS}, got {optimizer!r}")
+        if int(vocab) < 1 or int(dim) < 1 or int(bag) < 1:
+            raise ValueError("vocab, dim and bag must be >= 1")
+        self.vocab, self.dim, self.bag = int(vocab), int(dim), int(bag)
+        self.mode, self.optimizer, self.out_dtype = mode, optimizer, out_dtype
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("mindrec_amd ops run on the GPU only (no CPU fallback)")
+        self.lr = float(lr) if lr is not None else (5e-2 if optimizer == "ftrl" else 3.5e-4)
+        self.eps, self.use_nesterov = float(eps), bool(use_nesterov)
+        self.l1, self.l2, self.lr_power = float(l1), float(l2), float(lr_power)
+        self.beta1, self.beta2 = np.float32(beta1), np.float32(beta2)
+        self.beta1_power, self.beta2_power = np.float32(1.0), np.float32(1.0)
+        self.step_count = 0
+        # the table, initialised on the device by seed like the engines' (initializer('normal')), and the optimizer's two state arrays
+        self.table = torch.empty((self.vocab, self.dim), dtype=torch.float32, device=self.device)
+        ops.fill_normal_(self.table, seed=int(seed), sigma=float(sigma))
+        if optimizer == "ftrl":
+            self.accum = torch.full_like(self.table, float(initial_accum))
+            self.linear = torch.zeros_like(self.table)
+            self.state = (self.accum, self.linear)
+        else:
+            self.m = torch.zeros_like(self.table)
+            self.v = torch.zeros_like(self.table)
+            self.state = (self.m, self.v)
+        self._ids = self._mask = None
+
+    def _bags(self, ids):
+        if ids.dim() not in (2, 3) or ids.shape[-1] != self.bag:
+            raise TypeError(f"ids must be [B, {self.bag}] or [B, F, {self.bag}] (bags of {self.bag} ids)")
+        if self.optimizer == "adam" and ids.dtype != torch.int32:
+            raise TypeError("optimizer 'adam' takes int32 ids (the dense row update numbers rows in 32 bits)")
+        return ids.shape[0], (ids.shape[1] if ids.dim() == 3 else 1)
+
+    def lookup(self, ids, mask=None, out=None):
+        """ids [B, L] -> [B, dim]; ids [B, F, L] -> [B, F * dim] (field f in columns f * dim .. (f + 1) * dim - 1, the reference's
+        concat of its pooled fields).  mask: float32 0/1 (or any weight) per id, None = all ones.  out: where the rows go -- for
+        [B, L] ids any [B, dim] column block with unit column stride; for [B, F, L] ids a contiguous [B, F * dim] tensor."""
+        B, F = self._bags(ids)
+        if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
+            raise TypeError("mask must be float32 of the shape of ids")
+        flat = ids.reshape(B * F, self.bag)
+        fmask = mask.reshape(B * F, self.bag) if mask is not None else None
+        if out is None:
+            out = torch.empty((B, F * self.dim), dtype=self.out_dtype, device=self.table.device)
+        elif tuple(out.shape) != (B, F * self.dim) or (F > 1 and not out.is_contiguous()):
+            raise TypeError("out must be [B, F * dim] (contiguous when ids hold more than one field)")
+        ops.gather_pool(self.table, flat, fmask, mode=self.mode, out=out if F == 1 else out.view(B * F, self.dim))
+        self._ids = flat.contiguous()
+        self._mask = fmask.contiguous() if fmask is not None else None
+        return out
+
+    def apply_(self, dy, grad_scale=1.0):
+        """The optimizer step for the gradient dy [B, F * dim] of the last lookup's result (float32; bfloat16 / float16 too under
+        'lazy_adam' and 'adam'): in place on the table and the optimizer state."""
+        if self._ids is None:
+            raise RuntimeError("apply_ follows a lookup")
+        ids, mask, L = self._ids, self._mask, self.bag
+        if dy.dim() != 2 or dy.shape[0] * dy.shape[1] != ids.shape[0] * self.dim or not dy.is_contiguous():
+            raise TypeError("dy must be the contiguous [B, F * dim] gradient of the last lookup's result")
+        g = dy.view(ids.shape[0], self.dim)
+        gs = float(np.float32(grad_scale) / np.float32(L)) if self.mode == "mean" else float(grad_scale)
+        plan = ops.sparse_plan(ids)
+        self.beta1_power = np.float32(self.beta1_power * self.beta1)
+        self.beta2_power = np.float32(self.beta2_power * self.beta2)
+        self.step_count += 1
+        akw = dict(lr=self.lr, beta1=float(self.beta1), beta2=float(self.beta2), eps=self.eps, beta1_power=float(self.beta1_power),
+                   beta2_power=float(self.beta2_power), use_nesterov=self.use_nesterov)
+        if self.optimizer == "lazy_adam":
+            ops.sparse_lazy_adam_(self.table, self.m, self.v, plan, g, mask, grad_scale=gs, pool=L, **akw)
+        elif self.optimizer == "ftrl":
+            ops.sparse_ftrl_(self.table, self.accum, self.linear, plan, g, mask, lr=self.lr, l1=self.l1, l2=self.l2,
+                             lr_power=self.lr_power, grad_scale=gs, pool=L)
+        else:
+            sums = ops.segment_sum(plan, g, mask, grad_scale=gs, pool=L)
+            ops.dense_adam_rows_l2_(self.table, self.m, self.v, plan, sums, 0.0, grad_scale=1.0, **akw)
+        return plan

@@ -178,19 +178,35 @@ def _max_norm(max_norm):
     return c
 
 
-def _call_clipped(max_norm, name, *args):
-    """_lib.call(name, *args) -- a LazyAdam apply -- armed with max_norm (mrec_sparse_apply_next_max_norm: the NEXT apply of this host
-    thread clips).  Everything is evaluated before the arm, and an exception between the arm and the apply (ctypes refusing an
-    argument) disarms again, so that no later apply of another table is clipped by mistake."""
-    if max_norm is None:
+def _pool(pool):
+    """pool=L as the C entry point takes it: an integer bag length >= 1 (None: the plain apply)."""
+    L = int(pool)
+    if L != pool or L < 1 or L >= 2 ** 31:
+        raise ValueError(f"pool must be an integer bag length >= 1, got {pool!r}")
+    return L
+
+
+def _call_clipped(max_norm, name, *args, pool=None):
+    """_lib.call(name, *args) -- a sparse apply -- armed with max_norm (mrec_sparse_apply_next_max_norm: the NEXT LazyAdam apply of this
+    host thread clips) and / or pool=L (mrec_sparse_apply_next_pool: the NEXT apply reads position i's gradient row from g[i // L]).
+    Everything is evaluated before the arm, and an exception between the arm and the apply (ctypes refusing an argument) disarms
+    again, so that no later apply of another table is clipped or pooled by mistake."""
+    if max_norm is None and pool is None:
         _lib.call(name, *args)
         return
-    c = _max_norm(max_norm)
-    _lib.call("mrec_sparse_apply_next_max_norm", c)
+    c = None if max_norm is None else _max_norm(max_norm)
+    L = None if pool is None else _pool(pool)
     try:
+        if c is not None:
+            _lib.call("mrec_sparse_apply_next_max_norm", c)
+        if L is not None:
+            _lib.call("mrec_sparse_apply_next_pool", L)
         _lib.call(name, *args)
     except BaseException:
-        _lib.lib().mrec_sparse_apply_next_max_norm(0.0)      # (EINVAL: leaves nothing armed; the C side disarms on its own refusals)
+        if c is not None:
+            _lib.lib().mrec_sparse_apply_next_max_norm(0.0)      # (EINVAL: leaves nothing armed; the C side disarms on its own refusals)
+        if L is not None:
+            _lib.lib().mrec_sparse_apply_next_pool(1)            # (1: the plain apply)
         raise
 
 
@@ -221,6 +237,44 @@ def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32, m
         return out.view(tuple(ids.shape) + (D,))
     _lib.call(fn + sfx, _ptr(table), V, ld, D, _ptr(flat), n, _ptr(row_scale), _ptr(out), _stream())
     return out.view(tuple(ids.shape) + (D,))
+
+
+_OUT_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+def gather_pool(table, ids, mask=None, mode="mean", out=None, out_dtype=torch.float32):
+    """The multi-hot lookup, Gather -> Mul(mask) -> ReduceMean / ReduceSum over the bag axis in one pass
+    (wide_and_deep_multitable/src/wide_and_deep.py:301-346,377-418): ids [..., L] -> [..., D], out[b] = sum_l table[ids[b, l]] *
+    mask[b, l] in slot order (fp32), divided by L for mode="mean" -- by the bag's length, not by its number of unmasked slots, as
+    ReduceMean does.  mask: float32, one value per id (None: all ones).  out: a [B, D] tensor or column block (unit column stride;
+    its other columns are left alone) in float32 / bfloat16 / float16; 16-bit outputs are rounded once, at the end."""
+    _need_cuda(table, ids, mask, out)
+    V, D, ld = _table(table)
+    sfx = _suffix(ids)
+    if ids.dim() < 1:
+        raise TypeError("ids must be [..., L]: a bag of L ids per sample")
+    if mode not in ("sum", "mean"):
+        raise ValueError(f"gather_pool mode must be 'sum' or 'mean', got {mode!r}")
+    L = ids.shape[-1]
+    flat = ids.reshape(-1, L).contiguous()
+    B = flat.shape[0]
+    if mask is not None:
+        if mask.dtype != torch.float32 or mask.numel() != flat.numel():
+            raise TypeError("mask must be float32 with one value per id")
+        mask = mask.reshape(B, L).contiguous()
+    if out is None:
+        if out_dtype not in _OUT_KIND:
+            raise TypeError("gather_pool out_dtype must be float32, bfloat16 or float16")
+        out = torch.empty((B, D), dtype=out_dtype, device=table.device)
+        ret = out.view(tuple(ids.shape[:-1]) + (D,))
+    else:
+        if out.dtype not in _OUT_KIND or out.dim() != 2 or tuple(out.shape) != (B, D) or out.stride(1) != 1:
+            raise TypeError("gather_pool out must be a [B, D] float32 / bfloat16 / float16 tensor with unit column stride")
+        ret = out
+    ldo = out.stride(0) if B > 1 else D
+    _lib.call("mrec_gather_pool", _ptr(table), V, ld, D, _ptr(flat), 4 if sfx == "i32" else 8, B, L, _ptr(mask),
+              1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
+    return ret
 
 
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
@@ -342,13 +396,17 @@ def wide_sum(w, ids, wts, bias=None):
     return out
 
 
-def _grads(plan, g, D, allow_bf16=False):
+def _grads(plan, g, D, allow_bf16=False, pool=None):
+    """the gradient rows and their stride: one row per position, or (pool=L) one per bag of L positions, ceil(n / L) of them"""
     if g.dtype != torch.float32 and not (allow_bf16 and g.dtype in (torch.bfloat16, torch.float16)):
         raise TypeError("row gradients must be float32" + (", bfloat16 or float16" if allow_bf16 else ""))
-    g2 = g.reshape(plan.n, D)
+    rows = plan.n if pool is None else -(-plan.n // _pool(pool))
+    if pool is not None and g.numel() != rows * D:
+        raise TypeError(f"pool={pool}: g must hold ceil(n / pool) = {rows} gradient rows of {D} columns")
+    g2 = g.reshape(rows, D)
     if g2.stride(1) != 1:
         g2 = g2.contiguous()
-    return g2, (g2.stride(0) if plan.n > 1 else D)
+    return g2, (g2.stride(0) if rows > 1 else D)
 
 
 def _row_scale(plan, row_scale):
@@ -370,35 +428,39 @@ def apply_window(D, aligned=True):
     return int(_lib.lib().mrec_sparse_apply_window(D, int(aligned)))
 
 
-def segment_sum(plan, g, row_scale=None, grad_scale=1.0):
+def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None):
     """ops.UnsortedSegmentSum over the plan's groups: returns an [n, D] buffer whose first U rows
-    are the per-unique-id sums (rows >= U are unspecified)."""
+    are the per-unique-id sums (rows >= U are unspecified).  pool=L: the plan's positions are bags of L (gather_pool's ids), g is
+    [ceil(n / L), D] and position i's gradient row is g[i // L] (row_scale stays per position: the mask)."""
     _need_cuda(g, row_scale)
     D = g.shape[-1]
-    g2, ldg = _grads(plan, g, D, allow_bf16=True)
+    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool)
     rs = _row_scale(plan, row_scale)
     out = torch.empty((max(plan.n, 1), D), dtype=torch.float32, device=g.device)
     ws = _apply_ws(plan, D, g.device)
     if g2.dtype == torch.float32:
-        _lib.call("mrec_segment_sum_f32", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                  _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream())
+        _call_clipped(None, "mrec_segment_sum_f32", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
+                      _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(), pool=pool)
     else:       # 16-bit row gradients (what the mixed-precision MLP backward produces): widened exactly, summed in fp32
-        _lib.call("mrec_segment_sum_g16", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                  _ptr(g2), 1 if g2.dtype == torch.bfloat16 else 2, ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream())
+        _call_clipped(None, "mrec_segment_sum_g16", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
+                      _ptr(g2), 1 if g2.dtype == torch.bfloat16 else 2, ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(),
+                      pool=pool)
     return out
 
 
 def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_power=0.9,
-                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False, max_norm=None):
+                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False, max_norm=None, pool=None):
     """nn.LazyAdam on a RowTensor gradient (wide_and_deep.py:420-422): in place on p, m, v.  max_norm=c: the gradients are those
     of rows the lookup clipped to c (gather_rows(..., max_norm=c) of the same p): each touched row's summed gradient G becomes
-    (c / n)(G - (p.G / n^2) p) where n = |p| > c (mrec_sparse_apply_next_max_norm); D % 4 == 0, D <= 256."""
+    (c / n)(G - (p.G / n^2) p) where n = |p| > c (mrec_sparse_apply_next_max_norm); D % 4 == 0, D <= 256.  pool=L: the bprop of
+    gather_pool -- g is [ceil(n / L), D], one row per bag, and position i's gradient row is g[i // L] (segment_sum); not with
+    max_norm."""
     _need_cuda(p, m, v, g, row_scale)
     V, D, ld = _table(p)
     for t in (m, v):
         if _table(t) != (V, D, ld):
             raise ValueError("p, m, v must share shape and row stride")
-    g2, ldg = _grads(plan, g, D, allow_bf16=True)
+    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, p.device)
     sfx = _suffix(plan.uniq_buf)
@@ -407,7 +469,7 @@ def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, be
     args = (_ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets),
             plan.n, _ptr(g2), ldg, _ptr(rs), lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(ws),
             ws.numel(), _stream())
-    _call_clipped(max_norm, fn + sfx, *args)
+    _call_clipped(max_norm, fn + sfx, *args, pool=pool)
 
 
 class ApplyFinish(C.Structure):      # mrec_apply_finish_t
@@ -511,20 +573,20 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
     return None
 
 
-def sparse_ftrl_(var, accum, linear, plan, g, row_scale=None, lr=5e-2, l1=1e-8, l2=1e-8, lr_power=-0.5, grad_scale=1.0):
-    """nn.FTRL sparse apply (wide_and_deep.py:423-430): in place on var, accum, linear."""
+def sparse_ftrl_(var, accum, linear, plan, g, row_scale=None, lr=5e-2, l1=1e-8, l2=1e-8, lr_power=-0.5, grad_scale=1.0, pool=None):
+    """nn.FTRL sparse apply (wide_and_deep.py:423-430): in place on var, accum, linear.  pool=L: as sparse_lazy_adam_."""
     _need_cuda(var, accum, linear, g, row_scale)
     V, D, ld = _table(var)
     for t in (accum, linear):
         if _table(t) != (V, D, ld):
             raise ValueError("var, accum, linear must share shape and row stride")
-    g2, ldg = _grads(plan, g, D)
+    g2, ldg = _grads(plan, g, D, pool=pool)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, var.device)
     sfx = _suffix(plan.uniq_buf)
-    _lib.call(f"mrec_sparse_ftrl_f32_{sfx}", _ptr(var), _ptr(accum), _ptr(linear), V, ld, D, _ptr(plan.uniq_buf),
-              _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, l1,
-              l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _stream())
+    _call_clipped(None, f"mrec_sparse_ftrl_f32_{sfx}", _ptr(var), _ptr(accum), _ptr(linear), V, ld, D, _ptr(plan.uniq_buf),
+                  _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, l1,
+                  l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _stream(), pool=pool)
 
 
 def _flat_same(*ts):

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""The multi-hot path against the composition it replaces, kernel time by kernel time ("multi-hot fields").
+
+  rocprofv3 --kernel-trace --output-format csv -d OUT -- python tools/pool_bench.py run SHAPE > OUT/labels.json
+  python tools/pool_bench.py reduce OUT/labels.json <the run's *_kernel_trace.csv>
+
+`run` issues, five times each and in rotation, the four variants at one shape, every repeat behind a marker launch (a one-row
+k_fill_normal), and prints the order of the repeats; `reduce` cuts the trace's dispatches (in start order) at the markers and adds
+up the kernel times of every repeat.  Nothing is timed on the host.
+  fwd_pool   ops.gather_pool (mean)                                       -- one kernel
+  fwd_comp   the composition available without it: ops.gather_rows into [B*F*L, D] with the mask as row_scale, torch sum over the
+             bag axis, torch divide by L
+  bwd_pool   ops.sparse_lazy_adam_(pool=L) on dy [B*F, D]
+  bwd_comp   dy expanded to [B*F*L, D] (torch repeat_interleave) + the plain ops.sparse_lazy_adam_
+The plan of the ids is built once, outside the repeats: both backward variants take the same one.
+SHAPE: "ref" = V 20 900, D 64, B 131 072, F 6, L 8, Zipf-like ids (the reference's multi-hot table; L stands in for its
+dataset's bag lengths); "large" = V 20 000 000, D 64, B*F 786 432 bags, L 8, uniform ids (rows do not sit in cache)."""
+import csv
+import json
+import os
+import sys
+from statistics import median
+
+REPEATS = 5
+VARIANTS = ("fwd_comp", "fwd_pool", "bwd_comp", "bwd_pool")
+
+
+def run(shape):
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from mindrec_amd import ops
+    dev = torch.device("cuda:0")
+    D, L, bags = 64, 8, 131072 * 6
+    V = 20900 if shape == "ref" else 20_000_000
+    rng = np.random.default_rng(7)
+    if shape == "ref":
+        ids = np.minimum(rng.zipf(1.2, size=(bags, L)) - 1, V - 1).astype(np.int32)
+    else:
+        ids = rng.integers(0, V, size=(bags, L)).astype(np.int32)
+    tid = torch.from_numpy(ids).to(dev)
+    mask = torch.from_numpy((rng.random((bags, L)) < 0.7).astype(np.float32)).to(dev)
+    table = torch.empty((V, D), dtype=torch.float32, device=dev)
+    ops.fill_normal_(table, seed=1, sigma=0.01)
+    m, v = torch.zeros_like(table), torch.zeros_like(table)
+    dy = torch.from_numpy(rng.standard_normal((bags, D)).astype(np.float32)).to(dev)
+    plan = ops.sparse_plan(tid)
+    marker = torch.empty((1, 4), dtype=torch.float32, device=dev)
+    rows = torch.empty((bags * L, D), dtype=torch.float32, device=dev)
+    pooled = torch.empty((bags, D), dtype=torch.float32, device=dev)
+    kw = dict(beta1_power=0.9, beta2_power=0.999, grad_scale=1.0 / L)
+
+    def variant(name):
+        if name == "fwd_pool":
+            ops.gather_pool(table, tid, mask, mode="mean", out=pooled)
+        elif name == "fwd_comp":
+            ops.gather_rows(table, tid, mask, out=rows)
+            torch.sum(rows.view(bags, L, D), dim=1, out=pooled)
+            pooled.div_(float(L))
+        elif name == "bwd_pool":
+            ops.sparse_lazy_adam_(table, m, v, plan, dy, mask, pool=L, **kw)
+        else:
+            big = dy.repeat_interleave(L, 0)
+            ops.sparse_lazy_adam_(table, m, v, plan, big, mask, **kw)
+
+    for name in VARIANTS:                      # warm-up: code objects, workspaces, the allocator
+        variant(name)
+    torch.cuda.synchronize()
+    order = []
+    for r in range(REPEATS):
+        for q in range(len(VARIANTS)):
+            name = VARIANTS[(r + q) % len(VARIANTS)]
+            ops.fill_normal_(marker, seed=r, sigma=1.0)
+            variant(name)
+            order.append(name)
+    ops.fill_normal_(marker, seed=99, sigma=1.0)
+    torch.cuda.synchronize()
+    need_fwd = bags * L * D * 4 + bags * D * 4 + bags * L * 8          # rows read, pooled rows written, ids + mask read
+    print(json.dumps(dict(shape=shape, V=V, D=D, L=L, bags=bags, warmup_markers=0, order=order, fwd_bytes_needed=need_fwd)))
+
+
+def reduce(labels_path, trace_path):
+    lab = json.load(open(labels_path))
+    rows = list(csv.DictReader(open(trace_path)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    marks = [i for i, r in enumerate(rows) if "k_fill_normal" in r["Kernel_Name"]]
+    order = lab["order"]
+    marks = marks[-(len(order) + 1):]         # (the table's own initialisation is the first k_fill_normal of the run)
+    assert len(marks) == len(order) + 1, (len(marks), len(order))
+    per = {k: [] for k in VARIANTS}
+    kernels = {k: {} for k in VARIANTS}
+    for j, name in enumerate(order):
+        seg = rows[marks[j] + 1: marks[j + 1]]
+        per[name].append(sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in seg) / 1e3)
+        for r in seg:
+            k = r["Kernel_Name"].replace("(anonymous namespace)::", "")[:90]
+            kernels[name].setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    print(f"shape {lab['shape']}: V={lab['V']} D={lab['D']} L={lab['L']} bags={lab['bags']}; sum of kernel times per repeat, us")
+    for name in VARIANTS:
+        x = per[name]
+        print(f"  {name:9s} median {median(x):9.1f}  min {min(x):9.1f}  max {max(x):9.1f}  spread {100 * (max(x) - min(x)) / median(x):5.1f} %  ({', '.join(f'{t:.1f}' for t in x)})")
+        for k, ts in kernels[name].items():
+            print(f"      {median(ts):9.1f} us x {len(ts) // len(x)}  {k}")
+    fp, fc, bp, bc = (median(per[k]) for k in ("fwd_pool", "fwd_comp", "bwd_pool", "bwd_comp"))
+    print(f"  forward  pooled / composition = {fp / fc:.3f};  needed bytes {lab['fwd_bytes_needed'] / 1e6:.1f} MB -> {lab['fwd_bytes_needed'] / fp / 1e6:.3f} TB/s "
+          f"= {100 * lab['fwd_bytes_needed'] / fp / 1e6 / 8.0:.1f} % of 8 TB/s")
+    print(f"  backward pooled / composition = {bp / bc:.3f}")
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 3 and sys.argv[1] == "run":
+        run(sys.argv[2])
+    elif len(sys.argv) == 4 and sys.argv[1] == "reduce":
+        reduce(sys.argv[2], sys.argv[3])
+    else:
+        sys.exit(__doc__)
