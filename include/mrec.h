@@ -192,6 +192,20 @@ int mrec_gather_rows_wide_clip(const float* table, int64_t V, int64_t ld, int32_
 #define MREC_POOL_MAX_BAG 4096
 int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B, int32_t L,
                      const float* mask, int32_t mode, void* out, int32_t out_kind, int64_t ldo, void* stream);
+/* The FIELDS form: F bags of UNEQUAL lengths L_0 .. L_{F-1} per sample over one table (every multi-hot field of the reference has a
+ * bag length of its own: src/datasets.py:290-313, input_shape_dict), laid out back to back.  ids [B, Ls] contiguous, Ls = sum L_f,
+ * field f in slots off_f .. off_f + L_f - 1 (off_f = L_0 + .. + L_{f-1}); mask [B, Ls] or null; field_len: HOST int32[F], read
+ * during the call only.  Field f of sample b is pooled into out[b * ldo + f * D .. + D) (the reference's Concat, :348-349):
+ * out rows ldo ELEMENTS apart (0: F * D; ldo >= F * D).  Per bag the arithmetic is mrec_gather_pool's exactly -- product then add,
+ * no fma, ascending slot order, slot 0 starts the sum, an id outside [0, V) contributes a +0.0 row, 16-bit outputs rounded once --
+ * and mode 1 divides ONCE by (float)L_f, the FIELD's own length.  ONE launch, whose work item is a (sample, field) bag; the
+ * per-field offsets and lengths travel by value in the kernel's arguments: no device allocation, no copy, no synchronisation --
+ * capturable like mrec_gather_pool.  Limits: 1 <= F <= MREC_POOL_MAX_FIELDS and Ls <= MREC_POOL_MAX_BAG (beyond: MREC_EUNSUPPORTED),
+ * every L_f >= 1 (else MREC_EINVAL), B * F < 2^31 (beyond: MREC_EUNSUPPORTED).  Argument errors are reported before any HIP call. */
+#define MREC_POOL_MAX_FIELDS 64
+int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
+                            int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
+                            int64_t ldo, void* stream);
 
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row
@@ -444,6 +458,25 @@ int mrec_sparse_apply_next_max_norm(float max_norm);
  * forms (mrec_sparse_lazy_adam_wide(_defer)), with constant columns armed (they are disarmed too), with max_norm, and for
  * n * L >= 2^32 (i / L is a 32-bit multiply-high).  L < 1: MREC_EINVAL, nothing is armed. */
 int mrec_sparse_apply_next_pool(int32_t L);
+/* The FIELDS form of the pooled apply: the bprop of mrec_gather_pool_fields.  The plan's n positions are samples of Ls = sum L_f ids,
+ * F bags back to back; g is the [B, F * D] gradient of the lookup's result viewed as [B * F, D] (ldg its row stride, n a multiple
+ * of Ls: ceil(n / Ls) * F rows are addressed).  mrec_sparse_apply_next_pool_fields(F, field_len, field_scale) ARMS the NEXT apply of
+ * this host thread -- the entries mrec_sparse_apply_next_pool arms -- so that position i, with b = i / Ls, s = i - b * Ls and f the
+ * field whose slots hold s, contributes
+ *     x_i = fp32( fp32( g[b * F + f] * row_scale[i] ) * field_scale[f] )
+ * field_scale[f] (HOST float[F], like field_len read during the arming call only) takes the place of the call's scalar grad_scale in
+ * the product: grad_scale / L_f for the mean (ReduceMean's bprop divides by the FIELD's length), grad_scale for the sum.  The armed
+ * call's own grad_scale must be 1.0f: anything else returns MREC_EINVAL (and disarms) -- there is one scale per contribution, and
+ * it is the field's.  Windows, the tree of partial sums and the order of additions are the plain apply's; ids shared by several
+ * fields are summed over all of them and updated ONCE, as the reference's optimizer does with the summed gradient.  The
+ * slot-to-field map is a linear search over the F prefix offsets, held with the scales in the kernel's arguments: no device
+ * table, no allocation, no synchronisation.  i / Ls is a 32-bit multiply-high: n * Ls >= 2^32 is MREC_EUNSUPPORTED.  Armed for one
+ * call, disarmed by that call whether it runs or refuses; arming replaces an armed mrec_sparse_apply_next_pool and vice versa.
+ * The armed call launches kernels of its own (k_apply_main_fields); a call that is not armed, or armed with _next_pool, launches what
+ * it launched before this existed.  MREC_EUNSUPPORTED before any launch, and disarmed, for the folded wide forms, with constant
+ * columns armed (disarmed too) and with max_norm.  Arming errors leave nothing armed: F < 1, a null array, an L_f < 1 or a
+ * field_scale that is not finite: MREC_EINVAL; F > MREC_POOL_MAX_FIELDS or Ls > MREC_POOL_MAX_BAG: MREC_EUNSUPPORTED. */
+int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_len, const float* field_scale);
 int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, const float* g, void* shadow16, int shadow_kind, int64_t n,
                                      int32_t nseg, const float* const* slabs, const int64_t* starts, const int64_t* lens,
                                      const int32_t* splits, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,

@@ -378,6 +378,12 @@ struct ApplyGeom { int lpr; int G; int D; };
 // (the wide lane pointed at dummy lines for m / v: two more line requests per load and store).
 struct WideArgs { const float* gw; int F; int wcol; FtrlH h; unsigned magic; float* dummy; unsigned gws; };
 
+// The fields form of the pooled apply (mrec_sparse_apply_next_pool_fields): a sample is Ls = sum L_f positions, F bags back to back.
+// Position i -> b = i / Ls (multiply-high with `magic`, exact while i * Ls < 2^32: apply_impl), s = i - b * Ls, f = the last field whose
+// prefix offset off[f] <= s (a linear search: F wave-uniform compares on values the kernel's arguments hold); the gradient row is
+// g[b * F + f] and the second factor of the contribution is scale[f] in place of the call's grad_scale.
+struct FieldArgs { unsigned magic; int Ls; int F; int pad; unsigned short off[MREC_POOL_MAX_FIELDS]; float scale[MREC_POOL_MAX_FIELDS]; };
+
 // uniq == nullptr means "row = group number" (segment-sum into a dense [U, D] output).
 template <class K>
 __device__ __forceinline__ int64_t seg_row(const K* uniq, int seg) {
@@ -478,7 +484,9 @@ __device__ __forceinline__ void const_part_body(const ConstCols& cc, unsigned lo
 // (POOL: the pooled form, mrec_sparse_apply_next_pool -- position i's gradient row is g[i / L], i / L by multiply-high with pool_magic
 // as the wide lane's gw[i / F]; only that address differs, so the windows, the partial sums and their order are the plain apply's.  A
 // template argument: the instantiations without it are the code they were)
-template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false, bool POOL = false>
+// (FIELDS: the fields form, mrec_sparse_apply_next_pool_fields -- the gradient row is g[b * F + f] and the scale the field's, see
+// FieldArgs; again only where a position's row and scale come from differs, and again a template argument)
+template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false, bool POOL = false, bool FIELDS = false>
 __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
                                                     const int* __restrict__ spos, const int* __restrict__ sseg,
                                                     int n, const GT* __restrict__ g, int64_t ldg,
@@ -486,8 +494,10 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
                                                     float* __restrict__ carry_head, float* __restrict__ carry_tail,
                                                     int* __restrict__ owners, const int* __restrict__ seg_offsets,
                                                     const WideArgs& wa, const unsigned long long cmask = 0ull, const unsigned bid0 = 0u,
-                                                    const int* s_hid = nullptr, const unsigned pool_magic = 0u) {
+                                                    const int* s_hid = nullptr, const unsigned pool_magic = 0u,
+                                                    const FieldArgs* fa = nullptr) {
     static_assert(!POOL || (!WIDE && !HOT), "POOL: the plain windows only");
+    static_assert(!FIELDS || (!WIDE && !HOT && !POOL), "FIELDS: the plain windows only");
     constexpr int AW = ACfg<VEC>::AW, AB = ACfg<VEC>::AB, GP = ACfg<VEC>::GP;
     constexpr bool NT = ACfg<VEC>::NT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -638,12 +648,26 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
         if (s + jb >= e_end2) break;
         GBits<VEC, GT> gb[GP];
         float rsv[GP], gwq[GP];
+        float gsq[FIELDS ? GP : 1];                 // (FIELDS: the field's scale of every position of the batch)
 #pragma unroll
         for (int q = 0; q < GP; ++q) {
             const int pos = posw[jb + q];
             gwq[q] = 0.0f;
             if (WIDE) gwq[q] = wa.gw[(wa.F == 1 ? (unsigned)pos : __umulhi((unsigned)pos, wa.magic)) * wa.gws];
-            const int64_t grow = POOL ? (int64_t)__umulhi((unsigned)pos, pool_magic) : (int64_t)pos;      // (POOL: the bag's row, pos / L)
+            int64_t grow = POOL ? (int64_t)__umulhi((unsigned)pos, pool_magic) : (int64_t)pos;      // (POOL: the bag's row, pos / L)
+            if constexpr (FIELDS) {
+                const unsigned bs = fa->Ls == 1 ? (unsigned)pos : __umulhi((unsigned)pos, fa->magic);      // the sample, pos / Ls
+                const int sl = (int)((unsigned)pos - bs * (unsigned)fa->Ls);                              // the slot in the sample
+                int fld = 0;
+                float fsc = fa->scale[0];
+                for (int t = 1; t < fa->F; ++t) {               // (wave-uniform trip count and operands: scalar loads)
+                    const bool in = sl >= (int)fa->off[t];
+                    fld = in ? t : fld;
+                    fsc = in ? fa->scale[t] : fsc;
+                }
+                grow = (int64_t)bs * fa->F + fld;
+                gsq[q] = fsc;
+            }
             gload<NT>(gb[q], g + grow * ldg + (WIDE && wl ? 0 : col));               // (the wide lane's own gradient is gwq)
             rsv[q] = rscale ? rscale[pos] : 1.0f;
         }
@@ -677,7 +701,7 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
                 gwiden(xs[k], gb[sb * AB + k]);
                 if (WIDE && wl) { vzero(xs[k]); vset_x(xs[k], gwq[sb * AB + k]); }
                 if (rscale) vmul(xs[k], rsv[sb * AB + k]);
-                vmul(xs[k], gscale);
+                if constexpr (FIELDS) vmul(xs[k], gsq[sb * AB + k]); else vmul(xs[k], gscale);
                 vtouch(xs[k]);
             }
 #pragma unroll
@@ -793,6 +817,20 @@ __global__ __launch_bounds__(256) void k_apply_main_pool(Upd upd, int64_t V, int
     const WideArgs wa{};
     apply_main_body<VEC, K, Upd, GT, false, false, true>(upd, V, ld, uniq, spos, sseg, n, g, ldg, rscale, gscale, gm, carry_head, carry_tail,
                                                          owners, seg_offsets, wa, 0ull, 0u, nullptr, pool_magic);
+}
+
+// The fields form's windows (mrec_sparse_apply_next_pool_fields): apply_main_body with FIELDS, again a kernel of its own.
+template <int VEC, class K, class Upd, class GT>
+__global__ __launch_bounds__(256) void k_apply_main_fields(Upd upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
+                                                           const int* __restrict__ spos, const int* __restrict__ sseg,
+                                                           int n, const GT* __restrict__ g, int64_t ldg,
+                                                           const float* __restrict__ rscale, ApplyGeom gm,
+                                                           float* __restrict__ carry_head, float* __restrict__ carry_tail,
+                                                           int* __restrict__ owners, const int* __restrict__ seg_offsets,
+                                                           const FieldArgs fa) {
+    const WideArgs wa{};
+    apply_main_body<VEC, K, Upd, GT, false, false, false, true>(upd, V, ld, uniq, spos, sseg, n, g, ldg, rscale, 1.0f, gm, carry_head,
+                                                                carry_tail, owners, seg_offsets, wa, 0ull, 0u, nullptr, 0u, &fa);
 }
 
 // Finishes the runs that cross windows.  Partial 0 is the owner's tail, partials 1..k the heads of the
@@ -1126,10 +1164,13 @@ thread_local float t_max_norm = 0.0f;               // set by mrec_sparse_apply_
 thread_local int t_pool = 1;                        // set by mrec_sparse_apply_next_pool: the next apply reads position i's gradient row from g[i / L] (1: plain)
 // (armed for one call: every entry that can be the "next apply" takes it first thing, whether it then runs or refuses)
 inline int take_pool() { const int L = t_pool; t_pool = 1; return L; }
+thread_local FieldArgs t_fields = FieldArgs{};      // set by mrec_sparse_apply_next_pool_fields (F == 0: not armed); taken like t_pool
+inline bool take_fields(FieldArgs& fa) { fa = t_fields; t_fields.F = 0; return fa.F > 0; }
+inline void disarm_pool() { t_pool = 1; t_fields.F = 0; }
 // The pooled form is refused, before anything else is looked at, for the folded wide apply (its wide lane and its hot columns address
 // gradient rows by position themselves), behind max_norm, and with constant columns armed -- which are disarmed with it.
-inline bool pool_refused(int pool, bool wide, bool clip) {
-    if (pool <= 1) return false;
+inline bool pool_refused(bool armed, bool wide, bool clip) {
+    if (!armed) return false;
     const bool cc_armed = t_const.mask != nullptr;
     t_const = ConstCols{};
     return wide || clip || cc_armed;
@@ -1150,7 +1191,7 @@ template <class K, class Upd, class GT>
 int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, const int* sseg,
                const int* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale, float gscale,
                int Dc, int vec, const ApplyWs& w, hipStream_t st, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr, int pool = 1) {
+               const int64_t* nv = nullptr, int pool = 1, const FieldArgs* fields = nullptr) {
     ApplyGeom gm;
     gm.D = Dc + (wide ? 4 : 0);
     gm.lpr = Dc / vec + (wide ? 1 : 0);
@@ -1174,7 +1215,11 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
     do {                                                                                                                               \
         bool pooled = false;                                                                                                           \
         if constexpr (!Upd::kClip) {                                                                                                   \
-            if (pool > 1) {                                                                                                            \
+            if (fields) {                                                                                                              \
+                k_apply_main_fields<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gm,      \
+                                                                             w.carry_head, w.carry_tail, w.owners, seg_offsets, *fields); \
+                pooled = true;                                                                                                         \
+            } else if (pool > 1) {                                                                                                            \
                 k_apply_main_pool<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm, \
                                                                            w.carry_head, w.carry_tail, w.owners, seg_offsets, pmagic);  \
                 pooled = true;                                                                                                         \
@@ -1258,12 +1303,14 @@ template <class K, class Upd, class GT = float>
 int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const int32_t* spos, const int32_t* sseg,
                const int32_t* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale,
                float gscale, void* ws, size_t ws_bytes, void* stream, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr, int pool = 1) {
+               const int64_t* nv = nullptr, int pool = 1, const FieldArgs* fields = nullptr) {
     hipStream_t st = (hipStream_t)stream;
-    if (pool > 1 && (wide || Upd::kClip)) return MREC_EUNSUPPORTED;      // (refused by the entries already: pool_refused)
+    if ((pool > 1 || fields) && (wide || Upd::kClip)) return MREC_EUNSUPPORTED;      // (refused by the entries already: pool_refused)
+    if (fields && gscale != 1.0f) return MREC_EINVAL;      // the fields form: one scale per contribution, the field's
     if (n < 0 || D <= 0 || V < 0 || ld < D || ldg < D) return MREC_EINVAL;
     if (n == 0) return MREC_OK;
     if (pool > 1 && (uint64_t)n * (uint64_t)pool >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;      // pos / L by a 32-bit multiply-high
+    if (fields && (uint64_t)n * (uint64_t)fields->Ls >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;   // pos / Ls likewise
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!spos || !sseg || !seg_offsets || !g || !ws) return MREC_EINVAL;
     for (int i = 0; i < Upd::NS; ++i) if (!upd.s[i]) return MREC_EINVAL;
@@ -1294,7 +1341,7 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
         const int Dc = (D - c0 < CB) ? D - c0 : CB;
         Upd u2 = upd;
         for (int i = 0; i < Upd::NS; ++i) u2.s[i] = upd.s[i] + c0;
-        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, wide, ss, nv, pool);
+        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, wide, ss, nv, pool, fields);
         if (rc != MREC_OK) return rc;
     }
     return MREC_OK;
@@ -1309,7 +1356,9 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
     const float clip = t_max_norm;                 // (armed for this call only)
     t_max_norm = 0.0f;
     const int pool = take_pool();
-    if (pool_refused(pool, wide != nullptr, clip > 0.0f)) return MREC_EUNSUPPORTED;
+    FieldArgs fa;
+    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
+    if (pool_refused(pool > 1 || fields, wide != nullptr, clip > 0.0f)) return MREC_EUNSUPPORTED;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdAdam u;
     u.s[0] = p; u.s[1] = m; u.s[2] = v;
@@ -1322,10 +1371,10 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
         static_cast<UpdAdam&>(uc) = u;
         uc.clip = clip;
         return apply_impl<K, UpdAdamClip, GT>(uc, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                              stream, wide, ss, nv, pool);
+                                              stream, wide, ss, nv, pool, fields);
     }
     return apply_impl<K, UpdAdam, GT>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, wide, ss, nv, pool);
+                                  stream, wide, ss, nv, pool, fields);
 }
 
 template <class K>
@@ -1334,13 +1383,15 @@ int ftrl_impl(float* var, float* accum, float* linear, int64_t V, int64_t ld, in
               int64_t ldg, const float* rscale, float lr, float l1, float l2, float lr_power, float gscale, void* ws,
               size_t ws_bytes, void* stream) {
     const int pool = take_pool();
-    if (pool_refused(pool, false, false)) return MREC_EUNSUPPORTED;
+    FieldArgs fa;
+    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
+    if (pool_refused(pool > 1 || fields, false, false)) return MREC_EUNSUPPORTED;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdFtrl u;
     u.s[0] = var; u.s[1] = accum; u.s[2] = linear;
     u.h = FtrlH{lr, l1, l2, lr_power, gscale};
     return apply_impl<K, UpdFtrl>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, nullptr, nullptr, nullptr, pool);
+                                  stream, nullptr, nullptr, nullptr, pool, fields);
 }
 
 }  // namespace
@@ -1551,9 +1602,29 @@ MREC_API int mrec_sparse_apply_next_max_norm(float max_norm) {
 }
 
 MREC_API int mrec_sparse_apply_next_pool(int32_t L) {
-    t_pool = 1;
+    disarm_pool();
     if (L < 1) return MREC_EINVAL;
     t_pool = L;
+    return MREC_OK;
+}
+
+MREC_API int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_len, const float* field_scale) {
+    disarm_pool();
+    if (F < 1 || !field_len || !field_scale) return MREC_EINVAL;
+    if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
+    FieldArgs fa{};
+    int64_t Ls = 0;
+    for (int f = 0; f < F; ++f) {
+        if (field_len[f] < 1 || !(fabsf(field_scale[f]) <= 3.402823466e38f)) return MREC_EINVAL;
+        if (Ls + field_len[f] > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
+        fa.off[f] = (unsigned short)Ls;
+        fa.scale[f] = field_scale[f];
+        Ls += field_len[f];
+    }
+    fa.Ls = (int)Ls;
+    fa.F = F;
+    fa.magic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)Ls + 1);      // pos / Ls = umulhi(pos, magic) while pos * Ls < 2^32 (Ls == 1: not used)
+    t_fields = fa;
     return MREC_OK;
 }
 
@@ -1618,10 +1689,12 @@ MREC_API int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sort
     UpdStore u;
     u.s[0] = out;
     const int pool = take_pool();
-    if (pool_refused(pool, false, false)) return MREC_EUNSUPPORTED;
+    FieldArgs fa;
+    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
+    if (pool_refused(pool > 1 || fields, false, false)) return MREC_EUNSUPPORTED;
     // rows are group numbers; there are at most n groups
     return apply_impl<int32_t, UpdStore>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, g,
-                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool);
+                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool, fields);
 }
 
 /* ... over 16-bit row gradients (g_kind 1: bf16, 2: IEEE half), widened exactly and summed in fp32: what a rank of a row-sharded
@@ -1632,13 +1705,15 @@ MREC_API int mrec_segment_sum_g16(const int32_t* sorted_pos, const int32_t* sort
     UpdStore u;
     u.s[0] = out;
     const int pool = take_pool();
-    if (pool_refused(pool, false, false)) return MREC_EUNSUPPORTED;
+    FieldArgs fa;
+    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
+    if (pool_refused(pool > 1 || fields, false, false)) return MREC_EUNSUPPORTED;
     if (g_kind == 1)
         return apply_impl<int32_t, UpdStore, bf16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const bf16_t*)g,
-                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool);
+                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool, fields);
     if (g_kind == 2)
         return apply_impl<int32_t, UpdStore, f16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const f16_t*)g,
-                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool);
+                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool, fields);
     return MREC_EINVAL;
 }
 
@@ -1711,7 +1786,7 @@ MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V,
                                         float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F,
                                         int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                         size_t ws_bytes, void* step_state, const int64_t* n_valid_dev, void* stream) {
-    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; t_pool = 1; return MREC_EINVAL; }
+    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; disarm_pool(); return MREC_EINVAL; }
     WideArgs wa;
     wa.gw = gw; wa.F = F; wa.wcol = wide_col; wa.magic = 0; wa.dummy = nullptr; wa.gws = (unsigned)gw_stride;
     wa.h = FtrlH{ftrl_lr, l1, l2, lr_power, grad_scale};
@@ -1739,8 +1814,8 @@ MREC_API int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int6
                                               int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                               size_t ws_bytes, void* step_state, const int64_t* n_valid_dev,
                                               mrec_apply_finish_t* finish_out, void* stream) {
-    if (!finish_out) { t_max_norm = 0.0f; t_pool = 1; return MREC_EINVAL; }
-    if (D > 252) { t_max_norm = 0.0f; t_pool = 1; return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
+    if (!finish_out) { t_max_norm = 0.0f; disarm_pool(); return MREC_EINVAL; }
+    if (D > 252) { t_max_norm = 0.0f; disarm_pool(); return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
     ApplyFinish* f = (ApplyFinish*)finish_out;
     f->magic = 0u;
     f->clip = 0.0f;

@@ -24,6 +24,9 @@
 // adds in slot order.  The one store comes last.  Everything else (D % 4 != 0, misaligned rows or outputs, D == 1: the wide
 // weights) takes the same kernel at one column per lane.  Rows wider than a wave (D > 256 on the float4 path, D > 64 on the scalar
 // one) are walked in column blocks by the same lane-group.
+//
+// A second entry, mrec_gather_pool_fields, pools F bags of UNEQUAL lengths per sample in one launch (k_gather_pool_fields below, with
+// the mapping of its work items and why); mrec_gather_pool and what it launches are not touched by it.
 #include "mrec_common.h"
 #include "mrec_optim.h"
 #include "mrec_dense_adam.h"
@@ -123,7 +126,105 @@ __global__ __launch_bounds__(256) void k_gather_pool(const float* __restrict__ t
     }
 }
 
+// ---- the fields form (mrec_gather_pool_fields): F bags of lengths L_0 .. L_{F-1} per sample, back to back in a row of Ls = sum L_f ids
+// (the reference's multi-hot fields have one bag length EACH: src/datasets.py:290-313, input_shape_dict), pooled per field into
+// columns f * D .. (f + 1) * D - 1 of the sample's output row (the Concat at wide_and_deep.py:348-349).  One launch.
+//
+// Work-item mapping: a lane-group's work item is bag w = b * F + f -- SAMPLE-major, field-minor.  Neighbouring lane-groups of a wave
+// then take neighbouring fields of one sample and go on into the next sample: their ids (and mask values) are one contiguous stretch
+// of the [B, Ls] arrays -- G consecutive bags of a wave cover about G * Ls / F consecutive ids, the same cache lines -- and with
+// ldo == F * D their output rows are one contiguous stretch too.  The other choice, field-major (a wave = G samples of ONE field),
+// gives every lane-group of a wave the same trip count, but each lane-group's ids then sit Ls ids from its neighbour's: every id or
+// mask line a wave touches is fetched for L_f of its Ls entries, by F different waves at different times.  The id and mask reads are
+// the start of the kernel's chain of dependent loads (id -> row), so the mapping that fetches each of their lines once was chosen;
+// the price is that lane-groups of one wave run different numbers of PB-deep batches (ceil(L_f / PB): 1 for every field of the
+// reference's shapes at PB = 8), which costs nothing but idle lanes -- the kernel has no barriers.
+// The per-field (offset, length) pairs travel BY VALUE in the kernel's arguments, one 32-bit word per field (offset < 4096 and
+// length <= 4096 fit 16 bits each): no table in device memory, no copy, no allocation -- the entry stays capturable.  A lane reads
+// its field's word by a per-lane index: a cached load from the argument segment, once per lane.
+// Arithmetic: k_gather_pool's, per bag (slot 0 starts the sum, product then add in ascending slot order, one IEEE division by
+// (float)L_f -- the FIELD's length -- for the mean, 16-bit outputs rounded once).
+struct PoolFields { unsigned w[MREC_POOL_MAX_FIELDS]; };      // w[f] = off_f | L_f << 16
+
+template <int VEC, int PB, class K, class OT>
+__global__ __launch_bounds__(256) void k_gather_pool_fields(const float* __restrict__ table, int64_t V, int64_t ld, const K* __restrict__ ids,
+                                                            const float* __restrict__ mask, unsigned nbags, unsigned F, int Ls, int mode,
+                                                            OT* __restrict__ out, int64_t ldo, int D, PoolGeom gm, const PoolFields pf) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;                                      // spare lanes; this kernel has no barriers
+    const unsigned w = (blockIdx.x * 4u + (unsigned)wave) * (unsigned)gm.G + (unsigned)grp;      // (nbags = B * F < 2^31: no wrap)
+    const unsigned wc = w < nbags ? w : nbags - 1u;               // a bag past the end reads the last bag, and stores nothing
+    const unsigned b = wc / F, f = wc - b * F;
+    const unsigned fw = pf.w[f];
+    const int off = (int)(fw & 0xFFFFu), L = (int)(fw >> 16);
+    const K* __restrict__ idb = ids + (int64_t)b * Ls + off;
+    const float* __restrict__ mb = mask ? mask + (int64_t)b * Ls + off : nullptr;
+    OT* __restrict__ ob = out + (int64_t)b * ldo + (int64_t)f * D;
+    const int llast = L - 1;
+    const float fl = (float)L;
+    for (int col = sub * VEC; col < D; col += gm.lpr * VEC) {
+        Vf<VEC> acc = vzero((Vf<VEC>*)nullptr);
+        for (int l0 = 0; l0 < L; l0 += PB) {                      // (L is the FIELD's: lane-groups of a wave may walk different numbers of batches)
+            int64_t row[PB];
+            float mk[PB];
+            Vf<VEC> x[PB];
+            bool okr[PB];
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                const int lc = l0 + k < L ? l0 + k : llast;       // (a slot past the bag's end reads the bag's last id: inside the bag)
+                row[k] = (int64_t)idb[lc];
+                mk[k] = mb ? mb[lc] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                okr[k] = row[k] >= 0 && row[k] < V;
+                x[k] = vload(table + (okr[k] ? row[k] : 0) * ld + col, (Vf<VEC>*)nullptr);
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                vtouch(x[k]);
+                if (!okr[k]) x[k] = vzero((Vf<VEC>*)nullptr);
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                if (l0 + k < L) {
+                    const Vf<VEC> p = mb ? vscale(x[k], mk[k]) : x[k];
+                    acc = (l0 + k == 0) ? p : vadd(acc, p);       // slot 0 starts the sum
+                }
+            }
+        }
+        if (mode == 1) acc = vdiv(acc, fl);
+        if (w < nbags) vstore(ob + col, acc);
+    }
+}
+
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+template <class K, class OT>
+int pool_fields_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t B, int32_t F, int32_t Ls, int32_t maxL,
+                     const PoolFields& pf, const float* mask, int32_t mode, OT* out, int64_t ldo, hipStream_t st) {
+    // float4 lanes where the rows, and the 4-element quads of every field's output block, are aligned (D % 4 == 0: f * D too)
+    const uintptr_t oa = sizeof(OT) == 2 ? 7 : 15;
+    const bool vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
+    const int cols = vec ? D / 4 : D;
+    PoolGeom gm;
+    gm.lpr = cols < 64 ? cols : 64;
+    gm.G = 64 / gm.lpr;
+    const int64_t nbags = B * F;
+    const unsigned blocks = (unsigned)mrec_cdiv(nbags, (int64_t)4 * gm.G);
+#define MREC_POOLF_LAUNCH(VECN, PBN)                                                                                                  \
+    k_gather_pool_fields<VECN, PBN, K, OT><<<blocks, 256, 0, st>>>(table, V, ld, ids, mask, (unsigned)nbags, (unsigned)F, (int)Ls, (int)mode, \
+                                                                  out, ldo, (int)D, gm, pf)
+    if (vec) {
+        if (maxL <= 2) MREC_POOLF_LAUNCH(4, 2); else MREC_POOLF_LAUNCH(4, 8);
+    } else {
+        if (maxL <= 2) MREC_POOLF_LAUNCH(1, 2); else MREC_POOLF_LAUNCH(1, 8);
+    }
+#undef MREC_POOLF_LAUNCH
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
 
 template <class K, class OT>
 int pool_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t B, int32_t L, const float* mask, int32_t mode,
@@ -171,4 +272,40 @@ MREC_API int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t
     if (out_kind == 1) { MREC_POOL(int64_t, bf16o_t); }
     MREC_POOL(int64_t, f16o_t);
 #undef MREC_POOL
+}
+
+MREC_API int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
+                                     int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
+                                     int64_t ldo, void* stream) {
+    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || (mode != 0 && mode != 1)) return MREC_EINVAL;
+    if (B < 0 || F < 1 || D <= 0 || V < 0 || ld < D || !field_len) return MREC_EINVAL;
+    if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
+    PoolFields pf{};
+    int64_t Ls = 0;
+    int32_t maxL = 0;
+    for (int f = 0; f < F; ++f) {
+        const int32_t Lf = field_len[f];
+        if (Lf < 1) return MREC_EINVAL;
+        if (Ls + Lf > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
+        pf.w[f] = (unsigned)Ls | ((unsigned)Lf << 16);
+        Ls += Lf;
+        maxL = Lf > maxL ? Lf : maxL;
+    }
+    if (ldo == 0) ldo = (int64_t)F * D;
+    if (ldo < (int64_t)F * D) return MREC_EINVAL;
+    if (B * F > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;      // (bags are numbered in 32 bits)
+    if (B == 0) return MREC_OK;
+    if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
+    if (!table || !ids || !out) return MREC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+#define MREC_POOLF(KT, OT) return pool_fields_impl<KT, OT>(table, V, ld, D, (const KT*)ids, B, F, (int32_t)Ls, maxL, pf, mask, mode, (OT*)out, ldo, st)
+    if (id_bytes == 4) {
+        if (out_kind == 0) { MREC_POOLF(int32_t, float); }
+        if (out_kind == 1) { MREC_POOLF(int32_t, bf16o_t); }
+        MREC_POOLF(int32_t, f16o_t);
+    }
+    if (out_kind == 0) { MREC_POOLF(int64_t, float); }
+    if (out_kind == 1) { MREC_POOLF(int64_t, bf16o_t); }
+    MREC_POOLF(int64_t, f16o_t);
+#undef MREC_POOLF
 }

@@ -18,6 +18,24 @@ dy[i // L], the L-fold expanded gradient is never written).  Optimizers:
                (pool=L) + ops.dense_adam_rows_l2_ with l2_scaled = 0, which gives every row outside the plan a zero gradient -- so an
                untouched row's m and v decay and the row keeps moving on its momentum, exactly as under the dense optimizer.  32-bit
                ids only (that entry numbers rows in 32 bits).
+
+Fields of UNEQUAL bag lengths (every multi-hot field of the reference has its own: src/datasets.py:290-313, input_shape_dict): a tuple
+or list for `bag` selects the fields form,
+
+    emb = MultiHotEmbedding(vocab=20900, dim=64, bag=(3, 5, 4, 3, 4, 2), mode="mean", optimizer="adam")
+    x = emb.lookup(ids, mask)          # ids, mask [B, Ls], Ls = sum(bag), field f in slots off_f .. off_f + L_f - 1 -> [B, F * dim]
+    emb.apply_(dy)                     # ONE plan over all B * Ls ids, ONE apply
+
+Forward: ops.gather_pool_fields, one launch, the mean of field f divided by L_f.  Backward: position (b, s), s a slot of field f,
+contributes (dy[b, f * dim : (f + 1) * dim] * mask[b, s]) * gs_f with gs_f = fp32(grad_scale / L_f) for "mean" and grad_scale for "sum"
+(ops.* with fields=bag, field_scale=gs).  One plan, so an id that occurs in several fields receives the SUM of their gradients and
+ONE optimizer update per step, as the reference's optimizer does with the table's summed gradient -- a lookup and an apply_ per
+distinct length would update such a row once per call, which under LazyAdam, FTRL or dense Adam is a different result.  All three
+optimizers; an integer `bag` behaves as it always did, [B, F, L] ids included.
+The wide side of the reference's multi-hot fields (wide_and_deep.py:377-420: ReduceSum of every field's masked [V, 1] weights, the
+fields' sums added up) needs no fields form: a sum over fields of sums over slots is ONE bag of length Ls, mode "sum", dim = 1 --
+MultiHotEmbedding(vocab, 1, bag=sum(lengths), mode="sum", optimizer="ftrl") on the same [B, Ls] ids.
+
 Neither method synchronises with the host, so lookup + apply_ capture into one HIP graph on one stream.  The Adam bias-correction
 powers advance on the host with every apply_: a captured graph holds the powers of the steps it captured (replaying K captured
 steps repeats those K steps; it does not continue the count).  No torch arithmetic on the step."""
@@ -37,6 +55,10 @@ class MultiHotEmbedding:
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         if optimizer not in _OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {_OPTIMIZERS}, got {optimizer!r}")
+        self.fields = None                  # the fields form: the bag lengths (L_0, .., L_{F-1}); bag is then their sum
+        if isinstance(bag, (tuple, list)):
+            self.fields = ops._fields(bag)
+            bag = sum(self.fields)
         if int(vocab) < 1 or int(dim) < 1 or int(bag) < 1:
             raise ValueError("vocab, dim and bag must be >= 1")
         self.vocab, self.dim, self.bag = int(vocab), int(dim), int(bag)
@@ -64,6 +86,12 @@ class MultiHotEmbedding:
         self._ids = self._mask = None
 
     def _bags(self, ids):
+        if self.fields is not None:
+            if ids.dim() != 2 or ids.shape[1] != self.bag:
+                raise TypeError(f"ids must be [B, {self.bag}]: the bags of lengths {self.fields} back to back")
+            if self.optimizer == "adam" and ids.dtype != torch.int32:
+                raise TypeError("optimizer 'adam' takes int32 ids (the dense row update numbers rows in 32 bits)")
+            return ids.shape[0], len(self.fields)
         if ids.dim() not in (2, 3) or ids.shape[-1] != self.bag:
             raise TypeError(f"ids must be [B, {self.bag}] or [B, F, {self.bag}] (bags of {self.bag} ids)")
         if self.optimizer == "adam" and ids.dtype != torch.int32:
@@ -73,10 +101,16 @@ class MultiHotEmbedding:
     def lookup(self, ids, mask=None, out=None):
         """ids [B, L] -> [B, dim]; ids [B, F, L] -> [B, F * dim] (field f in columns f * dim .. (f + 1) * dim - 1, the reference's
         concat of its pooled fields).  mask: float32 0/1 (or any weight) per id, None = all ones.  out: where the rows go -- for
-        [B, L] ids any [B, dim] column block with unit column stride; for [B, F, L] ids a contiguous [B, F * dim] tensor."""
+        [B, L] ids any [B, dim] column block with unit column stride; for [B, F, L] ids a contiguous [B, F * dim] tensor.
+        Fields form (bag=(L_0, ..)): ids, mask [B, Ls] -> [B, F * dim]; out: any [B, F * dim] column block with unit column stride."""
         B, F = self._bags(ids)
         if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
             raise TypeError("mask must be float32 of the shape of ids")
+        if self.fields is not None:
+            out = ops.gather_pool_fields(self.table, ids, self.fields, mask, mode=self.mode, out=out, out_dtype=self.out_dtype)
+            self._ids = ids.contiguous()
+            self._mask = mask.contiguous() if mask is not None else None
+            return out
         flat = ids.reshape(B * F, self.bag)
         fmask = mask.reshape(B * F, self.bag) if mask is not None else None
         if out is None:
@@ -94,10 +128,16 @@ class MultiHotEmbedding:
         if self._ids is None:
             raise RuntimeError("apply_ follows a lookup")
         ids, mask, L = self._ids, self._mask, self.bag
-        if dy.dim() != 2 or dy.shape[0] * dy.shape[1] != ids.shape[0] * self.dim or not dy.is_contiguous():
+        nbags = ids.shape[0] * (len(self.fields) if self.fields is not None else 1)
+        if dy.dim() != 2 or dy.shape[0] * dy.shape[1] != nbags * self.dim or not dy.is_contiguous():
             raise TypeError("dy must be the contiguous [B, F * dim] gradient of the last lookup's result")
-        g = dy.view(ids.shape[0], self.dim)
-        gs = float(np.float32(grad_scale) / np.float32(L)) if self.mode == "mean" else float(grad_scale)
+        g = dy.view(nbags, self.dim)
+        if self.fields is not None:        # one scale per field in place of grad_scale, fields= in place of pool=
+            fs = tuple(float(np.float32(grad_scale) / np.float32(Lf)) if self.mode == "mean" else float(grad_scale) for Lf in self.fields)
+            pkw = dict(fields=self.fields, field_scale=fs)
+        else:
+            gs = float(np.float32(grad_scale) / np.float32(L)) if self.mode == "mean" else float(grad_scale)
+            pkw = dict(grad_scale=gs, pool=L)
         plan = ops.sparse_plan(ids)
         self.beta1_power = np.float32(self.beta1_power * self.beta1)
         self.beta2_power = np.float32(self.beta2_power * self.beta2)
@@ -105,11 +145,11 @@ class MultiHotEmbedding:
         akw = dict(lr=self.lr, beta1=float(self.beta1), beta2=float(self.beta2), eps=self.eps, beta1_power=float(self.beta1_power),
                    beta2_power=float(self.beta2_power), use_nesterov=self.use_nesterov)
         if self.optimizer == "lazy_adam":
-            ops.sparse_lazy_adam_(self.table, self.m, self.v, plan, g, mask, grad_scale=gs, pool=L, **akw)
+            ops.sparse_lazy_adam_(self.table, self.m, self.v, plan, g, mask, **pkw, **akw)
         elif self.optimizer == "ftrl":
             ops.sparse_ftrl_(self.table, self.accum, self.linear, plan, g, mask, lr=self.lr, l1=self.l1, l2=self.l2,
-                             lr_power=self.lr_power, grad_scale=gs, pool=L)
+                             lr_power=self.lr_power, **pkw)
         else:
-            sums = ops.segment_sum(plan, g, mask, grad_scale=gs, pool=L)
+            sums = ops.segment_sum(plan, g, mask, **pkw)
             ops.dense_adam_rows_l2_(self.table, self.m, self.v, plan, sums, 0.0, grad_scale=1.0, **akw)
         return plan

@@ -186,27 +186,66 @@ def _pool(pool):
     return L
 
 
-def _call_clipped(max_norm, name, *args, pool=None):
+MAX_FIELDS = 64        # MREC_POOL_MAX_FIELDS
+MAX_BAG = 4096         # MREC_POOL_MAX_BAG
+
+
+def _fields(field_len):
+    """fields=(L_0, .., L_{F-1}) as the C entry points take it: 1 .. MAX_FIELDS integer bag lengths >= 1 whose sum is at most MAX_BAG."""
+    if isinstance(field_len, (str, bytes)) or not hasattr(field_len, "__len__"):
+        raise ValueError(f"fields must be a tuple or list of bag lengths, got {field_len!r}")
+    lens = []
+    for L in field_len:
+        if isinstance(L, bool) or int(L) != L or int(L) < 1:
+            raise ValueError(f"fields must hold integer bag lengths >= 1, got {L!r}")
+        lens.append(int(L))
+    if not 1 <= len(lens) <= MAX_FIELDS:
+        raise ValueError(f"fields must hold 1 .. {MAX_FIELDS} bag lengths, got {len(lens)}")
+    if sum(lens) > MAX_BAG:
+        raise ValueError(f"the bag lengths of fields must add up to at most {MAX_BAG}, got {sum(lens)}")
+    return tuple(lens)
+
+
+def _field_scales(lens, field_scale, grad_scale):
+    """the per-field scales of a fields= apply: field_scale (one finite float per field; grad_scale must then be 1.0 -- a contribution
+    has ONE scale, its field's) or, without it, grad_scale for every field"""
+    if field_scale is None:
+        return (float(grad_scale),) * len(lens)
+    sc = tuple(float(x) for x in field_scale)
+    if len(sc) != len(lens) or not all(math.isfinite(x) for x in sc):
+        raise ValueError(f"field_scale must hold one finite number per field ({len(lens)}), got {field_scale!r}")
+    if float(grad_scale) != 1.0:
+        raise ValueError("field_scale takes the place of grad_scale: pass one or the other")
+    return sc
+
+
+def _call_clipped(max_norm, name, *args, pool=None, fields=None):
     """_lib.call(name, *args) -- a sparse apply -- armed with max_norm (mrec_sparse_apply_next_max_norm: the NEXT LazyAdam apply of this
-    host thread clips) and / or pool=L (mrec_sparse_apply_next_pool: the NEXT apply reads position i's gradient row from g[i // L]).
+    host thread clips) and / or pool=L (mrec_sparse_apply_next_pool: the NEXT apply reads position i's gradient row from g[i // L])
+    or fields=(lengths, scales) (mrec_sparse_apply_next_pool_fields: bags of unequal lengths, one scale per field).
     Everything is evaluated before the arm, and an exception between the arm and the apply (ctypes refusing an argument) disarms
     again, so that no later apply of another table is clipped or pooled by mistake."""
-    if max_norm is None and pool is None:
+    if max_norm is None and pool is None and fields is None:
         _lib.call(name, *args)
         return
     c = None if max_norm is None else _max_norm(max_norm)
     L = None if pool is None else _pool(pool)
+    if fields is not None:
+        lens, scales = fields
+        fl, fs = (C.c_int32 * len(lens))(*lens), (C.c_float * len(lens))(*scales)
     try:
         if c is not None:
             _lib.call("mrec_sparse_apply_next_max_norm", c)
         if L is not None:
             _lib.call("mrec_sparse_apply_next_pool", L)
+        if fields is not None:
+            _lib.call("mrec_sparse_apply_next_pool_fields", len(lens), fl, fs)
         _lib.call(name, *args)
     except BaseException:
         if c is not None:
             _lib.lib().mrec_sparse_apply_next_max_norm(0.0)      # (EINVAL: leaves nothing armed; the C side disarms on its own refusals)
-        if L is not None:
-            _lib.lib().mrec_sparse_apply_next_pool(1)            # (1: the plain apply)
+        if L is not None or fields is not None:
+            _lib.lib().mrec_sparse_apply_next_pool(1)            # (1: the plain apply; disarms the fields form too)
         raise
 
 
@@ -275,6 +314,39 @@ def gather_pool(table, ids, mask=None, mode="mean", out=None, out_dtype=torch.fl
     _lib.call("mrec_gather_pool", _ptr(table), V, ld, D, _ptr(flat), 4 if sfx == "i32" else 8, B, L, _ptr(mask),
               1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
     return ret
+
+
+def gather_pool_fields(table, ids, field_len, mask=None, mode="mean", out=None, out_dtype=torch.float32):
+    """gather_pool for F fields of UNEQUAL bag lengths over one table, in one launch (mrec_gather_pool_fields): ids [B, Ls], Ls =
+    sum(field_len), field f in slots off_f .. off_f + L_f - 1 (the fields back to back; src/datasets.py:290-313 gives every multi-hot
+    field of the reference a length of its own) -> [B, F * D] with field f pooled into columns f * D .. (f + 1) * D - 1 (the Concat at
+    wide_and_deep.py:348-349).  Per bag the arithmetic is gather_pool's; mode="mean" divides by the FIELD's own length.  mask: float32
+    [B, Ls] or None.  out: a [B, F * D] tensor or column block (unit column stride) in float32 / bfloat16 / float16."""
+    _need_cuda(table, ids, mask, out)
+    V, D, ld = _table(table)
+    sfx = _suffix(ids)
+    lens = _fields(field_len)
+    F, Ls = len(lens), sum(lens)
+    if mode not in ("sum", "mean"):
+        raise ValueError(f"gather_pool_fields mode must be 'sum' or 'mean', got {mode!r}")
+    if ids.dim() != 2 or ids.shape[1] != Ls:
+        raise TypeError(f"ids must be [B, {Ls}]: the bags of lengths {lens} back to back")
+    flat = ids.contiguous()
+    B = flat.shape[0]
+    if mask is not None:
+        if mask.dtype != torch.float32 or tuple(mask.shape) != (B, Ls):
+            raise TypeError("mask must be float32 of the shape of ids")
+        mask = mask.contiguous()
+    if out is None:
+        if out_dtype not in _OUT_KIND:
+            raise TypeError("gather_pool_fields out_dtype must be float32, bfloat16 or float16")
+        out = torch.empty((B, F * D), dtype=out_dtype, device=table.device)
+    elif out.dtype not in _OUT_KIND or out.dim() != 2 or tuple(out.shape) != (B, F * D) or out.stride(1) != 1:
+        raise TypeError("gather_pool_fields out must be a [B, F * D] float32 / bfloat16 / float16 tensor with unit column stride")
+    ldo = out.stride(0) if B > 1 else F * D
+    _lib.call("mrec_gather_pool_fields", _ptr(table), V, ld, D, _ptr(flat), 4 if sfx == "i32" else 8, B, F, (C.c_int32 * F)(*lens),
+              _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
+    return out
 
 
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
@@ -396,17 +468,39 @@ def wide_sum(w, ids, wts, bias=None):
     return out
 
 
-def _grads(plan, g, D, allow_bf16=False, pool=None):
-    """the gradient rows and their stride: one row per position, or (pool=L) one per bag of L positions, ceil(n / L) of them"""
+def _grads(plan, g, D, allow_bf16=False, pool=None, fields=None):
+    """the gradient rows and their stride: one row per position, or (pool=L) one per bag of L positions, ceil(n / L) of them, or
+    (fields=lengths) one per bag of a sample's F bags, n / sum(lengths) * F of them"""
     if g.dtype != torch.float32 and not (allow_bf16 and g.dtype in (torch.bfloat16, torch.float16)):
         raise TypeError("row gradients must be float32" + (", bfloat16 or float16" if allow_bf16 else ""))
-    rows = plan.n if pool is None else -(-plan.n // _pool(pool))
+    if fields is not None:
+        if pool is not None:
+            raise ValueError("pool= and fields= are two forms of the same thing: pass one")
+        Ls = sum(fields)
+        if plan.n % Ls:
+            raise TypeError(f"fields={fields}: the plan's {plan.n} positions are not whole samples of {Ls} ids")
+        rows = plan.n // Ls * len(fields)
+        if g.numel() != rows * D:
+            raise TypeError(f"fields={fields}: g must hold n / {Ls} * {len(fields)} = {rows} gradient rows of {D} columns")
+    else:
+        rows = plan.n if pool is None else -(-plan.n // _pool(pool))
     if pool is not None and g.numel() != rows * D:
         raise TypeError(f"pool={pool}: g must hold ceil(n / pool) = {rows} gradient rows of {D} columns")
     g2 = g.reshape(rows, D)
     if g2.stride(1) != 1:
         g2 = g2.contiguous()
     return g2, (g2.stride(0) if rows > 1 else D)
+
+
+def _fields_arm(fields, field_scale, grad_scale):
+    """(what _call_clipped arms, the grad_scale the armed call is given): the fields form takes its scales per field and 1.0 as the
+    call's own"""
+    if fields is None:
+        if field_scale is not None:
+            raise ValueError("field_scale goes with fields=")
+        return None, grad_scale
+    lens = _fields(fields)
+    return (lens, _field_scales(lens, field_scale, grad_scale)), 1.0
 
 
 def _row_scale(plan, row_scale):
@@ -428,39 +522,47 @@ def apply_window(D, aligned=True):
     return int(_lib.lib().mrec_sparse_apply_window(D, int(aligned)))
 
 
-def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None):
+def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None, fields=None, field_scale=None):
     """ops.UnsortedSegmentSum over the plan's groups: returns an [n, D] buffer whose first U rows
     are the per-unique-id sums (rows >= U are unspecified).  pool=L: the plan's positions are bags of L (gather_pool's ids), g is
-    [ceil(n / L), D] and position i's gradient row is g[i // L] (row_scale stays per position: the mask)."""
+    [ceil(n / L), D] and position i's gradient row is g[i // L] (row_scale stays per position: the mask).  fields=(L_0, .., L_{F-1})
+    (not with pool=): the plan's positions are samples of sum(L_f) ids, F bags back to back (gather_pool_fields' ids), g is the
+    [B, F * D] gradient seen as [B * F, D], and position i = b * Ls + s, s in field f, contributes (g[b * F + f] * row_scale[i]) *
+    field_scale[f]; field_scale (one float per field) takes the place of grad_scale, without it every field's scale is grad_scale."""
     _need_cuda(g, row_scale)
+    arm, grad_scale = _fields_arm(fields, field_scale, grad_scale)
     D = g.shape[-1]
-    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool)
+    if arm is not None and g.dim() == 2 and len(arm[0]) > 1 and g.shape[0] * sum(arm[0]) == plan.n and D % len(arm[0]) == 0:
+        D //= len(arm[0])                 # g as the lookup's result has it, [B, F * D]: the same memory as [B * F, D]
+    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool, fields=arm[0] if arm else None)
     rs = _row_scale(plan, row_scale)
     out = torch.empty((max(plan.n, 1), D), dtype=torch.float32, device=g.device)
     ws = _apply_ws(plan, D, g.device)
     if g2.dtype == torch.float32:
         _call_clipped(None, "mrec_segment_sum_f32", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                      _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(), pool=pool)
+                      _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(), pool=pool, fields=arm)
     else:       # 16-bit row gradients (what the mixed-precision MLP backward produces): widened exactly, summed in fp32
         _call_clipped(None, "mrec_segment_sum_g16", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
                       _ptr(g2), 1 if g2.dtype == torch.bfloat16 else 2, ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(),
-                      pool=pool)
+                      pool=pool, fields=arm)
     return out
 
 
 def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_power=0.9,
-                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False, max_norm=None, pool=None):
+                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False, max_norm=None, pool=None, fields=None, field_scale=None):
     """nn.LazyAdam on a RowTensor gradient (wide_and_deep.py:420-422): in place on p, m, v.  max_norm=c: the gradients are those
     of rows the lookup clipped to c (gather_rows(..., max_norm=c) of the same p): each touched row's summed gradient G becomes
     (c / n)(G - (p.G / n^2) p) where n = |p| > c (mrec_sparse_apply_next_max_norm); D % 4 == 0, D <= 256.  pool=L: the bprop of
     gather_pool -- g is [ceil(n / L), D], one row per bag, and position i's gradient row is g[i // L] (segment_sum); not with
-    max_norm."""
+    max_norm.  fields=(L_0, ..), field_scale: the bprop of gather_pool_fields, as segment_sum -- one plan over all the fields' ids, so
+    an id that occurs in several fields gets the sum of their gradients and ONE update; not with pool= or max_norm."""
     _need_cuda(p, m, v, g, row_scale)
     V, D, ld = _table(p)
     for t in (m, v):
         if _table(t) != (V, D, ld):
             raise ValueError("p, m, v must share shape and row stride")
-    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool)
+    arm, grad_scale = _fields_arm(fields, field_scale, grad_scale)
+    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool, fields=arm[0] if arm else None)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, p.device)
     sfx = _suffix(plan.uniq_buf)
@@ -469,7 +571,7 @@ def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, be
     args = (_ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets),
             plan.n, _ptr(g2), ldg, _ptr(rs), lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(ws),
             ws.numel(), _stream())
-    _call_clipped(max_norm, fn + sfx, *args, pool=pool)
+    _call_clipped(max_norm, fn + sfx, *args, pool=pool, fields=arm)
 
 
 class ApplyFinish(C.Structure):      # mrec_apply_finish_t
@@ -573,20 +675,23 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
     return None
 
 
-def sparse_ftrl_(var, accum, linear, plan, g, row_scale=None, lr=5e-2, l1=1e-8, l2=1e-8, lr_power=-0.5, grad_scale=1.0, pool=None):
-    """nn.FTRL sparse apply (wide_and_deep.py:423-430): in place on var, accum, linear.  pool=L: as sparse_lazy_adam_."""
+def sparse_ftrl_(var, accum, linear, plan, g, row_scale=None, lr=5e-2, l1=1e-8, l2=1e-8, lr_power=-0.5, grad_scale=1.0, pool=None,
+                 fields=None, field_scale=None):
+    """nn.FTRL sparse apply (wide_and_deep.py:423-430): in place on var, accum, linear.  pool=L, fields=(L_0, ..) / field_scale: as
+    sparse_lazy_adam_."""
     _need_cuda(var, accum, linear, g, row_scale)
     V, D, ld = _table(var)
     for t in (accum, linear):
         if _table(t) != (V, D, ld):
             raise ValueError("var, accum, linear must share shape and row stride")
-    g2, ldg = _grads(plan, g, D, pool=pool)
+    arm, grad_scale = _fields_arm(fields, field_scale, grad_scale)
+    g2, ldg = _grads(plan, g, D, pool=pool, fields=arm[0] if arm else None)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, var.device)
     sfx = _suffix(plan.uniq_buf)
     _call_clipped(None, f"mrec_sparse_ftrl_f32_{sfx}", _ptr(var), _ptr(accum), _ptr(linear), V, ld, D, _ptr(plan.uniq_buf),
                   _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, l1,
-                  l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _stream(), pool=pool)
+                  l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _stream(), pool=pool, fields=arm)
 
 
 def _flat_same(*ts):
