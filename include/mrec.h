@@ -200,7 +200,8 @@ int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const
  * no fma, ascending slot order, slot 0 starts the sum, an id outside [0, V) contributes a +0.0 row, 16-bit outputs rounded once --
  * and mode 1 divides ONCE by (float)L_f, the FIELD's own length.  ONE launch, whose work item is a (sample, field) bag; the
  * per-field offsets and lengths travel by value in the kernel's arguments: no device allocation, no copy, no synchronisation --
- * capturable like mrec_gather_pool.  Limits: 1 <= F <= MREC_POOL_MAX_FIELDS and Ls <= MREC_POOL_MAX_BAG (beyond: MREC_EUNSUPPORTED),
+ * capturable.  mrec_gather_pool is this entry with F = 1 and field_len = {L}: one kernel, k_gather_pool_fields, serves both.
+ * Limits: 1 <= F <= MREC_POOL_MAX_FIELDS and Ls <= MREC_POOL_MAX_BAG (beyond: MREC_EUNSUPPORTED),
  * every L_f >= 1 (else MREC_EINVAL), B * F < 2^31 (beyond: MREC_EUNSUPPORTED).  Argument errors are reported before any HIP call. */
 #define MREC_POOL_MAX_FIELDS 64
 int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
@@ -453,10 +454,12 @@ int mrec_sparse_apply_next_max_norm(float max_norm);
  * stride; contribution i stays (g[i / L] * row_scale[i]) * grad_scale with row_scale by POSITION (the mask, 1 / L folded in by the
  * caller or into grad_scale), and the windows, the tree of partials and so the order of additions are those of the plain apply
  * on the L-fold expanded gradient -- which is never materialised.  Armed for one call, disarmed by that call whether it runs or
- * refuses; L == 1 is the plain apply (and disarms).  The armed call launches kernels of its own (k_apply_main_pool); not armed, a
- * call launches what it launched before this existed.  MREC_EUNSUPPORTED before any launch, and disarmed, for the folded wide
- * forms (mrec_sparse_lazy_adam_wide(_defer)), with constant columns armed (they are disarmed too), with max_norm, and for
- * n * L >= 2^32 (i / L is a 32-bit multiply-high).  L < 1: MREC_EINVAL, nothing is armed. */
+ * refuses; L == 1 is the plain apply (and disarms).  This is the one-field case of mrec_sparse_apply_next_pool_fields below (F = 1,
+ * field_len = {L}, the field's scale = the armed call's own grad_scale) without that entry's limits: any L >= 1, n need not be a
+ * multiple of L.  The armed call launches that form's windows, k_apply_main_fields, a kernel of its own, then k_apply_long; not
+ * armed, or at L == 1, a call launches k_apply_main + k_apply_long, what it launched before this existed.  MREC_EUNSUPPORTED before
+ * any launch, and disarmed, for the folded wide forms (mrec_sparse_lazy_adam_wide(_defer)), with constant columns armed (they are
+ * disarmed too), with max_norm, and for n * L >= 2^32 (i / L is a 32-bit multiply-high).  L < 1: MREC_EINVAL, nothing is armed. */
 int mrec_sparse_apply_next_pool(int32_t L);
 /* The FIELDS form of the pooled apply: the bprop of mrec_gather_pool_fields.  The plan's n positions are samples of Ls = sum L_f ids,
  * F bags back to back; g is the [B, F * D] gradient of the lookup's result viewed as [B * F, D] (ldg its row stride, n a multiple
@@ -472,8 +475,9 @@ int mrec_sparse_apply_next_pool(int32_t L);
  * slot-to-field map is a linear search over the F prefix offsets, held with the scales in the kernel's arguments: no device
  * table, no allocation, no synchronisation.  i / Ls is a 32-bit multiply-high: n * Ls >= 2^32 is MREC_EUNSUPPORTED.  Armed for one
  * call, disarmed by that call whether it runs or refuses; arming replaces an armed mrec_sparse_apply_next_pool and vice versa.
- * The armed call launches kernels of its own (k_apply_main_fields); a call that is not armed, or armed with _next_pool, launches what
- * it launched before this existed.  MREC_EUNSUPPORTED before any launch, and disarmed, for the folded wide forms, with constant
+ * The armed call launches the pooled windows, k_apply_main_fields (the kernel a call armed with _next_pool launches too), then
+ * k_apply_long; a call that is not armed launches k_apply_main + k_apply_long, what it launched before this existed.
+ * MREC_EUNSUPPORTED before any launch, and disarmed, for the folded wide forms, with constant
  * columns armed (disarmed too) and with max_norm.  Arming errors leave nothing armed: F < 1, a null array, an L_f < 1 or a
  * field_scale that is not finite: MREC_EINVAL; F > MREC_POOL_MAX_FIELDS or Ls > MREC_POOL_MAX_BAG: MREC_EUNSUPPORTED. */
 int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_len, const float* field_scale);

@@ -378,11 +378,13 @@ struct ApplyGeom { int lpr; int G; int D; };
 // (the wide lane pointed at dummy lines for m / v: two more line requests per load and store).
 struct WideArgs { const float* gw; int F; int wcol; FtrlH h; unsigned magic; float* dummy; unsigned gws; };
 
-// The fields form of the pooled apply (mrec_sparse_apply_next_pool_fields): a sample is Ls = sum L_f positions, F bags back to back.
+// The pooled apply (mrec_sparse_apply_next_pool_fields): a sample is Ls = sum L_f positions, F bags back to back.
 // Position i -> b = i / Ls (multiply-high with `magic`, exact while i * Ls < 2^32: apply_impl), s = i - b * Ls, f = the last field whose
 // prefix offset off[f] <= s (a linear search: F wave-uniform compares on values the kernel's arguments hold); the gradient row is
 // g[b * F + f] and the second factor of the contribution is scale[f] in place of the call's grad_scale.
-struct FieldArgs { unsigned magic; int Ls; int F; int pad; unsigned short off[MREC_POOL_MAX_FIELDS]; float scale[MREC_POOL_MAX_FIELDS]; };
+// mrec_sparse_apply_next_pool(L) is F = 1, Ls = L (any L: off[0] = 0 and Ls is an int) with call_scale set: scale[0] is then the armed
+// call's own grad_scale, filled in when the call takes the arm (take_fields).
+struct FieldArgs { unsigned magic; int Ls; int F; int call_scale; unsigned short off[MREC_POOL_MAX_FIELDS]; float scale[MREC_POOL_MAX_FIELDS]; };
 
 // uniq == nullptr means "row = group number" (segment-sum into a dense [U, D] output).
 template <class K>
@@ -481,12 +483,12 @@ __device__ __forceinline__ void const_part_body(const ConstCols& cc, unsigned lo
 }
 
 // (WIDE: MREC_WPS4 waves per SIMD asked of the register allocator)
-// (POOL: the pooled form, mrec_sparse_apply_next_pool -- position i's gradient row is g[i / L], i / L by multiply-high with pool_magic
-// as the wide lane's gw[i / F]; only that address differs, so the windows, the partial sums and their order are the plain apply's.  A
-// template argument: the instantiations without it are the code they were)
-// (FIELDS: the fields form, mrec_sparse_apply_next_pool_fields -- the gradient row is g[b * F + f] and the scale the field's, see
-// FieldArgs; again only where a position's row and scale come from differs, and again a template argument)
-template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false, bool POOL = false, bool FIELDS = false>
+// (FIELDS: the pooled form, mrec_sparse_apply_next_pool / _next_pool_fields -- position i's gradient row is g[b * F + f] and the scale the
+// field's, see FieldArgs; only where a position's row and scale come from differs, so the windows, the partial sums and their order are
+// the plain apply's.  A template argument: the instantiations without it are the code they were)
+// (ONE, with FIELDS: F == 1 and Ls > 1, what mrec_sparse_apply_next_pool arms -- the row is g[i / Ls] and the one scale travels as
+// gscale: no field search, no per-position scale registers, 2.5 % of the windows' time where the table sits in cache)
+template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false, bool FIELDS = false, bool ONE = false>
 __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
                                                     const int* __restrict__ spos, const int* __restrict__ sseg,
                                                     int n, const GT* __restrict__ g, int64_t ldg,
@@ -494,10 +496,9 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
                                                     float* __restrict__ carry_head, float* __restrict__ carry_tail,
                                                     int* __restrict__ owners, const int* __restrict__ seg_offsets,
                                                     const WideArgs& wa, const unsigned long long cmask = 0ull, const unsigned bid0 = 0u,
-                                                    const int* s_hid = nullptr, const unsigned pool_magic = 0u,
-                                                    const FieldArgs* fa = nullptr) {
-    static_assert(!POOL || (!WIDE && !HOT), "POOL: the plain windows only");
-    static_assert(!FIELDS || (!WIDE && !HOT && !POOL), "FIELDS: the plain windows only");
+                                                    const int* s_hid = nullptr, const FieldArgs* fa = nullptr) {
+    static_assert(!FIELDS || (!WIDE && !HOT), "FIELDS: the plain windows only");
+    static_assert(!ONE || FIELDS, "ONE: a form of FIELDS");
     constexpr int AW = ACfg<VEC>::AW, AB = ACfg<VEC>::AB, GP = ACfg<VEC>::GP;
     constexpr bool NT = ACfg<VEC>::NT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -648,14 +649,16 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
         if (s + jb >= e_end2) break;
         GBits<VEC, GT> gb[GP];
         float rsv[GP], gwq[GP];
-        float gsq[FIELDS ? GP : 1];                 // (FIELDS: the field's scale of every position of the batch)
+        float gsq[FIELDS && !ONE ? GP : 1];         // (FIELDS: the field's scale of every position of the batch)
 #pragma unroll
         for (int q = 0; q < GP; ++q) {
             const int pos = posw[jb + q];
             gwq[q] = 0.0f;
             if (WIDE) gwq[q] = wa.gw[(wa.F == 1 ? (unsigned)pos : __umulhi((unsigned)pos, wa.magic)) * wa.gws];
-            int64_t grow = POOL ? (int64_t)__umulhi((unsigned)pos, pool_magic) : (int64_t)pos;      // (POOL: the bag's row, pos / L)
-            if constexpr (FIELDS) {
+            int64_t grow = (int64_t)pos;
+            if constexpr (ONE) {
+                grow = (int64_t)__umulhi((unsigned)pos, fa->magic);       // the bag's row, pos / Ls
+            } else if constexpr (FIELDS) {
                 const unsigned bs = fa->Ls == 1 ? (unsigned)pos : __umulhi((unsigned)pos, fa->magic);      // the sample, pos / Ls
                 const int sl = (int)((unsigned)pos - bs * (unsigned)fa->Ls);                              // the slot in the sample
                 int fld = 0;
@@ -701,7 +704,7 @@ __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64
                 gwiden(xs[k], gb[sb * AB + k]);
                 if (WIDE && wl) { vzero(xs[k]); vset_x(xs[k], gwq[sb * AB + k]); }
                 if (rscale) vmul(xs[k], rsv[sb * AB + k]);
-                if constexpr (FIELDS) vmul(xs[k], gsq[sb * AB + k]); else vmul(xs[k], gscale);
+                if constexpr (FIELDS && !ONE) vmul(xs[k], gsq[sb * AB + k]); else vmul(xs[k], gscale);
                 vtouch(xs[k]);
             }
 #pragma unroll
@@ -804,23 +807,9 @@ __global__ __launch_bounds__(256, WIDE ? MREC_WPS4 : 1) void k_apply_main(Upd up
         ss->ends[(unsigned)ss->step % kStampRing][blockIdx.x & 63u] = (unsigned long long)wall_clock64();
 }
 
-// The pooled apply's windows (mrec_sparse_apply_next_pool): apply_main_body with POOL, a kernel of its own so that k_apply_main's
-// instantiations keep their code and their names.  No step state, no stamps: the plain (not folded) entries have neither.
-template <int VEC, class K, class Upd, class GT>
-__global__ __launch_bounds__(256) void k_apply_main_pool(Upd upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
-                                                         const int* __restrict__ spos, const int* __restrict__ sseg,
-                                                         int n, const GT* __restrict__ g, int64_t ldg,
-                                                         const float* __restrict__ rscale, float gscale, ApplyGeom gm,
-                                                         float* __restrict__ carry_head, float* __restrict__ carry_tail,
-                                                         int* __restrict__ owners, const int* __restrict__ seg_offsets,
-                                                         unsigned pool_magic) {
-    const WideArgs wa{};
-    apply_main_body<VEC, K, Upd, GT, false, false, true>(upd, V, ld, uniq, spos, sseg, n, g, ldg, rscale, gscale, gm, carry_head, carry_tail,
-                                                         owners, seg_offsets, wa, 0ull, 0u, nullptr, pool_magic);
-}
-
-// The fields form's windows (mrec_sparse_apply_next_pool_fields): apply_main_body with FIELDS, again a kernel of its own.
-template <int VEC, class K, class Upd, class GT>
+// The pooled apply's windows (mrec_sparse_apply_next_pool, _next_pool_fields): apply_main_body with FIELDS, a kernel of its own so that
+// k_apply_main's instantiations keep their code and their names.  No step state, no stamps: the plain (not folded) entries have neither.
+template <int VEC, class K, class Upd, class GT, bool ONE>
 __global__ __launch_bounds__(256) void k_apply_main_fields(Upd upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
                                                            const int* __restrict__ spos, const int* __restrict__ sseg,
                                                            int n, const GT* __restrict__ g, int64_t ldg,
@@ -829,8 +818,8 @@ __global__ __launch_bounds__(256) void k_apply_main_fields(Upd upd, int64_t V, i
                                                            int* __restrict__ owners, const int* __restrict__ seg_offsets,
                                                            const FieldArgs fa) {
     const WideArgs wa{};
-    apply_main_body<VEC, K, Upd, GT, false, false, false, true>(upd, V, ld, uniq, spos, sseg, n, g, ldg, rscale, 1.0f, gm, carry_head,
-                                                                carry_tail, owners, seg_offsets, wa, 0ull, 0u, nullptr, 0u, &fa);
+    apply_main_body<VEC, K, Upd, GT, false, false, true, ONE>(upd, V, ld, uniq, spos, sseg, n, g, ldg, rscale, ONE ? fa.scale[0] : 1.0f, gm,
+                                                              carry_head, carry_tail, owners, seg_offsets, wa, 0ull, 0u, nullptr, &fa);
 }
 
 // Finishes the runs that cross windows.  Partial 0 is the owner's tail, partials 1..k the heads of the
@@ -1161,19 +1150,25 @@ thread_local hipEvent_t t_prof_start = nullptr, t_prof_stop = nullptr;
 thread_local ApplyFinish* t_defer = nullptr;        // set by mrec_sparse_lazy_adam_wide_defer: the finishing pass is handed back, not launched
 thread_local ConstCols t_const = ConstCols{};       // set by mrec_sparse_apply_next_const_cols: the next wide apply takes constant columns out of its windows
 thread_local float t_max_norm = 0.0f;               // set by mrec_sparse_apply_next_max_norm: the next LazyAdam apply clips (0: none)
-thread_local int t_pool = 1;                        // set by mrec_sparse_apply_next_pool: the next apply reads position i's gradient row from g[i / L] (1: plain)
-// (armed for one call: every entry that can be the "next apply" takes it first thing, whether it then runs or refuses)
-inline int take_pool() { const int L = t_pool; t_pool = 1; return L; }
-thread_local FieldArgs t_fields = FieldArgs{};      // set by mrec_sparse_apply_next_pool_fields (F == 0: not armed); taken like t_pool
-inline bool take_fields(FieldArgs& fa) { fa = t_fields; t_fields.F = 0; return fa.F > 0; }
-inline void disarm_pool() { t_pool = 1; t_fields.F = 0; }
-// The pooled form is refused, before anything else is looked at, for the folded wide apply (its wide lane and its hot columns address
-// gradient rows by position themselves), behind max_norm, and with constant columns armed -- which are disarmed with it.
-inline bool pool_refused(bool armed, bool wide, bool clip) {
-    if (!armed) return false;
+thread_local FieldArgs t_fields = FieldArgs{};      // set by mrec_sparse_apply_next_pool / _next_pool_fields: the next apply is pooled (F == 0: not armed)
+inline void disarm_fields() { t_fields.F = 0; }
+// Armed for one call: every entry that can be the "next apply" takes the arm first thing, whether it then runs or refuses.  MREC_OK and
+// *fields = &fa (armed) or nullptr (the plain apply); any other code is the entry's answer, with nothing left armed.  The pooled form is
+// refused, before anything else is looked at, for the folded wide apply (its wide lane and its hot columns address gradient rows by
+// position themselves), behind max_norm, and with constant columns armed -- which are disarmed with it.  A contribution has ONE scale
+// besides its row_scale: the call's grad_scale under mrec_sparse_apply_next_pool, else the field's -- and grad_scale must be 1.0.
+inline int take_fields(FieldArgs& fa, const FieldArgs** fields, float gscale, bool wide, bool clip) {
+    fa = t_fields;
+    disarm_fields();
+    *fields = nullptr;
+    if (fa.F == 0) return MREC_OK;
     const bool cc_armed = t_const.mask != nullptr;
     t_const = ConstCols{};
-    return wide || clip || cc_armed;
+    if (wide || clip || cc_armed) return MREC_EUNSUPPORTED;
+    if (fa.call_scale) fa.scale[0] = gscale;
+    else if (gscale != 1.0f) return MREC_EINVAL;
+    *fields = &fa;
+    return MREC_OK;
 }
 
 struct ApplyWs { float* carry_head; float* carry_tail; int* owners; int* n_owners; float* dummy; float* cpart; };
@@ -1191,7 +1186,7 @@ template <class K, class Upd, class GT>
 int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, const int* sseg,
                const int* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale, float gscale,
                int Dc, int vec, const ApplyWs& w, hipStream_t st, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr, int pool = 1, const FieldArgs* fields = nullptr) {
+               const int64_t* nv = nullptr, const FieldArgs* fields = nullptr) {
     ApplyGeom gm;
     gm.D = Dc + (wide ? 4 : 0);
     gm.lpr = Dc / vec + (wide ? 1 : 0);
@@ -1209,25 +1204,20 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
     const unsigned lblocks = (unsigned)mrec_cdiv(nsw, (int64_t)(16 * gm.G < 256 ? 16 * gm.G : 256));      // k_apply_long: 4 windows per lane-group, 4 G lane-groups, 256 at most
     const hipEvent_t ev0 = t_prof_start, ev1 = t_prof_stop;
     t_prof_start = t_prof_stop = nullptr;
-    const unsigned pmagic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(pool > 1 ? pool : 1) + 1);      // pos / L = umulhi(pos, pmagic) while pos * L < 2^32 (apply_impl)
-    // the pooled windows (pool > 1; refused before this for the folded wide forms and max_norm): k_apply_main_pool, else k_apply_main
+    // the pooled windows (fields; refused before this for the folded wide forms and max_norm): k_apply_main_fields, else k_apply_main
 #define MREC_APPLY_MAIN(VECN)                                                                                                          \
     do {                                                                                                                               \
-        bool pooled = false;                                                                                                           \
-        if constexpr (!Upd::kClip) {                                                                                                   \
-            if (fields) {                                                                                                              \
-                k_apply_main_fields<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gm,      \
-                                                                             w.carry_head, w.carry_tail, w.owners, seg_offsets, *fields); \
-                pooled = true;                                                                                                         \
-            } else if (pool > 1) {                                                                                                            \
-                k_apply_main_pool<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm, \
-                                                                           w.carry_head, w.carry_tail, w.owners, seg_offsets, pmagic);  \
-                pooled = true;                                                                                                         \
-            }                                                                                                                          \
-        }                                                                                                                              \
-        if (!pooled)                                                                                                                   \
+        if (Upd::kClip || !fields)                                                                                                     \
             k_apply_main<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,      \
                                                                   w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);          \
+        else if constexpr (!Upd::kClip) {                                                                                              \
+            if (fields->F == 1 && fields->Ls > 1)                                                                                      \
+                k_apply_main_fields<VECN, K, Upd, GT, true><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gm,  \
+                                                                                   w.carry_head, w.carry_tail, w.owners, seg_offsets, *fields); \
+            else                                                                                                                       \
+                k_apply_main_fields<VECN, K, Upd, GT, false><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gm, \
+                                                                                    w.carry_head, w.carry_tail, w.owners, seg_offsets, *fields); \
+        }                                                                                                                              \
     } while (0)
     if (ev0) MREC_HIP_CHECK(hipEventRecord(ev0, st));
     if (nv && !(vec == 4 && wide)) return MREC_EUNSUPPORTED;
@@ -1303,14 +1293,12 @@ template <class K, class Upd, class GT = float>
 int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const int32_t* spos, const int32_t* sseg,
                const int32_t* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale,
                float gscale, void* ws, size_t ws_bytes, void* stream, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr, int pool = 1, const FieldArgs* fields = nullptr) {
+               const int64_t* nv = nullptr, const FieldArgs* fields = nullptr) {
     hipStream_t st = (hipStream_t)stream;
-    if ((pool > 1 || fields) && (wide || Upd::kClip)) return MREC_EUNSUPPORTED;      // (refused by the entries already: pool_refused)
-    if (fields && gscale != 1.0f) return MREC_EINVAL;      // the fields form: one scale per contribution, the field's
+    if (fields && (wide || Upd::kClip)) return MREC_EUNSUPPORTED;      // (refused by the entries already: take_fields)
     if (n < 0 || D <= 0 || V < 0 || ld < D || ldg < D) return MREC_EINVAL;
     if (n == 0) return MREC_OK;
-    if (pool > 1 && (uint64_t)n * (uint64_t)pool >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;      // pos / L by a 32-bit multiply-high
-    if (fields && (uint64_t)n * (uint64_t)fields->Ls >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;   // pos / Ls likewise
+    if (fields && (uint64_t)n * (uint64_t)fields->Ls >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;   // pos / Ls by a 32-bit multiply-high
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!spos || !sseg || !seg_offsets || !g || !ws) return MREC_EINVAL;
     for (int i = 0; i < Upd::NS; ++i) if (!upd.s[i]) return MREC_EINVAL;
@@ -1341,7 +1329,7 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
         const int Dc = (D - c0 < CB) ? D - c0 : CB;
         Upd u2 = upd;
         for (int i = 0; i < Upd::NS; ++i) u2.s[i] = upd.s[i] + c0;
-        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, wide, ss, nv, pool, fields);
+        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, wide, ss, nv, fields);
         if (rc != MREC_OK) return rc;
     }
     return MREC_OK;
@@ -1355,10 +1343,9 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
                    const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr) {
     const float clip = t_max_norm;                 // (armed for this call only)
     t_max_norm = 0.0f;
-    const int pool = take_pool();
     FieldArgs fa;
-    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
-    if (pool_refused(pool > 1 || fields, wide != nullptr, clip > 0.0f)) return MREC_EUNSUPPORTED;
+    const FieldArgs* fields;
+    if (const int rc = take_fields(fa, &fields, gscale, wide != nullptr, clip > 0.0f)) return rc;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdAdam u;
     u.s[0] = p; u.s[1] = m; u.s[2] = v;
@@ -1371,10 +1358,10 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
         static_cast<UpdAdam&>(uc) = u;
         uc.clip = clip;
         return apply_impl<K, UpdAdamClip, GT>(uc, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                              stream, wide, ss, nv, pool, fields);
+                                              stream, wide, ss, nv, fields);
     }
     return apply_impl<K, UpdAdam, GT>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, wide, ss, nv, pool, fields);
+                                  stream, wide, ss, nv, fields);
 }
 
 template <class K>
@@ -1382,16 +1369,15 @@ int ftrl_impl(float* var, float* accum, float* linear, int64_t V, int64_t ld, in
               const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const float* g,
               int64_t ldg, const float* rscale, float lr, float l1, float l2, float lr_power, float gscale, void* ws,
               size_t ws_bytes, void* stream) {
-    const int pool = take_pool();
     FieldArgs fa;
-    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
-    if (pool_refused(pool > 1 || fields, false, false)) return MREC_EUNSUPPORTED;
+    const FieldArgs* fields;
+    if (const int rc = take_fields(fa, &fields, gscale, false, false)) return rc;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdFtrl u;
     u.s[0] = var; u.s[1] = accum; u.s[2] = linear;
     u.h = FtrlH{lr, l1, l2, lr_power, gscale};
     return apply_impl<K, UpdFtrl>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, nullptr, nullptr, nullptr, pool, fields);
+                                  stream, nullptr, nullptr, nullptr, fields);
 }
 
 }  // namespace
@@ -1602,14 +1588,20 @@ MREC_API int mrec_sparse_apply_next_max_norm(float max_norm) {
 }
 
 MREC_API int mrec_sparse_apply_next_pool(int32_t L) {
-    disarm_pool();
+    disarm_fields();
     if (L < 1) return MREC_EINVAL;
-    t_pool = L;
+    if (L == 1) return MREC_OK;          // the plain apply
+    FieldArgs fa{};
+    fa.F = 1;
+    fa.Ls = L;
+    fa.call_scale = 1;
+    fa.magic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)L + 1);        // pos / L = umulhi(pos, magic) while pos * L < 2^32
+    t_fields = fa;
     return MREC_OK;
 }
 
 MREC_API int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_len, const float* field_scale) {
-    disarm_pool();
+    disarm_fields();
     if (F < 1 || !field_len || !field_scale) return MREC_EINVAL;
     if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
     FieldArgs fa{};
@@ -1688,13 +1680,12 @@ MREC_API int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sort
                                   int32_t D, float* out, void* ws, size_t ws_bytes, void* stream) {
     UpdStore u;
     u.s[0] = out;
-    const int pool = take_pool();
     FieldArgs fa;
-    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
-    if (pool_refused(pool > 1 || fields, false, false)) return MREC_EUNSUPPORTED;
+    const FieldArgs* fields;
+    if (const int rc = take_fields(fa, &fields, grad_scale, false, false)) return rc;
     // rows are group numbers; there are at most n groups
     return apply_impl<int32_t, UpdStore>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, g,
-                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool, fields);
+                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, fields);
 }
 
 /* ... over 16-bit row gradients (g_kind 1: bf16, 2: IEEE half), widened exactly and summed in fp32: what a rank of a row-sharded
@@ -1704,16 +1695,15 @@ MREC_API int mrec_segment_sum_g16(const int32_t* sorted_pos, const int32_t* sort
                                   int32_t D, float* out, void* ws, size_t ws_bytes, void* stream) {
     UpdStore u;
     u.s[0] = out;
-    const int pool = take_pool();
     FieldArgs fa;
-    const FieldArgs* fields = take_fields(fa) ? &fa : nullptr;
-    if (pool_refused(pool > 1 || fields, false, false)) return MREC_EUNSUPPORTED;
+    const FieldArgs* fields;
+    if (const int rc = take_fields(fa, &fields, grad_scale, false, false)) return rc;
     if (g_kind == 1)
         return apply_impl<int32_t, UpdStore, bf16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const bf16_t*)g,
-                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool, fields);
+                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, fields);
     if (g_kind == 2)
         return apply_impl<int32_t, UpdStore, f16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const f16_t*)g,
-                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, pool, fields);
+                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, fields);
     return MREC_EINVAL;
 }
 
@@ -1786,7 +1776,7 @@ MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V,
                                         float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F,
                                         int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                         size_t ws_bytes, void* step_state, const int64_t* n_valid_dev, void* stream) {
-    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; disarm_pool(); return MREC_EINVAL; }
+    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; disarm_fields(); return MREC_EINVAL; }
     WideArgs wa;
     wa.gw = gw; wa.F = F; wa.wcol = wide_col; wa.magic = 0; wa.dummy = nullptr; wa.gws = (unsigned)gw_stride;
     wa.h = FtrlH{ftrl_lr, l1, l2, lr_power, grad_scale};
@@ -1814,8 +1804,8 @@ MREC_API int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int6
                                               int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                               size_t ws_bytes, void* step_state, const int64_t* n_valid_dev,
                                               mrec_apply_finish_t* finish_out, void* stream) {
-    if (!finish_out) { t_max_norm = 0.0f; disarm_pool(); return MREC_EINVAL; }
-    if (D > 252) { t_max_norm = 0.0f; disarm_pool(); return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
+    if (!finish_out) { t_max_norm = 0.0f; disarm_fields(); return MREC_EINVAL; }
+    if (D > 252) { t_max_norm = 0.0f; disarm_fields(); return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
     ApplyFinish* f = (ApplyFinish*)finish_out;
     f->magic = 0u;
     f->clip = 0.0f;

@@ -14,8 +14,11 @@
 // ascending slot order; 16-bit outputs are rounded once, at the end.  Every output is therefore bit-reproducible on the host
 // (tests/_pool_ref.py), and L = 1 / mode 0 is mrec_gather_rows bit for bit.
 //
-// ONE entry, mrec_gather_pool, with id_bytes / out_kind arguments (the style of mrec_gather_rows_wide) instead of six names: the
-// six instantiations differ in two template arguments, and a caller that holds a tensor holds its element size.
+// TWO entries, ONE kernel.  mrec_gather_pool_fields pools F bags of lengths L_0 .. L_{F-1} per sample (k_gather_pool_fields below,
+// with the mapping of its work items and why); mrec_gather_pool, bags of one length L, is that with F = 1 and field_len = {L} --
+// the same launch path, the same arithmetic (F == 1 selects the kernel's ONE instantiations, which find their bag without a
+// division).  Both take id_bytes / out_kind arguments (the style of mrec_gather_rows_wide) instead of six names each: the six
+// instantiations differ in two template arguments, and a caller that holds a tensor holds its element size.
 //
 // Shape of the kernel: k_gather_rows' (mrec_gather.hip).  lpr = D / 4 lanes per bag on the float4 path (D % 4 == 0, 16-byte
 // aligned rows), G = 64 / lpr bags per wave; a lane-group keeps PB row loads in flight: the PB ids and mask values of a batch of
@@ -24,9 +27,6 @@
 // adds in slot order.  The one store comes last.  Everything else (D % 4 != 0, misaligned rows or outputs, D == 1: the wide
 // weights) takes the same kernel at one column per lane.  Rows wider than a wave (D > 256 on the float4 path, D > 64 on the scalar
 // one) are walked in column blocks by the same lane-group.
-//
-// A second entry, mrec_gather_pool_fields, pools F bags of UNEQUAL lengths per sample in one launch (k_gather_pool_fields below, with
-// the mapping of its work items and why); mrec_gather_pool and what it launches are not touched by it.
 #include "mrec_common.h"
 #include "mrec_optim.h"
 #include "mrec_dense_adam.h"
@@ -76,59 +76,9 @@ __device__ __forceinline__ void vstore(f16o_t* p, const Vf<1>& x) { p->v = __bui
 
 struct PoolGeom { int lpr; int G; };      // lanes per bag, bags per wave
 
-// PB: slots in flight per lane-group (2 for bags of one or two slots, 8 for longer ones: 8 float4 rows = 32 registers)
-template <int VEC, int PB, class K, class OT>
-__global__ __launch_bounds__(256) void k_gather_pool(const float* __restrict__ table, int64_t V, int64_t ld, const K* __restrict__ ids,
-                                                     const float* __restrict__ mask, int64_t B, int L, int mode, OT* __restrict__ out,
-                                                     int64_t ldo, int D, PoolGeom gm) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
-    if (grp >= gm.G) return;                                      // spare lanes; this kernel has no barriers
-    const int64_t b = ((int64_t)blockIdx.x * 4 + wave) * gm.G + grp;
-    const int64_t bc = b < B ? b : B - 1;
-    const K* __restrict__ idb = ids + bc * L;
-    const float* __restrict__ mb = mask ? mask + bc * L : nullptr;
-    const int llast = L - 1;
-    const float fl = (float)L;
-    for (int col = sub * VEC; col < D; col += gm.lpr * VEC) {
-        Vf<VEC> acc = vzero((Vf<VEC>*)nullptr);
-        for (int l0 = 0; l0 < L; l0 += PB) {                      // (L is the launch's: every lane-group walks the same batches)
-            int64_t row[PB];
-            float mk[PB];
-            Vf<VEC> x[PB];
-            bool okr[PB];
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                const int lc = l0 + k < L ? l0 + k : llast;
-                row[k] = (int64_t)idb[lc];
-                mk[k] = mb ? mb[lc] : 1.0f;
-            }
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                okr[k] = row[k] >= 0 && row[k] < V;
-                x[k] = vload(table + (okr[k] ? row[k] : 0) * ld + col, (Vf<VEC>*)nullptr);
-            }
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                vtouch(x[k]);
-                if (!okr[k]) x[k] = vzero((Vf<VEC>*)nullptr);
-            }
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                if (l0 + k < L) {
-                    const Vf<VEC> p = mb ? vscale(x[k], mk[k]) : x[k];
-                    acc = (l0 + k == 0) ? p : vadd(acc, p);       // slot 0 starts the sum (L = 1: the lookup's product, bit for bit)
-                }
-            }
-        }
-        if (mode == 1) acc = vdiv(acc, fl);
-        if (b < B) vstore(out + b * ldo + col, acc);
-    }
-}
-
-// ---- the fields form (mrec_gather_pool_fields): F bags of lengths L_0 .. L_{F-1} per sample, back to back in a row of Ls = sum L_f ids
-// (the reference's multi-hot fields have one bag length EACH: src/datasets.py:290-313, input_shape_dict), pooled per field into
-// columns f * D .. (f + 1) * D - 1 of the sample's output row (the Concat at wide_and_deep.py:348-349).  One launch.
+// F bags of lengths L_0 .. L_{F-1} per sample, back to back in a row of Ls = sum L_f ids (the reference's multi-hot fields have one
+// bag length EACH: src/datasets.py:290-313, input_shape_dict), pooled per field into columns f * D .. (f + 1) * D - 1 of the sample's
+// output row (the Concat at wide_and_deep.py:348-349).  One launch.  (mrec_gather_pool: F = 1, the sample is the bag.)
 //
 // Work-item mapping: a lane-group's work item is bag w = b * F + f -- SAMPLE-major, field-minor.  Neighbouring lane-groups of a wave
 // then take neighbouring fields of one sample and go on into the next sample: their ids (and mask values) are one contiguous stretch
@@ -142,11 +92,14 @@ __global__ __launch_bounds__(256) void k_gather_pool(const float* __restrict__ t
 // The per-field (offset, length) pairs travel BY VALUE in the kernel's arguments, one 32-bit word per field (offset < 4096 and
 // length <= 4096 fit 16 bits each): no table in device memory, no copy, no allocation -- the entry stays capturable.  A lane reads
 // its field's word by a per-lane index: a cached load from the argument segment, once per lane.
-// Arithmetic: k_gather_pool's, per bag (slot 0 starts the sum, product then add in ascending slot order, one IEEE division by
+// Arithmetic: the file header's, per bag (slot 0 starts the sum, product then add in ascending slot order, one IEEE division by
 // (float)L_f -- the FIELD's length -- for the mean, 16-bit outputs rounded once).
+// PB: slots in flight per lane-group (2 for bags of one or two slots, 8 for longer ones: 8 float4 rows = 32 registers)
+// ONE: F == 1, the sample is the bag (every mrec_gather_pool call): b = w, offset 0, length Ls -- without the division by F and the
+// per-lane load from the argument segment, which cost 17 % where the table sits in cache; the rest is one text.
 struct PoolFields { unsigned w[MREC_POOL_MAX_FIELDS]; };      // w[f] = off_f | L_f << 16
 
-template <int VEC, int PB, class K, class OT>
+template <int VEC, int PB, class K, class OT, bool ONE>
 __global__ __launch_bounds__(256) void k_gather_pool_fields(const float* __restrict__ table, int64_t V, int64_t ld, const K* __restrict__ ids,
                                                             const float* __restrict__ mask, unsigned nbags, unsigned F, int Ls, int mode,
                                                             OT* __restrict__ out, int64_t ldo, int D, PoolGeom gm, const PoolFields pf) {
@@ -155,8 +108,8 @@ __global__ __launch_bounds__(256) void k_gather_pool_fields(const float* __restr
     if (grp >= gm.G) return;                                      // spare lanes; this kernel has no barriers
     const unsigned w = (blockIdx.x * 4u + (unsigned)wave) * (unsigned)gm.G + (unsigned)grp;      // (nbags = B * F < 2^31: no wrap)
     const unsigned wc = w < nbags ? w : nbags - 1u;               // a bag past the end reads the last bag, and stores nothing
-    const unsigned b = wc / F, f = wc - b * F;
-    const unsigned fw = pf.w[f];
+    const unsigned b = ONE ? wc : wc / F, f = wc - b * F;
+    const unsigned fw = ONE ? (unsigned)Ls << 16 : pf.w[f];
     const int off = (int)(fw & 0xFFFFu), L = (int)(fw >> 16);
     const K* __restrict__ idb = ids + (int64_t)b * Ls + off;
     const float* __restrict__ mb = mask ? mask + (int64_t)b * Ls + off : nullptr;
@@ -190,7 +143,7 @@ __global__ __launch_bounds__(256) void k_gather_pool_fields(const float* __restr
             for (int k = 0; k < PB; ++k) {
                 if (l0 + k < L) {
                     const Vf<VEC> p = mb ? vscale(x[k], mk[k]) : x[k];
-                    acc = (l0 + k == 0) ? p : vadd(acc, p);       // slot 0 starts the sum
+                    acc = (l0 + k == 0) ? p : vadd(acc, p);       // slot 0 starts the sum (L = 1: the lookup's product, bit for bit)
                 }
             }
         }
@@ -202,8 +155,8 @@ __global__ __launch_bounds__(256) void k_gather_pool_fields(const float* __restr
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 template <class K, class OT>
-int pool_fields_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t B, int32_t F, int32_t Ls, int32_t maxL,
-                     const PoolFields& pf, const float* mask, int32_t mode, OT* out, int64_t ldo, hipStream_t st) {
+int pool_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t B, int32_t F, int32_t Ls, int32_t maxL,
+              const PoolFields& pf, const float* mask, int32_t mode, OT* out, int64_t ldo, hipStream_t st) {
     // float4 lanes where the rows, and the 4-element quads of every field's output block, are aligned (D % 4 == 0: f * D too)
     const uintptr_t oa = sizeof(OT) == 2 ? 7 : 15;
     const bool vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
@@ -213,56 +166,33 @@ int pool_fields_impl(const float* table, int64_t V, int64_t ld, int32_t D, const
     gm.G = 64 / gm.lpr;
     const int64_t nbags = B * F;
     const unsigned blocks = (unsigned)mrec_cdiv(nbags, (int64_t)4 * gm.G);
-#define MREC_POOLF_LAUNCH(VECN, PBN)                                                                                                  \
-    k_gather_pool_fields<VECN, PBN, K, OT><<<blocks, 256, 0, st>>>(table, V, ld, ids, mask, (unsigned)nbags, (unsigned)F, (int)Ls, (int)mode, \
-                                                                  out, ldo, (int)D, gm, pf)
+#define MREC_POOL_LAUNCH1(VECN, PBN, ONE)                                                                                             \
+    k_gather_pool_fields<VECN, PBN, K, OT, ONE><<<blocks, 256, 0, st>>>(table, V, ld, ids, mask, (unsigned)nbags, (unsigned)F, (int)Ls,       \
+                                                                       (int)mode, out, ldo, (int)D, gm, pf)
+#define MREC_POOL_LAUNCH(VECN, PBN) do { if (F == 1) MREC_POOL_LAUNCH1(VECN, PBN, true); else MREC_POOL_LAUNCH1(VECN, PBN, false); } while (0)
     if (vec) {
-        if (maxL <= 2) MREC_POOLF_LAUNCH(4, 2); else MREC_POOLF_LAUNCH(4, 8);
+        if (maxL <= 2) MREC_POOL_LAUNCH(4, 2); else MREC_POOL_LAUNCH(4, 8);
     } else {
-        if (maxL <= 2) MREC_POOLF_LAUNCH(1, 2); else MREC_POOLF_LAUNCH(1, 8);
-    }
-#undef MREC_POOLF_LAUNCH
-    MREC_LAUNCH_CHECK();
-    return MREC_OK;
-}
-
-template <class K, class OT>
-int pool_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t B, int32_t L, const float* mask, int32_t mode,
-              OT* out, int64_t ldo, hipStream_t st) {
-    // float4 lanes where the rows, and the 4-element quads of the output rows, are aligned; else one column per lane
-    const uintptr_t oa = sizeof(OT) == 2 ? 7 : 15;
-    const bool vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
-    const int cols = vec ? D / 4 : D;
-    PoolGeom gm;
-    gm.lpr = cols < 64 ? cols : 64;
-    gm.G = 64 / gm.lpr;
-    const unsigned blocks = (unsigned)mrec_cdiv(B, (int64_t)4 * gm.G);
-#define MREC_POOL_LAUNCH(VECN, PBN) \
-    k_gather_pool<VECN, PBN, K, OT><<<blocks, 256, 0, st>>>(table, V, ld, ids, mask, B, (int)L, (int)mode, out, ldo, (int)D, gm)
-    if (vec) {
-        if (L <= 2) MREC_POOL_LAUNCH(4, 2); else MREC_POOL_LAUNCH(4, 8);
-    } else {
-        if (L <= 2) MREC_POOL_LAUNCH(1, 2); else MREC_POOL_LAUNCH(1, 8);
+        if (maxL <= 2) MREC_POOL_LAUNCH(1, 2); else MREC_POOL_LAUNCH(1, 8);
     }
 #undef MREC_POOL_LAUNCH
+#undef MREC_POOL_LAUNCH1
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
 
-}  // namespace
-
-MREC_API int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B, int32_t L,
-                              const float* mask, int32_t mode, void* out, int32_t out_kind, int64_t ldo, void* stream) {
-    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || (mode != 0 && mode != 1)) return MREC_EINVAL;
-    if (B < 0 || L < 1 || D <= 0 || V < 0 || ld < D) return MREC_EINVAL;
-    if (ldo == 0) ldo = D;
-    if (ldo < D) return MREC_EINVAL;
-    if (L > MREC_POOL_MAX_BAG || B > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;
+// what both entries check first, and what both do last (pf: the bags of a sample, Ls ids, the longest maxL)
+inline bool pool_args_ok(int32_t id_bytes, int32_t out_kind, int32_t mode, int64_t B, int32_t D, int64_t V, int64_t ld) {
+    return (id_bytes == 4 || id_bytes == 8) && out_kind >= 0 && out_kind <= 2 && (mode == 0 || mode == 1) && B >= 0 && D > 0 && V >= 0 && ld >= D;
+}
+int pool_run(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B, int32_t F, int32_t Ls,
+             int32_t maxL, const PoolFields& pf, const float* mask, int32_t mode, void* out, int32_t out_kind, int64_t ldo, void* stream) {
+    if (B * F > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;      // (bags are numbered in 32 bits)
     if (B == 0) return MREC_OK;
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!table || !ids || !out) return MREC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-#define MREC_POOL(KT, OT) return pool_impl<KT, OT>(table, V, ld, D, (const KT*)ids, B, L, mask, mode, (OT*)out, ldo, st)
+#define MREC_POOL(KT, OT) return pool_impl<KT, OT>(table, V, ld, D, (const KT*)ids, B, F, Ls, maxL, pf, mask, mode, (OT*)out, ldo, st)
     if (id_bytes == 4) {
         if (out_kind == 0) { MREC_POOL(int32_t, float); }
         if (out_kind == 1) { MREC_POOL(int32_t, bf16o_t); }
@@ -274,11 +204,23 @@ MREC_API int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t
 #undef MREC_POOL
 }
 
+}  // namespace
+
+MREC_API int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B, int32_t L,
+                              const float* mask, int32_t mode, void* out, int32_t out_kind, int64_t ldo, void* stream) {
+    if (!pool_args_ok(id_bytes, out_kind, mode, B, D, V, ld) || L < 1) return MREC_EINVAL;
+    if (ldo == 0) ldo = D;
+    if (ldo < D) return MREC_EINVAL;
+    if (L > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
+    PoolFields pf{};
+    pf.w[0] = (unsigned)L << 16;         // one field: offset 0, length L
+    return pool_run(table, V, ld, D, ids, id_bytes, B, 1, L, L, pf, mask, mode, out, out_kind, ldo, stream);
+}
+
 MREC_API int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
                                      int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
                                      int64_t ldo, void* stream) {
-    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || (mode != 0 && mode != 1)) return MREC_EINVAL;
-    if (B < 0 || F < 1 || D <= 0 || V < 0 || ld < D || !field_len) return MREC_EINVAL;
+    if (!pool_args_ok(id_bytes, out_kind, mode, B, D, V, ld) || F < 1 || !field_len) return MREC_EINVAL;
     if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
     PoolFields pf{};
     int64_t Ls = 0;
@@ -293,19 +235,5 @@ MREC_API int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, 
     }
     if (ldo == 0) ldo = (int64_t)F * D;
     if (ldo < (int64_t)F * D) return MREC_EINVAL;
-    if (B * F > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;      // (bags are numbered in 32 bits)
-    if (B == 0) return MREC_OK;
-    if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
-    if (!table || !ids || !out) return MREC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-#define MREC_POOLF(KT, OT) return pool_fields_impl<KT, OT>(table, V, ld, D, (const KT*)ids, B, F, (int32_t)Ls, maxL, pf, mask, mode, (OT*)out, ldo, st)
-    if (id_bytes == 4) {
-        if (out_kind == 0) { MREC_POOLF(int32_t, float); }
-        if (out_kind == 1) { MREC_POOLF(int32_t, bf16o_t); }
-        MREC_POOLF(int32_t, f16o_t);
-    }
-    if (out_kind == 0) { MREC_POOLF(int64_t, float); }
-    if (out_kind == 1) { MREC_POOLF(int64_t, bf16o_t); }
-    MREC_POOLF(int64_t, f16o_t);
-#undef MREC_POOLF
+    return pool_run(table, V, ld, D, ids, id_bytes, B, F, (int32_t)Ls, maxL, pf, mask, mode, out, out_kind, ldo, stream);
 }

@@ -8,14 +8,15 @@ gradient applied in place.
     ...                                # the model's forward and backward produce dy, the gradient of x
     emb.apply_(dy)                     # one plan of the looked-up ids, one pooled apply
 
-Forward: ops.gather_pool (mrec_gather_pool: no [B * L, dim] intermediate).  Backward: position (b, l) of a bag contributes
+Forward: one pooled lookup (ops.gather_pool_fields: no [B * L, dim] intermediate).  Backward: position (b, l) of a bag contributes
 (dy[b] * mask[b, l]) * gs to row ids[b, l], gs = grad_scale for mode "sum" and fp32(grad_scale / L) for "mean" (ReduceMean's bprop
-divides by the bag's length); ops.sparse_plan over the ids and the pooled sparse apply (pool=L: the gradient rows are read as
-dy[i // L], the L-fold expanded gradient is never written).  Optimizers:
+divides by the bag's length); ops.sparse_plan over the ids and the pooled sparse apply (the gradient rows are read as dy[i // L], the
+L-fold expanded gradient is never written).  An integer `bag` is the one-field case of the fields form below, fields=(L,), over
+the ids seen as [B * F, L].  Optimizers:
   "lazy_adam"  nn.LazyAdam on the touched rows (ops.sparse_lazy_adam_);
   "ftrl"       nn.FTRL on the touched rows (ops.sparse_ftrl_): the wide weights, dim = 1, mode "sum";
   "adam"       dense nn.Adam over the whole table, the reference's choice for this model (wide_and_deep.py:532-535): ops.segment_sum
-               (pool=L) + ops.dense_adam_rows_l2_ with l2_scaled = 0, which gives every row outside the plan a zero gradient -- so an
+               (fields=) + ops.dense_adam_rows_l2_ with l2_scaled = 0, which gives every row outside the plan a zero gradient -- so an
                untouched row's m and v decay and the row keeps moving on its momentum, exactly as under the dense optimizer.  32-bit
                ids only (that entry numbers rows in 32 bits).
 
@@ -31,7 +32,8 @@ contributes (dy[b, f * dim : (f + 1) * dim] * mask[b, s]) * gs_f with gs_f = fp3
 (ops.* with fields=bag, field_scale=gs).  One plan, so an id that occurs in several fields receives the SUM of their gradients and
 ONE optimizer update per step, as the reference's optimizer does with the table's summed gradient -- a lookup and an apply_ per
 distinct length would update such a row once per call, which under LazyAdam, FTRL or dense Adam is a different result.  All three
-optimizers; an integer `bag` behaves as it always did, [B, F, L] ids included.
+optimizers.  `emb.fields` holds the bag lengths in both forms -- (L,) for an integer `bag` -- and `emb.bag` their sum; a sample's ids may
+hold at most ops.MAX_BAG = 4096 slots (a longer `bag` is refused by lookup with ValueError).
 The wide side of the reference's multi-hot fields (wide_and_deep.py:377-420: ReduceSum of every field's masked [V, 1] weights, the
 fields' sums added up) needs no fields form: a sum over fields of sums over slots is ONE bag of length Ls, mode "sum", dim = 1 --
 MultiHotEmbedding(vocab, 1, bag=sum(lengths), mode="sum", optimizer="ftrl") on the same [B, Ls] ids.
@@ -55,13 +57,16 @@ class MultiHotEmbedding:
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         if optimizer not in _OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {_OPTIMIZERS}, got {optimizer!r}")
-        self.fields = None                  # the fields form: the bag lengths (L_0, .., L_{F-1}); bag is then their sum
         if isinstance(bag, (tuple, list)):
-            self.fields = ops._fields(bag)
-            bag = sum(self.fields)
-        if int(vocab) < 1 or int(dim) < 1 or int(bag) < 1:
+            bag = ops._fields(bag)
+        elif int(bag) < 1:
             raise ValueError("vocab, dim and bag must be >= 1")
-        self.vocab, self.dim, self.bag = int(vocab), int(dim), int(bag)
+        else:
+            bag = (int(bag),)
+        if int(vocab) < 1 or int(dim) < 1:
+            raise ValueError("vocab, dim and bag must be >= 1")
+        self.fields = bag                   # the bag lengths (L_0, .., L_{F-1}) of a sample; bag is their sum
+        self.vocab, self.dim, self.bag = int(vocab), int(dim), sum(bag)
         self.mode, self.optimizer, self.out_dtype = mode, optimizer, out_dtype
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -86,14 +91,9 @@ class MultiHotEmbedding:
         self._ids = self._mask = None
 
     def _bags(self, ids):
-        if self.fields is not None:
-            if ids.dim() != 2 or ids.shape[1] != self.bag:
-                raise TypeError(f"ids must be [B, {self.bag}]: the bags of lengths {self.fields} back to back")
-            if self.optimizer == "adam" and ids.dtype != torch.int32:
-                raise TypeError("optimizer 'adam' takes int32 ids (the dense row update numbers rows in 32 bits)")
-            return ids.shape[0], len(self.fields)
-        if ids.dim() not in (2, 3) or ids.shape[-1] != self.bag:
-            raise TypeError(f"ids must be [B, {self.bag}] or [B, F, {self.bag}] (bags of {self.bag} ids)")
+        """(B, G): ids [B, Ls] are B samples of one group of the fields; one field also takes [B, G, L], G bags of its length per sample"""
+        if ids.dim() not in ((2, 3) if len(self.fields) == 1 else (2,)) or ids.shape[-1] != self.bag:
+            raise TypeError(f"ids must be [B, {self.bag}] (the bags of lengths {self.fields} back to back), or [B, F, {self.bag}] for one length")
         if self.optimizer == "adam" and ids.dtype != torch.int32:
             raise TypeError("optimizer 'adam' takes int32 ids (the dense row update numbers rows in 32 bits)")
         return ids.shape[0], (ids.shape[1] if ids.dim() == 3 else 1)
@@ -103,21 +103,17 @@ class MultiHotEmbedding:
         concat of its pooled fields).  mask: float32 0/1 (or any weight) per id, None = all ones.  out: where the rows go -- for
         [B, L] ids any [B, dim] column block with unit column stride; for [B, F, L] ids a contiguous [B, F * dim] tensor.
         Fields form (bag=(L_0, ..)): ids, mask [B, Ls] -> [B, F * dim]; out: any [B, F * dim] column block with unit column stride."""
-        B, F = self._bags(ids)
+        B, G = self._bags(ids)
         if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
             raise TypeError("mask must be float32 of the shape of ids")
-        if self.fields is not None:
-            out = ops.gather_pool_fields(self.table, ids, self.fields, mask, mode=self.mode, out=out, out_dtype=self.out_dtype)
-            self._ids = ids.contiguous()
-            self._mask = mask.contiguous() if mask is not None else None
-            return out
-        flat = ids.reshape(B * F, self.bag)
-        fmask = mask.reshape(B * F, self.bag) if mask is not None else None
+        W = len(self.fields) * self.dim        # columns of one group of the fields
+        flat = ids.reshape(B * G, self.bag)
+        fmask = mask.reshape(B * G, self.bag) if mask is not None else None
         if out is None:
-            out = torch.empty((B, F * self.dim), dtype=self.out_dtype, device=self.table.device)
-        elif tuple(out.shape) != (B, F * self.dim) or (F > 1 and not out.is_contiguous()):
+            out = torch.empty((B, G * W), dtype=self.out_dtype, device=self.table.device)
+        elif tuple(out.shape) != (B, G * W) or (G > 1 and not out.is_contiguous()):
             raise TypeError("out must be [B, F * dim] (contiguous when ids hold more than one field)")
-        ops.gather_pool(self.table, flat, fmask, mode=self.mode, out=out if F == 1 else out.view(B * F, self.dim))
+        ops.gather_pool_fields(self.table, flat, self.fields, fmask, mode=self.mode, out=out if G == 1 else out.view(B * G, W))
         self._ids = flat.contiguous()
         self._mask = fmask.contiguous() if fmask is not None else None
         return out
@@ -127,17 +123,14 @@ class MultiHotEmbedding:
         'lazy_adam' and 'adam'): in place on the table and the optimizer state."""
         if self._ids is None:
             raise RuntimeError("apply_ follows a lookup")
-        ids, mask, L = self._ids, self._mask, self.bag
-        nbags = ids.shape[0] * (len(self.fields) if self.fields is not None else 1)
+        ids, mask = self._ids, self._mask
+        nbags = ids.shape[0] * len(self.fields)
         if dy.dim() != 2 or dy.shape[0] * dy.shape[1] != nbags * self.dim or not dy.is_contiguous():
             raise TypeError("dy must be the contiguous [B, F * dim] gradient of the last lookup's result")
         g = dy.view(nbags, self.dim)
-        if self.fields is not None:        # one scale per field in place of grad_scale, fields= in place of pool=
-            fs = tuple(float(np.float32(grad_scale) / np.float32(Lf)) if self.mode == "mean" else float(grad_scale) for Lf in self.fields)
-            pkw = dict(fields=self.fields, field_scale=fs)
-        else:
-            gs = float(np.float32(grad_scale) / np.float32(L)) if self.mode == "mean" else float(grad_scale)
-            pkw = dict(grad_scale=gs, pool=L)
+        # one scale per field in place of grad_scale
+        fs = tuple(float(np.float32(grad_scale) / np.float32(Lf)) if self.mode == "mean" else float(grad_scale) for Lf in self.fields)
+        pkw = dict(fields=self.fields, field_scale=fs)
         plan = ops.sparse_plan(ids)
         self.beta1_power = np.float32(self.beta1_power * self.beta1)
         self.beta2_power = np.float32(self.beta2_power * self.beta2)

@@ -219,33 +219,27 @@ def _field_scales(lens, field_scale, grad_scale):
     return sc
 
 
-def _call_clipped(max_norm, name, *args, pool=None, fields=None):
+def _call_clipped(max_norm, name, *args, arm=None):
     """_lib.call(name, *args) -- a sparse apply -- armed with max_norm (mrec_sparse_apply_next_max_norm: the NEXT LazyAdam apply of this
-    host thread clips) and / or pool=L (mrec_sparse_apply_next_pool: the NEXT apply reads position i's gradient row from g[i // L])
-    or fields=(lengths, scales) (mrec_sparse_apply_next_pool_fields: bags of unequal lengths, one scale per field).
+    host thread clips) and / or arm = (entry, *its arguments), the pooled form (_pooled: mrec_sparse_apply_next_pool, the NEXT apply
+    reads position i's gradient row from g[i // L], or mrec_sparse_apply_next_pool_fields, bags of unequal lengths, one scale per field).
     Everything is evaluated before the arm, and an exception between the arm and the apply (ctypes refusing an argument) disarms
     again, so that no later apply of another table is clipped or pooled by mistake."""
-    if max_norm is None and pool is None and fields is None:
+    if max_norm is None and arm is None:
         _lib.call(name, *args)
         return
     c = None if max_norm is None else _max_norm(max_norm)
-    L = None if pool is None else _pool(pool)
-    if fields is not None:
-        lens, scales = fields
-        fl, fs = (C.c_int32 * len(lens))(*lens), (C.c_float * len(lens))(*scales)
     try:
         if c is not None:
             _lib.call("mrec_sparse_apply_next_max_norm", c)
-        if L is not None:
-            _lib.call("mrec_sparse_apply_next_pool", L)
-        if fields is not None:
-            _lib.call("mrec_sparse_apply_next_pool_fields", len(lens), fl, fs)
+        if arm is not None:
+            _lib.call(*arm)
         _lib.call(name, *args)
     except BaseException:
         if c is not None:
             _lib.lib().mrec_sparse_apply_next_max_norm(0.0)      # (EINVAL: leaves nothing armed; the C side disarms on its own refusals)
-        if L is not None or fields is not None:
-            _lib.lib().mrec_sparse_apply_next_pool(1)            # (1: the plain apply; disarms the fields form too)
+        if arm is not None:
+            _lib.lib().mrec_sparse_apply_next_pool(1)            # (1: the plain apply; disarms either form)
         raise
 
 
@@ -281,6 +275,27 @@ def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32, m
 _OUT_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
+def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype):
+    """the one lookup behind gather_pool and gather_pool_fields (mrec_gather_pool_fields): ids, mask [B, sum(lens)] -> out [B, F * D]"""
+    V, D, ld = _table(table)
+    sfx = _suffix(ids)
+    if mode not in ("sum", "mean"):
+        raise ValueError(f"{who} mode must be 'sum' or 'mean', got {mode!r}")
+    B, F = ids.shape[0], len(lens)
+    if out is None:
+        if out_dtype not in _OUT_KIND:
+            raise TypeError(f"{who} out_dtype must be float32, bfloat16 or float16")
+        out = torch.empty((B, F * D), dtype=out_dtype, device=table.device)
+    elif out.dtype not in _OUT_KIND or out.dim() != 2 or tuple(out.shape) != (B, F * D) or out.stride(1) != 1:
+        raise TypeError(f"{who} out must be a [{B}, {F * D}] float32 / bfloat16 / float16 tensor with unit column stride")
+    ldo = out.stride(0) if B > 1 else F * D
+    ids = ids.contiguous()
+    mask = mask.contiguous() if mask is not None else None
+    _lib.call("mrec_gather_pool_fields", _ptr(table), V, ld, D, _ptr(ids), 4 if sfx == "i32" else 8, B, F, (C.c_int32 * F)(*lens),
+              _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
+    return out
+
+
 def gather_pool(table, ids, mask=None, mode="mean", out=None, out_dtype=torch.float32):
     """The multi-hot lookup, Gather -> Mul(mask) -> ReduceMean / ReduceSum over the bag axis in one pass
     (wide_and_deep_multitable/src/wide_and_deep.py:301-346,377-418): ids [..., L] -> [..., D], out[b] = sum_l table[ids[b, l]] *
@@ -288,32 +303,16 @@ def gather_pool(table, ids, mask=None, mode="mean", out=None, out_dtype=torch.fl
     ReduceMean does.  mask: float32, one value per id (None: all ones).  out: a [B, D] tensor or column block (unit column stride;
     its other columns are left alone) in float32 / bfloat16 / float16; 16-bit outputs are rounded once, at the end."""
     _need_cuda(table, ids, mask, out)
-    V, D, ld = _table(table)
-    sfx = _suffix(ids)
     if ids.dim() < 1:
         raise TypeError("ids must be [..., L]: a bag of L ids per sample")
-    if mode not in ("sum", "mean"):
-        raise ValueError(f"gather_pool mode must be 'sum' or 'mean', got {mode!r}")
     L = ids.shape[-1]
-    flat = ids.reshape(-1, L).contiguous()
-    B = flat.shape[0]
+    flat = ids.reshape(-1, L)
     if mask is not None:
         if mask.dtype != torch.float32 or mask.numel() != flat.numel():
             raise TypeError("mask must be float32 with one value per id")
-        mask = mask.reshape(B, L).contiguous()
-    if out is None:
-        if out_dtype not in _OUT_KIND:
-            raise TypeError("gather_pool out_dtype must be float32, bfloat16 or float16")
-        out = torch.empty((B, D), dtype=out_dtype, device=table.device)
-        ret = out.view(tuple(ids.shape[:-1]) + (D,))
-    else:
-        if out.dtype not in _OUT_KIND or out.dim() != 2 or tuple(out.shape) != (B, D) or out.stride(1) != 1:
-            raise TypeError("gather_pool out must be a [B, D] float32 / bfloat16 / float16 tensor with unit column stride")
-        ret = out
-    ldo = out.stride(0) if B > 1 else D
-    _lib.call("mrec_gather_pool", _ptr(table), V, ld, D, _ptr(flat), 4 if sfx == "i32" else 8, B, L, _ptr(mask),
-              1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
-    return ret
+        mask = mask.reshape(flat.shape)
+    ret = _gather_pool("gather_pool", table, flat, (L,), mask, mode, out, out_dtype)        # one field: the sample is the bag
+    return ret if out is not None else ret.view(tuple(ids.shape[:-1]) + ret.shape[1:])
 
 
 def gather_pool_fields(table, ids, field_len, mask=None, mode="mean", out=None, out_dtype=torch.float32):
@@ -323,30 +322,12 @@ def gather_pool_fields(table, ids, field_len, mask=None, mode="mean", out=None, 
     wide_and_deep.py:348-349).  Per bag the arithmetic is gather_pool's; mode="mean" divides by the FIELD's own length.  mask: float32
     [B, Ls] or None.  out: a [B, F * D] tensor or column block (unit column stride) in float32 / bfloat16 / float16."""
     _need_cuda(table, ids, mask, out)
-    V, D, ld = _table(table)
-    sfx = _suffix(ids)
     lens = _fields(field_len)
-    F, Ls = len(lens), sum(lens)
-    if mode not in ("sum", "mean"):
-        raise ValueError(f"gather_pool_fields mode must be 'sum' or 'mean', got {mode!r}")
-    if ids.dim() != 2 or ids.shape[1] != Ls:
-        raise TypeError(f"ids must be [B, {Ls}]: the bags of lengths {lens} back to back")
-    flat = ids.contiguous()
-    B = flat.shape[0]
-    if mask is not None:
-        if mask.dtype != torch.float32 or tuple(mask.shape) != (B, Ls):
-            raise TypeError("mask must be float32 of the shape of ids")
-        mask = mask.contiguous()
-    if out is None:
-        if out_dtype not in _OUT_KIND:
-            raise TypeError("gather_pool_fields out_dtype must be float32, bfloat16 or float16")
-        out = torch.empty((B, F * D), dtype=out_dtype, device=table.device)
-    elif out.dtype not in _OUT_KIND or out.dim() != 2 or tuple(out.shape) != (B, F * D) or out.stride(1) != 1:
-        raise TypeError("gather_pool_fields out must be a [B, F * D] float32 / bfloat16 / float16 tensor with unit column stride")
-    ldo = out.stride(0) if B > 1 else F * D
-    _lib.call("mrec_gather_pool_fields", _ptr(table), V, ld, D, _ptr(flat), 4 if sfx == "i32" else 8, B, F, (C.c_int32 * F)(*lens),
-              _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
-    return out
+    if ids.dim() != 2 or ids.shape[1] != sum(lens):
+        raise TypeError(f"ids must be [B, {sum(lens)}]: the bags of lengths {lens} back to back")
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
+        raise TypeError("mask must be float32 of the shape of ids")
+    return _gather_pool("gather_pool_fields", table, ids, lens, mask, mode, out, out_dtype)
 
 
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
@@ -468,24 +449,17 @@ def wide_sum(w, ids, wts, bias=None):
     return out
 
 
-def _grads(plan, g, D, allow_bf16=False, pool=None, fields=None):
-    """the gradient rows and their stride: one row per position, or (pool=L) one per bag of L positions, ceil(n / L) of them, or
-    (fields=lengths) one per bag of a sample's F bags, n / sum(lengths) * F of them"""
+def _grads(plan, g, D, allow_bf16=False, rows=None):
+    """the gradient rows and their stride: one row per position, or (rows = (count, how it is counted): the pooled forms, _pooled) one
+    per bag"""
     if g.dtype != torch.float32 and not (allow_bf16 and g.dtype in (torch.bfloat16, torch.float16)):
         raise TypeError("row gradients must be float32" + (", bfloat16 or float16" if allow_bf16 else ""))
-    if fields is not None:
-        if pool is not None:
-            raise ValueError("pool= and fields= are two forms of the same thing: pass one")
-        Ls = sum(fields)
-        if plan.n % Ls:
-            raise TypeError(f"fields={fields}: the plan's {plan.n} positions are not whole samples of {Ls} ids")
-        rows = plan.n // Ls * len(fields)
-        if g.numel() != rows * D:
-            raise TypeError(f"fields={fields}: g must hold n / {Ls} * {len(fields)} = {rows} gradient rows of {D} columns")
+    if rows is None:
+        rows = plan.n
     else:
-        rows = plan.n if pool is None else -(-plan.n // _pool(pool))
-    if pool is not None and g.numel() != rows * D:
-        raise TypeError(f"pool={pool}: g must hold ceil(n / pool) = {rows} gradient rows of {D} columns")
+        rows, what = rows
+        if g.numel() != rows * D:
+            raise TypeError(f"{what} = {rows} gradient rows of {D} columns")
     g2 = g.reshape(rows, D)
     if g2.stride(1) != 1:
         g2 = g2.contiguous()
@@ -493,14 +467,34 @@ def _grads(plan, g, D, allow_bf16=False, pool=None, fields=None):
 
 
 def _fields_arm(fields, field_scale, grad_scale):
-    """(what _call_clipped arms, the grad_scale the armed call is given): the fields form takes its scales per field and 1.0 as the
-    call's own"""
+    """((lengths, scales) or None without fields=, the grad_scale the armed call is given): the fields form takes its scales per field
+    and 1.0 as the call's own"""
     if fields is None:
         if field_scale is not None:
             raise ValueError("field_scale goes with fields=")
         return None, grad_scale
     lens = _fields(fields)
     return (lens, _field_scales(lens, field_scale, grad_scale)), 1.0
+
+
+def _pooled(plan, pool, fields, field_scale, grad_scale):
+    """pool= / fields= of a sparse apply -> (arm, rows, grad_scale): what _call_clipped arms (None, None: the plain apply), the gradient
+    rows the armed call reads (their count and how it is counted, for _grads) and the grad_scale it is given.  pool=L: one row per bag of L positions, ceil(n / L) of them (the last
+    bag may be short); fields=lengths: one per bag of a sample's F bags, n / sum(lengths) * F of them (whole samples)."""
+    fa, grad_scale = _fields_arm(fields, field_scale, grad_scale)
+    if fa is None:
+        if pool is None:
+            return None, None, grad_scale
+        L = _pool(pool)
+        return ("mrec_sparse_apply_next_pool", L), (-(-plan.n // L), f"pool={L}: g must hold ceil(n / pool)"), grad_scale
+    if pool is not None:
+        raise ValueError("pool= and fields= are two forms of the same thing: pass one")
+    lens, scales = fa
+    F, Ls = len(lens), sum(lens)
+    if plan.n % Ls:
+        raise TypeError(f"fields={lens}: the plan's {plan.n} positions are not whole samples of {Ls} ids")
+    rows = (plan.n // Ls * F, f"fields={lens}: g must hold n / {Ls} * {F}")
+    return ("mrec_sparse_apply_next_pool_fields", F, (C.c_int32 * F)(*lens), (C.c_float * F)(*scales)), rows, grad_scale
 
 
 def _row_scale(plan, row_scale):
@@ -530,21 +524,22 @@ def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None, fields=None,
     [B, F * D] gradient seen as [B * F, D], and position i = b * Ls + s, s in field f, contributes (g[b * F + f] * row_scale[i]) *
     field_scale[f]; field_scale (one float per field) takes the place of grad_scale, without it every field's scale is grad_scale."""
     _need_cuda(g, row_scale)
-    arm, grad_scale = _fields_arm(fields, field_scale, grad_scale)
+    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
     D = g.shape[-1]
-    if arm is not None and g.dim() == 2 and len(arm[0]) > 1 and g.shape[0] * sum(arm[0]) == plan.n and D % len(arm[0]) == 0:
-        D //= len(arm[0])                 # g as the lookup's result has it, [B, F * D]: the same memory as [B * F, D]
-    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool, fields=arm[0] if arm else None)
+    F = len(fields) if fields is not None else 1
+    if F > 1 and g.dim() == 2 and g.shape[0] * sum(fields) == plan.n and D % F == 0:
+        D //= F                           # g as the lookup's result has it, [B, F * D]: the same memory as [B * F, D]
+    g2, ldg = _grads(plan, g, D, allow_bf16=True, rows=rows)
     rs = _row_scale(plan, row_scale)
     out = torch.empty((max(plan.n, 1), D), dtype=torch.float32, device=g.device)
     ws = _apply_ws(plan, D, g.device)
     if g2.dtype == torch.float32:
         _call_clipped(None, "mrec_segment_sum_f32", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                      _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(), pool=pool, fields=arm)
+                      _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(), arm=arm)
     else:       # 16-bit row gradients (what the mixed-precision MLP backward produces): widened exactly, summed in fp32
         _call_clipped(None, "mrec_segment_sum_g16", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
                       _ptr(g2), 1 if g2.dtype == torch.bfloat16 else 2, ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(),
-                      pool=pool, fields=arm)
+                      arm=arm)
     return out
 
 
@@ -561,8 +556,8 @@ def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, be
     for t in (m, v):
         if _table(t) != (V, D, ld):
             raise ValueError("p, m, v must share shape and row stride")
-    arm, grad_scale = _fields_arm(fields, field_scale, grad_scale)
-    g2, ldg = _grads(plan, g, D, allow_bf16=True, pool=pool, fields=arm[0] if arm else None)
+    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
+    g2, ldg = _grads(plan, g, D, allow_bf16=True, rows=rows)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, p.device)
     sfx = _suffix(plan.uniq_buf)
@@ -571,7 +566,7 @@ def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, be
     args = (_ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets),
             plan.n, _ptr(g2), ldg, _ptr(rs), lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(ws),
             ws.numel(), _stream())
-    _call_clipped(max_norm, fn + sfx, *args, pool=pool, fields=arm)
+    _call_clipped(max_norm, fn + sfx, *args, arm=arm)
 
 
 class ApplyFinish(C.Structure):      # mrec_apply_finish_t
@@ -684,14 +679,14 @@ def sparse_ftrl_(var, accum, linear, plan, g, row_scale=None, lr=5e-2, l1=1e-8, 
     for t in (accum, linear):
         if _table(t) != (V, D, ld):
             raise ValueError("var, accum, linear must share shape and row stride")
-    arm, grad_scale = _fields_arm(fields, field_scale, grad_scale)
-    g2, ldg = _grads(plan, g, D, pool=pool, fields=arm[0] if arm else None)
+    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
+    g2, ldg = _grads(plan, g, D, rows=rows)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, var.device)
     sfx = _suffix(plan.uniq_buf)
     _call_clipped(None, f"mrec_sparse_ftrl_f32_{sfx}", _ptr(var), _ptr(accum), _ptr(linear), V, ld, D, _ptr(plan.uniq_buf),
                   _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, l1,
-                  l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _stream(), pool=pool, fields=arm)
+                  l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _stream(), arm=arm)
 
 
 def _flat_same(*ts):

@@ -1,5 +1,5 @@
-"""Multi-hot fields on the GPU: the pooled lookup (mrec_gather_pool) bit for bit against its host restatement (tests/_pool_ref.py), the
-pooled sparse apply (mrec_sparse_apply_next_pool) bit for bit against the restatement of the apply's order of additions (tests/
+"""Multi-hot fields on the GPU: the pooled lookup (ops.gather_pool, which runs mrec_gather_pool_fields with one field, and the C entry
+mrec_gather_pool itself) bit for bit against its host restatement (tests/_pool_ref.py), the pooled sparse apply (mrec_sparse_apply_next_pool) bit for bit against the restatement of the apply's order of additions (tests/
 _apply_order.py) AND against the plain apply on the explicitly expanded gradient, the arming rules, and MultiHotEmbedding's training
 loop, eager and captured.  Every comparison is on raw bits, over all rows (touched and untouched)."""
 import os
@@ -73,6 +73,26 @@ def test_gather_pool_bitwise(dev, D, L):
                 got = ops.gather_pool(tt, tid, tm, mode=mode, out_dtype=odt)
                 assert got.dtype == odt and tuple(got.shape) == (B, D)
                 _same(_bits(got), P.gather_pool(table, ids, mask, mode, _KIND[odt]), f"D={D} L={L} {idt} {odt} {mode}")
+
+
+@pytest.mark.parametrize("D,L", [(64, 2), (64, 7), (3, 1), (3, 9)])
+def test_mrec_gather_pool_entry_bitwise(dev, D, L):
+    """the C entry itself (ops.gather_pool goes through mrec_gather_pool_fields): float4 and single-column lanes, two and eight slots
+    in flight, int32 and int64 ids, mean into fp32 and sum into bf16, ldo = 0 (the default row stride)"""
+    from mindrec_amd import _lib, ops
+    rng = np.random.default_rng(D * 10 + L)
+    V, B = 700, 517
+    table = rng.standard_normal((V, D)).astype(np.float32)
+    tt = T(table, dev)
+    mask = _masks(rng, B, L)
+    tm = T(mask, dev)
+    for idt, mode, odt in ((np.int32, "mean", torch.float32), (np.int64, "sum", torch.bfloat16)):
+        ids = _bag_ids(rng, B, L, V, idt)
+        tid = T(ids, dev)
+        out = torch.empty((B, D), dtype=odt, device=dev)
+        _lib.call("mrec_gather_pool", ops._ptr(tt), V, D, D, ops._ptr(tid), ids.itemsize, B, L, ops._ptr(tm), 1 if mode == "mean" else 0,
+                  ops._ptr(out), ops._OUT_KIND[odt], 0, ops._stream())
+        _same(_bits(out), P.gather_pool(table, ids, mask, mode, _KIND[odt]), f"mrec_gather_pool D={D} L={L} {mode} {odt}")
 
 
 @pytest.mark.parametrize("D,L", [(1, 7), (3, 2), (64, 8), (80, 33), (252, 1), (260, 7), (70, 8)])
@@ -262,6 +282,34 @@ def test_pooled_apply_bitwise(dev, op, D, gdt, L, regime):
     for name, x, y, ref in zip("012", ta, tb, st):
         _same(x.cpu().numpy(), ref, f"{op} state {name} vs restatement")
         assert torch.equal(x.view(torch.int32), y.view(torch.int32)), f"{op} state {name}: pooled vs the expanded gradient"
+
+
+@pytest.mark.parametrize("L,n,D,binary_mask", [(5000, 5003, 4, False), (3, 30, 6, True)])
+def test_pooled_apply_one_length_as_one_field(dev, L, n, D, binary_mask):
+    """pool=L runs the fields form's windows with one field, and two cases are its own.  L = 5000: above the fields form's cap of 4096
+    bag slots and above the 16-bit range of a field offset, n = 5003: the last bag is partial (three positions) -- 2 gradient rows.
+    L = 3, grad_scale = 0.37 under a 0/1 mask, D = 6 (8-byte lanes): the contribution's second factor is the armed call's own
+    grad_scale.  int32 ids drawn from 8 rows (long runs), segment sum and LazyAdam, against the host restatement alone."""
+    from mindrec_amd import ops
+    rng = np.random.default_rng(L + n)
+    V, gs = 8, 0.37
+    ids = rng.integers(0, V, size=n).astype(np.int32)
+    rows = -(-n // L)
+    vec = A.lane_width(D, D, D, [0], 0, 4)
+    aw = ops.apply_window(D, vec == 4)
+    idx = A.Index(ids)
+    g, tg = _g_rows(rng, rows, D, torch.float32, dev)
+    rs = (rng.random(n) < 0.6).astype(np.float32) if binary_mask else (rng.random(n) + 0.25).astype(np.float32)
+    trs = T(rs, dev)
+    plan = ops.sparse_plan(T(ids, dev))
+    G = P.sums(idx, P.pooled_contributions(g, L, n, rs, gs), D, vec, aw)
+    _same(ops.segment_sum(plan, tg, trs, grad_scale=gs, pool=L)[: idx.U].cpu().numpy(), G, "pooled segment sum")
+    st = _state(rng, V, D, "adam")
+    ts = [T(a, dev) for a in st]
+    ops.sparse_lazy_adam_(*ts, plan, tg, trs, pool=L, beta1_power=0.81, beta2_power=0.998001, grad_scale=gs)
+    A.lazy_adam(*st, idx.uniq, G, b1_pow=0.81, b2_pow=0.998001)
+    for name, x, ref in zip("pmv", ts, st):
+        _same(x.cpu().numpy(), ref, f"pooled LazyAdam {name}")
 
 
 # ---- 3. arming ----------------------------------------------------------------------------------------------------------------------

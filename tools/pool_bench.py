@@ -44,27 +44,54 @@ FIELD_VARIANTS = ("fwd_perlen", "fwd_fields", "fwd_padded", "bwd_perlen", "bwd_f
 FIELDS = (3, 5, 4, 3, 4, 2)
 
 
-def run_fields(shape):
+def _setup(shape, id_shape, dy_shape):
+    """what both forms measure on: the table (V 20 900 and Zipf-like ids for "ref" / "fields-ref", else V 20 000 000 and uniform ids),
+    its LazyAdam state, ids and a 0/1 mask of id_shape, the pooled rows' gradient, and the one-row tensor of the marker launches"""
     import numpy as np
     import torch
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from mindrec_amd import ops
     dev = torch.device("cuda:0")
-    D, B, lens = 64, 131072, FIELDS
-    F, Ls, Lmax = len(lens), sum(lens), max(lens)
-    V = 20900 if shape == "fields-ref" else 20_000_000
+    ref = shape in ("ref", "fields-ref")
+    V = 20900 if ref else 20_000_000
     rng = np.random.default_rng(7)
-    if shape == "fields-ref":
-        ids = np.minimum(rng.zipf(1.2, size=(B, Ls)) - 1, V - 1).astype(np.int32)
+    if ref:
+        ids = np.minimum(rng.zipf(1.2, size=id_shape) - 1, V - 1).astype(np.int32)
     else:
-        ids = rng.integers(0, V, size=(B, Ls)).astype(np.int32)
+        ids = rng.integers(0, V, size=id_shape).astype(np.int32)
     tid = torch.from_numpy(ids).to(dev)
-    mask = torch.from_numpy((rng.random((B, Ls)) < 0.7).astype(np.float32)).to(dev)
-    table = torch.empty((V, D), dtype=torch.float32, device=dev)
+    mask = torch.from_numpy((rng.random(id_shape) < 0.7).astype(np.float32)).to(dev)
+    table = torch.empty((V, 64), dtype=torch.float32, device=dev)
     ops.fill_normal_(table, seed=1, sigma=0.01)
     m, v = torch.zeros_like(table), torch.zeros_like(table)
-    dy = torch.from_numpy(rng.standard_normal((B, F * D)).astype(np.float32)).to(dev)
+    dy = torch.from_numpy(rng.standard_normal(dy_shape).astype(np.float32)).to(dev)
     marker = torch.empty((1, 4), dtype=torch.float32, device=dev)
+    return ops, torch, V, tid, mask, table, m, v, dy, marker
+
+
+def _rotate(ops, torch, marker, variants, variant):
+    """every variant once (warm-up: code objects, workspaces, the allocator), then REPEATS rounds of all of them in rotation, each
+    repeat behind a marker launch; returns the order of the repeats"""
+    for name in variants:
+        variant(name)
+    torch.cuda.synchronize()
+    order = []
+    for r in range(REPEATS):
+        for q in range(len(variants)):
+            name = variants[(r + q) % len(variants)]
+            ops.fill_normal_(marker, seed=r, sigma=1.0)
+            variant(name)
+            order.append(name)
+    ops.fill_normal_(marker, seed=99, sigma=1.0)
+    torch.cuda.synchronize()
+    return order
+
+
+def run_fields(shape):
+    D, B, lens = 64, 131072, FIELDS
+    F, Ls, Lmax = len(lens), sum(lens), max(lens)
+    ops, torch, V, tid, mask, table, m, v, dy, marker = _setup(shape, (B, Ls), (B, F * D))
+    dev = table.device
     pooled = torch.empty((B, F * D), dtype=torch.float32, device=dev)
     offs = [sum(lens[:f]) for f in range(F)]
     by_len = {}                                   # distinct length -> its fields
@@ -104,18 +131,7 @@ def run_fields(shape):
             ops.sparse_lazy_adam_(table, m, v, plan, dy.view(B * F, D), (mask[:, pad_slots] * pad_keep).contiguous(), pool=Lmax,
                                   grad_scale=1.0 / Lmax, **akw)
 
-    for name in FIELD_VARIANTS:                # warm-up: code objects, workspaces, the allocator
-        variant(name)
-    torch.cuda.synchronize()
-    order = []
-    for r in range(REPEATS):
-        for q in range(len(FIELD_VARIANTS)):
-            name = FIELD_VARIANTS[(r + q) % len(FIELD_VARIANTS)]
-            ops.fill_normal_(marker, seed=r, sigma=1.0)
-            variant(name)
-            order.append(name)
-    ops.fill_normal_(marker, seed=99, sigma=1.0)
-    torch.cuda.synchronize()
+    order = _rotate(ops, torch, marker, FIELD_VARIANTS, variant)
     need_fwd = B * Ls * D * 4 + B * F * D * 4 + B * Ls * 8          # rows read, pooled rows written, ids + mask read
     print(json.dumps(dict(shape=shape, V=V, D=D, L=list(lens), bags=B * F, warmup_markers=0, order=order, fwd_bytes_needed=need_fwd,
                           variants=list(FIELD_VARIANTS))))
@@ -124,28 +140,11 @@ def run_fields(shape):
 def run(shape):
     if shape.startswith("fields-"):
         return run_fields(shape)
-    import numpy as np
-    import torch
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from mindrec_amd import ops
-    dev = torch.device("cuda:0")
     D, L, bags = 64, 8, 131072 * 6
-    V = 20900 if shape == "ref" else 20_000_000
-    rng = np.random.default_rng(7)
-    if shape == "ref":
-        ids = np.minimum(rng.zipf(1.2, size=(bags, L)) - 1, V - 1).astype(np.int32)
-    else:
-        ids = rng.integers(0, V, size=(bags, L)).astype(np.int32)
-    tid = torch.from_numpy(ids).to(dev)
-    mask = torch.from_numpy((rng.random((bags, L)) < 0.7).astype(np.float32)).to(dev)
-    table = torch.empty((V, D), dtype=torch.float32, device=dev)
-    ops.fill_normal_(table, seed=1, sigma=0.01)
-    m, v = torch.zeros_like(table), torch.zeros_like(table)
-    dy = torch.from_numpy(rng.standard_normal((bags, D)).astype(np.float32)).to(dev)
+    ops, torch, V, tid, mask, table, m, v, dy, marker = _setup(shape, (bags, L), (bags, D))
     plan = ops.sparse_plan(tid)
-    marker = torch.empty((1, 4), dtype=torch.float32, device=dev)
-    rows = torch.empty((bags * L, D), dtype=torch.float32, device=dev)
-    pooled = torch.empty((bags, D), dtype=torch.float32, device=dev)
+    rows = torch.empty((bags * L, D), dtype=torch.float32, device=table.device)
+    pooled = torch.empty((bags, D), dtype=torch.float32, device=table.device)
     kw = dict(beta1_power=0.9, beta2_power=0.999, grad_scale=1.0 / L)
 
     def variant(name):
@@ -161,18 +160,7 @@ def run(shape):
             big = dy.repeat_interleave(L, 0)
             ops.sparse_lazy_adam_(table, m, v, plan, big, mask, **kw)
 
-    for name in VARIANTS:                      # warm-up: code objects, workspaces, the allocator
-        variant(name)
-    torch.cuda.synchronize()
-    order = []
-    for r in range(REPEATS):
-        for q in range(len(VARIANTS)):
-            name = VARIANTS[(r + q) % len(VARIANTS)]
-            ops.fill_normal_(marker, seed=r, sigma=1.0)
-            variant(name)
-            order.append(name)
-    ops.fill_normal_(marker, seed=99, sigma=1.0)
-    torch.cuda.synchronize()
+    order = _rotate(ops, torch, marker, VARIANTS, variant)
     need_fwd = bags * L * D * 4 + bags * D * 4 + bags * L * 8          # rows read, pooled rows written, ids + mask read
     print(json.dumps(dict(shape=shape, V=V, D=D, L=L, bags=bags, warmup_markers=0, order=order, fwd_bytes_needed=need_fwd)))
 
