@@ -38,6 +38,9 @@ The wide side of the reference's multi-hot fields (wide_and_deep.py:377-420: Red
 fields' sums added up) needs no fields form: a sum over fields of sums over slots is ONE bag of length Ls, mode "sum", dim = 1 --
 MultiHotEmbedding(vocab, 1, bag=sum(lengths), mode="sum", optimizer="ftrl") on the same [B, Ls] ids.
 
+Both sides of the same fields at once -- the [V, dim] table AND the [V] wide weights, by the same ids and mask, both applies from ONE
+plan: MultiHotWideDeep, at the end of this file.
+
 Neither method synchronises with the host, so lookup + apply_ capture into one HIP graph on one stream.  The Adam bias-correction
 powers advance on the host with every apply_: a captured graph holds the powers of the steps it captured (replaying K captured
 steps repeats those K steps; it does not continue the count).  No torch arithmetic on the step."""
@@ -118,9 +121,12 @@ class MultiHotEmbedding:
         self._mask = fmask.contiguous() if fmask is not None else None
         return out
 
-    def apply_(self, dy, grad_scale=1.0):
+    def apply_(self, dy, grad_scale=1.0, plan=None):
         """The optimizer step for the gradient dy [B, F * dim] of the last lookup's result (float32; bfloat16 / float16 too under
-        'lazy_adam' and 'adam'): in place on the table and the optimizer state."""
+        'lazy_adam' and 'adam'): in place on the table and the optimizer state.  plan: an ops.sparse_plan to apply with instead of
+        building one -- the CALLER's contract: it is ops.sparse_plan of exactly the ids of the last lookup (the same [B, Ls] ids, no
+        skip_negative); it is not checked, and a plan of other ids updates other rows.  For several tables looked up by the same
+        ids (MultiHotWideDeep below): one plan, handed to each.  None: the plan is built here.  Returns the plan it applied with."""
         if self._ids is None:
             raise RuntimeError("apply_ follows a lookup")
         ids, mask = self._ids, self._mask
@@ -131,7 +137,10 @@ class MultiHotEmbedding:
         # one scale per field in place of grad_scale
         fs = tuple(float(np.float32(grad_scale) / np.float32(Lf)) if self.mode == "mean" else float(grad_scale) for Lf in self.fields)
         pkw = dict(fields=self.fields, field_scale=fs)
-        plan = ops.sparse_plan(ids)
+        if plan is None:
+            plan = ops.sparse_plan(ids)
+        elif plan.n != ids.numel():
+            raise ValueError(f"plan holds {plan.n} positions, the last lookup's ids {ids.numel()}")
         self.beta1_power = np.float32(self.beta1_power * self.beta1)
         self.beta2_power = np.float32(self.beta2_power * self.beta2)
         self.step_count += 1
@@ -145,4 +154,67 @@ class MultiHotEmbedding:
         else:
             sums = ops.segment_sum(plan, g, mask, **pkw)
             ops.dense_adam_rows_l2_(self.table, self.m, self.v, plan, sums, 0.0, grad_scale=1.0, **akw)
+        return plan
+
+
+class MultiHotWideDeep:
+    """The deep and the wide side of multi-hot fields, looked up by the same ids and the same mask (every id field of the reference's
+    multitable Wide&Deep is read twice: rows of a [V, D] table, pooled per field, wide_and_deep.py:291-346, and a [V] weight vector,
+    summed over everything, :366-420; the table belongs to Adam and the weights to FTRL, :525-535):
+
+        pair = MultiHotWideDeep(vocab=20900, dim=64, bag=(3, 5, 4, 3, 4, 2), mode="mean", optimizer="adam", wide_optimizer="ftrl")
+        x, w = pair.lookup(ids, mask)      # ids, mask [B, Ls] -> x [B, F * dim], w [B] float32: the two halves' lookups
+        ...
+        pair.apply_(dy, dwide)             # dy [B, F * dim], dwide [B]: ONE plan of the ids, then the deep apply and the wide apply
+
+    pair.deep is MultiHotEmbedding(vocab, dim, bag, mode, optimizer) and pair.wide is MultiHotEmbedding(vocab, 1, sum(bag), "sum",
+    wide_optimizer): they hold the tables and the optimizer state, and x, w and every table and state array are bit for bit what those
+    two objects give when driven separately (deep.lookup / wide.lookup, deep.apply_ / wide.apply_ -- two plans where this builds one).
+    The lookup is the two halves' two launches: a one-launch kernel for both sides was built and measured, and was slower than the two
+    where the table sits in cache, so it is not here.
+    Arguments without a prefix go to the deep half, wide_* to the wide half.  bag: an int (one field) or a tuple; ids are [B, Ls]
+    only.  bag=(1,) * n with mask=None is the single-hot case: n rows side by side (Gather + Flatten) and the sum of their n wide
+    weights.  Neither method synchronises with the host: lookup + apply_ capture into one HIP graph on one stream."""
+
+    def __init__(self, vocab, dim, bag, mode="mean", optimizer="lazy_adam", wide_optimizer="ftrl", device="cuda:0", seed=0, wide_seed=1,
+                 sigma=0.01, wide_sigma=0.01, lr=None, wide_lr=None, beta1=0.9, beta2=0.999, eps=1e-8, use_nesterov=False, l1=1e-8, l2=1e-8,
+                 lr_power=-0.5, initial_accum=1.0, out_dtype=torch.float32):
+        if wide_optimizer not in _OPTIMIZERS:
+            raise ValueError(f"wide_optimizer must be one of {_OPTIMIZERS}, got {wide_optimizer!r}")
+        hyper = dict(device=device, beta1=beta1, beta2=beta2, eps=eps, use_nesterov=use_nesterov, l1=l1, l2=l2, lr_power=lr_power,
+                     initial_accum=initial_accum)
+        self.deep = MultiHotEmbedding(vocab, dim, bag, mode=mode, optimizer=optimizer, seed=seed, sigma=sigma, lr=lr, out_dtype=out_dtype,
+                                      **hyper)
+        self.wide = MultiHotEmbedding(vocab, 1, self.deep.bag, mode="sum", optimizer=wide_optimizer, seed=wide_seed, sigma=wide_sigma,
+                                      lr=wide_lr, **hyper)
+        self.fields, self.bag = self.deep.fields, self.deep.bag
+
+    def lookup(self, ids, mask=None, out=None, wide_out=None):
+        """ids, mask [B, Ls] -> (x [B, F * dim], w [B] float32).  out: any [B, F * dim] column block with unit column stride;
+        wide_out: a float32 [B] tensor of any positive stride (a column of a wider matrix)."""
+        deep, wide = self.deep, self.wide
+        if ids.dim() != 2:
+            raise TypeError(f"ids must be [B, {self.bag}] (the bags of lengths {self.fields} back to back)")
+        B = deep._bags(ids)[0]
+        if wide_out is None:
+            wide_out = torch.empty((B,), dtype=torch.float32, device=wide.table.device)
+        elif wide_out.dtype != torch.float32 or wide_out.dim() != 1 or wide_out.shape[0] != B or (B > 1 and wide_out.stride(0) < 1):
+            raise TypeError(f"wide_out must be a float32 [{B}] tensor (any positive stride: a column of a wider matrix)")
+        x = deep.lookup(ids, mask, out=out)
+        wide.lookup(ids, mask, out=wide_out.unsqueeze(1))      # ([B, 1] with wide_out's stride: the lookup's column block)
+        wide._ids, wide._mask = deep._ids, deep._mask          # one copy of the ids: apply_ checks that both halves hold it
+        return x, wide_out
+
+    def apply_(self, dy, dwide, grad_scale=1.0):
+        """The optimizer steps of both halves for dy [B, F * dim], the gradient of x, and dwide [B] (contiguous float32), the gradient
+        of w: one ops.sparse_plan of the last lookup's ids, shared.  Returns the plan."""
+        if self.deep._ids is None or self.deep._ids is not self.wide._ids:
+            raise RuntimeError("apply_ follows a lookup of the pair")
+        B = self.deep._ids.shape[0]
+        # checked here, before the deep half is touched: a refusal must not leave the pair half-stepped
+        if dwide.dtype != torch.float32 or dwide.device != self.wide.table.device or dwide.numel() != B or not dwide.is_contiguous():
+            raise TypeError("dwide must be the contiguous float32 [B] gradient of the last lookup's wide sums, on the tables' device")
+        plan = ops.sparse_plan(self.deep._ids)
+        self.deep.apply_(dy, grad_scale, plan=plan)
+        self.wide.apply_(dwide.view(B, 1), grad_scale, plan=plan)
         return plan
