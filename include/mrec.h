@@ -207,6 +207,22 @@ int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const
 int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
                             int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
                             int64_t ldo, void* stream);
+/* The KEYED form: mrec_gather_pool_fields over the rows of a hash table (MapParameter / HashEmbeddingLookup, mindspore_rec/ops/
+ * embedding.py:136-205) whose multi-hot fields hold raw keys.  rows [B, Ls] int32: the row numbers mrec_map_lookup gave for keys
+ * [B, Ls] (key_bytes 4 / 8, contiguous, the same layout); table: the map's value rows, V = its capacity.  Per slot: a row in [0, V)
+ * contributes table[row]; any other row (-1: a key the lookup did not insert, or dropped because the table is full) contributes the
+ * key's DEFAULT row -- sigma >= 0: sigma * N(0,1) keyed by (seed, key, column); sigma < 0: the constant `fill` (mrec_map_table_t's
+ * triple) -- bit for bit what mrec_map_fill_missing writes for that key, in the same columns, generated in registers: MapTensorGet
+ * reads a key that is not in the table as its default value, not as zeros.  The contribution is then multiplied by the mask, added
+ * and divided exactly as in mrec_gather_pool_fields (product then add, no fma, ascending slot order, slot 0 starts the sum, one IEEE
+ * division by (float)L_f, 16-bit outputs rounded once); with every row in [0, V) the result is mrec_gather_pool_fields' over the
+ * same row numbers, and no key is read.  field_len, mask, mode, out, out_kind, ldo and the limits: as mrec_gather_pool_fields.
+ * MREC_EINVAL: key_bytes not 4 / 8, F < 1, an L_f < 1, sigma or fill not finite, null pointers; MREC_EUNSUPPORTED: F >
+ * MREC_POOL_MAX_FIELDS, Ls > MREC_POOL_MAX_BAG, B * F >= 2^31 -- all before any HIP call.  One launch (k_gather_pool_fields_keyed, a
+ * kernel of its own beside k_gather_pool_fields), no allocation, no synchronisation: capturable. */
+int mrec_gather_pool_fields_keyed(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* rows, const void* keys,
+                                  int32_t key_bytes, int64_t B, int32_t F, const int32_t* field_len, const float* mask, int32_t mode,
+                                  uint64_t seed, float sigma, float fill, void* out, int32_t out_kind, int64_t ldo, void* stream);
 
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row

@@ -538,11 +538,8 @@ __global__ __launch_bounds__(HB) void k_map_fill_missing(const K* __restrict__ k
             const int64_t kk = ((int64_t)__shfl((int)(key >> 32), src, 64) << 32) | (uint32_t)__shfl((int)key, src, 64);
             float* dst = out + (base + src) * ldo;
             for (int c = 2 * lane; c < tb.D; c += 128) {          // a lane fills a pair of columns: one transform
-                float z0 = tb.fill, z1 = tb.fill;
-                if (tb.sigma >= 0.0f) {
-                    mrec_det_normal2(tb.seed, kk, c >> 1, z0, z1);
-                    z0 *= tb.sigma; z1 *= tb.sigma;
-                }
+                float z0, z1;
+                mrec_map_default2(tb.seed, tb.sigma, tb.fill, kk, c >> 1, z0, z1);
                 dst[c] = z0;
                 if (c + 1 < tb.D) dst[c + 1] = z1;
             }

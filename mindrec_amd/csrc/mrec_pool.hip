@@ -20,6 +20,9 @@
 // division).  Both take id_bytes / out_kind arguments (the style of mrec_gather_rows_wide) instead of six names each: the six
 // instantiations differ in two template arguments, and a caller that holds a tensor holds its element size.
 //
+// A third entry, mrec_gather_pool_fields_keyed, is the fields form over the rows of a hash table (MapParameter), where a key that is
+// not in the table reads as its default row: a kernel of its own, k_gather_pool_fields_keyed, at the end of this file.
+//
 // Shape of the kernel: k_gather_rows' (mrec_gather.hip).  lpr = D / 4 lanes per bag on the float4 path (D % 4 == 0, 16-byte
 // aligned rows), G = 64 / lpr bags per wave; a lane-group keeps PB row loads in flight: the PB ids and mask values of a batch of
 // slots, then the PB rows, all requested unconditionally (a slot past the bag's end reads the bag's last id, an id out of range
@@ -30,6 +33,7 @@
 #include "mrec_common.h"
 #include "mrec_optim.h"
 #include "mrec_dense_adam.h"
+#include "mrec_rng.h"
 
 namespace {
 
@@ -204,6 +208,137 @@ int pool_run(const float* table, int64_t V, int64_t ld, int32_t D, const void* i
 #undef MREC_POOL
 }
 
+// ===== the KEYED form: the pooled lookup over the rows of a hash table (MapParameter) ==================================================
+// ids are the int32 row numbers the map's index gave for the sample's keys (KeyIndex.lookup: -1 for a key that is not in the table --
+// not inserted by this call, or dropped because the table is full), keys the keys themselves.  MapTensorGet reads such a key as its
+// DEFAULT row, not as zeros, so a slot whose row is outside [0, V) contributes mrec_map_default2 of its key (mrec_rng.h: the text
+// mrec_map_fill_missing writes those rows with, the same values in the same columns), generated in registers for the columns the
+// lane holds.  Everything else is k_gather_pool_fields, statement for statement: sample-major bags, PB slots in flight, the rows
+// requested unconditionally at clamped addresses, product then add in ascending slot order, one division, one store; no barriers, LDS
+// or atomics.  The key of a slot is loaded only where its row is missing -- in the stage that requests the rows, so it adds no level to
+// the chain of dependent loads, and a lookup of resident keys reads no key at all -- and the generator (a logarithm, a root and a
+// sine / cosine pair per two columns) runs under the same condition.
+// A kernel of its own, with its own instantiations: k_gather_pool_fields above keeps its symbols and its code.
+struct MapDefault { uint64_t seed; float sigma; float fill; };
+
+__device__ __forceinline__ Vf<4> vdefault(const MapDefault& d, int64_t key, int col, Vf<4>*) {      // (col is a multiple of 4)
+    Vf<4> r;
+    mrec_map_default2(d.seed, d.sigma, d.fill, key, col >> 1, r.v.x, r.v.y);
+    mrec_map_default2(d.seed, d.sigma, d.fill, key, (col >> 1) + 1, r.v.z, r.v.w);
+    return r;
+}
+__device__ __forceinline__ Vf<1> vdefault(const MapDefault& d, int64_t key, int col, Vf<1>*) {
+    float z0, z1;
+    mrec_map_default2(d.seed, d.sigma, d.fill, key, col >> 1, z0, z1);
+    Vf<1> r;
+    r.v = (col & 1) ? z1 : z0;
+    return r;
+}
+
+template <int VEC, int PB, class K, class OT, bool ONE>
+__global__ __launch_bounds__(256) void k_gather_pool_fields_keyed(const float* __restrict__ table, int64_t V, int64_t ld,
+                                                                  const int32_t* __restrict__ ids, const K* __restrict__ keys,
+                                                                  const float* __restrict__ mask, unsigned nbags, unsigned F, int Ls, int mode,
+                                                                  OT* __restrict__ out, int64_t ldo, int D, PoolGeom gm, const MapDefault dv,
+                                                                  const PoolFields pf) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;                                      // spare lanes; this kernel has no barriers
+    const unsigned w = (blockIdx.x * 4u + (unsigned)wave) * (unsigned)gm.G + (unsigned)grp;      // (nbags = B * F < 2^31: no wrap)
+    const unsigned wc = w < nbags ? w : nbags - 1u;               // a bag past the end reads the last bag, and stores nothing
+    const unsigned b = ONE ? wc : wc / F, f = wc - b * F;
+    const unsigned fw = ONE ? (unsigned)Ls << 16 : pf.w[f];
+    const int off = (int)(fw & 0xFFFFu), L = (int)(fw >> 16);
+    const int32_t* __restrict__ idb = ids + (int64_t)b * Ls + off;
+    const K* __restrict__ kb = keys + (int64_t)b * Ls + off;
+    const float* __restrict__ mb = mask ? mask + (int64_t)b * Ls + off : nullptr;
+    OT* __restrict__ ob = out + (int64_t)b * ldo + (int64_t)f * D;
+    const int llast = L - 1;
+    const float fl = (float)L;
+    for (int col = sub * VEC; col < D; col += gm.lpr * VEC) {
+        Vf<VEC> acc = vzero((Vf<VEC>*)nullptr);
+        for (int l0 = 0; l0 < L; l0 += PB) {
+            int64_t row[PB], key[PB];
+            float mk[PB];
+            Vf<VEC> x[PB];
+            bool okr[PB];
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                const int lc = l0 + k < L ? l0 + k : llast;       // (a slot past the bag's end reads the bag's last id: inside the bag)
+                row[k] = (int64_t)idb[lc];
+                mk[k] = mb ? mb[lc] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                okr[k] = row[k] >= 0 && row[k] < V;
+                x[k] = vload(table + (okr[k] ? row[k] : 0) * ld + col, (Vf<VEC>*)nullptr);
+                key[k] = 0;
+                if (!okr[k] && l0 + k < L) key[k] = (int64_t)kb[l0 + k];      // (the slot's own key: l0 + k < L, inside the bag)
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                vtouch(x[k]);
+                if (!okr[k]) x[k] = (l0 + k < L) ? vdefault(dv, key[k], col, (Vf<VEC>*)nullptr) : vzero((Vf<VEC>*)nullptr);
+            }
+#pragma unroll
+            for (int k = 0; k < PB; ++k) {
+                if (l0 + k < L) {
+                    const Vf<VEC> p = mb ? vscale(x[k], mk[k]) : x[k];
+                    acc = (l0 + k == 0) ? p : vadd(acc, p);       // slot 0 starts the sum
+                }
+            }
+        }
+        if (mode == 1) acc = vdiv(acc, fl);
+        if (w < nbags) vstore(ob + col, acc);
+    }
+}
+
+template <class K, class OT>
+int pool_keyed_impl(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, const K* keys, int64_t B, int32_t F,
+                    int32_t Ls, int32_t maxL, const PoolFields& pf, const float* mask, int32_t mode, const MapDefault& dv, OT* out,
+                    int64_t ldo, hipStream_t st) {
+    const uintptr_t oa = sizeof(OT) == 2 ? 7 : 15;       // (pool_impl's choice of lanes)
+    const bool vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
+    const int cols = vec ? D / 4 : D;
+    PoolGeom gm;
+    gm.lpr = cols < 64 ? cols : 64;
+    gm.G = 64 / gm.lpr;
+    const int64_t nbags = B * F;
+    const unsigned blocks = (unsigned)mrec_cdiv(nbags, (int64_t)4 * gm.G);
+#define MREC_POOLK_LAUNCH1(VECN, PBN, ONE)                                                                                            \
+    k_gather_pool_fields_keyed<VECN, PBN, K, OT, ONE><<<blocks, 256, 0, st>>>(table, V, ld, ids, keys, mask, (unsigned)nbags, (unsigned)F,    \
+                                                                             (int)Ls, (int)mode, out, ldo, (int)D, gm, dv, pf)
+#define MREC_POOLK_LAUNCH(VECN, PBN) do { if (F == 1) MREC_POOLK_LAUNCH1(VECN, PBN, true); else MREC_POOLK_LAUNCH1(VECN, PBN, false); } while (0)
+    if (vec) {
+        if (maxL <= 2) MREC_POOLK_LAUNCH(4, 2); else MREC_POOLK_LAUNCH(4, 8);
+    } else {
+        if (maxL <= 2) MREC_POOLK_LAUNCH(1, 2); else MREC_POOLK_LAUNCH(1, 8);
+    }
+#undef MREC_POOLK_LAUNCH
+#undef MREC_POOLK_LAUNCH1
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+// the bags of a sample from the caller's lengths: what both fields entries check, in this order
+int pool_fields_parse(int32_t F, const int32_t* field_len, PoolFields& pf, int32_t& Ls_out, int32_t& maxL_out) {
+    if (F < 1 || !field_len) return MREC_EINVAL;
+    if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
+    int64_t Ls = 0;
+    int32_t maxL = 0;
+    for (int f = 0; f < F; ++f) {
+        const int32_t Lf = field_len[f];
+        if (Lf < 1) return MREC_EINVAL;
+        if (Ls + Lf > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
+        pf.w[f] = (unsigned)Ls | ((unsigned)Lf << 16);
+        Ls += Lf;
+        maxL = Lf > maxL ? Lf : maxL;
+    }
+    Ls_out = (int32_t)Ls;
+    maxL_out = maxL;
+    return MREC_OK;
+}
+
 }  // namespace
 
 MREC_API int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B, int32_t L,
@@ -220,20 +355,42 @@ MREC_API int mrec_gather_pool(const float* table, int64_t V, int64_t ld, int32_t
 MREC_API int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
                                      int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
                                      int64_t ldo, void* stream) {
-    if (!pool_args_ok(id_bytes, out_kind, mode, B, D, V, ld) || F < 1 || !field_len) return MREC_EINVAL;
-    if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
+    if (!pool_args_ok(id_bytes, out_kind, mode, B, D, V, ld)) return MREC_EINVAL;
     PoolFields pf{};
-    int64_t Ls = 0;
-    int32_t maxL = 0;
-    for (int f = 0; f < F; ++f) {
-        const int32_t Lf = field_len[f];
-        if (Lf < 1) return MREC_EINVAL;
-        if (Ls + Lf > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
-        pf.w[f] = (unsigned)Ls | ((unsigned)Lf << 16);
-        Ls += Lf;
-        maxL = Lf > maxL ? Lf : maxL;
-    }
+    int32_t Ls = 0, maxL = 0;
+    const int rc = pool_fields_parse(F, field_len, pf, Ls, maxL);
+    if (rc != MREC_OK) return rc;
     if (ldo == 0) ldo = (int64_t)F * D;
     if (ldo < (int64_t)F * D) return MREC_EINVAL;
-    return pool_run(table, V, ld, D, ids, id_bytes, B, F, (int32_t)Ls, maxL, pf, mask, mode, out, out_kind, ldo, stream);
+    return pool_run(table, V, ld, D, ids, id_bytes, B, F, Ls, maxL, pf, mask, mode, out, out_kind, ldo, stream);
+}
+
+MREC_API int mrec_gather_pool_fields_keyed(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* rows, const void* keys,
+                                           int32_t key_bytes, int64_t B, int32_t F, const int32_t* field_len, const float* mask,
+                                           int32_t mode, uint64_t seed, float sigma, float fill, void* out, int32_t out_kind, int64_t ldo,
+                                           void* stream) {
+    if (!pool_args_ok(key_bytes, out_kind, mode, B, D, V, ld)) return MREC_EINVAL;
+    if (!(sigma - sigma == 0.0f) || !(fill - fill == 0.0f)) return MREC_EINVAL;      // NaN or infinite
+    PoolFields pf{};
+    int32_t Ls = 0, maxL = 0;
+    const int rc = pool_fields_parse(F, field_len, pf, Ls, maxL);
+    if (rc != MREC_OK) return rc;
+    if (ldo == 0) ldo = (int64_t)F * D;
+    if (ldo < (int64_t)F * D) return MREC_EINVAL;
+    if (B * F > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;      // (bags are numbered in 32 bits)
+    if (B == 0) return MREC_OK;
+    if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
+    if (!table || !rows || !keys || !out) return MREC_EINVAL;
+    const MapDefault dv{seed, sigma, fill};
+    hipStream_t st = (hipStream_t)stream;
+#define MREC_POOLK(KT, OT) return pool_keyed_impl<KT, OT>(table, V, ld, D, rows, (const KT*)keys, B, F, Ls, maxL, pf, mask, mode, dv, (OT*)out, ldo, st)
+    if (key_bytes == 4) {
+        if (out_kind == 0) { MREC_POOLK(int32_t, float); }
+        if (out_kind == 1) { MREC_POOLK(int32_t, bf16o_t); }
+        MREC_POOLK(int32_t, f16o_t);
+    }
+    if (out_kind == 0) { MREC_POOLK(int64_t, float); }
+    if (out_kind == 1) { MREC_POOLK(int64_t, bf16o_t); }
+    MREC_POOLK(int64_t, f16o_t);
+#undef MREC_POOLK
 }

@@ -85,3 +85,17 @@ __device__ __forceinline__ float mrec_det_normal(uint64_t seed, int64_t row, int
     mrec_det_normal2(seed, row, col >> 1, z0, z1);
     return (col & 1) ? z1 : z0;
 }
+
+// Columns 2 * pair and 2 * pair + 1 of the DEFAULT ROW of a MapParameter key: what MapTensorGet reads for a key that is not in the
+// table (sigma >= 0: sigma * N(0,1) keyed by (seed, key, column); sigma < 0: the constant `fill` -- mrec_map_table_t's rule).  One
+// text for every kernel that produces such rows outside the table: mrec_map_fill_missing writes them to memory, the keyed pooled
+// lookup (mrec_pool.hip) generates them in registers -- bit for bit the same values in the same columns.
+__device__ __forceinline__ void mrec_map_default2(uint64_t seed, float sigma, float fill, int64_t key, int32_t pair, float& z0, float& z1) {
+    z0 = fill;
+    z1 = fill;
+    if (sigma >= 0.0f) {
+        mrec_det_normal2(seed, key, pair, z0, z1);
+        z0 *= sigma;
+        z1 *= sigma;
+    }
+}

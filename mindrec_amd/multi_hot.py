@@ -41,6 +41,10 @@ MultiHotEmbedding(vocab, 1, bag=sum(lengths), mode="sum", optimizer="ftrl") on t
 Both sides of the same fields at once -- the [V, dim] table AND the [V] wide weights, by the same ids and mask, both applies from ONE
 plan: MultiHotWideDeep, at the end of this file.
 
+Fields that hold RAW KEYS -- entity, topic, category ids of a growing catalogue, the input of the reference's hash-table models
+(HashEmbeddingLookup over a MapParameter, mindspore_rec/ops/embedding.py:136-205) -- over a hash table instead of a [vocab, dim]
+array: MultiHotHashEmbedding, at the end of this file.
+
 Neither method synchronises with the host, so lookup + apply_ capture into one HIP graph on one stream.  The Adam bias-correction
 powers advance on the host with every apply_: a captured graph holds the powers of the steps it captured (replaying K captured
 steps repeats those K steps; it does not continue the count).  No torch arithmetic on the step."""
@@ -48,6 +52,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .experimental import MapParameter
 
 _OPTIMIZERS = ("lazy_adam", "ftrl", "adam")
 
@@ -218,3 +223,129 @@ class MultiHotWideDeep:
         self.deep.apply_(dy, grad_scale, plan=plan)
         self.wide.apply_(dwide.view(B, 1), grad_scale, plan=plan)
         return plan
+
+
+class MultiHotHashEmbedding:
+    """MultiHotEmbedding over a MapParameter: the multi-hot fields hold raw int keys, rows are created on first sight, admitted and
+    evicted by the map's filters, and a key that is not in the table reads as its DEFAULT row (MapTensorGet's contract), not as zeros.
+
+        emb = MultiHotHashEmbedding(dict(key_dtype=torch.int64, value_shape=64, capacity=1 << 20, permit_filter_value=2),
+                                    bag=(3, 5, 4, 3, 4, 2), mode="mean", optimizer="lazy_adam")
+        x = emb.lookup(keys, mask)               # keys, mask [B, Ls] -> [B, F * dim]; one training step of the table
+        ...
+        emb.apply_(dy)                           # one plan of the keys' admitted rows, one pooled apply on map.values and the slots
+        y = emb.lookup(keys, mask, train=False)  # evaluation / serving: probes only, nothing is inserted or counted
+
+    map_or_kwargs: a MapParameter (float32 values of one dimension, on a GPU) or the keyword arguments to build one; emb.map is it,
+    emb.dim its value_shape[0].  bag, mode, fields, MAX_BAG, the `out` column-block rules, out_dtype and the host-side bias-correction
+    powers: MultiHotEmbedding's.
+    lookup: MapParameter.lookup_rows over the B * Ls keys (train=True: insert=True -- new keys take rows and default values in the
+    values AND in the optimizer's slot tables, hits and last-seen steps are counted, map.step advances; train=False: a probe), then ONE
+    pooled launch, ops.gather_pool_fields_keyed: a slot whose key has a row contributes map.values[row], any other -- not inserted
+    by a probe, or dropped because the table is full -- the key's default row, generated in registers (no [B * Ls, dim] rows, which
+    MapParameter.get(insert_default_value=False) has to materialise to overlay them).
+    apply_: the keys' rows through MapParameter.admitted_rows -- un-admitted keys (seen in fewer than permit_filter_value training
+    lookups) and dropped keys are -1 -- then ops.sparse_plan over them and the pooled ops.sparse_lazy_adam_ / ops.sparse_ftrl_
+    (fields=, field_scale=, the mask) on map.values and the slot tables; the windows and the finishing pass of the apply skip a row
+    outside [0, capacity), so the -1 group is summed and dropped: such keys are not updated.  A key that occurs in several fields of a
+    sample gets the sum of their gradients and ONE update.
+    Optimizers: "lazy_adam" (slots "moment1", "moment2": nn.LazyAdam's names over a MapParameter) and "ftrl" ("accum" from
+    initial_accum, "linear"), created through MapParameter.add_slot so that every new key's slot rows start at their initial
+    values.  "adam", the dense whole-table update, is refused: a hash table has no "every row".  dim = 1, mode "sum", optimizer "ftrl"
+    over the same keys is the wide side.  Eviction is the map's (emb.map.evict()): an evicted key seen again is a new key.
+    Neither method synchronises with the host."""
+
+    def __init__(self, map_or_kwargs, bag, mode="mean", optimizer="lazy_adam", lr=None, beta1=0.9, beta2=0.999, eps=1e-8, use_nesterov=False,
+                 l1=1e-8, l2=1e-8, lr_power=-0.5, initial_accum=1.0, out_dtype=torch.float32):
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
+        if optimizer == "adam":
+            raise ValueError("optimizer 'adam' updates every row of a table: a hash table has no 'every row' (use 'lazy_adam' or 'ftrl')")
+        if optimizer not in ("lazy_adam", "ftrl"):
+            raise ValueError(f"optimizer must be 'lazy_adam' or 'ftrl', got {optimizer!r}")
+        if isinstance(bag, (tuple, list)):
+            bag = ops._fields(bag)
+        elif int(bag) < 1:
+            raise ValueError("bag must be >= 1")
+        else:
+            bag = (int(bag),)
+        device = map_or_kwargs.device if isinstance(map_or_kwargs, MapParameter) else torch.device(map_or_kwargs.get("device", "cuda:0"))
+        if device.type != "cuda":
+            raise RuntimeError("mindrec_amd ops run on the GPU only (no CPU fallback)")
+        self.map = map_or_kwargs if isinstance(map_or_kwargs, MapParameter) else MapParameter(**map_or_kwargs)
+        self.fields, self.bag = bag, sum(bag)
+        self.dim = self.map.value_shape[0]
+        self.mode, self.optimizer, self.out_dtype = mode, optimizer, out_dtype
+        self.device = self.map.device
+        self.lr = float(lr) if lr is not None else (5e-2 if optimizer == "ftrl" else 3.5e-4)
+        self.eps, self.use_nesterov = float(eps), bool(use_nesterov)
+        self.l1, self.l2, self.lr_power = float(l1), float(l2), float(lr_power)
+        self.beta1, self.beta2 = np.float32(beta1), np.float32(beta2)
+        self.beta1_power, self.beta2_power = np.float32(1.0), np.float32(1.0)
+        self.step_count = 0
+        if optimizer == "ftrl":
+            self.state = (self.map.add_slot("accum", float(initial_accum)), self.map.add_slot("linear", 0.0))
+        else:
+            self.state = (self.map.add_slot("moment1", 0.0), self.map.add_slot("moment2", 0.0))
+        self._rows = self._mask = None
+
+    def lookup(self, keys, mask=None, out=None, train=True):
+        """keys [B, Ls] of the map's key dtype (one field: [B, G, L] too, G bags per sample) -> [B, F * dim]; mask, out: as
+        MultiHotEmbedding.lookup.  train=True: one training step of the table (see the class); train=False: a probe, and no apply_
+        may follow it."""
+        if keys.dtype != self.map.key_dtype:
+            raise TypeError(f"keys must be {self.map.key_dtype}, the map's key dtype, got {keys.dtype}")
+        if keys.dim() not in ((2, 3) if len(self.fields) == 1 else (2,)) or keys.shape[-1] != self.bag:
+            raise TypeError(f"keys must be [B, {self.bag}] (the bags of lengths {self.fields} back to back), or [B, G, {self.bag}] for one length")
+        ops._need_cuda(keys, mask, out)
+        B, G = keys.shape[0], (keys.shape[1] if keys.dim() == 3 else 1)
+        if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(keys.shape)):
+            raise TypeError("mask must be float32 of the shape of keys")
+        W = len(self.fields) * self.dim
+        if out is None:
+            out = torch.empty((B, G * W), dtype=self.out_dtype, device=self.device)
+        elif tuple(out.shape) != (B, G * W) or (G > 1 and not out.is_contiguous()):
+            raise TypeError("out must be [B, F * dim] (contiguous when keys hold more than one bag per sample)")
+        flat = keys.reshape(B * G, self.bag).contiguous()
+        fmask = mask.reshape(B * G, self.bag).contiguous() if mask is not None else None
+        m = self.map
+        rows = m.lookup_rows(flat.view(-1), insert=bool(train))[2].view(B * G, self.bag)
+        ops.gather_pool_fields_keyed(m.values, rows, flat, self.fields, fmask, mode=self.mode, out=out if G == 1 else out.view(B * G, W),
+                                     default=(m._sigma, m._fill, m.seed))
+        self._rows = m.admitted_rows(rows) if train else None
+        self._mask = fmask
+        return out
+
+    def apply_(self, dy, grad_scale=1.0, plan=None):
+        """The optimizer step for the gradient dy [B, F * dim] of the last training lookup's result: in place on map.values and the
+        two slot tables.  plan: ops.sparse_plan of exactly that lookup's admitted rows (emb.rows), to apply with instead of building
+        one; not checked beyond its length.  Returns the plan it applied with."""
+        if self._rows is None:
+            raise RuntimeError("apply_ follows a lookup with train=True")
+        rows, mask = self._rows, self._mask
+        nbags = rows.shape[0] * len(self.fields)
+        if dy.dim() != 2 or dy.shape[0] * dy.shape[1] != nbags * self.dim or not dy.is_contiguous():
+            raise TypeError("dy must be the contiguous [B, F * dim] gradient of the last lookup's result")
+        g = dy.view(nbags, self.dim)
+        fs = tuple(float(np.float32(grad_scale) / np.float32(Lf)) if self.mode == "mean" else float(grad_scale) for Lf in self.fields)
+        pkw = dict(fields=self.fields, field_scale=fs)
+        if plan is None:
+            plan = ops.sparse_plan(rows)
+        elif plan.n != rows.numel():
+            raise ValueError(f"plan holds {plan.n} positions, the last lookup's keys {rows.numel()}")
+        self.beta1_power = np.float32(self.beta1_power * self.beta1)
+        self.beta2_power = np.float32(self.beta2_power * self.beta2)
+        self.step_count += 1
+        s0, s1 = self.state
+        if self.optimizer == "lazy_adam":
+            ops.sparse_lazy_adam_(self.map.values, s0, s1, plan, g, mask, lr=self.lr, beta1=float(self.beta1), beta2=float(self.beta2),
+                                  eps=self.eps, beta1_power=float(self.beta1_power), beta2_power=float(self.beta2_power),
+                                  use_nesterov=self.use_nesterov, **pkw)
+        else:
+            ops.sparse_ftrl_(self.map.values, s0, s1, plan, g, mask, lr=self.lr, l1=self.l1, l2=self.l2, lr_power=self.lr_power, **pkw)
+        return plan
+
+    @property
+    def rows(self):
+        """int32 [B, Ls]: the admitted rows of the last training lookup's keys (-1: un-admitted or dropped), what apply_ plans over"""
+        return self._rows

@@ -275,8 +275,9 @@ def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32, m
 _OUT_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
-def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype):
-    """the one lookup behind gather_pool and gather_pool_fields (mrec_gather_pool_fields): ids, mask [B, sum(lens)] -> out [B, F * D]"""
+def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype, keyed=None):
+    """the one lookup behind gather_pool, gather_pool_fields (mrec_gather_pool_fields) and gather_pool_fields_keyed
+    (mrec_gather_pool_fields_keyed; keyed = (keys, seed, sigma, fill)): ids, mask [B, sum(lens)] -> out [B, F * D]"""
     V, D, ld = _table(table)
     sfx = _suffix(ids)
     if mode not in ("sum", "mean"):
@@ -291,6 +292,13 @@ def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype):
     ldo = out.stride(0) if B > 1 else F * D
     ids = ids.contiguous()
     mask = mask.contiguous() if mask is not None else None
+    if keyed is not None:
+        keys, seed, sigma, fill = keyed
+        keys = keys.contiguous()
+        _lib.call("mrec_gather_pool_fields_keyed", _ptr(table), V, ld, D, _ptr(ids), _ptr(keys), keys.element_size(), B, F,
+                  (C.c_int32 * F)(*lens), _ptr(mask), 1 if mode == "mean" else 0, C.c_uint64(seed), sigma, fill, _ptr(out),
+                  _OUT_KIND[out.dtype], ldo, _stream())
+        return out
     _lib.call("mrec_gather_pool_fields", _ptr(table), V, ld, D, _ptr(ids), 4 if sfx == "i32" else 8, B, F, (C.c_int32 * F)(*lens),
               _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
     return out
@@ -328,6 +336,29 @@ def gather_pool_fields(table, ids, field_len, mask=None, mode="mean", out=None, 
     if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
         raise TypeError("mask must be float32 of the shape of ids")
     return _gather_pool("gather_pool_fields", table, ids, lens, mask, mode, out, out_dtype)
+
+
+def gather_pool_fields_keyed(values, rows, keys, fields, mask=None, mode="mean", out=None, out_dtype=torch.float32, *, default):
+    """gather_pool_fields over the rows of a hash table (MapParameter: HashEmbeddingLookup over a MapParameter, mindspore_rec/ops/
+    embedding.py:136-205) whose multi-hot fields hold raw keys, in one launch (mrec_gather_pool_fields_keyed).  values: the map's
+    [capacity, D] value rows; rows [B, Ls] int32: the row numbers KeyIndex.lookup gave for keys [B, Ls] (int32 / int64).  A slot
+    whose row is in [0, capacity) contributes values[row]; any other (-1: a key that was not inserted, or dropped because the table is
+    full) contributes the key's DEFAULT row, as MapTensorGet reads it -- bit for bit what KeyIndex.fill_missing writes, generated in
+    registers: no [B * Ls, D] intermediate.  default = (sigma, fill, seed), fill_missing's triple: sigma * N(0,1) keyed by (seed, key,
+    column), or -- sigma None -- the constant fill.  fields, mask, mode, out, out_dtype and the arithmetic: gather_pool_fields'."""
+    _need_cuda(values, rows, keys, mask, out)
+    lens = _fields(fields)
+    if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != sum(lens):
+        raise TypeError(f"rows must be int32 [B, {sum(lens)}]: the bags of lengths {lens} back to back")
+    if keys.dtype not in (torch.int32, torch.int64) or tuple(keys.shape) != tuple(rows.shape):
+        raise TypeError("keys must be int32 or int64 of the shape of rows")
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(rows.shape)):
+        raise TypeError("mask must be float32 of the shape of rows")
+    sigma, fill, seed = default
+    sigma, fill = (-1.0 if sigma is None else float(sigma)), float(fill or 0.0)
+    if not (math.isfinite(sigma) and math.isfinite(fill)):
+        raise ValueError(f"default must hold a finite sigma (or None) and a finite fill, got {default!r}")
+    return _gather_pool("gather_pool_fields_keyed", values, rows, lens, mask, mode, out, out_dtype, keyed=(keys, int(seed), sigma, fill))
 
 
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
