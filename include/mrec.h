@@ -223,6 +223,26 @@ int mrec_gather_pool_fields(const float* table, int64_t V, int64_t ld, int32_t D
 int mrec_gather_pool_fields_keyed(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* rows, const void* keys,
                                   int32_t key_bytes, int64_t B, int32_t F, const int32_t* field_len, const float* mask, int32_t mode,
                                   uint64_t seed, float sigma, float fill, void* out, int32_t out_kind, int64_t ldo, void* stream);
+/* max_norm over multi-hot fields: the two fields entries above with one argument more, `float max_norm` before `stream` (the style of
+ * the mrec_gather_rows_clip_* entries).  Every looked-up row x is clipped as an fp32 row -- x * (c / n) where n = sqrt(sum x_d^2) > c,
+ * x exactly otherwise: a tie is not clipped -- BEFORE its mask product (Gather -> ClipByNorm -> Mul(mask) -> ReduceMean / ReduceSum,
+ * the max_norm of HashEmbeddingLookup / nn.EmbeddingLookup over a bag); the sum of squares, the decision and the scaling are
+ * mrec_gather_rows_clip_*'s, operation for operation, so each slot's row is bit for bit what that lookup returns for its id, and the
+ * products, slot-order adds, the one division and the one rounding are those of the entries above.  Dense form: an id outside [0, V)
+ * is a zero row and is never clipped.  Keyed form: a slot whose row is outside [0, V) contributes its key's DEFAULT row, and that row
+ * is clipped like any other (MapTensorGet returns the default value and ClipByNorm follows it).  The backward side is
+ * mrec_sparse_apply_next_pool_fields_clip below.  Float4 rows in one column block only: D % 4 != 0, D > 256, ld or ldo not a multiple
+ * of 4, a table that is not 16-byte aligned or an output that is not (8-byte for 16-bit outputs): MREC_EUNSUPPORTED; max_norm not finite
+ * or <= 0: MREC_EINVAL; the other argument errors and limits as above -- all before any launch.  One launch each
+ * (k_gather_pool_fields_clip, a kernel of its own: the kernels of the entries above are not touched), no allocation, no synchronisation:
+ * capturable.  F = 1, field_len = {L} is the clipped mrec_gather_pool. */
+int mrec_gather_pool_fields_clip(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
+                                 int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
+                                 int64_t ldo, float max_norm, void* stream);
+int mrec_gather_pool_fields_keyed_clip(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* rows, const void* keys,
+                                       int32_t key_bytes, int64_t B, int32_t F, const int32_t* field_len, const float* mask, int32_t mode,
+                                       uint64_t seed, float sigma, float fill, void* out, int32_t out_kind, int64_t ldo, float max_norm,
+                                       void* stream);
 
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row
@@ -475,7 +495,9 @@ int mrec_sparse_apply_next_max_norm(float max_norm);
  * multiple of L.  The armed call launches that form's windows, k_apply_main_fields, a kernel of its own, then k_apply_long; not
  * armed, or at L == 1, a call launches k_apply_main + k_apply_long, what it launched before this existed.  MREC_EUNSUPPORTED before
  * any launch, and disarmed, for the folded wide forms (mrec_sparse_lazy_adam_wide(_defer)), with constant columns armed (they are
- * disarmed too), with max_norm, and for n * L >= 2^32 (i / L is a 32-bit multiply-high).  L < 1: MREC_EINVAL, nothing is armed. */
+ * disarmed too), with mrec_sparse_apply_next_max_norm armed on top of it (max_norm over bags has an arm of its own,
+ * mrec_sparse_apply_next_pool_fields_clip below), and for n * L >= 2^32 (i / L is a 32-bit multiply-high).  L < 1: MREC_EINVAL,
+ * nothing is armed. */
 int mrec_sparse_apply_next_pool(int32_t L);
 /* The FIELDS form of the pooled apply: the bprop of mrec_gather_pool_fields.  The plan's n positions are samples of Ls = sum L_f ids,
  * F bags back to back; g is the [B, F * D] gradient of the lookup's result viewed as [B * F, D] (ldg its row stride, n a multiple
@@ -494,9 +516,24 @@ int mrec_sparse_apply_next_pool(int32_t L);
  * The armed call launches the pooled windows, k_apply_main_fields (the kernel a call armed with _next_pool launches too), then
  * k_apply_long; a call that is not armed launches k_apply_main + k_apply_long, what it launched before this existed.
  * MREC_EUNSUPPORTED before any launch, and disarmed, for the folded wide forms, with constant
- * columns armed (disarmed too) and with max_norm.  Arming errors leave nothing armed: F < 1, a null array, an L_f < 1 or a
+ * columns armed (disarmed too) and with mrec_sparse_apply_next_max_norm armed on top of it (the clip over bags travels with the
+ * pooled arm: mrec_sparse_apply_next_pool_fields_clip below).  Arming errors leave nothing armed: F < 1, a null array, an L_f < 1 or a
  * field_scale that is not finite: MREC_EINVAL; F > MREC_POOL_MAX_FIELDS or Ls > MREC_POOL_MAX_BAG: MREC_EUNSUPPORTED. */
 int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_len, const float* field_scale);
+/* max_norm over the pooled apply: the bprop of mrec_gather_pool_fields_clip / _keyed_clip.  mrec_sparse_apply_next_pool_fields with the
+ * clip in the SAME arm: position i contributes x_i as above, the windows' partial sums stay unclipped, and -- J(x) G being linear in
+ * G -- each touched row's COMPLETED gradient sum G becomes J(x) G = (c / n)(G - (x.G / n^2) x) where the row x the update loads has
+ * n = |x| > c, once, at the update sites of mrec_sparse_apply_next_max_norm's apply (n^2 in the lookup's order of additions: the
+ * forward and the backward take one decision per row).  Same rules as _next_pool_fields: armed for ONE call of this host thread,
+ * disarmed by that call whether it runs or refuses, the armed call's grad_scale must be 1.0f (else MREC_EINVAL); arming replaces any
+ * other pooled arm, and either of the two arms above replaces this one.  F = 1 with field_scale = {grad_scale} is the equal-length
+ * case (mrec_sparse_apply_next_pool): there is no second entry.  The armed call launches k_apply_main_fields<.., UpdAdamClip, ..>,
+ * then the clip's finishing pass, k_apply_long<4, K, UpdAdamClip>.  max_norm not finite or <= 0: MREC_EINVAL, and the arming errors of
+ * _next_pool_fields, all with nothing left armed.  The armed call returns MREC_EUNSUPPORTED before any launch, and disarms, when it
+ * is not a LazyAdam apply (mrec_sparse_lazy_adam_{f32,bf16g,f16g}_{i32,i64}) -- FTRL, the segment sums -- or a folded wide form, for
+ * D % 4 != 0, D > 256 or rows that are not 16-byte aligned, with constant columns armed and with mrec_sparse_apply_next_max_norm armed
+ * on top of it. */
+int mrec_sparse_apply_next_pool_fields_clip(int32_t F, const int32_t* field_len, const float* field_scale, float max_norm);
 int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, const float* g, void* shadow16, int shadow_kind, int64_t n,
                                      int32_t nseg, const float* const* slabs, const int64_t* starts, const int64_t* lens,
                                      const int32_t* splits, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,

@@ -1150,23 +1150,30 @@ thread_local hipEvent_t t_prof_start = nullptr, t_prof_stop = nullptr;
 thread_local ApplyFinish* t_defer = nullptr;        // set by mrec_sparse_lazy_adam_wide_defer: the finishing pass is handed back, not launched
 thread_local ConstCols t_const = ConstCols{};       // set by mrec_sparse_apply_next_const_cols: the next wide apply takes constant columns out of its windows
 thread_local float t_max_norm = 0.0f;               // set by mrec_sparse_apply_next_max_norm: the next LazyAdam apply clips (0: none)
-thread_local FieldArgs t_fields = FieldArgs{};      // set by mrec_sparse_apply_next_pool / _next_pool_fields: the next apply is pooled (F == 0: not armed)
-inline void disarm_fields() { t_fields.F = 0; }
+thread_local FieldArgs t_fields = FieldArgs{};      // set by mrec_sparse_apply_next_pool / _next_pool_fields(_clip): the next apply is pooled (F == 0: not armed)
+thread_local float t_fields_clip = 0.0f;            // set by mrec_sparse_apply_next_pool_fields_clip with t_fields: that pooled apply clips (0: none)
+inline void disarm_fields() { t_fields.F = 0; t_fields_clip = 0.0f; }
 // Armed for one call: every entry that can be the "next apply" takes the arm first thing, whether it then runs or refuses.  MREC_OK and
 // *fields = &fa (armed) or nullptr (the plain apply); any other code is the entry's answer, with nothing left armed.  The pooled form is
 // refused, before anything else is looked at, for the folded wide apply (its wide lane and its hot columns address gradient rows by
 // position themselves), behind max_norm, and with constant columns armed -- which are disarmed with it.  A contribution has ONE scale
 // besides its row_scale: the call's grad_scale under mrec_sparse_apply_next_pool, else the field's -- and grad_scale must be 1.0.
-inline int take_fields(FieldArgs& fa, const FieldArgs** fields, float gscale, bool wide, bool clip) {
+// max_norm over the pooled form travels WITH the arm (mrec_sparse_apply_next_pool_fields_clip): *pool_clip is that arm's max_norm (0:
+// none), and an entry that passes no pool_clip -- anything but the plain LazyAdam apply -- refuses such an arm like the other cases.
+inline int take_fields(FieldArgs& fa, const FieldArgs** fields, float gscale, bool wide, bool clip, float* pool_clip = nullptr) {
     fa = t_fields;
+    const float pc = t_fields_clip;
     disarm_fields();
     *fields = nullptr;
+    if (pool_clip) *pool_clip = 0.0f;
     if (fa.F == 0) return MREC_OK;
     const bool cc_armed = t_const.mask != nullptr;
     t_const = ConstCols{};
     if (wide || clip || cc_armed) return MREC_EUNSUPPORTED;
+    if (pc > 0.0f && !pool_clip) return MREC_EUNSUPPORTED;
     if (fa.call_scale) fa.scale[0] = gscale;
     else if (gscale != 1.0f) return MREC_EINVAL;
+    if (pool_clip) *pool_clip = pc;
     *fields = &fa;
     return MREC_OK;
 }
@@ -1204,13 +1211,14 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
     const unsigned lblocks = (unsigned)mrec_cdiv(nsw, (int64_t)(16 * gm.G < 256 ? 16 * gm.G : 256));      // k_apply_long: 4 windows per lane-group, 4 G lane-groups, 256 at most
     const hipEvent_t ev0 = t_prof_start, ev1 = t_prof_stop;
     t_prof_start = t_prof_stop = nullptr;
-    // the pooled windows (fields; refused before this for the folded wide forms and max_norm): k_apply_main_fields, else k_apply_main
+    // the pooled windows (fields; refused before this for the folded wide forms and a separately armed max_norm; UpdAdamClip with
+    // fields is mrec_sparse_apply_next_pool_fields_clip's call): k_apply_main_fields, else k_apply_main
 #define MREC_APPLY_MAIN(VECN)                                                                                                          \
     do {                                                                                                                               \
-        if (Upd::kClip || !fields)                                                                                                     \
+        if (!fields)                                                                                                                   \
             k_apply_main<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,      \
                                                                   w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);          \
-        else if constexpr (!Upd::kClip) {                                                                                              \
+        else {                                                                                                                         \
             if (fields->F == 1 && fields->Ls > 1)                                                                                      \
                 k_apply_main_fields<VECN, K, Upd, GT, true><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gm,  \
                                                                                    w.carry_head, w.carry_tail, w.owners, seg_offsets, *fields); \
@@ -1295,7 +1303,7 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
                float gscale, void* ws, size_t ws_bytes, void* stream, const WideArgs* wide = nullptr, StepState* ss = nullptr,
                const int64_t* nv = nullptr, const FieldArgs* fields = nullptr) {
     hipStream_t st = (hipStream_t)stream;
-    if (fields && (wide || Upd::kClip)) return MREC_EUNSUPPORTED;      // (refused by the entries already: take_fields)
+    if (fields && wide) return MREC_EUNSUPPORTED;      // (refused by the entries already: take_fields)
     if (n < 0 || D <= 0 || V < 0 || ld < D || ldg < D) return MREC_EINVAL;
     if (n == 0) return MREC_OK;
     if (fields && (uint64_t)n * (uint64_t)fields->Ls >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;   // pos / Ls by a 32-bit multiply-high
@@ -1341,11 +1349,16 @@ int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t 
                    int64_t ldg, const float* rscale, float lr, float b1, float b2, float eps, float b1_pow,
                    float b2_pow, float gscale, int nesterov, void* ws, size_t ws_bytes, void* stream,
                    const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr) {
-    const float clip = t_max_norm;                 // (armed for this call only)
+    float clip = t_max_norm;                       // (armed for this call only)
     t_max_norm = 0.0f;
     FieldArgs fa;
     const FieldArgs* fields;
-    if (const int rc = take_fields(fa, &fields, gscale, wide != nullptr, clip > 0.0f)) return rc;
+    float pool_clip = 0.0f;                        // (max_norm of mrec_sparse_apply_next_pool_fields_clip: it came with the pooled arm)
+    if (const int rc = take_fields(fa, &fields, gscale, wide != nullptr, clip > 0.0f, &pool_clip)) return rc;
+    if (pool_clip > 0.0f) {
+        if (D % 4 || D > 256) return MREC_EUNSUPPORTED;      // (a width the clip cannot run at: the armed call's first answer)
+        clip = pool_clip;
+    }
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdAdam u;
     u.s[0] = p; u.s[1] = m; u.s[2] = v;
@@ -1617,6 +1630,15 @@ MREC_API int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_
     fa.F = F;
     fa.magic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)Ls + 1);      // pos / Ls = umulhi(pos, magic) while pos * Ls < 2^32 (Ls == 1: not used)
     t_fields = fa;
+    return MREC_OK;
+}
+
+MREC_API int mrec_sparse_apply_next_pool_fields_clip(int32_t F, const int32_t* field_len, const float* field_scale, float max_norm) {
+    disarm_fields();
+    if (!(max_norm > 0.0f) || !(max_norm <= 3.402823466e38f)) return MREC_EINVAL;
+    const int rc = mrec_sparse_apply_next_pool_fields(F, field_len, field_scale);
+    if (rc != MREC_OK) return rc;
+    t_fields_clip = max_norm;
     return MREC_OK;
 }
 

@@ -22,6 +22,8 @@
 //
 // A third entry, mrec_gather_pool_fields_keyed, is the fields form over the rows of a hash table (MapParameter), where a key that is
 // not in the table reads as its default row: a kernel of its own, k_gather_pool_fields_keyed, at the end of this file.
+// max_norm (mrec_gather_pool_fields_clip, mrec_gather_pool_fields_keyed_clip: every looked-up row clipped before its mask product) is
+// a third kernel, k_gather_pool_fields_clip, behind that one: the two above keep their symbols and their code.
 //
 // Shape of the kernel: k_gather_rows' (mrec_gather.hip).  lpr = D / 4 lanes per bag on the float4 path (D % 4 == 0, 16-byte
 // aligned rows), G = 64 / lpr bags per wave; a lane-group keeps PB row loads in flight: the PB ids and mask values of a batch of
@@ -34,6 +36,8 @@
 #include "mrec_optim.h"
 #include "mrec_dense_adam.h"
 #include "mrec_rng.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -320,6 +324,140 @@ int pool_keyed_impl(const float* table, int64_t V, int64_t ld, int32_t D, const 
     return MREC_OK;
 }
 
+// ===== max_norm: the pooled lookup with nn.ClipByNorm over every looked-up row ========================================================
+// HashEmbeddingLookup(max_norm=c) / nn.EmbeddingLookup(max_norm=c) (mindspore_rec/ops/embedding.py:156-161,202-205) clip each row
+// BEFORE the `* mask`; over bags that is Gather -> ClipByNorm -> Mul(mask) -> ReduceMean / ReduceSum.  The kernel is the two above,
+// statement for statement, with one stage more: once the PB rows of a batch of slots have landed and the rows that are not the table's
+// have been replaced -- a zero row in the dense form, the key's default row in the keyed form (MapTensorGet returns it and
+// ClipByNorm follows) -- every slot in flight takes mrec_row_sumsq, then mrec_clip_scale, and is scaled where n > c: the arithmetic
+// of k_gather_rows' clip instantiations (mrec_gather.hip), operation for operation, so a row reads the same bits through either
+// lookup and the sparse apply's Jacobian (clip_grad, mrec_apply.hip) takes the same decision.  A zero row has n = 0 and is never
+// clipped.  Then product, slot-order adds, one division, one store, as above.
+// Float4 rows only and ONE column block: D % 4 == 0, D <= 256, so a bag's lane-group is nd = D / 4 lanes that hold the whole row
+// (lpr == nd), the butterfly's partners are lanes lane0 .. lane0 + nd - 1 of the bag's OWN lane-group (lane0 = lane - sub), which
+// share L and so sit in the same iteration of the l0 loop: lane-groups of a wave that walk different numbers of batches never read
+// each other, and the spare lanes that left at the top are nobody's partner.
+// One kernel for both forms: KEY = void is the dense form (ids of type I, no keys, no default), else the keyed form (I = int32_t).
+template <int PB, class I, class KEY, class OT, bool ONE>
+__global__ __launch_bounds__(256) void k_gather_pool_fields_clip(const float* __restrict__ table, int64_t V, int64_t ld,
+                                                                 const I* __restrict__ ids, const KEY* __restrict__ keys,
+                                                                 const float* __restrict__ mask, unsigned nbags, unsigned F, int Ls, int mode,
+                                                                 OT* __restrict__ out, int64_t ldo, int D, PoolGeom gm, float c,
+                                                                 const MapDefault dv, const PoolFields pf) {
+    constexpr bool KEYED = !std::is_void<KEY>::value;
+    typedef typename std::conditional<KEYED, KEY, int32_t>::type KT;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;                                      // spare lanes; this kernel has no barriers
+    const unsigned w = (blockIdx.x * 4u + (unsigned)wave) * (unsigned)gm.G + (unsigned)grp;      // (nbags = B * F < 2^31: no wrap)
+    const unsigned wc = w < nbags ? w : nbags - 1u;               // a bag past the end reads the last bag, and stores nothing
+    const unsigned b = ONE ? wc : wc / F, f = wc - b * F;
+    const unsigned fw = ONE ? (unsigned)Ls << 16 : pf.w[f];
+    const int off = (int)(fw & 0xFFFFu), L = (int)(fw >> 16);
+    const I* __restrict__ idb = ids + (int64_t)b * Ls + off;
+    const KT* __restrict__ kb = KEYED ? (const KT*)keys + (int64_t)b * Ls + off : nullptr;
+    const float* __restrict__ mb = mask ? mask + (int64_t)b * Ls + off : nullptr;
+    OT* __restrict__ ob = out + (int64_t)b * ldo + (int64_t)f * D;
+    const int llast = L - 1;
+    const float fl = (float)L;
+    const int col = sub * 4;                                      // (the lane-group holds the whole row: lpr == D / 4)
+    const int nd = gm.lpr, lane0 = lane - sub;
+    Vf<4> acc = vzero((Vf<4>*)nullptr);
+    for (int l0 = 0; l0 < L; l0 += PB) {
+        int64_t row[PB], key[PB];
+        float mk[PB];
+        Vf<4> x[PB];
+        bool okr[PB];
+#pragma unroll
+        for (int k = 0; k < PB; ++k) {
+            const int lc = l0 + k < L ? l0 + k : llast;           // (a slot past the bag's end reads the bag's last id: inside the bag)
+            row[k] = (int64_t)idb[lc];
+            mk[k] = mb ? mb[lc] : 1.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < PB; ++k) {
+            okr[k] = row[k] >= 0 && row[k] < V;
+            x[k] = vload(table + (okr[k] ? row[k] : 0) * ld + col, (Vf<4>*)nullptr);
+            key[k] = 0;
+            if constexpr (KEYED) {
+                if (!okr[k] && l0 + k < L) key[k] = (int64_t)kb[l0 + k];      // (the slot's own key: l0 + k < L, inside the bag)
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < PB; ++k) {
+            vtouch(x[k]);
+            if (!okr[k]) {
+                if constexpr (KEYED) x[k] = (l0 + k < L) ? vdefault(dv, key[k], col, (Vf<4>*)nullptr) : vzero((Vf<4>*)nullptr);
+                else x[k] = vzero((Vf<4>*)nullptr);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < PB; ++k) {                            // (every lane of the lane-group, every slot in flight: no branch around the butterfly)
+            float s;
+            if (mrec_clip_scale(mrec_row_sumsq(x[k].v, sub, nd, lane0), c, &s)) x[k] = vscale(x[k], s);
+        }
+#pragma unroll
+        for (int k = 0; k < PB; ++k) {
+            if (l0 + k < L) {
+                const Vf<4> p = mb ? vscale(x[k], mk[k]) : x[k];
+                acc = (l0 + k == 0) ? p : vadd(acc, p);           // slot 0 starts the sum
+            }
+        }
+    }
+    if (mode == 1) acc = vdiv(acc, fl);
+    if (w < nbags) vstore(ob + col, acc);
+}
+
+/* max_norm: finite and > 0 (else MREC_EINVAL) -- mrec_gather.hip's clip_check, first half */
+inline bool pool_clip_ok(float max_norm) { return max_norm > 0.0f && max_norm <= 3.402823466e38f; }
+
+template <class I, class KEY, class OT>
+int pool_clip_impl(const float* table, int64_t V, int64_t ld, int32_t D, const I* ids, const KEY* keys, int64_t B, int32_t F, int32_t Ls,
+                   int32_t maxL, const PoolFields& pf, const float* mask, int32_t mode, const MapDefault& dv, float c, OT* out, int64_t ldo,
+                   hipStream_t st) {
+    PoolGeom gm;
+    gm.lpr = D / 4;                                      // (D % 4 == 0, D <= 256: checked by pool_clip_run)
+    gm.G = 64 / gm.lpr;
+    const int64_t nbags = B * F;
+    const unsigned blocks = (unsigned)mrec_cdiv(nbags, (int64_t)4 * gm.G);
+#define MREC_POOLC_LAUNCH1(PBN, ONE)                                                                                                  \
+    k_gather_pool_fields_clip<PBN, I, KEY, OT, ONE><<<blocks, 256, 0, st>>>(table, V, ld, ids, keys, mask, (unsigned)nbags, (unsigned)F,     \
+                                                                           (int)Ls, (int)mode, out, ldo, (int)D, gm, c, dv, pf)
+#define MREC_POOLC_LAUNCH(PBN) do { if (F == 1) MREC_POOLC_LAUNCH1(PBN, true); else MREC_POOLC_LAUNCH1(PBN, false); } while (0)
+    if (maxL <= 2) MREC_POOLC_LAUNCH(2); else MREC_POOLC_LAUNCH(8);
+#undef MREC_POOLC_LAUNCH
+#undef MREC_POOLC_LAUNCH1
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+// what both _clip entries do behind their own argument checks (keys == nullptr / key_bytes == 0: the dense form, ids of id_bytes)
+int pool_clip_run(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, const void* keys,
+                  int32_t key_bytes, int64_t B, int32_t F, int32_t Ls, int32_t maxL, const PoolFields& pf, const float* mask, int32_t mode,
+                  const MapDefault& dv, float c, void* out, int32_t out_kind, int64_t ldo, void* stream) {
+    if (B * F > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;      // (bags are numbered in 32 bits)
+    // float4 rows in one column block, or nothing: a row's norm is one lane-group's
+    const uintptr_t oa = out_kind == 0 ? 15 : 7;
+    if (D % 4 != 0 || D > 256 || ld % 4 != 0 || ldo % 4 != 0 || !al16(table) || (((uintptr_t)out) & oa) != 0) return MREC_EUNSUPPORTED;
+    if (B == 0) return MREC_OK;
+    if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
+    if (!table || !ids || !out || (key_bytes && !keys)) return MREC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+#define MREC_POOLC(IT, KT, OT) return pool_clip_impl<IT, KT, OT>(table, V, ld, D, (const IT*)ids, (const KT*)keys, B, F, Ls, maxL, pf, mask, mode, dv, c, (OT*)out, ldo, st)
+#define MREC_POOLC_OUT(IT, KT)                                 \
+    do {                                                       \
+        if (out_kind == 0) { MREC_POOLC(IT, KT, float); }      \
+        if (out_kind == 1) { MREC_POOLC(IT, KT, bf16o_t); }    \
+        MREC_POOLC(IT, KT, f16o_t);                            \
+    } while (0)
+    if (key_bytes == 4) MREC_POOLC_OUT(int32_t, int32_t);
+    if (key_bytes == 8) MREC_POOLC_OUT(int32_t, int64_t);
+    if (id_bytes == 4) MREC_POOLC_OUT(int32_t, void);
+    MREC_POOLC_OUT(int64_t, void);
+#undef MREC_POOLC_OUT
+#undef MREC_POOLC
+}
+
 // the bags of a sample from the caller's lengths: what both fields entries check, in this order
 int pool_fields_parse(int32_t F, const int32_t* field_len, PoolFields& pf, int32_t& Ls_out, int32_t& maxL_out) {
     if (F < 1 || !field_len) return MREC_EINVAL;
@@ -393,4 +531,35 @@ MREC_API int mrec_gather_pool_fields_keyed(const float* table, int64_t V, int64_
     if (out_kind == 1) { MREC_POOLK(int64_t, bf16o_t); }
     MREC_POOLK(int64_t, f16o_t);
 #undef MREC_POOLK
+}
+
+/* ... with max_norm: every looked-up row is clipped (nn.ClipByNorm) before its mask product */
+MREC_API int mrec_gather_pool_fields_clip(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
+                                          int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
+                                          int64_t ldo, float max_norm, void* stream) {
+    if (!pool_args_ok(id_bytes, out_kind, mode, B, D, V, ld) || !pool_clip_ok(max_norm)) return MREC_EINVAL;
+    PoolFields pf{};
+    int32_t Ls = 0, maxL = 0;
+    const int rc = pool_fields_parse(F, field_len, pf, Ls, maxL);
+    if (rc != MREC_OK) return rc;
+    if (ldo == 0) ldo = (int64_t)F * D;
+    if (ldo < (int64_t)F * D) return MREC_EINVAL;
+    return pool_clip_run(table, V, ld, D, ids, id_bytes, nullptr, 0, B, F, Ls, maxL, pf, mask, mode, MapDefault{0, 0.0f, 0.0f}, max_norm, out,
+                         out_kind, ldo, stream);
+}
+
+MREC_API int mrec_gather_pool_fields_keyed_clip(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* rows, const void* keys,
+                                                int32_t key_bytes, int64_t B, int32_t F, const int32_t* field_len, const float* mask,
+                                                int32_t mode, uint64_t seed, float sigma, float fill, void* out, int32_t out_kind,
+                                                int64_t ldo, float max_norm, void* stream) {
+    if (!pool_args_ok(key_bytes, out_kind, mode, B, D, V, ld) || !pool_clip_ok(max_norm)) return MREC_EINVAL;
+    if (!(sigma - sigma == 0.0f) || !(fill - fill == 0.0f)) return MREC_EINVAL;      // NaN or infinite
+    PoolFields pf{};
+    int32_t Ls = 0, maxL = 0;
+    const int rc = pool_fields_parse(F, field_len, pf, Ls, maxL);
+    if (rc != MREC_OK) return rc;
+    if (ldo == 0) ldo = (int64_t)F * D;
+    if (ldo < (int64_t)F * D) return MREC_EINVAL;
+    return pool_clip_run(table, V, ld, D, rows, 4, keys, key_bytes, B, F, Ls, maxL, pf, mask, mode,
+                         MapDefault{seed, sigma, fill}, max_norm, out, out_kind, ldo, stream);
 }

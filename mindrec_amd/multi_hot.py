@@ -45,6 +45,12 @@ Fields that hold RAW KEYS -- entity, topic, category ids of a growing catalogue,
 (HashEmbeddingLookup over a MapParameter, mindspore_rec/ops/embedding.py:136-205) -- over a hash table instead of a [vocab, dim]
 array: MultiHotHashEmbedding, at the end of this file.
 
+max_norm=c on any of the three classes is the ClipByNorm of HashEmbeddingLookup(max_norm=c) / nn.EmbeddingLookup(max_norm=c)
+(mindspore_rec/ops/embedding.py:156-161,202-205) over bags: every looked-up row is clipped to norm c before its mask product -- still
+one pooled launch (ops.gather_pool_fields(max_norm=c)), train=False included -- and apply_ takes the gradient through the clip's Jacobian
+in the same pooled apply (ops.sparse_lazy_adam_(pool_max_norm=c)).  "lazy_adam" only, dim % 4 == 0, dim <= 256: anything else is
+refused at construction.
+
 Neither method synchronises with the host, so lookup + apply_ capture into one HIP graph on one stream.  The Adam bias-correction
 powers advance on the host with every apply_: a captured graph holds the powers of the steps it captured (replaying K captured
 steps repeats those K steps; it does not continue the count).  No torch arithmetic on the step."""
@@ -57,10 +63,22 @@ from .experimental import MapParameter
 _OPTIMIZERS = ("lazy_adam", "ftrl", "adam")
 
 
+def _clip_arg(max_norm, optimizer, dim):
+    """max_norm of a multi-hot class: None, or a finite float > 0 under 'lazy_adam' with float4 rows of one column block"""
+    if max_norm is None:
+        return None
+    c = ops._max_norm(max_norm)
+    if optimizer != "lazy_adam":
+        raise ValueError(f"max_norm: the pooled apply clips under optimizer 'lazy_adam' only, got {optimizer!r}")
+    if dim % 4 != 0 or dim > 256:
+        raise ValueError(f"max_norm: dim must be a multiple of 4 and at most 256, got {dim}")
+    return c
+
+
 class MultiHotEmbedding:
     def __init__(self, vocab, dim, bag, mode="mean", optimizer="lazy_adam", device="cuda:0", seed=0, sigma=0.01, lr=None, beta1=0.9,
                  beta2=0.999, eps=1e-8, use_nesterov=False, l1=1e-8, l2=1e-8, lr_power=-0.5, initial_accum=1.0,
-                 out_dtype=torch.float32):
+                 out_dtype=torch.float32, max_norm=None):
         if mode not in ("sum", "mean"):
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         if optimizer not in _OPTIMIZERS:
@@ -76,6 +94,7 @@ class MultiHotEmbedding:
         self.fields = bag                   # the bag lengths (L_0, .., L_{F-1}) of a sample; bag is their sum
         self.vocab, self.dim, self.bag = int(vocab), int(dim), sum(bag)
         self.mode, self.optimizer, self.out_dtype = mode, optimizer, out_dtype
+        self.max_norm = _clip_arg(max_norm, optimizer, self.dim)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("mindrec_amd ops run on the GPU only (no CPU fallback)")
@@ -121,7 +140,8 @@ class MultiHotEmbedding:
             out = torch.empty((B, G * W), dtype=self.out_dtype, device=self.table.device)
         elif tuple(out.shape) != (B, G * W) or (G > 1 and not out.is_contiguous()):
             raise TypeError("out must be [B, F * dim] (contiguous when ids hold more than one field)")
-        ops.gather_pool_fields(self.table, flat, self.fields, fmask, mode=self.mode, out=out if G == 1 else out.view(B * G, W))
+        ops.gather_pool_fields(self.table, flat, self.fields, fmask, mode=self.mode, out=out if G == 1 else out.view(B * G, W),
+                               max_norm=self.max_norm)
         self._ids = flat.contiguous()
         self._mask = fmask.contiguous() if fmask is not None else None
         return out
@@ -152,7 +172,7 @@ class MultiHotEmbedding:
         akw = dict(lr=self.lr, beta1=float(self.beta1), beta2=float(self.beta2), eps=self.eps, beta1_power=float(self.beta1_power),
                    beta2_power=float(self.beta2_power), use_nesterov=self.use_nesterov)
         if self.optimizer == "lazy_adam":
-            ops.sparse_lazy_adam_(self.table, self.m, self.v, plan, g, mask, **pkw, **akw)
+            ops.sparse_lazy_adam_(self.table, self.m, self.v, plan, g, mask, pool_max_norm=self.max_norm, **pkw, **akw)
         elif self.optimizer == "ftrl":
             ops.sparse_ftrl_(self.table, self.accum, self.linear, plan, g, mask, lr=self.lr, l1=self.l1, l2=self.l2,
                              lr_power=self.lr_power, **pkw)
@@ -179,17 +199,18 @@ class MultiHotWideDeep:
     where the table sits in cache, so it is not here.
     Arguments without a prefix go to the deep half, wide_* to the wide half.  bag: an int (one field) or a tuple; ids are [B, Ls]
     only.  bag=(1,) * n with mask=None is the single-hot case: n rows side by side (Gather + Flatten) and the sum of their n wide
-    weights.  Neither method synchronises with the host: lookup + apply_ capture into one HIP graph on one stream."""
+    weights.  max_norm=c clips the deep half's rows (MultiHotEmbedding(max_norm=c)); the wide weights are never clipped, as in the
+    fused step, and the plan stays shared.  Neither method synchronises with the host: lookup + apply_ capture into one HIP graph on one stream."""
 
     def __init__(self, vocab, dim, bag, mode="mean", optimizer="lazy_adam", wide_optimizer="ftrl", device="cuda:0", seed=0, wide_seed=1,
                  sigma=0.01, wide_sigma=0.01, lr=None, wide_lr=None, beta1=0.9, beta2=0.999, eps=1e-8, use_nesterov=False, l1=1e-8, l2=1e-8,
-                 lr_power=-0.5, initial_accum=1.0, out_dtype=torch.float32):
+                 lr_power=-0.5, initial_accum=1.0, out_dtype=torch.float32, max_norm=None):
         if wide_optimizer not in _OPTIMIZERS:
             raise ValueError(f"wide_optimizer must be one of {_OPTIMIZERS}, got {wide_optimizer!r}")
         hyper = dict(device=device, beta1=beta1, beta2=beta2, eps=eps, use_nesterov=use_nesterov, l1=l1, l2=l2, lr_power=lr_power,
                      initial_accum=initial_accum)
         self.deep = MultiHotEmbedding(vocab, dim, bag, mode=mode, optimizer=optimizer, seed=seed, sigma=sigma, lr=lr, out_dtype=out_dtype,
-                                      **hyper)
+                                      max_norm=max_norm, **hyper)      # (the deep half only: the [V] wide weights are never clipped)
         self.wide = MultiHotEmbedding(vocab, 1, self.deep.bag, mode="sum", optimizer=wide_optimizer, seed=wide_seed, sigma=wide_sigma,
                                       lr=wide_lr, **hyper)
         self.fields, self.bag = self.deep.fields, self.deep.bag
@@ -252,11 +273,12 @@ class MultiHotHashEmbedding:
     Optimizers: "lazy_adam" (slots "moment1", "moment2": nn.LazyAdam's names over a MapParameter) and "ftrl" ("accum" from
     initial_accum, "linear"), created through MapParameter.add_slot so that every new key's slot rows start at their initial
     values.  "adam", the dense whole-table update, is refused: a hash table has no "every row".  dim = 1, mode "sum", optimizer "ftrl"
-    over the same keys is the wide side.  Eviction is the map's (emb.map.evict()): an evicted key seen again is a new key.
+    over the same keys is the wide side.  max_norm=c: HashEmbeddingLookup(max_norm=c) over bags -- every slot's row, a missing key's
+    default row included, is clipped before its mask product, and apply_ applies through the clip ("lazy_adam" only).  Eviction is the map's (emb.map.evict()): an evicted key seen again is a new key.
     Neither method synchronises with the host."""
 
     def __init__(self, map_or_kwargs, bag, mode="mean", optimizer="lazy_adam", lr=None, beta1=0.9, beta2=0.999, eps=1e-8, use_nesterov=False,
-                 l1=1e-8, l2=1e-8, lr_power=-0.5, initial_accum=1.0, out_dtype=torch.float32):
+                 l1=1e-8, l2=1e-8, lr_power=-0.5, initial_accum=1.0, out_dtype=torch.float32, max_norm=None):
         if mode not in ("sum", "mean"):
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         if optimizer == "adam":
@@ -276,6 +298,7 @@ class MultiHotHashEmbedding:
         self.fields, self.bag = bag, sum(bag)
         self.dim = self.map.value_shape[0]
         self.mode, self.optimizer, self.out_dtype = mode, optimizer, out_dtype
+        self.max_norm = _clip_arg(max_norm, optimizer, self.dim)
         self.device = self.map.device
         self.lr = float(lr) if lr is not None else (5e-2 if optimizer == "ftrl" else 3.5e-4)
         self.eps, self.use_nesterov = float(eps), bool(use_nesterov)
@@ -311,7 +334,7 @@ class MultiHotHashEmbedding:
         m = self.map
         rows = m.lookup_rows(flat.view(-1), insert=bool(train))[2].view(B * G, self.bag)
         ops.gather_pool_fields_keyed(m.values, rows, flat, self.fields, fmask, mode=self.mode, out=out if G == 1 else out.view(B * G, W),
-                                     default=(m._sigma, m._fill, m.seed))
+                                     max_norm=self.max_norm, default=(m._sigma, m._fill, m.seed))
         self._rows = m.admitted_rows(rows) if train else None
         self._mask = fmask
         return out
@@ -340,7 +363,7 @@ class MultiHotHashEmbedding:
         if self.optimizer == "lazy_adam":
             ops.sparse_lazy_adam_(self.map.values, s0, s1, plan, g, mask, lr=self.lr, beta1=float(self.beta1), beta2=float(self.beta2),
                                   eps=self.eps, beta1_power=float(self.beta1_power), beta2_power=float(self.beta2_power),
-                                  use_nesterov=self.use_nesterov, **pkw)
+                                  use_nesterov=self.use_nesterov, pool_max_norm=self.max_norm, **pkw)
         else:
             ops.sparse_ftrl_(self.map.values, s0, s1, plan, g, mask, lr=self.lr, l1=self.l1, l2=self.l2, lr_power=self.lr_power, **pkw)
         return plan

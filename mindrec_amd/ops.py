@@ -275,10 +275,13 @@ def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32, m
 _OUT_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
-def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype, keyed=None):
+def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype, keyed=None, max_norm=None):
     """the one lookup behind gather_pool, gather_pool_fields (mrec_gather_pool_fields) and gather_pool_fields_keyed
-    (mrec_gather_pool_fields_keyed; keyed = (keys, seed, sigma, fill)): ids, mask [B, sum(lens)] -> out [B, F * D]"""
+    (mrec_gather_pool_fields_keyed; keyed = (keys, seed, sigma, fill)): ids, mask [B, sum(lens)] -> out [B, F * D].  max_norm: the
+    _clip entry of either, the same arguments with max_norm before the stream (None: the entry itself, as before)"""
     V, D, ld = _table(table)
+    clip = () if max_norm is None else (_max_norm(max_norm),)
+    tail = "_clip" if clip else ""
     sfx = _suffix(ids)
     if mode not in ("sum", "mean"):
         raise ValueError(f"{who} mode must be 'sum' or 'mean', got {mode!r}")
@@ -295,21 +298,22 @@ def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype, keyed=None):
     if keyed is not None:
         keys, seed, sigma, fill = keyed
         keys = keys.contiguous()
-        _lib.call("mrec_gather_pool_fields_keyed", _ptr(table), V, ld, D, _ptr(ids), _ptr(keys), keys.element_size(), B, F,
+        _lib.call("mrec_gather_pool_fields_keyed" + tail, _ptr(table), V, ld, D, _ptr(ids), _ptr(keys), keys.element_size(), B, F,
                   (C.c_int32 * F)(*lens), _ptr(mask), 1 if mode == "mean" else 0, C.c_uint64(seed), sigma, fill, _ptr(out),
-                  _OUT_KIND[out.dtype], ldo, _stream())
+                  _OUT_KIND[out.dtype], ldo, *clip, _stream())
         return out
-    _lib.call("mrec_gather_pool_fields", _ptr(table), V, ld, D, _ptr(ids), 4 if sfx == "i32" else 8, B, F, (C.c_int32 * F)(*lens),
-              _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, _stream())
+    _lib.call("mrec_gather_pool_fields" + tail, _ptr(table), V, ld, D, _ptr(ids), 4 if sfx == "i32" else 8, B, F, (C.c_int32 * F)(*lens),
+              _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, *clip, _stream())
     return out
 
 
-def gather_pool(table, ids, mask=None, mode="mean", out=None, out_dtype=torch.float32):
+def gather_pool(table, ids, mask=None, mode="mean", out=None, out_dtype=torch.float32, max_norm=None):
     """The multi-hot lookup, Gather -> Mul(mask) -> ReduceMean / ReduceSum over the bag axis in one pass
     (wide_and_deep_multitable/src/wide_and_deep.py:301-346,377-418): ids [..., L] -> [..., D], out[b] = sum_l table[ids[b, l]] *
     mask[b, l] in slot order (fp32), divided by L for mode="mean" -- by the bag's length, not by its number of unmasked slots, as
     ReduceMean does.  mask: float32, one value per id (None: all ones).  out: a [B, D] tensor or column block (unit column stride;
-    its other columns are left alone) in float32 / bfloat16 / float16; 16-bit outputs are rounded once, at the end."""
+    its other columns are left alone) in float32 / bfloat16 / float16; 16-bit outputs are rounded once, at the end.  max_norm=c: as
+    gather_pool_fields."""
     _need_cuda(table, ids, mask, out)
     if ids.dim() < 1:
         raise TypeError("ids must be [..., L]: a bag of L ids per sample")
@@ -319,33 +323,38 @@ def gather_pool(table, ids, mask=None, mode="mean", out=None, out_dtype=torch.fl
         if mask.dtype != torch.float32 or mask.numel() != flat.numel():
             raise TypeError("mask must be float32 with one value per id")
         mask = mask.reshape(flat.shape)
-    ret = _gather_pool("gather_pool", table, flat, (L,), mask, mode, out, out_dtype)        # one field: the sample is the bag
+    ret = _gather_pool("gather_pool", table, flat, (L,), mask, mode, out, out_dtype, max_norm=max_norm)        # one field: the sample is the bag
     return ret if out is not None else ret.view(tuple(ids.shape[:-1]) + ret.shape[1:])
 
 
-def gather_pool_fields(table, ids, field_len, mask=None, mode="mean", out=None, out_dtype=torch.float32):
+def gather_pool_fields(table, ids, field_len, mask=None, mode="mean", out=None, out_dtype=torch.float32, max_norm=None):
     """gather_pool for F fields of UNEQUAL bag lengths over one table, in one launch (mrec_gather_pool_fields): ids [B, Ls], Ls =
     sum(field_len), field f in slots off_f .. off_f + L_f - 1 (the fields back to back; src/datasets.py:290-313 gives every multi-hot
     field of the reference a length of its own) -> [B, F * D] with field f pooled into columns f * D .. (f + 1) * D - 1 (the Concat at
     wide_and_deep.py:348-349).  Per bag the arithmetic is gather_pool's; mode="mean" divides by the FIELD's own length.  mask: float32
-    [B, Ls] or None.  out: a [B, F * D] tensor or column block (unit column stride) in float32 / bfloat16 / float16."""
+    [B, Ls] or None.  out: a [B, F * D] tensor or column block (unit column stride) in float32 / bfloat16 / float16.  max_norm=c:
+    every looked-up row x is clipped to x * (c / |x|) where |x| > c BEFORE its mask product (mrec_gather_pool_fields_clip: the ClipByNorm
+    of nn.EmbeddingLookup(max_norm=c) over a bag; each slot's row is gather_rows(max_norm=c)'s, bit for bit); D % 4 == 0, D <= 256,
+    16-byte aligned rows and outputs.  Its backward: sparse_lazy_adam_(fields=, field_scale=, pool_max_norm=c)."""
     _need_cuda(table, ids, mask, out)
     lens = _fields(field_len)
     if ids.dim() != 2 or ids.shape[1] != sum(lens):
         raise TypeError(f"ids must be [B, {sum(lens)}]: the bags of lengths {lens} back to back")
     if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
         raise TypeError("mask must be float32 of the shape of ids")
-    return _gather_pool("gather_pool_fields", table, ids, lens, mask, mode, out, out_dtype)
+    return _gather_pool("gather_pool_fields", table, ids, lens, mask, mode, out, out_dtype, max_norm=max_norm)
 
 
-def gather_pool_fields_keyed(values, rows, keys, fields, mask=None, mode="mean", out=None, out_dtype=torch.float32, *, default):
+def gather_pool_fields_keyed(values, rows, keys, fields, mask=None, mode="mean", out=None, out_dtype=torch.float32, max_norm=None, *,
+                             default):
     """gather_pool_fields over the rows of a hash table (MapParameter: HashEmbeddingLookup over a MapParameter, mindspore_rec/ops/
     embedding.py:136-205) whose multi-hot fields hold raw keys, in one launch (mrec_gather_pool_fields_keyed).  values: the map's
     [capacity, D] value rows; rows [B, Ls] int32: the row numbers KeyIndex.lookup gave for keys [B, Ls] (int32 / int64).  A slot
     whose row is in [0, capacity) contributes values[row]; any other (-1: a key that was not inserted, or dropped because the table is
     full) contributes the key's DEFAULT row, as MapTensorGet reads it -- bit for bit what KeyIndex.fill_missing writes, generated in
     registers: no [B * Ls, D] intermediate.  default = (sigma, fill, seed), fill_missing's triple: sigma * N(0,1) keyed by (seed, key,
-    column), or -- sigma None -- the constant fill.  fields, mask, mode, out, out_dtype and the arithmetic: gather_pool_fields'."""
+    column), or -- sigma None -- the constant fill.  fields, mask, mode, out, out_dtype and the arithmetic: gather_pool_fields'.
+    max_norm=c (mrec_gather_pool_fields_keyed_clip): as gather_pool_fields; a missing key's default row is clipped like any other."""
     _need_cuda(values, rows, keys, mask, out)
     lens = _fields(fields)
     if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != sum(lens):
@@ -358,7 +367,8 @@ def gather_pool_fields_keyed(values, rows, keys, fields, mask=None, mode="mean",
     sigma, fill = (-1.0 if sigma is None else float(sigma)), float(fill or 0.0)
     if not (math.isfinite(sigma) and math.isfinite(fill)):
         raise ValueError(f"default must hold a finite sigma (or None) and a finite fill, got {default!r}")
-    return _gather_pool("gather_pool_fields_keyed", values, rows, lens, mask, mode, out, out_dtype, keyed=(keys, int(seed), sigma, fill))
+    return _gather_pool("gather_pool_fields_keyed", values, rows, lens, mask, mode, out, out_dtype, keyed=(keys, int(seed), sigma, fill),
+                        max_norm=max_norm)
 
 
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
@@ -508,10 +518,18 @@ def _fields_arm(fields, field_scale, grad_scale):
     return (lens, _field_scales(lens, field_scale, grad_scale)), 1.0
 
 
-def _pooled(plan, pool, fields, field_scale, grad_scale):
+def _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm=None):
     """pool= / fields= of a sparse apply -> (arm, rows, grad_scale): what _call_clipped arms (None, None: the plain apply), the gradient
     rows the armed call reads (their count and how it is counted, for _grads) and the grad_scale it is given.  pool=L: one row per bag of L positions, ceil(n / L) of them (the last
-    bag may be short); fields=lengths: one per bag of a sample's F bags, n / sum(lengths) * F of them (whole samples)."""
+    bag may be short); fields=lengths: one per bag of a sample's F bags, n / sum(lengths) * F of them (whole samples).
+    pool_max_norm=c: the clip travels with the pooled arm (mrec_sparse_apply_next_pool_fields_clip); pool=L is then its F = 1 case,
+    fields=(L,) with field_scale=(grad_scale,), and whole bags like every fields form."""
+    if pool_max_norm is not None:
+        c = _max_norm(pool_max_norm)
+        if pool is not None and fields is None and field_scale is None:
+            fields, field_scale, grad_scale, pool = (_pool(pool),), (float(grad_scale),), 1.0, None
+        elif fields is None:
+            raise ValueError("pool_max_norm goes with pool= or fields=: the plain apply takes max_norm=")
     fa, grad_scale = _fields_arm(fields, field_scale, grad_scale)
     if fa is None:
         if pool is None:
@@ -525,6 +543,8 @@ def _pooled(plan, pool, fields, field_scale, grad_scale):
     if plan.n % Ls:
         raise TypeError(f"fields={lens}: the plan's {plan.n} positions are not whole samples of {Ls} ids")
     rows = (plan.n // Ls * F, f"fields={lens}: g must hold n / {Ls} * {F}")
+    if pool_max_norm is not None:
+        return ("mrec_sparse_apply_next_pool_fields_clip", F, (C.c_int32 * F)(*lens), (C.c_float * F)(*scales), c), rows, grad_scale
     return ("mrec_sparse_apply_next_pool_fields", F, (C.c_int32 * F)(*lens), (C.c_float * F)(*scales)), rows, grad_scale
 
 
@@ -575,19 +595,23 @@ def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None, fields=None,
 
 
 def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_power=0.9,
-                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False, max_norm=None, pool=None, fields=None, field_scale=None):
+                      beta2_power=0.999, grad_scale=1.0, use_nesterov=False, max_norm=None, pool=None, fields=None, field_scale=None,
+                      pool_max_norm=None):
     """nn.LazyAdam on a RowTensor gradient (wide_and_deep.py:420-422): in place on p, m, v.  max_norm=c: the gradients are those
     of rows the lookup clipped to c (gather_rows(..., max_norm=c) of the same p): each touched row's summed gradient G becomes
     (c / n)(G - (p.G / n^2) p) where n = |p| > c (mrec_sparse_apply_next_max_norm); D % 4 == 0, D <= 256.  pool=L: the bprop of
     gather_pool -- g is [ceil(n / L), D], one row per bag, and position i's gradient row is g[i // L] (segment_sum); not with
     max_norm.  fields=(L_0, ..), field_scale: the bprop of gather_pool_fields, as segment_sum -- one plan over all the fields' ids, so
-    an id that occurs in several fields gets the sum of their gradients and ONE update; not with pool= or max_norm."""
+    an id that occurs in several fields gets the sum of their gradients and ONE update; not with pool= or max_norm.
+    pool_max_norm=c, with fields= (or pool=L, its one-field case): the bprop of gather_pool_fields(max_norm=c) -- the pooled apply
+    whose completed row sums go through the clip's Jacobian as under max_norm (mrec_sparse_apply_next_pool_fields_clip: the clip
+    travels with the pooled arm); D % 4 == 0, D <= 256.  max_norm= stays the plain apply's and is refused with pool= or fields=."""
     _need_cuda(p, m, v, g, row_scale)
     V, D, ld = _table(p)
     for t in (m, v):
         if _table(t) != (V, D, ld):
             raise ValueError("p, m, v must share shape and row stride")
-    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
+    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm)
     g2, ldg = _grads(plan, g, D, allow_bf16=True, rows=rows)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, p.device)

@@ -31,7 +31,23 @@ The FIELDS form (bags of unequal length: fields (3, 5, 4, 3, 4, 2) of one table,
               the same table (and an id that occurs under two lengths is updated twice: not the reference's result either)
   bwd_padded  one plan over the B * 6 * 5 padded ids + one ops.sparse_lazy_adam_(pool=5) (wrong scale for the mean, as above)
 Here the plans are INSIDE the repeats: planning once instead of once per length is part of what the fields form changes.
-"fields-ref" = V 20 900, Zipf-like ids; "fields-large" = V 20 000 000, uniform ids."""
+"fields-ref" = V 20 900, Zipf-like ids; "fields-large" = V 20 000 000, uniform ids.
+
+max_norm over the fields form (every looked-up row clipped before its mask product, the apply through the clip's Jacobian), at the
+same two shapes, c = the median row norm of the table so that both branches run:
+
+  rocprofv3 --kernel-trace --output-format csv -d OUT -- python tools/pool_bench.py run clip-fields-ref > OUT/labels.json   (or clip-fields-large)
+  python tools/pool_bench.py reduce OUT/labels.json <the run's *_kernel_trace.csv>
+
+  fwd_fields     ops.gather_pool_fields, no clip                              -- what the clip costs on top of
+  fwd_clip       ops.gather_pool_fields(max_norm=c)                           -- one kernel
+  fwd_clip_comp  the composition it replaces: ops.gather_rows(max_norm=c) into [B * 21, D] with the mask as row_scale, then a torch
+                 sum over each field's slots and a divide by L_f into its column block
+  bwd_fields     ops.sparse_lazy_adam_(fields=...), no clip
+  bwd_clip       ops.sparse_lazy_adam_(fields=..., pool_max_norm=c)
+  bwd_clip_comp  the composition it replaces: dy expanded to [B * 21, D] (index_select by the position's bag), row_scale = mask / L_f,
+                 then the plain clipped ops.sparse_lazy_adam_(max_norm=c)
+The plan is built once, outside the repeats: all three backward variants take the same one."""
 import csv
 import json
 import os
@@ -41,6 +57,7 @@ from statistics import median
 REPEATS = 5
 VARIANTS = ("fwd_comp", "fwd_pool", "bwd_comp", "bwd_pool")
 FIELD_VARIANTS = ("fwd_perlen", "fwd_fields", "fwd_padded", "bwd_perlen", "bwd_fields", "bwd_padded")
+CLIP_VARIANTS = ("fwd_fields", "fwd_clip", "fwd_clip_comp", "bwd_fields", "bwd_clip", "bwd_clip_comp")
 FIELDS = (3, 5, 4, 3, 4, 2)
 
 
@@ -52,7 +69,7 @@ def _setup(shape, id_shape, dy_shape):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from mindrec_amd import ops
     dev = torch.device("cuda:0")
-    ref = shape in ("ref", "fields-ref")
+    ref = shape in ("ref", "fields-ref", "clip-fields-ref")
     V = 20900 if ref else 20_000_000
     rng = np.random.default_rng(7)
     if ref:
@@ -137,7 +154,52 @@ def run_fields(shape):
                           variants=list(FIELD_VARIANTS))))
 
 
+def run_clip(shape):
+    D, B, lens = 64, 131072, FIELDS
+    F, Ls = len(lens), sum(lens)
+    ops, torch, V, tid, mask, table, m, v, dy, marker = _setup(shape, (B, Ls), (B, F * D))
+    dev = table.device
+    c = float(table[:65536].norm(dim=1).median())            # the median row norm: half of the rows are clipped
+    pooled = torch.empty((B, F * D), dtype=torch.float32, device=dev)
+    rows = torch.empty((B * Ls, D), dtype=torch.float32, device=dev)
+    offs = [sum(lens[:f]) for f in range(F)]
+    fs = tuple(1.0 / L for L in lens)
+    slot_field = torch.tensor([f for f, L in enumerate(lens) for _ in range(L)], device=dev)
+    bag_row = (torch.arange(B, device=dev).view(B, 1) * F + slot_field.view(1, Ls)).reshape(-1)      # position -> its bag's gradient row
+    slot_scale = torch.tensor([fs[f] for f, L in enumerate(lens) for _ in range(L)], dtype=torch.float32, device=dev)
+    plan = ops.sparse_plan(tid)
+    akw = dict(beta1_power=0.9, beta2_power=0.999)
+
+    def variant(name):
+        if name == "fwd_fields":
+            ops.gather_pool_fields(table, tid, lens, mask, mode="mean", out=pooled)
+        elif name == "fwd_clip":
+            ops.gather_pool_fields(table, tid, lens, mask, mode="mean", out=pooled, max_norm=c)
+        elif name == "fwd_clip_comp":
+            ops.gather_rows(table, tid, mask, out=rows, max_norm=c)
+            r3 = rows.view(B, Ls, D)
+            for f, L in enumerate(lens):
+                blk = pooled[:, f * D:(f + 1) * D]
+                torch.sum(r3[:, offs[f]:offs[f] + L], dim=1, out=blk)
+                blk.div_(float(L))
+        elif name == "bwd_fields":
+            ops.sparse_lazy_adam_(table, m, v, plan, dy, mask, fields=lens, field_scale=fs, **akw)
+        elif name == "bwd_clip":
+            ops.sparse_lazy_adam_(table, m, v, plan, dy, mask, fields=lens, field_scale=fs, pool_max_norm=c, **akw)
+        else:
+            big = dy.view(B * F, D).index_select(0, bag_row)
+            rs = (mask * slot_scale).view(-1)
+            ops.sparse_lazy_adam_(table, m, v, plan, big, rs, max_norm=c, **akw)
+
+    order = _rotate(ops, torch, marker, CLIP_VARIANTS, variant)
+    need_fwd = B * Ls * D * 4 + B * F * D * 4 + B * Ls * 8          # rows read, pooled rows written, ids + mask read
+    print(json.dumps(dict(shape=shape, V=V, D=D, L=list(lens), bags=B * F, warmup_markers=0, order=order, fwd_bytes_needed=need_fwd,
+                          variants=list(CLIP_VARIANTS), max_norm=c)))
+
+
 def run(shape):
+    if shape.startswith("clip-fields-"):
+        return run_clip(shape)
     if shape.startswith("fields-"):
         return run_fields(shape)
     D, L, bags = 64, 8, 131072 * 6
@@ -188,6 +250,13 @@ def reduce(labels_path, trace_path):
         print(f"  {name:9s} median {median(x):9.1f}  min {min(x):9.1f}  max {max(x):9.1f}  spread {100 * (max(x) - min(x)) / median(x):5.1f} %  ({', '.join(f'{t:.1f}' for t in x)})")
         for k, ts in kernels[name].items():
             print(f"      {median(ts):9.1f} us x {len(ts) // len(x)}  {k}")
+    if "fwd_clip" in per:
+        ff, fc, fcc, bf, bc, bcc = (median(per[k]) for k in CLIP_VARIANTS)
+        print(f"  max_norm = {lab['max_norm']:.6f}")
+        print(f"  forward  clip / plain pooled = {fc / ff:.3f};  clip / composition = {fc / fcc:.3f};  needed bytes "
+              f"{lab['fwd_bytes_needed'] / 1e6:.1f} MB -> {lab['fwd_bytes_needed'] / fc / 1e6:.3f} TB/s")
+        print(f"  backward clip / plain pooled = {bc / bf:.3f};  clip / composition = {bc / bcc:.3f}")
+        return
     if "fwd_fields" in per:
         ff, fl, fpad, bf, bl, bpad = (median(per[k]) for k in ("fwd_fields", "fwd_perlen", "fwd_padded", "bwd_fields", "bwd_perlen", "bwd_padded"))
         print(f"  forward  fields / per-length = {ff / fl:.3f};  fields / padded (wrong mean) = {ff / fpad:.3f};  needed bytes "
