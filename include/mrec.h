@@ -1047,6 +1047,29 @@ int mrec_x3_gemm_dgrad_workspace_bytes(int64_t M, int32_t K, int32_t N, size_t* 
 int mrec_x3_gemm_dgrad(const uint16_t* dyparts, const uint16_t* wparts, int64_t M, int32_t K, int32_t N, float* dx, int64_t lddx,
                        const float* h, int64_t ldh, float scale, float* colsum, uint16_t* parts_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- evaluation metrics: exact integer counts (mrec_metric.hip) -----------------------------------------------------------
+ * Both calls only count: no float is ever added on the device, so the outputs are exact and the same bits on every run.  Neither
+ * synchronises; the caller reads the few output words when it wants the number.
+ *
+ * mrec_auc_counts: out4 = {twoU, P, N, n_nan} over n rows, 1 <= n < 2^31.  A row is positive iff label > 0.5f; P / N count the
+ *   positives / negatives; twoU = sum over positives i of (2 #{negatives j: pred_j < pred_i} + #{negatives j: pred_j == pred_i}) under
+ *   IEEE comparison (-0.0 == +0.0, denormals and infinities in order).  AUC = twoU / (2 P N): the trapezoidal ROC area, ties as one
+ *   half.  n_nan counts the NaN predictions, which take no part in the other three counts.  Three stable 11 + 11 + 10 bit radix
+ *   passes over an order-preserving key with the class as the value, prefix counts of both classes over the sorted order, the
+ *   tie-group boundaries compacted and neighbours paired: no step is serial in the length of a tie group.
+ *
+ * mrec_group_rank_hist: out = {hist[0..topk-1], G} for MAP@topk grouped by a display id, 1 <= topk <= 64, pad_to >= 0, n < 2^30.
+ *   inv[i] in [0, *n_groups_dev) is row i's group (mrec_dedup_*'s inverse index of the ids; *n_groups_dev its unique count).  Per group,
+ *   rows in ascending index: the clicked row c is the first one holding the group's maximal label; rank = #{rows of the group with
+ *   pred > pred[c]}, plus pad_to - m when the group has m < pad_to rows and pred[c] < 0 (every group counts as padded to pad_to
+ *   candidates of score 0.0); rank < topk adds one to hist[rank].  G = *n_groups_dev.  MAP = (sum_r hist[r] / (r + 1)) / G.
+ *   No step is serial in the size of a group. */
+int mrec_auc_ws_bytes(int64_t n, size_t* out);
+int mrec_auc_counts(const float* pred, const float* label, int64_t n, int64_t* out4, void* ws, size_t ws_bytes, void* stream);
+int mrec_group_rank_ws_bytes(int64_t n, size_t* out);
+int mrec_group_rank_hist(const float* pred, const float* label, const int32_t* inv, const int64_t* n_groups_dev, int64_t n,
+                         int32_t topk, int32_t pad_to, int64_t* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

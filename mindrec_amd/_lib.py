@@ -224,6 +224,10 @@ _SIGS = {
     "mrec_dense_adam_rows_l2_f32": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _f32, _vp, _int,
                                     _vp, _vp, _sz, _vp],
     "mrec_crc32c_host": [C.c_char_p, _sz, _vp],
+    "mrec_auc_ws_bytes": [_i64, _szp],
+    "mrec_auc_counts": [_vp, _vp, _i64, _vp, _vp, _sz, _vp],
+    "mrec_group_rank_ws_bytes": [_i64, _szp],
+    "mrec_group_rank_hist": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp],
 }
 _RESTYPES = {"mrec_strerror": C.c_char_p, "mrec_map_counters_dev": _vp, "mrec_map_row_keys_dev": _vp}
 

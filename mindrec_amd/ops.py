@@ -2059,3 +2059,60 @@ def fm_backward_(g, vx, colsum, dout):
     B, F_, D = vx.shape
     _lib.call("mrec_fm_bwd_f32", _ptr(vx.contiguous()), _ptr(colsum), _ptr(dout.contiguous()), B, F_, D, _ptr(g), _stream())
     return g
+
+
+# ---- evaluation metrics ------------------------------------------------------------------------
+def _metric_rows(who, **vecs):
+    """The row vectors of a metric call: 1-D, contiguous, of one length n >= 1, on the GPU.  name=(tensor, dtypes)."""
+    n = None
+    for name, (t, dtypes) in vecs.items():
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+            raise TypeError(f"{who}: {name} must be a tensor of dtype {' / '.join(str(d) for d in dtypes)}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous 1-D tensor, got shape {tuple(t.shape)} strides {t.stride()}")
+        n = t.numel() if n is None else n
+        if t.numel() != n:
+            raise ValueError(f"{who}: {name} holds {t.numel()} rows, not {n}")
+    if n == 0:
+        raise ValueError(f"{who}: no rows")
+    try:
+        _need_cuda(*(t for t, _ in vecs.values()))
+    except RuntimeError as e:
+        raise TypeError(f"{who}: {e}") from None
+    return n
+
+
+def auc_counts(pred, label):
+    """int64 [4] on the device: {twoU, P, N, n_nan} of float32 pred [n], label [n] (positive iff label > 0.5); the ROC area of
+    models/wide_deep/src/metrics.py:44 (roc_auc_score) is twoU / (2 P N) -- include/mrec.h 'evaluation metrics'.  Exact counts, the
+    same bits on every run; no host synchronisation."""
+    f32 = (torch.float32,)
+    n = _metric_rows("auc_counts", pred=(pred, f32), label=(label, f32))
+    if n >= 1 << 31:
+        raise ValueError(f"auc_counts: {n} rows, at most 2^31 - 1")
+    out = torch.empty(4, dtype=torch.int64, device=pred.device)
+    ws = workspace("auc", _lib.query_bytes("mrec_auc_ws_bytes", n), pred.device)
+    _lib.call("mrec_auc_counts", _ptr(pred), _ptr(label), n, _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def group_rank_hist(pred, label, group, topk=12, pad_to=30):
+    """int64 [topk + 1] on the device: {hist[0..topk-1], G} for MAP@topk grouped by `group` (int32 / int64 [n], any values) -- the
+    counts behind models/wide_and_deep_multitable/src/metrics.py:70-107 (new_compute_mAP): hist[r] = groups whose clicked row (the
+    first one holding the group's maximal label, np.argmax) has r rows of the group predicted above it, every group counted as padded to
+    pad_to candidates of score 0.0; G = groups.  MAP = (sum_r hist[r] / (r + 1)) / G.  Grouping is ops.unique's inverse index; no
+    host synchronisation."""
+    f32 = (torch.float32,)
+    if not isinstance(topk, int) or not 1 <= topk <= 64:
+        raise ValueError(f"group_rank_hist: topk must be an int in 1..64, got {topk!r}")
+    if not isinstance(pad_to, int) or not 0 <= pad_to < 1 << 31:
+        raise ValueError(f"group_rank_hist: pad_to must be an int >= 0, got {pad_to!r}")
+    n = _metric_rows("group_rank_hist", pred=(pred, f32), label=(label, f32), group=(group, (torch.int32, torch.int64)))
+    if n >= 1 << 30:
+        raise ValueError(f"group_rank_hist: {n} rows, at most 2^30 - 1")
+    d = unique(group)
+    out = torch.empty(topk + 1, dtype=torch.int64, device=pred.device)
+    ws = workspace("group_rank", _lib.query_bytes("mrec_group_rank_ws_bytes", n), pred.device)
+    _lib.call("mrec_group_rank_hist", _ptr(pred), _ptr(label), _ptr(d.inv), _ptr(d.n_uniq_dev), n, topk, pad_to, _ptr(out), _ptr(ws),
+              ws.numel(), _stream())
+    return out
