@@ -725,7 +725,8 @@ int mrec_tail_fwd_bwd(int32_t f16, const uint16_t* x, int64_t ldx, const uint16_
  * widened by the caller); MindRec reserves -1 and -2 (embedding.py:55-56) and so do we not: no
  * key value is reserved here.  Rows are handed out in order 0,1,2,... of first insertion
  * (deterministic: misses are numbered in the order they appear in `keys`); erased rows go to a
- * free list and are reused in erase order once fresh rows run out. */
+ * free list in erase order and are reused once fresh rows run out, the row erased last first (a stack).
+ * With neither a fresh nor a free row left a new key is dropped: row -1 at every position, counted once. */
 typedef struct mrec_map mrec_map_t;
 int mrec_map_bytes(int64_t capacity_rows, size_t* out);
 int mrec_map_create(mrec_map_t** out, void* mem, size_t mem_bytes, int64_t capacity_rows, void* stream);
@@ -795,7 +796,9 @@ int mrec_map_lookup(mrec_map_t* h, const void* keys, int32_t key_bytes, int64_t 
  * the key's first occurrence (`out_table`: which of `tables` is the one being read; out rows 16-byte aligned, ldo % 4 == 0).
  * rows_gather[i] = the row a gather behind this call reads for position i, -1 where `out` holds the row already -- follow with
  * mrec_gather_rows_f32_skip_i32(table, V, ld, D, rows_gather, n, out, stream).  A lookup of all-new keys moves the new rows
- * once (generator -> table and output) instead of three times (generator -> table -> gather -> output). */
+ * once (generator -> table and output) instead of three times (generator -> table -> gather -> output).  A key DROPPED because
+ * the table is full reads its default row too, at every position (rows_out = rows_gather = -1 there, out written here): like an
+ * un-admitted key it is read but not stored. */
 int mrec_map_lookup_out(mrec_map_t* h, const void* keys, int32_t key_bytes, int64_t n, const int64_t* n_dev, uint32_t flags,
                         int64_t step, int32_t permit, const mrec_map_table_t* tables, int32_t n_tables, int32_t* rows_out,
                         int32_t* rows_admitted_out, float* out, int64_t ldo, int32_t out_table, int32_t* rows_gather, void* ws,

@@ -246,7 +246,8 @@ __global__ __launch_bounds__(HB) void k_map_export(MapDev m, const int* __restri
 //           the next row -- fresh rows in order, then the free list -- and enters the index.  Row numbers therefore
 //           follow the order of first appearance in `keys`, as a sequential insert loop would hand them out.
 //   finish: default values for the new rows of every table (values + optimizer slots), row numbers for the later
-//           positions of new keys, the admission mask.
+//           positions of new keys, the admission mask.  With an output (mrec_map_lookup_out) every position of a key that was
+//           DROPPED because the table is full reads the key's default row, as an un-admitted key does: no table row is written.
 constexpr int kEmptyPos = 0x7f7f7f7f;
 constexpr unsigned kMFlagA = 1u << 30, kMFlagP = 2u << 30, kMFlagMask = 3u << 30;
 constexpr uint32_t F_INSERT = 1u, F_UNIQUE = 2u, F_TRAIN = 4u, F_PRIMED = 8u, F_SKIP_PAD = 16u;
@@ -455,8 +456,8 @@ __global__ __launch_bounds__(HB) void k_map_place(MapDev m, const K* __restrict_
 }
 
 template <class K>
-__global__ __launch_bounds__(HB) void k_map_finish(MapDev m, MapTabs tabs, int64_t n_max, const int64_t* __restrict__ n_dev,
-                                                   uint32_t flags, int permit, int* __restrict__ rows_out,
+__global__ __launch_bounds__(HB) void k_map_finish(MapDev m, MapTabs tabs, const K* __restrict__ keys, int64_t n_max,
+                                                   const int64_t* __restrict__ n_dev, uint32_t flags, int permit, int* __restrict__ rows_out,
                                                    int* __restrict__ rows_adm, LookupWs w, int ntiles) {
     const int64_t tid = (int64_t)blockIdx.x * HB + threadIdx.x, nthreads = (int64_t)gridDim.x * HB;
     const bool inserting = (flags & F_INSERT) != 0;
@@ -479,10 +480,10 @@ __global__ __launch_bounds__(HB) void k_map_finish(MapDev m, MapTabs tabs, int64
                 const int64_t r = r0 + rin;
                 if (rin >= rpw || r >= n_new) continue;
                 const int row = w.newrow[r];
-                if (row < 0) continue;
-                const int64_t key = w.newkey[r];
-                float* dst = tb.rows + (int64_t)row * tb.ld;
                 float* dst2 = (w.out && t == w.out_tab) ? w.out + (int64_t)w.newpos[r] * w.ldo : nullptr;       // the lookup's output row of the key's first position
+                if (row < 0 && !dst2) continue;          // (a dropped key owns no table row; its output row reads the default all the same)
+                const int64_t key = w.newkey[r];
+                float* dst = row >= 0 ? tb.rows + (int64_t)row * tb.ld : nullptr;
                 if (vec) {
                     for (int c = sub * 4; c < tb.D; c += lpr * 4) {
                         float4 v;
@@ -493,13 +494,13 @@ __global__ __launch_bounds__(HB) void k_map_finish(MapDev m, MapTabs tabs, int64
                         } else {
                             v = make_float4(tb.fill, tb.fill, tb.fill, tb.fill);
                         }
-                        *(float4*)(dst + c) = v;
+                        if (dst) *(float4*)(dst + c) = v;
                         if (dst2) *(float4*)(dst2 + c) = v;
                     }
                 } else {
                     for (int c = 0; c < tb.D; ++c) {
                         const float x = tb.sigma >= 0.0f ? tb.sigma * mrec_det_normal(tb.seed, key, c) : tb.fill;
-                        dst[c] = x;
+                        if (dst) dst[c] = x;
                         if (dst2) dst2[c] = x;
                     }
                 }
@@ -515,6 +516,19 @@ __global__ __launch_bounds__(HB) void k_map_finish(MapDev m, MapTabs tabs, int64
             row = w.srank[w.sidx[i]];
             rows_out[i] = row;
             if (w.rows_gather) w.rows_gather[i] = row;      // a LATER position of a new key: the gather behind this call reads the new row
+            if (row < 0 && w.out) {
+                // a position of a DROPPED key (the table is full -- never the steady state): its default row, which no table
+                // row holds, so the gather behind this call leaves it alone (the first position is rewritten with the same bits)
+                const MapTab tb = tabs.t[w.out_tab];
+                const int64_t key = (int64_t)keys[i];
+                float* dst = w.out + i * w.ldo;
+                for (int c = 0; c < tb.D; c += 2) {
+                    float z0, z1;
+                    mrec_map_default2(tb.seed, tb.sigma, tb.fill, key, c >> 1, z0, z1);
+                    dst[c] = z0;
+                    if (c + 1 < tb.D) dst[c + 1] = z1;
+                }
+            }
         }
         if (rows_adm) rows_adm[i] = (row >= 0 && m.hits[row] >= permit) ? row : -1;
     }
@@ -895,7 +909,7 @@ static int map_lookup_impl(mrec_map* h, const K* keys, int64_t n, const int64_t*
     if (inserting) k_map_place<K><<<ntiles, HB, 0, st>>>(h->d, keys, n, n_dev, flags, (int)step, rows_out, w, ntiles);
     if (inserting || rows_adm) {
         const unsigned gf = g < 2048 ? g : 2048;
-        k_map_finish<K><<<gf, HB, 0, st>>>(h->d, tabs, n, n_dev, flags, permit, rows_out, rows_adm, w, ntiles);
+        k_map_finish<K><<<gf, HB, 0, st>>>(h->d, tabs, keys, n, n_dev, flags, permit, rows_out, rows_adm, w, ntiles);
     }
     MREC_LAUNCH_CHECK();
     return MREC_OK;

@@ -137,12 +137,14 @@ class MapParameter:
 
     # ---- MapTensorGet / Put / Erase -----------------------------------------------------------
     def get(self, key_tensor, insert_default_value=True):
-        """MapTensorGet: 4 launches (the lookup chain + the row gather), 3 without insertion (probe, gather, defaults)."""
+        """MapTensorGet: 4 launches (the lookup chain + the row gather), 3 without insertion (probe, gather, defaults).  A key
+        that is not in the table afterwards -- not inserted, or dropped because the table is full -- reads its default row."""
         keys = self._keys(key_tensor)
         D = self.value_shape[0]
         if insert_default_value and D % 4 == 0 and D <= 256:
             # one pass over the rows of NEW keys less: the kernel that generates their default rows writes them to the table AND to
-            # the output; the gather behind it moves the rows of the keys that were there (and of later positions of new keys)
+            # the output; the gather behind it moves the rows of the keys that were there (and of later positions of new keys).
+            # The same kernel writes the default rows of keys it had to DROP (table full), which the gather leaves alone.
             out = torch.empty((keys.numel(), D), dtype=torch.float32, device=self.device)
             train = self._track
             if train:
@@ -153,9 +155,9 @@ class MapParameter:
             return out
         _, _, rows_pos = self.lookup_rows(keys, insert=insert_default_value)
         out = ops.gather_rows(self.values, rows_pos)
-        if not insert_default_value:
-            # missing keys read as their default row, without being inserted (no host round trip: a kernel overlays them)
-            self.index.fill_missing(keys, rows_pos, out, self._sigma, self._fill, self.seed)
+        # keys without a row -- not inserted, or dropped by a full table -- read as their default row (no host round trip: a
+        # kernel overlays them; it only reads the row numbers where every key is resident)
+        self.index.fill_missing(keys, rows_pos, out, self._sigma, self._fill, self.seed)
         return out
 
     def put(self, key_tensor, value_tensor):

@@ -887,6 +887,21 @@ class KeyIndex:
         """int64 [C] view: the key each row holds (valid for live rows)."""
         return self._view(_lib.lib().mrec_map_row_keys_dev(self._h), 8 * self.capacity, torch.int64)
 
+    @property
+    def n_slots(self):
+        """S: slots of the open-addressing array, max(1024, the power of two >= 2 * capacity)."""
+        S = 1024
+        while S < 2 * self.capacity:
+            S <<= 1
+        return S
+
+    def slots(self):
+        """Read-only look at the slot array (tests): (key int64 [S], row int32 [S]) views of the index's own buffer, whose
+        first S * 16 bytes are the slots (int64 key, int32 row, int32 pad); row -1 = empty, -2 = tombstone."""
+        off = self._base - self._mem.data_ptr()
+        raw = self._mem[off: off + 16 * self.n_slots]
+        return raw.view(torch.int64)[0::2], raw.view(torch.int32)[2::4]
+
     def _ws(self, n):
         nb = _lib.query_bytes("mrec_map_workspace_bytes", max(n, 1))
         return workspace("map", nb, self.device)
