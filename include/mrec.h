@@ -156,7 +156,7 @@ int mrec_gather_rows_wide_ex(const float* table, int64_t V, int64_t ld, int32_t 
  * as an fp32 row, becomes x * (c / n) where n = sqrt(sum of x_d^2) > c and stays x exactly otherwise -- a tie is not clipped, nor
  * is a zero row (ids outside [0, V)) -- and is then multiplied by row_scale, rounded and dropped out as without the clip.  The
  * sum of squares is added in an order that depends on the column index only (the same order the sparse apply's Jacobian uses,
- * so the lookup and the apply of one step take one clip decision per row; mrec_sparse_apply_next_max_norm below).  out: float*
+ * so the lookup and the apply of one step take one clip decision per row; mrec_apply_opts_t.max_norm below).  out: float*
  * for the f32 entries, uint16_t* for bf16 / f16.  max_norm not finite or <= 0: MREC_EINVAL; D % 4 != 0, D > 256 (the wide form:
  * D > 252), or rows that are not 16-byte aligned: MREC_EUNSUPPORTED -- all before any launch.  The wide word is not clipped. */
 int mrec_gather_rows_clip_f32_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, int64_t n,
@@ -231,7 +231,7 @@ int mrec_gather_pool_fields_keyed(const float* table, int64_t V, int64_t ld, int
  * products, slot-order adds, the one division and the one rounding are those of the entries above.  Dense form: an id outside [0, V)
  * is a zero row and is never clipped.  Keyed form: a slot whose row is outside [0, V) contributes its key's DEFAULT row, and that row
  * is clipped like any other (MapTensorGet returns the default value and ClipByNorm follows it).  The backward side is
- * mrec_sparse_apply_next_pool_fields_clip below.  Float4 rows in one column block only: D % 4 != 0, D > 256, ld or ldo not a multiple
+ * mrec_apply_opts_t's fields form with max_norm, below.  Float4 rows in one column block only: D % 4 != 0, D > 256, ld or ldo not a multiple
  * of 4, a table that is not 16-byte aligned or an output that is not (8-byte for 16-bit outputs): MREC_EUNSUPPORTED; max_norm not finite
  * or <= 0: MREC_EINVAL; the other argument errors and limits as above -- all before any launch.  One launch each
  * (k_gather_pool_fields_clip, a kernel of its own: the kernels of the entries above are not touched), no allocation, no synchronisation:
@@ -265,15 +265,71 @@ int mrec_sparse_apply_workspace_bytes(int64_t n, int32_t D, size_t* out);
  * reference order); longer runs are a fixed tree of window partials. */
 int mrec_sparse_apply_window(int32_t D, int aligned16);
 
+/* Options of ONE sparse apply, passed to the call they modify (`opts`, the argument before `stream` of the twelve entries below:
+ * mrec_segment_sum_f32 / _g16, mrec_sparse_lazy_adam_{f32,bf16g,f16g}_{i32,i64}, mrec_sparse_ftrl_f32_{i32,i64},
+ * mrec_sparse_lazy_adam_wide(_defer)).  NULL is the plain apply.  The record and its two host arrays are read during the call only; the
+ * library keeps no state between calls, so one call's options never reach another.
+ *   struct_bytes  sizeof(mrec_apply_opts_t); anything else: MREC_EINVAL.
+ *   max_norm      0: none.  c > 0, finite: the backward side of the lookups' max_norm.  The clip y = x * (c / n) (n = |x| > c) has the
+ *                 Jacobian J(x) = (c / n)(I - x x^T / n^2), and J is linear, so the sum of a row's gradients over the step goes through
+ *                 it once: each touched row's completed gradient sum G becomes J(x) G where the row x the update loads -- the row the
+ *                 step's lookup read -- has n > c, and stays G otherwise (n^2 in the lookup's order of additions: the forward and the
+ *                 backward take one decision per row).  Window partial sums stay unclipped; the wide record's FTRL is not touched; no
+ *                 hot columns under it.  LazyAdam entries only; D % 4 == 0, D <= 256 (252 with the wide record), 16-byte aligned rows.
+ *   pool          1: none.  L > 1: the pooled form, the bprop of mrec_gather_pool (wide_and_deep_multitable/src/wide_and_deep.py:
+ *                 301-346,377-418): position i = b * L + l reads its gradient row from g[i / L]; g is then [ceil(n / L), D], ldg its row
+ *                 stride, and contribution i stays (g[i / L] * row_scale[i]) * grad_scale with row_scale by POSITION (the mask; 1 / L
+ *                 folded in by the caller or into grad_scale).  Any L, n need not be a multiple of L.  The one-field case of the fields
+ *                 form (F = 1, field_len = {L}, the field's scale = the call's own grad_scale) without that form's limits.
+ *   n_fields, field_len, field_scale
+ *                 all 0 / NULL: none.  The FIELDS form, the bprop of mrec_gather_pool_fields (pool must then be 1): the plan's n
+ *                 positions are samples of Ls = sum L_f ids, F = n_fields bags back to back; g is the [B, F * D] gradient of the lookup's
+ *                 result viewed as [B * F, D] (n a multiple of Ls: ceil(n / Ls) * F rows are addressed).  Position i, with b = i / Ls,
+ *                 s = i - b * Ls and f the field whose slots hold s, contributes
+ *                     x_i = fp32( fp32( g[b * F + f] * row_scale[i] ) * field_scale[f] )
+ *                 field_len: HOST int32[F]; field_scale: HOST float[F], in place of the call's scalar grad_scale -- grad_scale / L_f for
+ *                 the mean (ReduceMean's bprop divides by the FIELD's length), grad_scale for the sum -- and the call's own grad_scale
+ *                 must be 1.0f: there is one scale per contribution, and it is the field's.  Ids shared by several fields are summed
+ *                 over all of them and updated ONCE.  With max_norm: the bprop of mrec_gather_pool_fields_clip / _keyed_clip, the
+ *                 completed sums clipped as above (plain LazyAdam entries only).
+ *   const_state, const_ids, const_id_bytes, const_B
+ *                 all 0 / NULL: none.  The hot columns of mrec_const_cols_detect (below) for the folded wide entries; any other entry
+ *                 runs as if they were not given.
+ * Either pooled form keeps the windows, the tree of partial sums and so the order of additions of the plain apply on the expanded
+ * gradient, which is never materialised; it launches k_apply_main_fields (then k_apply_long) where the plain apply launches k_apply_main.
+ * Refusals, all before any launch, in this order:
+ *   1. the record itself -- MREC_EINVAL: struct_bytes; max_norm not 0 and not a finite number > 0; pool < 1; pool > 1 with the fields
+ *      form; n_fields < 1 with either array given; a null array; an L_f < 1; a field_scale that is not finite; one of const_state /
+ *      const_ids without the other, const_B outside [0, 2^30], const_id_bytes not 4 / 8.  MREC_EUNSUPPORTED: n_fields >
+ *      MREC_POOL_MAX_FIELDS; Ls > MREC_POOL_MAX_BAG.
+ *   2. combinations -- MREC_EUNSUPPORTED: a pooled form on the folded wide entries or with constant columns; max_norm with pool > 1;
+ *      max_norm on anything but a LazyAdam entry, and with the fields form on anything but mrec_sparse_lazy_adam_{f32,bf16g,f16g}_*.
+ *      Then MREC_EINVAL: the fields form with grad_scale != 1.  Then MREC_EUNSUPPORTED: max_norm at D % 4 != 0 or D > 256 (252).
+ *   3. the entry's own checks, among them MREC_EUNSUPPORTED for a pooled form over n * Ls >= 2^32 positions (i / Ls is a 32-bit
+ *      multiply-high).  (The folded wide entries look at uniq_bytes, g_kind, gw_stride -- and _defer at finish_out and D -- before 1.) */
+typedef struct mrec_apply_opts {
+    uint32_t struct_bytes;
+    float max_norm;
+    int32_t pool;
+    int32_t n_fields;
+    const int32_t* field_len;
+    const float* field_scale;
+    const void* const_state;
+    const void* const_ids;
+    int64_t const_B;
+    int32_t const_id_bytes;
+    int32_t reserved;          /* ignored */
+} mrec_apply_opts_t;
+
 /* ops.UnsortedSegmentSum (bprop of Gather; models/wide_deep/op_precision.ini:2-3):
  * out[u, :] = sum of contributions of group u, u < U; out is [>=U, D] contiguous. */
 int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets,
                          int64_t n, const float* g, int64_t ldg, const float* row_scale, float grad_scale,
-                         int32_t D, float* out, void* ws, size_t ws_bytes, void* stream);
+                         int32_t D, float* out, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 /* The same over 16-bit row gradients (g_kind 1: bf16, 2: IEEE half; ldg in 16-bit elements), widened exactly, summed in fp32. */
 int mrec_segment_sum_g16(const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets,
                          int64_t n, const void* g, int32_t g_kind, int64_t ldg, const float* row_scale, float grad_scale,
-                         int32_t D, float* out, void* ws, size_t ws_bytes, void* stream);
+                         int32_t D, float* out, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 
 /* nn.LazyAdam on a RowTensor gradient (wide_and_deep.py:420-422).  b1_pow/b2_pow are
  * beta^t AFTER this step's multiply.  Rows outside [0,V) are skipped. */
@@ -282,13 +338,13 @@ int mrec_sparse_lazy_adam_f32_i32(float* p, float* m, float* v, int64_t V, int64
                                   const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                   const float* row_scale, float lr, float b1, float b2, float eps,
                                   float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                  size_t ws_bytes, void* stream);
+                                  size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 int mrec_sparse_lazy_adam_f32_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
                                   const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                   const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                   const float* row_scale, float lr, float b1, float b2, float eps,
                                   float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                  size_t ws_bytes, void* stream);
+                                  size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 
 /* LazyAdam with bf16 row gradients g[n, D] (what the mixed-precision MLP's backward hands back;
  * the Cast bprop would widen them to fp32 first -- the kernel widens on load, bit-identically). */
@@ -297,13 +353,13 @@ int mrec_sparse_lazy_adam_bf16g_i32(float* p, float* m, float* v, int64_t V, int
                                     const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                     const float* row_scale, float lr, float b1, float b2, float eps,
                                     float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                    size_t ws_bytes, void* stream);
+                                    size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 int mrec_sparse_lazy_adam_bf16g_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
                                     const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                     const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                     const float* row_scale, float lr, float b1, float b2, float eps,
                                     float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                    size_t ws_bytes, void* stream);
+                                    size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 
 /* LazyAdam with IEEE half row gradients (widened exactly on load). */
 int mrec_sparse_lazy_adam_f16g_i32(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
@@ -311,13 +367,13 @@ int mrec_sparse_lazy_adam_f16g_i32(float* p, float* m, float* v, int64_t V, int6
                                    const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                    const float* row_scale, float lr, float b1, float b2, float eps,
                                    float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                   size_t ws_bytes, void* stream);
+                                   size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 int mrec_sparse_lazy_adam_f16g_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
                                    const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                    const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                    const float* row_scale, float lr, float b1, float b2, float eps,
                                    float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                   size_t ws_bytes, void* stream);
+                                   size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 
 /* LazyAdam on the deep columns AND FTRL on the wide record of the same fused rows, one pass: the wide table's
  * Unique + UnsortedSegmentSum + FusedSparseFtrl (wide_and_deep.py:423-430) ride the deep table's row visit.  Row layout:
@@ -340,7 +396,7 @@ int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V, int64_t 
                                const float* row_scale, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,
                                float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F, int32_t wide_col, float ftrl_lr,
                                float l1, float l2, float lr_power, void* ws, size_t ws_bytes, void* step_state,
-                               const int64_t* n_valid_dev, void* stream);
+                               const int64_t* n_valid_dev, const mrec_apply_opts_t* opts, void* stream);
 
 /* ---- step scalars in device memory ------------------------------------------------------------------------------
  * nn.Adam / nn.LazyAdam keep beta1_power and beta2_power as Parameters that the optimizer's own graph multiplies by
@@ -376,12 +432,12 @@ int mrec_sparse_ftrl_f32_i32(float* var, float* accum, float* linear, int64_t V,
                              const int32_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                              const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                              const float* row_scale, float lr, float l1, float l2, float lr_power,
-                             float grad_scale, void* ws, size_t ws_bytes, void* stream);
+                             float grad_scale, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 int mrec_sparse_ftrl_f32_i64(float* var, float* accum, float* linear, int64_t V, int64_t ld, int32_t D,
                              const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                              const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                              const float* row_scale, float lr, float l1, float l2, float lr_power,
-                             float grad_scale, void* ws, size_t ws_bytes, void* stream);
+                             float grad_scale, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream);
 
 /* ---- dense optimizers (whole tensor) ------------------------------------------------------
  * nn.Adam / nn.FTRL on dense gradients (wide_and_deep.py:435-445; deep_and_cross.py:342-344). */
@@ -453,7 +509,8 @@ int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int64_t V, in
                                      const float* row_scale, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,
                                      float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F, int32_t wide_col,
                                      float ftrl_lr, float l1, float l2, float lr_power, void* ws, size_t ws_bytes, void* step_state,
-                                     const int64_t* n_valid_dev, mrec_apply_finish_t* finish_out, void* stream);
+                                     const int64_t* n_valid_dev, mrec_apply_finish_t* finish_out, const mrec_apply_opts_t* opts,
+                                     void* stream);
 /* Hot columns.  The reference's Criteo pipeline gives each of the 13 dense features ONE id (datasets/criteo_1tb/process_data.py:138-147:
  * the feature's value travels as the weight), so a 39-field batch holds 13 fields whose id is the same in every sample: a third of the
  * positions, in 13 runs of B entries of the inverted index.  mrec_const_cols_detect finds the fields of ids[B, F] (F <= 64) in which ONE
@@ -461,79 +518,16 @@ int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int64_t V, in
  * lies in [0, V) and occurs in no other field (min_count = B: constant columns; smaller: also a field's dominant id), and leaves them
  * as a bit mask and their ids in `state`: MREC_CONST_COLS_STATE_BYTES of device memory, ZEROED ONCE by the caller and owned by these
  * calls from then on (counters, a word of failed candidates and a ticket that the launch's last workgroup clears again: one launch, no
- * memset; a batch without a candidate costs 16 F loads per workgroup).  mrec_sparse_apply_next_const_cols arms the NEXT
- * mrec_sparse_lazy_adam_wide(_defer) call of this host thread (ids: the same [B, F] batch the plan was built from, 32-bit, B <= 65536;
- * otherwise the call runs as if not armed): it launches the HOT variant of the apply kernel, whose windows skip the entries that hold a
+ * memset; a batch without a candidate costs 16 F loads per workgroup).  A mrec_sparse_lazy_adam_wide(_defer) call whose options record
+ * names that state (mrec_apply_opts_t: const_state, const_ids -- the same [B, F] batch the plan was built from, 32-bit, B <= 65536;
+ * otherwise the call runs as if it named none) launches the HOT variant of the apply kernel, whose windows skip the entries that hold a
  * field's hot id, whose first workgroups add those entries' gradient rows up sample by sample (no index: a field sits at a fixed offset
  * of every gradient row, neighbouring hot fields adjacent), and whose finishing pass (own launch, or the workgroups handed back in
  * mrec_apply_finish_t) updates the hot rows: same products, a fixed order of additions (another one than the windows': the sums agree to
- * rounding).  Not armed, the call launches the plain kernel: not an instruction of this path.  (nullptr, nullptr, 0, 0) disarms.
+ * rounding).  Without them the call launches the plain kernel: not an instruction of this path.
  * Replaces the optimizer-side Unique + UnsortedSegmentSum + LazyAdam / FTRL of those rows (wide_and_deep.py:420-430, 490-492). */
 #define MREC_CONST_COLS_STATE_BYTES 2592
 int mrec_const_cols_detect(const void* ids, int32_t id_bytes, int64_t B, int32_t F, int64_t V, int64_t min_count, void* state, void* stream);
-int mrec_sparse_apply_next_const_cols(const void* state, const void* ids, int32_t id_bytes, int64_t B);
-/* max_norm on the backward side.  The lookup's clip y = x * (c / n) (n = |x| > c) has the Jacobian J(x) = (c / n)(I - x x^T / n^2),
- * and J is linear, so the sum of a row's gradients over the step goes through it once: mrec_sparse_apply_next_max_norm(c) ARMS the
- * NEXT LazyAdam apply of this host thread (mrec_sparse_lazy_adam_{f32,bf16g,f16g}_{i32,i64}, mrec_sparse_lazy_adam_wide(_defer);
- * the "arm the next call" precedent of mrec_sparse_apply_next_const_cols, so that no existing entry changes), which replaces each
- * touched row's completed gradient sum G by J(x) G where the row x it loads -- the row the step's lookup read -- has n > c, and
- * leaves G alone otherwise (n from the lookup's order of additions: the same decision).  Window partial sums stay unclipped; the
- * wide record's FTRL is not touched; the call runs the plain windows (no hot columns).  The armed call returns MREC_EUNSUPPORTED
- * for D % 4 != 0, D > 256, D > 252 with the wide record, or rows that are not 16-byte aligned, before any launch; it disarms
- * either way.  max_norm not finite or <= 0: MREC_EINVAL (nothing is armed). */
-int mrec_sparse_apply_next_max_norm(float max_norm);
-/* The pooled form of the sparse apply: the bprop of the multi-hot pattern above (wide_and_deep_multitable/src/wide_and_deep.py:
- * 301-346,377-418) gives position i = b * L + l the gradient row dy[b, :] * mask[b, l] (times 1 / L for the mean), so
- * mrec_sparse_apply_next_pool(L) ARMS the NEXT apply of this host thread (mrec_segment_sum_f32 / _g16,
- * mrec_sparse_lazy_adam_{f32,bf16g,f16g}_{i32,i64}, mrec_sparse_ftrl_f32_{i32,i64}; the precedent of
- * mrec_sparse_apply_next_max_norm) to read position i's gradient row from g[i / L]: g is then [ceil(n / L), D], ldg its row
- * stride; contribution i stays (g[i / L] * row_scale[i]) * grad_scale with row_scale by POSITION (the mask, 1 / L folded in by the
- * caller or into grad_scale), and the windows, the tree of partials and so the order of additions are those of the plain apply
- * on the L-fold expanded gradient -- which is never materialised.  Armed for one call, disarmed by that call whether it runs or
- * refuses; L == 1 is the plain apply (and disarms).  This is the one-field case of mrec_sparse_apply_next_pool_fields below (F = 1,
- * field_len = {L}, the field's scale = the armed call's own grad_scale) without that entry's limits: any L >= 1, n need not be a
- * multiple of L.  The armed call launches that form's windows, k_apply_main_fields, a kernel of its own, then k_apply_long; not
- * armed, or at L == 1, a call launches k_apply_main + k_apply_long, what it launched before this existed.  MREC_EUNSUPPORTED before
- * any launch, and disarmed, for the folded wide forms (mrec_sparse_lazy_adam_wide(_defer)), with constant columns armed (they are
- * disarmed too), with mrec_sparse_apply_next_max_norm armed on top of it (max_norm over bags has an arm of its own,
- * mrec_sparse_apply_next_pool_fields_clip below), and for n * L >= 2^32 (i / L is a 32-bit multiply-high).  L < 1: MREC_EINVAL,
- * nothing is armed. */
-int mrec_sparse_apply_next_pool(int32_t L);
-/* The FIELDS form of the pooled apply: the bprop of mrec_gather_pool_fields.  The plan's n positions are samples of Ls = sum L_f ids,
- * F bags back to back; g is the [B, F * D] gradient of the lookup's result viewed as [B * F, D] (ldg its row stride, n a multiple
- * of Ls: ceil(n / Ls) * F rows are addressed).  mrec_sparse_apply_next_pool_fields(F, field_len, field_scale) ARMS the NEXT apply of
- * this host thread -- the entries mrec_sparse_apply_next_pool arms -- so that position i, with b = i / Ls, s = i - b * Ls and f the
- * field whose slots hold s, contributes
- *     x_i = fp32( fp32( g[b * F + f] * row_scale[i] ) * field_scale[f] )
- * field_scale[f] (HOST float[F], like field_len read during the arming call only) takes the place of the call's scalar grad_scale in
- * the product: grad_scale / L_f for the mean (ReduceMean's bprop divides by the FIELD's length), grad_scale for the sum.  The armed
- * call's own grad_scale must be 1.0f: anything else returns MREC_EINVAL (and disarms) -- there is one scale per contribution, and
- * it is the field's.  Windows, the tree of partial sums and the order of additions are the plain apply's; ids shared by several
- * fields are summed over all of them and updated ONCE, as the reference's optimizer does with the summed gradient.  The
- * slot-to-field map is a linear search over the F prefix offsets, held with the scales in the kernel's arguments: no device
- * table, no allocation, no synchronisation.  i / Ls is a 32-bit multiply-high: n * Ls >= 2^32 is MREC_EUNSUPPORTED.  Armed for one
- * call, disarmed by that call whether it runs or refuses; arming replaces an armed mrec_sparse_apply_next_pool and vice versa.
- * The armed call launches the pooled windows, k_apply_main_fields (the kernel a call armed with _next_pool launches too), then
- * k_apply_long; a call that is not armed launches k_apply_main + k_apply_long, what it launched before this existed.
- * MREC_EUNSUPPORTED before any launch, and disarmed, for the folded wide forms, with constant
- * columns armed (disarmed too) and with mrec_sparse_apply_next_max_norm armed on top of it (the clip over bags travels with the
- * pooled arm: mrec_sparse_apply_next_pool_fields_clip below).  Arming errors leave nothing armed: F < 1, a null array, an L_f < 1 or a
- * field_scale that is not finite: MREC_EINVAL; F > MREC_POOL_MAX_FIELDS or Ls > MREC_POOL_MAX_BAG: MREC_EUNSUPPORTED. */
-int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_len, const float* field_scale);
-/* max_norm over the pooled apply: the bprop of mrec_gather_pool_fields_clip / _keyed_clip.  mrec_sparse_apply_next_pool_fields with the
- * clip in the SAME arm: position i contributes x_i as above, the windows' partial sums stay unclipped, and -- J(x) G being linear in
- * G -- each touched row's COMPLETED gradient sum G becomes J(x) G = (c / n)(G - (x.G / n^2) x) where the row x the update loads has
- * n = |x| > c, once, at the update sites of mrec_sparse_apply_next_max_norm's apply (n^2 in the lookup's order of additions: the
- * forward and the backward take one decision per row).  Same rules as _next_pool_fields: armed for ONE call of this host thread,
- * disarmed by that call whether it runs or refuses, the armed call's grad_scale must be 1.0f (else MREC_EINVAL); arming replaces any
- * other pooled arm, and either of the two arms above replaces this one.  F = 1 with field_scale = {grad_scale} is the equal-length
- * case (mrec_sparse_apply_next_pool): there is no second entry.  The armed call launches k_apply_main_fields<.., UpdAdamClip, ..>,
- * then the clip's finishing pass, k_apply_long<4, K, UpdAdamClip>.  max_norm not finite or <= 0: MREC_EINVAL, and the arming errors of
- * _next_pool_fields, all with nothing left armed.  The armed call returns MREC_EUNSUPPORTED before any launch, and disarms, when it
- * is not a LazyAdam apply (mrec_sparse_lazy_adam_{f32,bf16g,f16g}_{i32,i64}) -- FTRL, the segment sums -- or a folded wide form, for
- * D % 4 != 0, D > 256 or rows that are not 16-byte aligned, with constant columns armed and with mrec_sparse_apply_next_max_norm armed
- * on top of it. */
-int mrec_sparse_apply_next_pool_fields_clip(int32_t F, const int32_t* field_len, const float* field_scale, float max_norm);
 int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, const float* g, void* shadow16, int shadow_kind, int64_t n,
                                      int32_t nseg, const float* const* slabs, const int64_t* starts, const int64_t* lens,
                                      const int32_t* splits, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,

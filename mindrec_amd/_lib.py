@@ -52,7 +52,7 @@ _SIGS = {
     "mrec_gather_rows_f16_i64": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
     "mrec_gather_rows_wide": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _i32, _vp],
     "mrec_sparse_lazy_adam_wide": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp,
-                                   _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _sz, _vp, _vp, _vp],
+                                   _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _sz, _vp, _vp, _vp, _vp],
     "mrec_gather_rows_wide_ex": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _i32,
                                  C.c_uint32, _vp, _vp],
     "mrec_shard_route_slots_workspace_bytes": [_i64, _i32, _szp],
@@ -71,18 +71,13 @@ _SIGS = {
     "mrec_wide_sum_f32_i64": [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "mrec_sparse_apply_workspace_bytes": [_i64, _i32, _szp],
     "mrec_const_cols_detect": [_vp, _i32, _i64, _i32, _i64, _i64, _vp, _vp],
-    "mrec_sparse_apply_next_const_cols": [_vp, _vp, _i32, _i64],
-    "mrec_sparse_apply_next_max_norm": [_f32],
-    "mrec_sparse_apply_next_pool": [_i32],
     "mrec_gather_pool": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _i64, _vp],
-    "mrec_sparse_apply_next_pool_fields": [_i32, _vp, _vp],
     "mrec_gather_pool_fields": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _i64, _vp],
     "mrec_gather_pool_fields_keyed": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _u64, _f32, _f32, _vp, _i32, _i64,
                                       _vp],
     "mrec_gather_pool_fields_clip": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _i64, _f32, _vp],
     "mrec_gather_pool_fields_keyed_clip": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _u64, _f32, _f32, _vp, _i32,
                                            _i64, _f32, _vp],
-    "mrec_sparse_apply_next_pool_fields_clip": [_i32, _vp, _vp, _f32],
     "mrec_gather_rows_clip_f32_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
     "mrec_gather_rows_clip_f32_i64": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
     "mrec_gather_rows_clip_bf16_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
@@ -92,29 +87,29 @@ _SIGS = {
     "mrec_gather_rows_wide_clip": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _i32,
                                    C.c_uint32, _vp, _f32, _vp],
     "mrec_sparse_apply_window": [_i32, _int],
-    "mrec_segment_sum_f32": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _i32, _vp, _vp, _sz, _vp],
-    "mrec_segment_sum_g16": [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _f32, _i32, _vp, _vp, _sz, _vp],
+    "mrec_segment_sum_f32": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _f32, _i32, _vp, _vp, _sz, _vp, _vp],
+    "mrec_segment_sum_g16": [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _f32, _i32, _vp, _vp, _sz, _vp, _vp],
     "mrec_sparse_lazy_adam_f32_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                      _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp],
+                                      _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp, _vp],
     "mrec_sparse_lazy_adam_f32_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                      _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp],
+                                      _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp, _vp],
     "mrec_sparse_lazy_adam_bf16g_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                        _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp],
+                                        _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp, _vp],
     "mrec_sparse_lazy_adam_bf16g_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                        _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp],
+                                        _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp, _vp],
     "mrec_sparse_lazy_adam_f16g_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                       _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp],
+                                       _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp, _vp],
     "mrec_sparse_lazy_adam_f16g_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                       _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp],
+                                       _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _sz, _vp, _vp],
     "mrec_sparse_ftrl_f32_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                 _f32, _f32, _f32, _f32, _f32, _vp, _sz, _vp],
+                                 _f32, _f32, _f32, _f32, _f32, _vp, _sz, _vp, _vp],
     "mrec_sparse_ftrl_f32_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                 _f32, _f32, _f32, _f32, _f32, _vp, _sz, _vp],
+                                 _f32, _f32, _f32, _f32, _f32, _vp, _sz, _vp, _vp],
     "mrec_dense_adam_f32": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp],
     "mrec_dense_adam_ex_f32": [_vp, _vp, _vp, _vp, _int, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp],
     "mrec_sparse_lazy_adam_wide_defer": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp,
                                          _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _sz,
-                                         _vp, _vp, _vp, _vp],
+                                         _vp, _vp, _vp, _vp, _vp],
     "mrec_dense_adam_slabs_finish_f32": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32,
                                          _f32, _f32, _int, _vp, _vp, _vp, _vp],
     "mrec_x3_parts_elems": [_i64, _i64, _vp],

@@ -295,7 +295,7 @@ struct UpdStore {  // UnsortedSegmentSum: out[u,:] = sum
     __device__ __forceinline__ void elem(float* st, float g) const { st[0] = g; }
 };
 
-// LazyAdam behind max_norm (mrec_sparse_apply_next_max_norm): the row's completed gradient sum G goes through the clip's Jacobian,
+// LazyAdam behind max_norm (mrec_apply_opts_t.max_norm): the row's completed gradient sum G goes through the clip's Jacobian,
 // G' = (c / n) (G - (x.G / n^2) x) where n = |x| > c, x = the pre-update row p the update loads anyway (= what the step's lookup
 // read: one row, one decision -- n^2 in mrec_row_sumsq's order, as in the lookup).  Its own type: the plain LazyAdam kernels are
 // not touched.
@@ -378,12 +378,12 @@ struct ApplyGeom { int lpr; int G; int D; };
 // (the wide lane pointed at dummy lines for m / v: two more line requests per load and store).
 struct WideArgs { const float* gw; int F; int wcol; FtrlH h; unsigned magic; float* dummy; unsigned gws; };
 
-// The pooled apply (mrec_sparse_apply_next_pool_fields): a sample is Ls = sum L_f positions, F bags back to back.
+// The pooled apply (mrec_apply_opts_t: n_fields / field_len / field_scale): a sample is Ls = sum L_f positions, F bags back to back.
 // Position i -> b = i / Ls (multiply-high with `magic`, exact while i * Ls < 2^32: apply_impl), s = i - b * Ls, f = the last field whose
 // prefix offset off[f] <= s (a linear search: F wave-uniform compares on values the kernel's arguments hold); the gradient row is
 // g[b * F + f] and the second factor of the contribution is scale[f] in place of the call's grad_scale.
-// mrec_sparse_apply_next_pool(L) is F = 1, Ls = L (any L: off[0] = 0 and Ls is an int) with call_scale set: scale[0] is then the armed
-// call's own grad_scale, filled in when the call takes the arm (take_fields).
+// The record's pool = L is F = 1, Ls = L (any L: off[0] = 0 and Ls is an int) with call_scale set: scale[0] is then the call's own
+// grad_scale (apply_opts).
 struct FieldArgs { unsigned magic; int Ls; int F; int call_scale; unsigned short off[MREC_POOL_MAX_FIELDS]; float scale[MREC_POOL_MAX_FIELDS]; };
 
 // uniq == nullptr means "row = group number" (segment-sum into a dense [U, D] output).
@@ -408,6 +408,10 @@ __device__ __forceinline__ int64_t seg_row(const K* uniq, int seg) {
 constexpr int kConstMax = 64;        // hot columns handled: every field can be one (F <= 64)
 constexpr int kConstLG = 1024;       // chunks of 64 consecutive samples the partial-sum pass cuts the batch into, at most (B <= 65536)
 struct ConstCols { const unsigned long long* mask; const long long* hid; const void* ids0; float* part; int B, rr, nlg; unsigned cblocks; int id_bytes; };
+// the state of mrec_const_cols_detect (k_const_cols below writes it; ConstCols points at its mask and ids)
+struct ConstState { unsigned long long badmask; unsigned ticket, pad; unsigned long long mask; unsigned long long pad2; long long hid[64]; unsigned cnt[8][64]; };
+static_assert(sizeof(ConstState) == MREC_CONST_COLS_STATE_BYTES, "mrec.h: MREC_CONST_COLS_STATE_BYTES");
+static_assert(sizeof(mrec_apply_opts_t) == 64, "mrec.h: mrec_apply_opts_t");
 
 // bit f: field f is a constant column (at most kConstMax bits; written by k_const_cols' last workgroup: one scalar load here)
 __device__ __forceinline__ unsigned long long const_mask(const unsigned long long* __restrict__ mask) { return *mask; }
@@ -483,10 +487,10 @@ __device__ __forceinline__ void const_part_body(const ConstCols& cc, unsigned lo
 }
 
 // (WIDE: MREC_WPS4 waves per SIMD asked of the register allocator)
-// (FIELDS: the pooled form, mrec_sparse_apply_next_pool / _next_pool_fields -- position i's gradient row is g[b * F + f] and the scale the
+// (FIELDS: the pooled form, mrec_apply_opts_t's pool / fields members -- position i's gradient row is g[b * F + f] and the scale the
 // field's, see FieldArgs; only where a position's row and scale come from differs, so the windows, the partial sums and their order are
 // the plain apply's.  A template argument: the instantiations without it are the code they were)
-// (ONE, with FIELDS: F == 1 and Ls > 1, what mrec_sparse_apply_next_pool arms -- the row is g[i / Ls] and the one scale travels as
+// (ONE, with FIELDS: F == 1 and Ls > 1, the record's pool = L -- the row is g[i / Ls] and the one scale travels as
 // gscale: no field search, no per-position scale registers, 2.5 % of the windows' time where the table sits in cache)
 template <int VEC, class K, class Upd, class GT, bool WIDE = false, bool HOT = false, bool FIELDS = false, bool ONE = false>
 __device__ __forceinline__ void apply_main_body(const Upd& upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
@@ -807,7 +811,7 @@ __global__ __launch_bounds__(256, WIDE ? MREC_WPS4 : 1) void k_apply_main(Upd up
         ss->ends[(unsigned)ss->step % kStampRing][blockIdx.x & 63u] = (unsigned long long)wall_clock64();
 }
 
-// The pooled apply's windows (mrec_sparse_apply_next_pool, _next_pool_fields): apply_main_body with FIELDS, a kernel of its own so that
+// The pooled apply's windows (mrec_apply_opts_t: pool, the fields form): apply_main_body with FIELDS, a kernel of its own so that
 // k_apply_main's instantiations keep their code and their names.  No step state, no stamps: the plain (not folded) entries have neither.
 template <int VEC, class K, class Upd, class GT, bool ONE>
 __global__ __launch_bounds__(256) void k_apply_main_fields(Upd upd, int64_t V, int64_t ld, const K* __restrict__ uniq,
@@ -1147,34 +1151,54 @@ __global__ __launch_bounds__(256) void k_finish_dense_adam_clip(ApplyFinish f, D
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 thread_local hipEvent_t t_prof_start = nullptr, t_prof_stop = nullptr;
-thread_local ApplyFinish* t_defer = nullptr;        // set by mrec_sparse_lazy_adam_wide_defer: the finishing pass is handed back, not launched
-thread_local ConstCols t_const = ConstCols{};       // set by mrec_sparse_apply_next_const_cols: the next wide apply takes constant columns out of its windows
-thread_local float t_max_norm = 0.0f;               // set by mrec_sparse_apply_next_max_norm: the next LazyAdam apply clips (0: none)
-thread_local FieldArgs t_fields = FieldArgs{};      // set by mrec_sparse_apply_next_pool / _next_pool_fields(_clip): the next apply is pooled (F == 0: not armed)
-thread_local float t_fields_clip = 0.0f;            // set by mrec_sparse_apply_next_pool_fields_clip with t_fields: that pooled apply clips (0: none)
-inline void disarm_fields() { t_fields.F = 0; t_fields_clip = 0.0f; }
-// Armed for one call: every entry that can be the "next apply" takes the arm first thing, whether it then runs or refuses.  MREC_OK and
-// *fields = &fa (armed) or nullptr (the plain apply); any other code is the entry's answer, with nothing left armed.  The pooled form is
-// refused, before anything else is looked at, for the folded wide apply (its wide lane and its hot columns address gradient rows by
-// position themselves), behind max_norm, and with constant columns armed -- which are disarmed with it.  A contribution has ONE scale
-// besides its row_scale: the call's grad_scale under mrec_sparse_apply_next_pool, else the field's -- and grad_scale must be 1.0.
-// max_norm over the pooled form travels WITH the arm (mrec_sparse_apply_next_pool_fields_clip): *pool_clip is that arm's max_norm (0:
-// none), and an entry that passes no pool_clip -- anything but the plain LazyAdam apply -- refuses such an arm like the other cases.
-inline int take_fields(FieldArgs& fa, const FieldArgs** fields, float gscale, bool wide, bool clip, float* pool_clip = nullptr) {
-    fa = t_fields;
-    const float pc = t_fields_clip;
-    disarm_fields();
-    *fields = nullptr;
-    if (pool_clip) *pool_clip = 0.0f;
-    if (fa.F == 0) return MREC_OK;
-    const bool cc_armed = t_const.mask != nullptr;
-    t_const = ConstCols{};
-    if (wide || clip || cc_armed) return MREC_EUNSUPPORTED;
-    if (pc > 0.0f && !pool_clip) return MREC_EUNSUPPORTED;
-    if (fa.call_scale) fa.scale[0] = gscale;
-    else if (gscale != 1.0f) return MREC_EINVAL;
-    if (pool_clip) *pool_clip = pc;
-    *fields = &fa;
+// What an mrec_apply_opts_t asks of ONE apply, decoded: fa.F == 0: not pooled; clip == 0: no max_norm; cc.mask == nullptr: no constant
+// columns; defer: the finishing pass is handed back, not launched (mrec_sparse_lazy_adam_wide_defer fills it in, not the record).
+struct ApplyOpts { FieldArgs fa; float clip; ConstCols cc; ApplyFinish* defer; };
+// Every entry that takes a record decodes it first thing (adam: a LazyAdam apply; wide: its folded wide form).  First the record on its
+// own, then the combinations the kernels do not cover -- the pooled form on the folded wide apply (its wide lane and its hot columns
+// address gradient rows by position themselves) or with constant columns, max_norm with pool = L or on anything but LazyAdam -- then
+// the scale: a contribution has ONE besides its row_scale, the call's grad_scale under pool = L, else the field's -- and grad_scale
+// must be 1.0.  Any code but MREC_OK is the entry's answer.
+inline int apply_opts(const mrec_apply_opts_t* r, float gscale, bool adam, bool wide, ApplyOpts& o) {
+    o = ApplyOpts{};
+    if (!r) return MREC_OK;
+    if (r->struct_bytes != sizeof(mrec_apply_opts_t)) return MREC_EINVAL;
+    if (r->max_norm != 0.0f && !(r->max_norm > 0.0f && r->max_norm <= 3.402823466e38f)) return MREC_EINVAL;
+    if (r->pool < 1) return MREC_EINVAL;
+    const bool by_field = r->n_fields != 0 || r->field_len || r->field_scale;
+    FieldArgs& fa = o.fa;
+    int64_t Ls = r->pool;
+    if (by_field) {
+        const int F = r->n_fields;
+        if (r->pool != 1 || F < 1 || !r->field_len || !r->field_scale) return MREC_EINVAL;
+        if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
+        Ls = 0;
+        for (int f = 0; f < F; ++f) {
+            if (r->field_len[f] < 1 || !(fabsf(r->field_scale[f]) <= 3.402823466e38f)) return MREC_EINVAL;
+            if (Ls + r->field_len[f] > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
+            fa.off[f] = (unsigned short)Ls;
+            fa.scale[f] = r->field_scale[f];
+            Ls += r->field_len[f];
+        }
+        fa.F = F;
+    } else if (r->pool > 1) {
+        fa.F = 1;
+        fa.call_scale = 1;
+        fa.scale[0] = gscale;
+    }
+    fa.Ls = (int)Ls;
+    fa.magic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)Ls + 1);      // pos / Ls = umulhi(pos, magic) while pos * Ls < 2^32 (Ls == 1: not used)
+    if ((r->const_state == nullptr) != (r->const_ids == nullptr) || r->const_B < 0 || r->const_B > (int64_t(1) << 30) ||
+        (r->const_ids && r->const_id_bytes != 4 && r->const_id_bytes != 8))
+        return MREC_EINVAL;
+    if (r->const_state) {
+        const ConstState* cs = (const ConstState*)r->const_state;
+        o.cc.mask = &cs->mask; o.cc.hid = cs->hid; o.cc.ids0 = r->const_ids; o.cc.B = (int)r->const_B; o.cc.id_bytes = r->const_id_bytes;
+    }
+    o.clip = r->max_norm;
+    if (fa.F && (wide || o.cc.mask)) return MREC_EUNSUPPORTED;
+    if (o.clip > 0.0f && (!adam || (fa.F && !by_field))) return MREC_EUNSUPPORTED;
+    if (by_field && gscale != 1.0f) return MREC_EINVAL;
     return MREC_OK;
 }
 
@@ -1192,8 +1216,9 @@ size_t apply_ws_bytes(int64_t n, int32_t D) {
 template <class K, class Upd, class GT>
 int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, const int* sseg,
                const int* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale, float gscale,
-               int Dc, int vec, const ApplyWs& w, hipStream_t st, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr, const FieldArgs* fields = nullptr) {
+               int Dc, int vec, const ApplyWs& w, hipStream_t st, const ApplyOpts& o, const WideArgs* wide = nullptr, StepState* ss = nullptr,
+               const int64_t* nv = nullptr) {
+    const FieldArgs* fields = o.fa.F ? &o.fa : nullptr;
     ApplyGeom gm;
     gm.D = Dc + (wide ? 4 : 0);
     gm.lpr = Dc / vec + (wide ? 1 : 0);
@@ -1211,8 +1236,8 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
     const unsigned lblocks = (unsigned)mrec_cdiv(nsw, (int64_t)(16 * gm.G < 256 ? 16 * gm.G : 256));      // k_apply_long: 4 windows per lane-group, 4 G lane-groups, 256 at most
     const hipEvent_t ev0 = t_prof_start, ev1 = t_prof_stop;
     t_prof_start = t_prof_stop = nullptr;
-    // the pooled windows (fields; refused before this for the folded wide forms and a separately armed max_norm; UpdAdamClip with
-    // fields is mrec_sparse_apply_next_pool_fields_clip's call): k_apply_main_fields, else k_apply_main
+    // the pooled windows (fields; refused before this for the folded wide forms; UpdAdamClip with fields is the record's max_norm over
+    // its fields form): k_apply_main_fields, else k_apply_main
 #define MREC_APPLY_MAIN(VECN)                                                                                                          \
     do {                                                                                                                               \
         if (!fields)                                                                                                                   \
@@ -1229,10 +1254,9 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
     } while (0)
     if (ev0) MREC_HIP_CHECK(hipEventRecord(ev0, st));
     if (nv && !(vec == 4 && wide)) return MREC_EUNSUPPORTED;
-    // constant columns (armed for this call by mrec_sparse_apply_next_const_cols): the batch is B = n / F samples of F fields, ids of
-    // the table's key width, LazyAdam on the fused rows -- anything else runs every column through the windows
-    ConstCols cc = t_const;
-    t_const = ConstCols{};
+    // constant columns (the record's const_* members): the batch is B = n / F samples of F fields, ids of the table's key width,
+    // LazyAdam on the fused rows -- anything else runs every column through the windows
+    ConstCols cc = o.cc;
     if (!(vec == 4 && wide && std::is_same<Upd, UpdAdam>::value && sizeof(K) == 4 && !nv && cc.mask && cc.ids0 && wa.F >= 1 && wa.F <= 64 &&
           n % wa.F == 0 && cc.B == (int)(n / wa.F) && cc.B > 0 && cc.B <= 64 * kConstLG && wa.gws == 1 && cc.id_bytes == (int)sizeof(K)))
         cc = ConstCols{};
@@ -1255,9 +1279,9 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
             k_apply_main<4, K, Upd, GT, true><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,
                                                              w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss, nv, cc);
         if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
-        if (t_defer) {
+        if (o.defer) {
             if constexpr (IsAdam<Upd>::value) {
-                ApplyFinish* f = t_defer;
+                ApplyFinish* f = o.defer;
                 f->upd = upd; f->V = V; f->ld = ld; f->uniq = uniq; f->key_bytes = (int)sizeof(K); f->sseg = sseg; f->seg_offsets = seg_offsets;
                 f->n = (int)n; f->gm = gm; f->carry_head = w.carry_head; f->carry_tail = w.carry_tail; f->owners = w.owners; f->nsw = (int)nsw;
                 f->wa = wa; f->ss = ss; f->nv = nv; f->lblocks = lblocks; f->magic = kFinishMagic;
@@ -1300,13 +1324,12 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
 template <class K, class Upd, class GT = float>
 int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const int32_t* spos, const int32_t* sseg,
                const int32_t* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale,
-               float gscale, void* ws, size_t ws_bytes, void* stream, const WideArgs* wide = nullptr, StepState* ss = nullptr,
-               const int64_t* nv = nullptr, const FieldArgs* fields = nullptr) {
+               float gscale, void* ws, size_t ws_bytes, void* stream, const ApplyOpts& o, const WideArgs* wide = nullptr,
+               StepState* ss = nullptr, const int64_t* nv = nullptr) {
     hipStream_t st = (hipStream_t)stream;
-    if (fields && wide) return MREC_EUNSUPPORTED;      // (refused by the entries already: take_fields)
     if (n < 0 || D <= 0 || V < 0 || ld < D || ldg < D) return MREC_EINVAL;
     if (n == 0) return MREC_OK;
-    if (fields && (uint64_t)n * (uint64_t)fields->Ls >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;   // pos / Ls by a 32-bit multiply-high
+    if (o.fa.F && (uint64_t)n * (uint64_t)o.fa.Ls >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;   // pos / Ls by a 32-bit multiply-high
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!spos || !sseg || !seg_offsets || !g || !ws) return MREC_EINVAL;
     for (int i = 0; i < Upd::NS; ++i) if (!upd.s[i]) return MREC_EINVAL;
@@ -1337,7 +1360,7 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
         const int Dc = (D - c0 < CB) ? D - c0 : CB;
         Upd u2 = upd;
         for (int i = 0; i < Upd::NS; ++i) u2.s[i] = upd.s[i] + c0;
-        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, wide, ss, nv, fields);
+        int rc = apply_cols<K, Upd, GT>(u2, V, ld, uniq, spos, sseg, seg_offsets, n, g + c0, ldg, rscale, gscale, Dc, vec, w, st, o, wide, ss, nv);
         if (rc != MREC_OK) return rc;
     }
     return MREC_OK;
@@ -1347,50 +1370,41 @@ template <class K, class GT = float>
 int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const K* uniq,
                    const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const GT* g,
                    int64_t ldg, const float* rscale, float lr, float b1, float b2, float eps, float b1_pow,
-                   float b2_pow, float gscale, int nesterov, void* ws, size_t ws_bytes, void* stream,
-                   const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr) {
-    float clip = t_max_norm;                       // (armed for this call only)
-    t_max_norm = 0.0f;
-    FieldArgs fa;
-    const FieldArgs* fields;
-    float pool_clip = 0.0f;                        // (max_norm of mrec_sparse_apply_next_pool_fields_clip: it came with the pooled arm)
-    if (const int rc = take_fields(fa, &fields, gscale, wide != nullptr, clip > 0.0f, &pool_clip)) return rc;
-    if (pool_clip > 0.0f) {
-        if (D % 4 || D > 256) return MREC_EUNSUPPORTED;      // (a width the clip cannot run at: the armed call's first answer)
-        clip = pool_clip;
-    }
+                   float b2_pow, float gscale, int nesterov, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream,
+                   const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr, ApplyFinish* defer = nullptr) {
+    ApplyOpts o;
+    if (const int rc = apply_opts(opts, gscale, true, wide != nullptr, o)) return rc;
+    o.defer = defer;
+    if (o.clip > 0.0f && (D % 4 || D > (wide ? 252 : 256))) return MREC_EUNSUPPORTED;      // (a width the clip cannot run at)
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdAdam u;
     u.s[0] = p; u.s[1] = m; u.s[2] = v;
     u.h.lr_t = lr * sqrtf(1.0f - b2_pow) / (1.0f - b1_pow);
     u.h.b1 = b1; u.h.b2 = b2; u.h.omb1 = 1.0f - b1; u.h.omb2 = 1.0f - b2; u.h.eps = eps; u.h.gscale = gscale;
     u.h.nesterov = nesterov;
-    if (clip > 0.0f) {
-        if (D % 4 || D > (wide ? 252 : 256)) return MREC_EUNSUPPORTED;
+    if (o.clip > 0.0f) {
         UpdAdamClip uc;
         static_cast<UpdAdam&>(uc) = u;
-        uc.clip = clip;
+        uc.clip = o.clip;
         return apply_impl<K, UpdAdamClip, GT>(uc, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                              stream, wide, ss, nv, fields);
+                                              stream, o, wide, ss, nv);
     }
     return apply_impl<K, UpdAdam, GT>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, wide, ss, nv, fields);
+                                  stream, o, wide, ss, nv);
 }
 
 template <class K>
 int ftrl_impl(float* var, float* accum, float* linear, int64_t V, int64_t ld, int32_t D, const K* uniq,
               const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const float* g,
               int64_t ldg, const float* rscale, float lr, float l1, float l2, float lr_power, float gscale, void* ws,
-              size_t ws_bytes, void* stream) {
-    FieldArgs fa;
-    const FieldArgs* fields;
-    if (const int rc = take_fields(fa, &fields, gscale, false, false)) return rc;
+              size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
+    ApplyOpts o;
+    if (const int rc = apply_opts(opts, gscale, false, false, o)) return rc;
     if (!uniq && n > 0) return MREC_EINVAL;
     UpdFtrl u;
     u.s[0] = var; u.s[1] = accum; u.s[2] = linear;
     u.h = FtrlH{lr, l1, l2, lr_power, gscale};
-    return apply_impl<K, UpdFtrl>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, nullptr, nullptr, nullptr, fields);
+    return apply_impl<K, UpdFtrl>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes, stream, o);
 }
 
 }  // namespace
@@ -1430,8 +1444,6 @@ __global__ void k_step_advance(StepState* s, float lr, float b1, float b2) {
 // whatever the kernels beside this one have dirtied in L2, 17 us per step when it was tried), and that last workgroup turns the
 // survivors into the mask and the ids the apply's kernels read, and clears counters, word and ticket for the next batch: no memset
 // node, no second launch.
-struct ConstState { unsigned long long badmask; unsigned ticket, pad; unsigned long long mask; unsigned long long pad2; long long hid[64]; unsigned cnt[8][64]; };
-static_assert(sizeof(ConstState) == MREC_CONST_COLS_STATE_BYTES, "mrec.h: MREC_CONST_COLS_STATE_BYTES");
 template <class K>
 __global__ __launch_bounds__(256) void k_const_cols(const K* __restrict__ ids, int64_t n, int F, int64_t V, unsigned min_count, ConstState* __restrict__ st) {
     __shared__ long long c[64];
@@ -1586,61 +1598,6 @@ MREC_API int mrec_const_cols_detect(const void* ids, int32_t id_bytes, int64_t B
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
-MREC_API int mrec_sparse_apply_next_const_cols(const void* state, const void* ids, int32_t id_bytes, int64_t B) {
-    if ((state == nullptr) != (ids == nullptr) || B < 0 || B > (int64_t(1) << 30) || (ids && id_bytes != 4 && id_bytes != 8)) return MREC_EINVAL;
-    t_const = ConstCols{};
-    if (state) { t_const.mask = &((const ConstState*)state)->mask; t_const.hid = ((const ConstState*)state)->hid; t_const.ids0 = ids; t_const.B = (int)B; t_const.id_bytes = id_bytes; }
-    return MREC_OK;
-}
-
-MREC_API int mrec_sparse_apply_next_max_norm(float max_norm) {
-    t_max_norm = 0.0f;
-    if (!(max_norm > 0.0f) || !(max_norm <= 3.402823466e38f)) return MREC_EINVAL;
-    t_max_norm = max_norm;
-    return MREC_OK;
-}
-
-MREC_API int mrec_sparse_apply_next_pool(int32_t L) {
-    disarm_fields();
-    if (L < 1) return MREC_EINVAL;
-    if (L == 1) return MREC_OK;          // the plain apply
-    FieldArgs fa{};
-    fa.F = 1;
-    fa.Ls = L;
-    fa.call_scale = 1;
-    fa.magic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)L + 1);        // pos / L = umulhi(pos, magic) while pos * L < 2^32
-    t_fields = fa;
-    return MREC_OK;
-}
-
-MREC_API int mrec_sparse_apply_next_pool_fields(int32_t F, const int32_t* field_len, const float* field_scale) {
-    disarm_fields();
-    if (F < 1 || !field_len || !field_scale) return MREC_EINVAL;
-    if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
-    FieldArgs fa{};
-    int64_t Ls = 0;
-    for (int f = 0; f < F; ++f) {
-        if (field_len[f] < 1 || !(fabsf(field_scale[f]) <= 3.402823466e38f)) return MREC_EINVAL;
-        if (Ls + field_len[f] > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
-        fa.off[f] = (unsigned short)Ls;
-        fa.scale[f] = field_scale[f];
-        Ls += field_len[f];
-    }
-    fa.Ls = (int)Ls;
-    fa.F = F;
-    fa.magic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)Ls + 1);      // pos / Ls = umulhi(pos, magic) while pos * Ls < 2^32 (Ls == 1: not used)
-    t_fields = fa;
-    return MREC_OK;
-}
-
-MREC_API int mrec_sparse_apply_next_pool_fields_clip(int32_t F, const int32_t* field_len, const float* field_scale, float max_norm) {
-    disarm_fields();
-    if (!(max_norm > 0.0f) || !(max_norm <= 3.402823466e38f)) return MREC_EINVAL;
-    const int rc = mrec_sparse_apply_next_pool_fields(F, field_len, field_scale);
-    if (rc != MREC_OK) return rc;
-    t_fields_clip = max_norm;
-    return MREC_OK;
-}
 
 MREC_API int mrec_step_state_init(void* state, float beta1_power, float beta2_power, int64_t step, void* stream) {
     if (!state || step < 0) return MREC_EINVAL;
@@ -1699,33 +1656,31 @@ MREC_API int mrec_sparse_apply_workspace_bytes(int64_t n, int32_t D, size_t* out
 
 MREC_API int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets,
                                   int64_t n, const float* g, int64_t ldg, const float* row_scale, float grad_scale,
-                                  int32_t D, float* out, void* ws, size_t ws_bytes, void* stream) {
+                                  int32_t D, float* out, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     UpdStore u;
     u.s[0] = out;
-    FieldArgs fa;
-    const FieldArgs* fields;
-    if (const int rc = take_fields(fa, &fields, grad_scale, false, false)) return rc;
+    ApplyOpts o;
+    if (const int rc = apply_opts(opts, grad_scale, false, false, o)) return rc;
     // rows are group numbers; there are at most n groups
     return apply_impl<int32_t, UpdStore>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, g,
-                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, fields);
+                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, o);
 }
 
 /* ... over 16-bit row gradients (g_kind 1: bf16, 2: IEEE half), widened exactly and summed in fp32: what a rank of a row-sharded
  * step sends an owner when it exchanges UNIQUE ids -- one fp32 sum per unique id instead of one 16-bit row per position. */
 MREC_API int mrec_segment_sum_g16(const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets,
                                   int64_t n, const void* g, int32_t g_kind, int64_t ldg, const float* row_scale, float grad_scale,
-                                  int32_t D, float* out, void* ws, size_t ws_bytes, void* stream) {
+                                  int32_t D, float* out, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     UpdStore u;
     u.s[0] = out;
-    FieldArgs fa;
-    const FieldArgs* fields;
-    if (const int rc = take_fields(fa, &fields, grad_scale, false, false)) return rc;
+    ApplyOpts o;
+    if (const int rc = apply_opts(opts, grad_scale, false, false, o)) return rc;
     if (g_kind == 1)
         return apply_impl<int32_t, UpdStore, bf16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const bf16_t*)g,
-                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, fields);
+                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, o);
     if (g_kind == 2)
         return apply_impl<int32_t, UpdStore, f16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const f16_t*)g,
-                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, nullptr, nullptr, nullptr, fields);
+                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, o);
     return MREC_EINVAL;
 }
 
@@ -1734,18 +1689,18 @@ MREC_API int mrec_sparse_lazy_adam_f32_i32(float* p, float* m, float* v, int64_t
                                            const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                            const float* row_scale, float lr, float b1, float b2, float eps,
                                            float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                           size_t ws_bytes, void* stream) {
+                                           size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return lazy_adam_impl<int32_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg, row_scale,
-                                   lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, stream);
+                                   lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream);
 }
 MREC_API int mrec_sparse_lazy_adam_f32_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
                                            const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                            const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                            const float* row_scale, float lr, float b1, float b2, float eps,
                                            float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                           size_t ws_bytes, void* stream) {
+                                           size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return lazy_adam_impl<int64_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg, row_scale,
-                                   lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, stream);
+                                   lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream);
 }
 
 MREC_API int mrec_sparse_lazy_adam_bf16g_i32(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
@@ -1753,20 +1708,20 @@ MREC_API int mrec_sparse_lazy_adam_bf16g_i32(float* p, float* m, float* v, int64
                                              const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                              const float* row_scale, float lr, float b1, float b2, float eps,
                                              float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                             size_t ws_bytes, void* stream) {
+                                             size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return lazy_adam_impl<int32_t, bf16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
                                            (const bf16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                           nesterov, ws, ws_bytes, stream);
+                                           nesterov, ws, ws_bytes, opts, stream);
 }
 MREC_API int mrec_sparse_lazy_adam_bf16g_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
                                              const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                              const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                              const float* row_scale, float lr, float b1, float b2, float eps,
                                              float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                             size_t ws_bytes, void* stream) {
+                                             size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return lazy_adam_impl<int64_t, bf16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
                                            (const bf16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                           nesterov, ws, ws_bytes, stream);
+                                           nesterov, ws, ws_bytes, opts, stream);
 }
 
 MREC_API int mrec_sparse_lazy_adam_f16g_i32(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
@@ -1774,38 +1729,38 @@ MREC_API int mrec_sparse_lazy_adam_f16g_i32(float* p, float* m, float* v, int64_
                                             const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                             const float* row_scale, float lr, float b1, float b2, float eps,
                                             float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                            size_t ws_bytes, void* stream) {
+                                            size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return lazy_adam_impl<int32_t, f16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
                                           (const f16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                          nesterov, ws, ws_bytes, stream);
+                                          nesterov, ws, ws_bytes, opts, stream);
 }
 MREC_API int mrec_sparse_lazy_adam_f16g_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
                                             const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                             const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
                                             const float* row_scale, float lr, float b1, float b2, float eps,
                                             float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                            size_t ws_bytes, void* stream) {
+                                            size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return lazy_adam_impl<int64_t, f16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
                                           (const f16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                          nesterov, ws, ws_bytes, stream);
+                                          nesterov, ws, ws_bytes, opts, stream);
 }
 
-/* LazyAdam on the deep columns + FTRL on the wide record of the same fused rows, one pass (see include/mrec.h) */
-MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const void* uniq,
-                                        int32_t uniq_bytes, const int32_t* sorted_pos, const int32_t* sorted_seg,
-                                        const int32_t* seg_offsets, int64_t n, const void* g, int32_t g_kind, int64_t ldg,
-                                        const float* row_scale, float lr, float b1, float b2, float eps, float b1_pow,
-                                        float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F,
-                                        int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
-                                        size_t ws_bytes, void* step_state, const int64_t* n_valid_dev, void* stream) {
-    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) { t_max_norm = 0.0f; disarm_fields(); return MREC_EINVAL; }
+/* LazyAdam on the deep columns + FTRL on the wide record of the same fused rows, one pass (see include/mrec.h); defer: the finishing
+ * pass is handed back in *defer instead of launched */
+static int lazy_adam_wide(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const void* uniq, int32_t uniq_bytes,
+                          const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets, int64_t n, const void* g,
+                          int32_t g_kind, int64_t ldg, const float* row_scale, float lr, float b1, float b2, float eps, float b1_pow,
+                          float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F, int32_t wide_col,
+                          float ftrl_lr, float l1, float l2, float lr_power, void* ws, size_t ws_bytes, void* step_state,
+                          const int64_t* n_valid_dev, const mrec_apply_opts_t* opts, ApplyFinish* defer, void* stream) {
+    if ((uniq_bytes != 4 && uniq_bytes != 8) || g_kind < 0 || g_kind > 2 || gw_stride < 1 || gw_stride > (1 << 20)) return MREC_EINVAL;
     WideArgs wa;
     wa.gw = gw; wa.F = F; wa.wcol = wide_col; wa.magic = 0; wa.dummy = nullptr; wa.gws = (unsigned)gw_stride;
     wa.h = FtrlH{ftrl_lr, l1, l2, lr_power, grad_scale};
 #define MREC_WIDE_CALL(KT, GT)                                                                                          \
     return lazy_adam_impl<KT, GT>(p, m, v, V, ld, D, (const KT*)uniq, sorted_pos, sorted_seg, seg_offsets, n, (const GT*)g, ldg, \
-                                  row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, stream, &wa,      \
-                                  (StepState*)step_state, n_valid_dev)
+                                  row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream, &wa, \
+                                  (StepState*)step_state, n_valid_dev, defer)
     if (uniq_bytes == 4) {
         if (g_kind == 0) { MREC_WIDE_CALL(int32_t, float); }
         if (g_kind == 1) { MREC_WIDE_CALL(int32_t, bf16_t); }
@@ -1817,6 +1772,19 @@ MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V,
 #undef MREC_WIDE_CALL
 }
 
+MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const void* uniq,
+                                        int32_t uniq_bytes, const int32_t* sorted_pos, const int32_t* sorted_seg,
+                                        const int32_t* seg_offsets, int64_t n, const void* g, int32_t g_kind, int64_t ldg,
+                                        const float* row_scale, float lr, float b1, float b2, float eps, float b1_pow,
+                                        float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F,
+                                        int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
+                                        size_t ws_bytes, void* step_state, const int64_t* n_valid_dev, const mrec_apply_opts_t* opts,
+                                        void* stream) {
+    return lazy_adam_wide(p, m, v, V, ld, D, uniq, uniq_bytes, sorted_pos, sorted_seg, seg_offsets, n, g, g_kind, ldg, row_scale, lr, b1, b2,
+                          eps, b1_pow, b2_pow, grad_scale, nesterov, gw, gw_stride, F, wide_col, ftrl_lr, l1, l2, lr_power, ws, ws_bytes,
+                          step_state, n_valid_dev, opts, nullptr, stream);
+}
+
 /* The same with the finishing pass handed back instead of launched (see include/mrec.h). */
 MREC_API int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const void* uniq,
                                               int32_t uniq_bytes, const int32_t* sorted_pos, const int32_t* sorted_seg,
@@ -1825,17 +1793,15 @@ MREC_API int mrec_sparse_lazy_adam_wide_defer(float* p, float* m, float* v, int6
                                               float b2_pow, float grad_scale, int nesterov, const float* gw, int64_t gw_stride, int32_t F,
                                               int32_t wide_col, float ftrl_lr, float l1, float l2, float lr_power, void* ws,
                                               size_t ws_bytes, void* step_state, const int64_t* n_valid_dev,
-                                              mrec_apply_finish_t* finish_out, void* stream) {
-    if (!finish_out) { t_max_norm = 0.0f; disarm_fields(); return MREC_EINVAL; }
-    if (D > 252) { t_max_norm = 0.0f; disarm_fields(); return MREC_EUNSUPPORTED; }            // (one column block: one finishing pass)
+                                              mrec_apply_finish_t* finish_out, const mrec_apply_opts_t* opts, void* stream) {
+    if (!finish_out) return MREC_EINVAL;
+    if (D > 252) return MREC_EUNSUPPORTED;            // (one column block: one finishing pass)
     ApplyFinish* f = (ApplyFinish*)finish_out;
     f->magic = 0u;
     f->clip = 0.0f;
-    t_defer = f;
-    const int rc = mrec_sparse_lazy_adam_wide(p, m, v, V, ld, D, uniq, uniq_bytes, sorted_pos, sorted_seg, seg_offsets, n, g, g_kind, ldg,
-                                              row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, gw, gw_stride, F, wide_col,
-                                              ftrl_lr, l1, l2, lr_power, ws, ws_bytes, step_state, n_valid_dev, stream);
-    t_defer = nullptr;
+    const int rc = lazy_adam_wide(p, m, v, V, ld, D, uniq, uniq_bytes, sorted_pos, sorted_seg, seg_offsets, n, g, g_kind, ldg, row_scale, lr,
+                                  b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, gw, gw_stride, F, wide_col, ftrl_lr, l1, l2, lr_power,
+                                  ws, ws_bytes, step_state, n_valid_dev, opts, f, stream);
     if (rc == MREC_OK && f->magic != kFinishMagic) { f->lblocks = 0; f->cfin = 0; f->magic = kFinishMagic; }      // (n == 0: nothing to finish)
     return rc;
 }
@@ -1903,15 +1869,15 @@ MREC_API int mrec_sparse_ftrl_f32_i32(float* var, float* accum, float* linear, i
                                       const int32_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                       const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                       const float* row_scale, float lr, float l1, float l2, float lr_power,
-                                      float grad_scale, void* ws, size_t ws_bytes, void* stream) {
+                                      float grad_scale, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return ftrl_impl<int32_t>(var, accum, linear, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg,
-                              row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, stream);
+                              row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, opts, stream);
 }
 MREC_API int mrec_sparse_ftrl_f32_i64(float* var, float* accum, float* linear, int64_t V, int64_t ld, int32_t D,
                                       const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                       const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                       const float* row_scale, float lr, float l1, float l2, float lr_power,
-                                      float grad_scale, void* ws, size_t ws_bytes, void* stream) {
+                                      float grad_scale, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
     return ftrl_impl<int64_t>(var, accum, linear, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg,
-                              row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, stream);
+                              row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, opts, stream);
 }

@@ -219,28 +219,18 @@ def _field_scales(lens, field_scale, grad_scale):
     return sc
 
 
-def _call_clipped(max_norm, name, *args, arm=None):
-    """_lib.call(name, *args) -- a sparse apply -- armed with max_norm (mrec_sparse_apply_next_max_norm: the NEXT LazyAdam apply of this
-    host thread clips) and / or arm = (entry, *its arguments), the pooled form (_pooled: mrec_sparse_apply_next_pool, the NEXT apply
-    reads position i's gradient row from g[i // L], or mrec_sparse_apply_next_pool_fields, bags of unequal lengths, one scale per field).
-    Everything is evaluated before the arm, and an exception between the arm and the apply (ctypes refusing an argument) disarms
-    again, so that no later apply of another table is clipped or pooled by mistake."""
-    if max_norm is None and arm is None:
-        _lib.call(name, *args)
-        return
-    c = None if max_norm is None else _max_norm(max_norm)
-    try:
-        if c is not None:
-            _lib.call("mrec_sparse_apply_next_max_norm", c)
-        if arm is not None:
-            _lib.call(*arm)
-        _lib.call(name, *args)
-    except BaseException:
-        if c is not None:
-            _lib.lib().mrec_sparse_apply_next_max_norm(0.0)      # (EINVAL: leaves nothing armed; the C side disarms on its own refusals)
-        if arm is not None:
-            _lib.lib().mrec_sparse_apply_next_pool(1)            # (1: the plain apply; disarms either form)
-        raise
+class ApplyOpts(C.Structure):      # mrec_apply_opts_t: the options of ONE sparse apply, passed to the call they modify
+    _fields_ = [("struct_bytes", C.c_uint32), ("max_norm", C.c_float), ("pool", C.c_int32), ("n_fields", C.c_int32),
+                ("field_len", C.POINTER(C.c_int32)), ("field_scale", C.POINTER(C.c_float)), ("const_state", C.c_void_p),
+                ("const_ids", C.c_void_p), ("const_B", C.c_int64), ("const_id_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, **members):
+        """the plain apply's record plus `members`; an array given for field_len / field_scale stays referenced by the record"""
+        super().__init__(**{"struct_bytes": C.sizeof(ApplyOpts), "pool": 1, **members})
+
+
+def _opts_ptr(opts):
+    return None if opts is None else C.byref(opts)
 
 
 def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32, max_norm=None):
@@ -508,8 +498,8 @@ def _grads(plan, g, D, allow_bf16=False, rows=None):
 
 
 def _fields_arm(fields, field_scale, grad_scale):
-    """((lengths, scales) or None without fields=, the grad_scale the armed call is given): the fields form takes its scales per field
-    and 1.0 as the call's own"""
+    """((lengths, scales) or None without fields=, the grad_scale the call is given): the fields form takes its scales per field and
+    1.0 as the call's own"""
     if fields is None:
         if field_scale is not None:
             raise ValueError("field_scale goes with fields=")
@@ -519,11 +509,12 @@ def _fields_arm(fields, field_scale, grad_scale):
 
 
 def _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm=None):
-    """pool= / fields= of a sparse apply -> (arm, rows, grad_scale): what _call_clipped arms (None, None: the plain apply), the gradient
-    rows the armed call reads (their count and how it is counted, for _grads) and the grad_scale it is given.  pool=L: one row per bag of L positions, ceil(n / L) of them (the last
-    bag may be short); fields=lengths: one per bag of a sample's F bags, n / sum(lengths) * F of them (whole samples).
-    pool_max_norm=c: the clip travels with the pooled arm (mrec_sparse_apply_next_pool_fields_clip); pool=L is then its F = 1 case,
-    fields=(L,) with field_scale=(grad_scale,), and whole bags like every fields form."""
+    """pool= / fields= of a sparse apply -> (opts, rows, grad_scale): the call's ApplyOpts (None: the plain apply), the gradient rows it
+    reads (their count and how it is counted, for _grads; None: one per position) and the grad_scale it is given.  pool=L: one row per
+    bag of L positions, ceil(n / L) of them (the last bag may be short); fields=lengths: one per bag of a sample's F bags,
+    n / sum(lengths) * F of them (whole samples).  pool_max_norm=c: the record's max_norm beside its fields form; pool=L is then that
+    form's F = 1 case, fields=(L,) with field_scale=(grad_scale,), and whole bags like every fields form."""
+    c = 0.0
     if pool_max_norm is not None:
         c = _max_norm(pool_max_norm)
         if pool is not None and fields is None and field_scale is None:
@@ -535,7 +526,7 @@ def _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm=None):
         if pool is None:
             return None, None, grad_scale
         L = _pool(pool)
-        return ("mrec_sparse_apply_next_pool", L), (-(-plan.n // L), f"pool={L}: g must hold ceil(n / pool)"), grad_scale
+        return ApplyOpts(pool=L), (-(-plan.n // L), f"pool={L}: g must hold ceil(n / pool)"), grad_scale
     if pool is not None:
         raise ValueError("pool= and fields= are two forms of the same thing: pass one")
     lens, scales = fa
@@ -543,9 +534,7 @@ def _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm=None):
     if plan.n % Ls:
         raise TypeError(f"fields={lens}: the plan's {plan.n} positions are not whole samples of {Ls} ids")
     rows = (plan.n // Ls * F, f"fields={lens}: g must hold n / {Ls} * {F}")
-    if pool_max_norm is not None:
-        return ("mrec_sparse_apply_next_pool_fields_clip", F, (C.c_int32 * F)(*lens), (C.c_float * F)(*scales), c), rows, grad_scale
-    return ("mrec_sparse_apply_next_pool_fields", F, (C.c_int32 * F)(*lens), (C.c_float * F)(*scales)), rows, grad_scale
+    return ApplyOpts(n_fields=F, field_len=(C.c_int32 * F)(*lens), field_scale=(C.c_float * F)(*scales), max_norm=c), rows, grad_scale
 
 
 def _row_scale(plan, row_scale):
@@ -575,7 +564,7 @@ def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None, fields=None,
     [B, F * D] gradient seen as [B * F, D], and position i = b * Ls + s, s in field f, contributes (g[b * F + f] * row_scale[i]) *
     field_scale[f]; field_scale (one float per field) takes the place of grad_scale, without it every field's scale is grad_scale."""
     _need_cuda(g, row_scale)
-    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
+    opts, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
     D = g.shape[-1]
     F = len(fields) if fields is not None else 1
     if F > 1 and g.dim() == 2 and g.shape[0] * sum(fields) == plan.n and D % F == 0:
@@ -585,12 +574,12 @@ def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None, fields=None,
     out = torch.empty((max(plan.n, 1), D), dtype=torch.float32, device=g.device)
     ws = _apply_ws(plan, D, g.device)
     if g2.dtype == torch.float32:
-        _call_clipped(None, "mrec_segment_sum_f32", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                      _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(), arm=arm)
+        _lib.call("mrec_segment_sum_f32", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
+                  _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _opts_ptr(opts), _stream())
     else:       # 16-bit row gradients (what the mixed-precision MLP backward produces): widened exactly, summed in fp32
-        _call_clipped(None, "mrec_segment_sum_g16", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                      _ptr(g2), 1 if g2.dtype == torch.bfloat16 else 2, ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _stream(),
-                      arm=arm)
+        _lib.call("mrec_segment_sum_g16", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
+                  _ptr(g2), 1 if g2.dtype == torch.bfloat16 else 2, ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(),
+                  _opts_ptr(opts), _stream())
     return out
 
 
@@ -599,29 +588,35 @@ def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, be
                       pool_max_norm=None):
     """nn.LazyAdam on a RowTensor gradient (wide_and_deep.py:420-422): in place on p, m, v.  max_norm=c: the gradients are those
     of rows the lookup clipped to c (gather_rows(..., max_norm=c) of the same p): each touched row's summed gradient G becomes
-    (c / n)(G - (p.G / n^2) p) where n = |p| > c (mrec_sparse_apply_next_max_norm); D % 4 == 0, D <= 256.  pool=L: the bprop of
+    (c / n)(G - (p.G / n^2) p) where n = |p| > c (mrec_apply_opts_t.max_norm); D % 4 == 0, D <= 256.  pool=L: the bprop of
     gather_pool -- g is [ceil(n / L), D], one row per bag, and position i's gradient row is g[i // L] (segment_sum); not with
     max_norm.  fields=(L_0, ..), field_scale: the bprop of gather_pool_fields, as segment_sum -- one plan over all the fields' ids, so
     an id that occurs in several fields gets the sum of their gradients and ONE update; not with pool= or max_norm.
     pool_max_norm=c, with fields= (or pool=L, its one-field case): the bprop of gather_pool_fields(max_norm=c) -- the pooled apply
-    whose completed row sums go through the clip's Jacobian as under max_norm (mrec_sparse_apply_next_pool_fields_clip: the clip
-    travels with the pooled arm); D % 4 == 0, D <= 256.  max_norm= stays the plain apply's and is refused with pool= or fields=."""
+    whose completed row sums go through the clip's Jacobian as under max_norm (the record's max_norm beside its fields form);
+    D % 4 == 0, D <= 256.  max_norm= stays the plain apply's and is refused with pool= or fields=."""
     _need_cuda(p, m, v, g, row_scale)
     V, D, ld = _table(p)
     for t in (m, v):
         if _table(t) != (V, D, ld):
             raise ValueError("p, m, v must share shape and row stride")
-    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm)
+    opts, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm)
     g2, ldg = _grads(plan, g, D, allow_bf16=True, rows=rows)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, p.device)
     sfx = _suffix(plan.uniq_buf)
     fn = {torch.float32: "mrec_sparse_lazy_adam_f32_", torch.bfloat16: "mrec_sparse_lazy_adam_bf16g_",
           torch.float16: "mrec_sparse_lazy_adam_f16g_"}[g2.dtype]
-    args = (_ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets),
-            plan.n, _ptr(g2), ldg, _ptr(rs), lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(ws),
-            ws.numel(), _stream())
-    _call_clipped(max_norm, fn + sfx, *args, arm=arm)
+    if max_norm is not None:
+        c = _max_norm(max_norm)
+        if opts is None:
+            opts = ApplyOpts()
+        elif opts.n_fields:      # the record holds ONE max_norm, and beside fields= it is pool_max_norm's: MREC_EUNSUPPORTED, as ever
+            raise _lib.MrecError(fn + sfx, -3, "(max_norm= with fields=: the pooled apply takes pool_max_norm=)")
+        opts.max_norm = c
+    _lib.call(fn + sfx, _ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), _ptr(plan.sorted_pos), _ptr(plan.sorted_seg),
+              _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale,
+              int(use_nesterov), _ptr(ws), ws.numel(), _opts_ptr(opts), _stream())
 
 
 class ApplyFinish(C.Structure):      # mrec_apply_finish_t
@@ -702,16 +697,18 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
             beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(gw), int(gws), int(F), int(wide_col),
             ftrl_lr, l1, l2, lr_power, _ptr(ws), ws.numel(), _ptr(step_state.buf) if step_state is not None else None,
             _ptr(getattr(plan, "n_valid_dev", None)))
-    keep_cc = None
+    opts = keep_cc = None
     if max_norm is not None and const_cols is not None and const_cols[0] is not None:
         raise ValueError("max_norm: the hot-column apply has no clip (const_cols=None)")
-    if const_cols is not None and const_cols[0] is not None:
+    if max_norm is not None:
+        opts = ApplyOpts(max_norm=_max_norm(max_norm))
+    elif const_cols is not None and const_cols[0] is not None:
         bad, ids = const_cols
         _need_cuda(bad, ids)
         if (ids.dim() != 2 or ids.shape[1] != F or ids.numel() != plan.n or not ids.is_contiguous()
                 or ids.element_size() != plan.uniq_buf.element_size() or bad.dtype != torch.int32 or bad.numel() * 4 != CONST_COLS_STATE_BYTES):
             raise TypeError("const_cols: (the state of const_cols_detect, the contiguous [n / F, F] id batch of the plan, ids of the table's key width)")
-        _lib.call("mrec_sparse_apply_next_const_cols", _ptr(bad), _ptr(ids), ids.element_size(), ids.shape[0])
+        opts = ApplyOpts(const_state=_ptr(bad), const_ids=_ptr(ids), const_id_bytes=ids.element_size(), const_B=ids.shape[0])
         keep_cc = (bad, ids)
     if defer:
         # the finishing pass (runs of duplicates that cross windows of the sorted index) is handed back: dense_adam_slabs_(...,
@@ -719,9 +716,9 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
         # the tables: run the finish before any of them is reused.
         fin = ApplyFinish()
         fin.keep = (ws, plan, p, g2, rs, gw, keep_cc)
-        _call_clipped(max_norm, "mrec_sparse_lazy_adam_wide_defer", *args, C.cast(C.pointer(fin), C.c_void_p), _stream())
+        _lib.call("mrec_sparse_lazy_adam_wide_defer", *args, C.byref(fin), _opts_ptr(opts), _stream())
         return fin
-    _call_clipped(max_norm, "mrec_sparse_lazy_adam_wide", *args, _stream())
+    _lib.call("mrec_sparse_lazy_adam_wide", *args, _opts_ptr(opts), _stream())
     return None
 
 
@@ -734,14 +731,14 @@ def sparse_ftrl_(var, accum, linear, plan, g, row_scale=None, lr=5e-2, l1=1e-8, 
     for t in (accum, linear):
         if _table(t) != (V, D, ld):
             raise ValueError("var, accum, linear must share shape and row stride")
-    arm, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
+    opts, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
     g2, ldg = _grads(plan, g, D, rows=rows)
     rs = _row_scale(plan, row_scale)
     ws = _apply_ws(plan, D, var.device)
     sfx = _suffix(plan.uniq_buf)
-    _call_clipped(None, f"mrec_sparse_ftrl_f32_{sfx}", _ptr(var), _ptr(accum), _ptr(linear), V, ld, D, _ptr(plan.uniq_buf),
-                  _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, l1,
-                  l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _stream(), arm=arm)
+    _lib.call(f"mrec_sparse_ftrl_f32_{sfx}", _ptr(var), _ptr(accum), _ptr(linear), V, ld, D, _ptr(plan.uniq_buf),
+              _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, l1,
+              l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _opts_ptr(opts), _stream())
 
 
 def _flat_same(*ts):

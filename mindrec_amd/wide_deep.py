@@ -104,7 +104,7 @@ class WideDeepConfig:
     max_norm: Optional[float] = None   # HashEmbeddingLookup / nn.EmbeddingLookup(max_norm=c) of the DEEP table (embedding.py:156-161,
                                        # 202-205): every looked-up row x is clipped to x * (c / |x|) where |x| > c before the mask
                                        # multiply, in training and in predict(); the sparse apply takes the gradient through the clip
-                                       # (include/mrec.h, mrec_sparse_apply_next_max_norm).  One GPU, sparse, resident tables (dense or
+                                       # (include/mrec.h, mrec_apply_opts_t.max_norm).  One GPU, sparse, resident tables (dense or
                                        # dynamic_embedding), emb_dim % 4 == 0 and <= 252.  Hot-column detection is off under it (the
                                        # hot-column apply has no clip).  The wide table is never clipped.
 

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY: the fields form of the multi-hot path (mrec_gather_pool_fields, mrec_sparse_apply_next_pool_fields)
+"""TEST INFRASTRUCTURE ONLY: the fields form of the multi-hot path (mrec_gather_pool_fields, the fields form of mrec_apply_opts_t)
 restated on the host in np.float32, on top of tests/_pool_ref.py and tests/_apply_order.py, which it does not change.
 
 A sample is Ls = sum(field_len) slots, F bags back to back: field f holds slots off_f .. off_f + L_f - 1, off_f = L_0 + .. + L_{f-1}.

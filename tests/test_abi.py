@@ -44,6 +44,37 @@ def test_version_and_strerror():
     assert l.mrec_strerror(-99) == b"unknown error"
 
 
+def test_apply_opts_mirror_matches_the_header():
+    """ops.ApplyOpts is mrec_apply_opts_t member for member: names and order from include/mrec.h, C types by their natural layout (the
+    library pins sizeof to the same 64 bytes with a static_assert, and refuses a record whose struct_bytes is anything else)"""
+    from mindrec_amd import _lib, ops
+    text = open(os.path.join(ROOT, "include", "mrec.h")).read()
+    body = re.search(r"typedef struct mrec_apply_opts \{(.*?)\} mrec_apply_opts_t;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    members = [(t.strip(), n) for t, n in re.findall(r"([A-Za-z0-9_ ]+?[ *]+)([a-z_A-Z0-9]+);", body)]
+    ctype = {"uint32_t": C.c_uint32, "float": C.c_float, "int32_t": C.c_int32, "int64_t": C.c_int64,
+             "const int32_t*": C.POINTER(C.c_int32), "const float*": C.POINTER(C.c_float), "const void*": C.c_void_p}
+    assert [(n, ctype[t]) for t, n in members] == list(ops.ApplyOpts._fields_)
+    assert members[0] == ("uint32_t", "struct_bytes")
+    assert C.sizeof(ops.ApplyOpts) == 64
+    offsets = {n: getattr(ops.ApplyOpts, n).offset for _, n in members}
+    assert offsets == dict(struct_bytes=0, max_norm=4, pool=8, n_fields=12, field_len=16, field_scale=24, const_state=32, const_ids=40,
+                           const_B=48, const_id_bytes=56, reserved=60)
+    plain = ops.ApplyOpts()
+    assert (plain.struct_bytes, plain.max_norm, plain.pool, plain.n_fields) == (64, 0.0, 1, 0)
+    # every entry that takes the record takes it right before the stream
+    l = _lib.lib()
+    decl = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    takers = re.findall(r"\bint (mrec_[a-z0-9_]+)\(([^;]*?)const mrec_apply_opts_t\* opts,\s*void\* stream\);", decl)
+    assert sorted(n for n, _ in takers) == sorted(
+        ["mrec_segment_sum_f32", "mrec_segment_sum_g16", "mrec_sparse_lazy_adam_wide", "mrec_sparse_lazy_adam_wide_defer"]
+        + [f"mrec_sparse_lazy_adam_{g}_{k}" for g in ("f32", "bf16g", "f16g") for k in ("i32", "i64")]
+        + [f"mrec_sparse_ftrl_f32_{k}" for k in ("i32", "i64")])
+    for name, args in takers:
+        assert len(getattr(l, name).argtypes) == args.count(",") + 2, name
+    assert l.mrec_version() >= 101      # (100: the options were armed by entries of their own)
+
+
 def test_workspace_queries_and_validation():
     from mindrec_amd import _lib
     n = 16384 * 39

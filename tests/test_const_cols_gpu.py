@@ -1,4 +1,4 @@
-"""Constant columns (mrec_const_cols_detect + mrec_sparse_apply_next_const_cols, include/mrec.h): the fields of a batch whose id is the
+"""Constant columns (mrec_const_cols_detect + the const_* members of mrec_apply_opts_t, include/mrec.h): the fields of a batch whose id is the
 same in every sample -- what the reference's Criteo pipeline gives the 13 dense features (datasets/criteo_1tb/process_data.py:138-147)
 -- are summed sample by sample by the folded apply's own launch instead of through the inverted index.  Checked: the detection against
 a numpy restatement (ragged cases: a column equal in all but one sample, an id that also occurs in another field, an id outside the

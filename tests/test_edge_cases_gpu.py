@@ -69,7 +69,7 @@ def test_workspace_too_small_is_reported(dev):
     p = torch.zeros((100, 8), device=dev)
     g = torch.zeros((n, 8), device=dev)
     assert l.mrec_sparse_lazy_adam_f32_i32(vp(p), vp(p), vp(p), 100, 8, 8, vp(uniq), vp(inv), vp(inv), vp(inv), n, vp(g), 8,
-                                           None, 0.1, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0, vp(ws), ws.numel(), st) == -2
+                                           None, 0.1, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0, vp(ws), ws.numel(), None, st) == -2
     torch.cuda.synchronize()
 
 

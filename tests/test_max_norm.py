@@ -30,39 +30,43 @@ def test_clip_entry_points_validate_before_any_launch():
     assert w(*args(80, float("nan"))) == EINVAL
     assert w(*args(256, 1.0)) == EUNSUPPORTED                                                # > 252 with the wide word
     assert w(*args(82, 1.0)) == EUNSUPPORTED
-    # the apply is armed by a call of its own: a bad bound arms nothing, an armed call with an unsupported width is refused
-    for bad in (0.0, -2.0, float("inf"), float("nan")):
-        assert l.mrec_sparse_apply_next_max_norm(bad) == EINVAL
+    # the apply takes the bound in its options record: a bad bound is refused first, an unsupported width before any launch
+    from mindrec_amd import ops
+    rec = lambda c: C.byref(ops.ApplyOpts(max_norm=c))  # noqa: E731
     f = l.mrec_sparse_lazy_adam_f32_i32
     out = C.c_size_t()
-    # (n == 0: the plain call returns before any launch; armed, the width is checked first)
-    plain = (None, None, None, 10, 80, 78, None, None, None, None, 0, None, 80, None, 1e-3, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0, None, 0,
-             None)
-    assert f(*plain) == 0
-    assert l.mrec_sparse_apply_next_max_norm(1.0) == 0
-    assert f(*plain) == EUNSUPPORTED
-    assert f(*plain) == 0                                  # the refusal disarmed it
+    # (n == 0: the plain call returns before any launch; under max_norm, the width is checked first)
+    plain = (None, None, None, 10, 80, 78, None, None, None, None, 0, None, 80, None, 1e-3, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0, None, 0)
+    ok = (None, None, None, 10, 80, 80) + plain[6:]
+    for bad in (-2.0, float("inf"), float("nan")):
+        assert f(*ok, rec(bad), None) == EINVAL
+    assert f(*ok, rec(0.0), None) == 0 and f(*plain, rec(0.0), None) == 0      # 0: none
+    assert f(*ok, rec(1.0), None) == 0
+    assert f(*plain, None, None) == 0
+    assert f(*plain, rec(1.0), None) == EUNSUPPORTED
+    assert f(*plain, None, None) == 0                      # the same call without the record: plain
     wide = l.mrec_sparse_lazy_adam_wide
     wargs = (None, None, None, 10, 260, 256, None, 4, None, None, None, 0, None, 0, 256, None, 1e-3, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0,
-             None, 1, 1, 256, 5e-2, 1e-8, 1e-8, -0.5, None, 0, None, None, None)
-    assert l.mrec_sparse_apply_next_max_norm(1.0) == 0
-    assert wide(*wargs) == EUNSUPPORTED                    # 256 + the wide record
+             None, 1, 1, 256, 5e-2, 1e-8, 1e-8, -0.5, None, 0, None, None)
+    assert wide(*wargs, rec(1.0), None) == EUNSUPPORTED    # 256 + the wide record
+    assert wide(*wargs, None, None) == 0
     assert l.mrec_sparse_apply_workspace_bytes(10, 80, C.byref(out)) == 0
 
 
 def test_an_apply_that_never_ran_leaves_nothing_armed():
-    """ops arms the apply (mrec_sparse_apply_next_max_norm) right before calling it; when the call is refused before it reaches the
-    library -- here ctypes rejects its arguments -- the arm is taken back, so the next apply of the thread is not clipped."""
+    """max_norm travels in the refused call's own arguments: when a call is refused before it reaches the library -- here ctypes
+    rejects its arguments -- or by the library, the next apply of the thread is not clipped."""
     from mindrec_amd import _lib, ops
     l = _lib.lib()
-    plain = (None, None, None, 10, 80, 78, None, None, None, None, 0, None, 80, None, 1e-3, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0, None, 0,
-             None)
+    plain = (None, None, None, 10, 80, 78, None, None, None, None, 0, None, 80, None, 1e-3, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0, None, 0)
+    rec = C.byref(ops.ApplyOpts(max_norm=0.5))
     with pytest.raises(C.ArgumentError):
-        ops._call_clipped(0.5, "mrec_sparse_lazy_adam_f32_i32", *plain[:-1], object())
-    assert l.mrec_sparse_lazy_adam_f32_i32(*plain) == 0      # not armed: D = 78 is fine without max_norm (armed: EUNSUPPORTED)
-    with pytest.raises(_lib.MrecError):
-        ops._call_clipped(0.5, "mrec_sparse_lazy_adam_f32_i32", *plain)      # armed, refused by the library, which disarms
-    assert l.mrec_sparse_lazy_adam_f32_i32(*plain) == 0
+        _lib.call("mrec_sparse_lazy_adam_f32_i32", *plain, rec, object())
+    assert l.mrec_sparse_lazy_adam_f32_i32(*plain, None, None) == 0      # D = 78 is fine without max_norm (with it: EUNSUPPORTED)
+    with pytest.raises(_lib.MrecError) as e:
+        _lib.call("mrec_sparse_lazy_adam_f32_i32", *plain, rec, None)     # refused by the library
+    assert e.value.code == EUNSUPPORTED
+    assert l.mrec_sparse_lazy_adam_f32_i32(*plain, None, None) == 0
 
 
 @pytest.mark.parametrize("over,what", [(dict(host_cache_rows=1000), "host_cache_rows"), (dict(sparse=False), "sparse=False"),

@@ -1,6 +1,6 @@
-"""The multi-hot entry points (mrec_gather_pool, mrec_sparse_apply_next_pool) on a machine without a GPU: declared, exported and
-bound; argument errors come back before any HIP call (null pointers everywhere); a refused arm leaves nothing armed; the Python
-wrappers refuse CPU tensors."""
+"""The multi-hot entry points (mrec_gather_pool, the pool member of mrec_apply_opts_t) on a machine without a GPU: declared, exported
+and bound; argument errors come back before any HIP call (null pointers everywhere); a refused record changes nothing for the call
+after it; the Python wrappers refuse CPU tensors."""
 import ctypes as C
 import os
 import re
@@ -9,7 +9,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = -1, -3
-NEW = ("mrec_gather_pool", "mrec_sparse_apply_next_pool")
+NEW = ("mrec_gather_pool",)
 
 
 def test_new_symbols_declared_exported_and_bound():
@@ -21,7 +21,7 @@ def test_new_symbols_declared_exported_and_bound():
         assert name in declared, f"{name} is not declared in include/mrec.h"
         assert name in _lib.EXPORTED, f"{name} is not in the binding table"
         assert getattr(l, name).argtypes is not None
-    assert "MREC_POOL_MAX_BAG 4096" in text
+    assert "MREC_POOL_MAX_BAG 4096" in text and "int32_t pool;" in text and "} mrec_apply_opts_t;" in text
 
 
 def _pool(l, V=10, ld=8, D=8, id_bytes=4, B=5, L=3, mode=1, out_kind=0, ldo=0):
@@ -47,26 +47,35 @@ def test_gather_pool_argument_errors_before_any_hip_call():
     assert _pool(l) == EINVAL                    # null pointers
 
 
-def test_next_pool_refuses_and_leaves_nothing_armed():
-    """(0) and (-1) are MREC_EINVAL and disarm; what 'armed' means is visible without a GPU: an armed segment sum over n * L >= 2^32
-    positions is refused as unsupported before it looks at its (null) pointers, a plain one gets as far as the pointers."""
-    from mindrec_amd import _lib
-    l = _lib.lib()
-    n = 1 << 30
+def _rec(**members):
+    from mindrec_amd import ops
+    return C.byref(ops.ApplyOpts(**members))
 
-    def seg():
-        return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, 1.0, 4, None, None, 0, None)
+
+def test_next_pool_refuses_and_leaves_nothing_armed():
+    """pool = 0 and -1 are MREC_EINVAL; what the pooled form means is visible without a GPU: a pooled segment sum over n * L >= 2^32
+    positions is refused as unsupported before it looks at its (null) pointers, a plain one gets as far as the pointers -- and the
+    same call with opts = NULL right afterwards is the plain call: nothing travels from one call to the next."""
+    from mindrec_amd import _lib, ops
+    l = _lib.lib()
+
+    def seg(opts=None, n=1 << 30):
+        return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, 1.0, 4, None, None, 0, opts, None)
 
     assert seg() == EINVAL                                         # plain: null pointers
-    assert l.mrec_sparse_apply_next_pool(4) == 0
-    assert seg() == EUNSUPPORTED                                   # armed: n * L = 2^32
+    assert seg(_rec(pool=4)) == EUNSUPPORTED                       # pooled: n * L = 2^32
     assert seg() == EINVAL                                         # ... for that one call
+    assert seg(n=0) == 0                                           # (nothing to do: a call that only a bad record can fail)
     for bad in (0, -1):
-        assert l.mrec_sparse_apply_next_pool(4) == 0
-        assert l.mrec_sparse_apply_next_pool(bad) == EINVAL
-        assert seg() == EINVAL                                     # nothing armed
-    assert l.mrec_sparse_apply_next_pool(1) == 0                   # L = 1 is the plain apply
-    assert seg() == EINVAL
+        assert seg(_rec(pool=bad), n=0) == EINVAL
+        assert seg(_rec(pool=bad)) == EINVAL
+        assert seg() == EINVAL and seg(n=0) == 0                   # the plain call after it
+    assert seg(_rec(pool=1)) == EINVAL and seg(_rec(pool=1), n=0) == 0      # L = 1 is the plain apply
+    rec = ops.ApplyOpts(pool=4)
+    for wrong in (0, 4, C.sizeof(ops.ApplyOpts) - 8, C.sizeof(ops.ApplyOpts) + 8):
+        rec.struct_bytes = wrong
+        assert seg(C.byref(rec), n=0) == EINVAL, wrong             # a record of another size is not read at all
+    assert seg() == EINVAL and seg(n=0) == 0
 
 
 def test_next_pool_refused_for_the_folded_wide_apply_and_max_norm():
@@ -77,29 +86,26 @@ def test_next_pool_refused_for_the_folded_wide_apply_and_max_norm():
              None, 1, 2, 4, 5e-2, 1e-8, 1e-8, -0.5, None, 0, None, None)
     fin = (C.c_ubyte * 448)()
 
-    def wide():
-        return l.mrec_sparse_lazy_adam_wide(*wargs, None)
+    def wide(opts=None):
+        return l.mrec_sparse_lazy_adam_wide(*wargs, opts, None)
 
-    def defer():
-        return l.mrec_sparse_lazy_adam_wide_defer(*wargs, C.cast(fin, C.c_void_p), None)
+    def defer(opts=None):
+        return l.mrec_sparse_lazy_adam_wide_defer(*wargs, C.cast(fin, C.c_void_p), opts, None)
 
-    def adam():
+    def adam(opts=None):
         return l.mrec_sparse_lazy_adam_f32_i32(None, None, None, 10, 4, 4, None, None, None, None, 16, None, 4, None, 1e-3, 0.9, 0.999, 1e-8,
-                                               0.9, 0.999, 1.0, 0, None, 0, None)
+                                               0.9, 0.999, 1.0, 0, None, 0, opts, None)
 
     def seg():
-        return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, 1.0, 4, None, None, 0, None)
+        return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, 1.0, 4, None, None, 0, None, None)
 
     plain = (wide(), defer(), adam())
     assert EUNSUPPORTED not in plain
     for call in (wide, defer):
-        assert l.mrec_sparse_apply_next_pool(2) == 0
-        assert call() == EUNSUPPORTED
-        assert seg() == EINVAL                                     # disarmed by the refusal
-    assert l.mrec_sparse_apply_next_pool(2) == 0
-    assert l.mrec_sparse_apply_next_max_norm(1.0) == 0
-    assert adam() == EUNSUPPORTED                                  # max_norm and pool together
-    assert seg() == EINVAL and (wide(), defer(), adam()) == plain  # ... disarms both
+        assert call(_rec(pool=2)) == EUNSUPPORTED
+        assert seg() == EINVAL                                     # the call after the refusal is plain
+    assert adam(_rec(pool=2, max_norm=1.0)) == EUNSUPPORTED        # max_norm and pool together
+    assert seg() == EINVAL and (wide(), defer(), adam()) == plain  # ... and plain calls after it
 
 
 def test_cpu_tensors_refused():

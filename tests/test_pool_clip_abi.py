@@ -1,6 +1,6 @@
-"""max_norm over multi-hot fields (mrec_gather_pool_fields_clip, mrec_gather_pool_fields_keyed_clip,
-mrec_sparse_apply_next_pool_fields_clip) on a machine without a GPU: declared, exported and bound; argument errors and the float4
-limits come back before any HIP call (null device pointers everywhere); a refused or invalid arm leaves nothing armed; the clip arm is
+"""max_norm over multi-hot fields (mrec_gather_pool_fields_clip, mrec_gather_pool_fields_keyed_clip, max_norm beside the fields form in
+mrec_apply_opts_t) on a machine without a GPU: declared, exported and bound; argument errors and the float4 limits come back before any
+HIP call (null device pointers everywhere); a refused or invalid record changes nothing for the call after it; the pooled clip is
 refused by everything that is not a plain LazyAdam apply; the Python wrappers and the three classes check max_norm on the host."""
 import ctypes as C
 import os
@@ -10,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = -1, -3
-NEW = ("mrec_gather_pool_fields_clip", "mrec_gather_pool_fields_keyed_clip", "mrec_sparse_apply_next_pool_fields_clip")
+NEW = ("mrec_gather_pool_fields_clip", "mrec_gather_pool_fields_keyed_clip")
 MAX_FIELDS, MAX_BAG = 64, 4096
 BAD_NORMS = (0.0, -1.0, float("inf"), float("nan"))
 
@@ -33,10 +33,10 @@ def test_new_symbols_declared_exported_and_bound():
         assert name in _lib.EXPORTED, f"{name} is not in the binding table"
         assert getattr(l, name).argtypes is not None
     # the existing argument lists plus `float max_norm` before `stream`
-    for name in NEW[:2]:
+    for name in NEW:
         plain = getattr(l, name[: -len("_clip")]).argtypes
         assert list(getattr(l, name).argtypes) == list(plain[:-1]) + [C.c_float] + list(plain[-1:])
-    assert list(getattr(l, NEW[2]).argtypes) == list(l.mrec_sparse_apply_next_pool_fields.argtypes) + [C.c_float]
+    assert "float max_norm;" in text and "} mrec_apply_opts_t;" in text      # the apply's clip: a member of the options record
 
 
 def _poolc(l, V=10, ld=8, D=8, id_bytes=4, B=5, lens=(3, 5, 4), F=None, mode=1, out_kind=0, ldo=0, c=0.5):
@@ -83,131 +83,126 @@ def test_clip_lookups_argument_errors_before_any_hip_call(call):
         assert call(l, sigma=float("nan")) == EINVAL and call(l, fill=float("inf")) == EINVAL
 
 
-def _seg(l, n=1 << 30, gs=1.0):
-    return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, gs, 4, None, None, 0, None)
-
-
-def _adam(l, D=4, n=16, gs=1.0):      # (ld = ldg = D)
-    return l.mrec_sparse_lazy_adam_f32_i32(None, None, None, 10, D, D, None, None, None, None, n, None, D, None, 1e-3, 0.9, 0.999, 1e-8,
-                                           0.9, 0.999, gs, 0, None, 0, None)
-
-
-def _ftrl(l):
-    return l.mrec_sparse_ftrl_f32_i32(None, None, None, 10, 4, 4, None, None, None, None, 16, None, 4, None, 5e-2, 1e-8, 1e-8, -0.5, 1.0,
-                                      None, 0, None)
-
-
 LENS, SC = (1, 2, 1), (1.0, 0.5, 1.0)                                 # Ls = 4: n = 2^30 positions are n * Ls = 2^32
 
 
-def _arm(l, c=0.5, F=3, lens=LENS, sc=SC):
-    return l.mrec_sparse_apply_next_pool_fields_clip(F, _i32(lens) if lens is not None else None, _f32(sc) if sc is not None else None, c)
+def _rec(c=0.5, F=3, lens=LENS, sc=SC, **members):
+    """the record of a pooled apply under the clip, by reference"""
+    from mindrec_amd import ops
+    return C.byref(ops.ApplyOpts(n_fields=F, field_len=_i32(lens) if lens is not None else None,
+                                 field_scale=_f32(sc) if sc is not None else None, max_norm=c, **members))
+
+
+def _seg(l, opts=None, n=1 << 30, gs=1.0):
+    return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, gs, 4, None, None, 0, opts, None)
+
+
+def _adam(l, opts=None, D=4, n=16, gs=1.0):      # (ld = ldg = D)
+    return l.mrec_sparse_lazy_adam_f32_i32(None, None, None, 10, D, D, None, None, None, None, n, None, D, None, 1e-3, 0.9, 0.999, 1e-8,
+                                           0.9, 0.999, gs, 0, None, 0, opts, None)
+
+
+def _ftrl(l, opts=None, n=16):
+    return l.mrec_sparse_ftrl_f32_i32(None, None, None, 10, 4, 4, None, None, None, None, n, None, 4, None, 5e-2, 1e-8, 1e-8, -0.5, 1.0,
+                                      None, 0, opts, None)
 
 
 def test_clip_arm_is_for_one_call():
-    """What 'armed' means is visible without a GPU: a segment sum refuses the clip arm as unsupported before it looks at its (null)
-    pointers (an armed segment sum over n * Ls >= 2^32 positions is refused either way); a plain one gets as far as the pointers."""
+    """What the pooled clip means is visible without a GPU: a segment sum refuses it as unsupported before it looks at its (null)
+    pointers (a pooled segment sum over n * Ls >= 2^32 positions is refused either way); a plain one gets as far as the pointers."""
     from mindrec_amd import _lib
     l = _lib.lib()
     assert _seg(l) == EINVAL                                          # plain: null pointers
-    assert _arm(l) == 0
-    assert _seg(l) == EUNSUPPORTED                                    # armed
+    assert _seg(l, _rec()) == EUNSUPPORTED                            # with the record
+    assert _seg(l, _rec(), n=0) == EUNSUPPORTED and _seg(l, n=0) == 0
     assert _seg(l) == EINVAL                                          # ... for that one call
-    assert _arm(l) == 0
-    assert _adam(l) == EINVAL                                         # a LazyAdam apply takes the arm (and stops at its null pointers)
+    assert _adam(l, _rec()) == EINVAL                                 # a LazyAdam apply takes it (and stops at its null pointers)
+    assert _adam(l, _rec(), n=0) == 0
     assert _seg(l) == EINVAL
-    assert _arm(l) == 0
-    assert _adam(l, gs=0.5) == EINVAL and _seg(l) == EINVAL           # grad_scale must be 1: refused, and disarmed
-    assert _arm(l, F=1, lens=(4,), sc=(0.25,)) == 0                   # F = 1 with field_scale = {grad_scale}: the equal-length case
-    assert _seg(l) == EUNSUPPORTED and _seg(l) == EINVAL
+    assert _adam(l, _rec(), gs=0.5) == EINVAL and _adam(l, _rec(), gs=0.5, n=0) == EINVAL      # grad_scale must be 1
+    assert _adam(l, n=0, gs=0.5) == 0 and _seg(l) == EINVAL           # ... and the plain call after it
+    one = dict(F=1, lens=(4,), sc=(0.25,))                            # F = 1 with field_scale = {grad_scale}: the equal-length case
+    assert _adam(l, _rec(**one), n=0) == 0
+    assert _seg(l, _rec(**one)) == EUNSUPPORTED and _seg(l) == EINVAL
 
 
 def test_clip_arm_errors_leave_nothing_armed():
     from mindrec_amd import _lib
     l = _lib.lib()
-    bad = [dict(c=c) for c in BAD_NORMS] + [dict(F=0), dict(F=-2), dict(lens=None), dict(sc=None), dict(lens=(1, 0, 1)),
-                                            dict(sc=(1.0, float("nan"), 1.0)), dict(sc=(1.0, float("inf"), 1.0))]
+    # (max_norm = 0.0, an error of the old arming entry, is the record's "none": the fields form without a clip -- last lines)
+    bad = [dict(c=c) for c in BAD_NORMS if c != 0.0] + [dict(F=0), dict(F=-2), dict(lens=None), dict(sc=None), dict(lens=(1, 0, 1)),
+                                                        dict(sc=(1.0, float("nan"), 1.0)), dict(sc=(1.0, float("inf"), 1.0))]
     for kw in bad:
-        assert _arm(l) == 0
-        assert _arm(l, **kw) == EINVAL, kw
-        assert _seg(l) == EINVAL, kw                                  # nothing armed: the earlier arm is gone too
-        assert l.mrec_sparse_apply_next_pool_fields(3, _i32(LENS), _f32(SC)) == 0
-        assert _arm(l, **kw) == EINVAL, kw                            # ... and so is an earlier arm of the plain fields form
-        assert _seg(l) == EINVAL, kw
-    assert _arm(l) == 0
-    assert _arm(l, F=2, lens=(MAX_BAG, 1), sc=(1.0, 1.0)) == EUNSUPPORTED
-    assert _seg(l) == EINVAL
-    assert _arm(l) == 0
-    assert _arm(l, F=MAX_FIELDS + 1, lens=(1,) * (MAX_FIELDS + 1), sc=(1.0,) * (MAX_FIELDS + 1)) == EUNSUPPORTED
-    assert _seg(l) == EINVAL
+        assert _adam(l, _rec(**kw), n=0) == EINVAL, kw                # answered first, whatever else the call holds
+        assert _seg(l, _rec(**kw), n=0) == EINVAL, kw                 # ... before the entry is asked whether it takes a clip at all
+        assert _seg(l) == EINVAL and _adam(l, n=0) == 0, kw           # the plain calls after it
+        assert _seg(l, _rec(**dict(kw, c=kw.get("c", 0.0))), n=0) == EINVAL, kw      # ... and the same error without the clip
+    assert _adam(l, _rec(F=2, lens=(MAX_BAG, 1), sc=(1.0, 1.0)), n=0) == EUNSUPPORTED
+    assert _adam(l, n=0) == 0
+    assert _adam(l, _rec(F=MAX_FIELDS + 1, lens=(1,) * (MAX_FIELDS + 1), sc=(1.0,) * (MAX_FIELDS + 1)), n=0) == EUNSUPPORTED
+    assert _adam(l, n=0) == 0
+    # the plain max_norm of a LazyAdam apply: the same four bounds
+    from mindrec_amd import ops
+    for c in BAD_NORMS:
+        rc = _adam(l, C.byref(ops.ApplyOpts(max_norm=c)), n=0)
+        assert rc == (0 if c == 0.0 else EINVAL), c
+    assert _ftrl(l, _rec(c=0.0), n=0) == 0 and _ftrl(l, _rec(c=0.5), n=0) == EUNSUPPORTED      # 0.0: no clip, FTRL takes the fields form
 
 
 def test_the_pooled_arms_replace_each_other():
-    from mindrec_amd import _lib
+    """one record, one form: the clip is a member beside the fields form, so a record without it is the plain pooled apply (FTRL
+    refuses the pooled clip, and runs into its null pointers under a plain pooled form), and pool = L takes no clip"""
+    from mindrec_amd import _lib, ops
     l = _lib.lib()
-    # the clip arm, then a plain pooled arm: the clip is gone (FTRL refuses a clip arm, and runs into its null pointers under a plain one)
-    assert _arm(l) == 0
-    assert l.mrec_sparse_apply_next_pool_fields(3, _i32(LENS), _f32(SC)) == 0
-    assert _ftrl(l) == EINVAL
-    assert _arm(l) == 0
-    assert l.mrec_sparse_apply_next_pool(4) == 0
-    assert _ftrl(l) == EINVAL
-    assert _arm(l) == 0
-    assert l.mrec_sparse_apply_next_pool(1) == 0                      # the plain apply: disarms
-    assert _seg(l) == EINVAL
-    # a plain pooled arm, then the clip arm: the clip arm holds
-    assert l.mrec_sparse_apply_next_pool(4) == 0
-    assert _arm(l) == 0
-    assert _ftrl(l) == EUNSUPPORTED
-    assert _ftrl(l) == EINVAL
+    assert _ftrl(l, _rec()) == EUNSUPPORTED
+    assert _ftrl(l, _rec(c=0.0)) == EINVAL and _ftrl(l, _rec(c=0.0), n=0) == 0
+    assert _ftrl(l, C.byref(ops.ApplyOpts(pool=4))) == EINVAL and _ftrl(l, C.byref(ops.ApplyOpts(pool=4)), n=0) == 0
+    assert _ftrl(l, C.byref(ops.ApplyOpts(pool=4, max_norm=0.5)), n=0) == EUNSUPPORTED
+    assert _adam(l, C.byref(ops.ApplyOpts(pool=4, max_norm=0.5)), n=0) == EUNSUPPORTED
+    assert _ftrl(l, _rec(pool=4), n=0) == EINVAL                      # pool = L and the fields form in one record
+    assert _seg(l, C.byref(ops.ApplyOpts(pool=1))) == EINVAL          # pool = 1: the plain apply
+    assert _ftrl(l) == EINVAL and _ftrl(l, n=0) == 0
 
 
 def test_clip_arm_refused_by_everything_but_the_plain_lazy_adam_apply():
-    from mindrec_amd import _lib
+    from mindrec_amd import _lib, ops
     l = _lib.lib()
     wargs = (None, None, None, 10, 8, 4, None, 4, None, None, None, 16, None, 0, 4, None, 1e-3, 0.9, 0.999, 1e-8, 0.9, 0.999, 1.0, 0,
              None, 1, 2, 4, 5e-2, 1e-8, 1e-8, -0.5, None, 0, None, None)
     fin = (C.c_ubyte * 448)()
 
-    def wide():
-        return l.mrec_sparse_lazy_adam_wide(*wargs, None)
+    def wide(opts=None):
+        return l.mrec_sparse_lazy_adam_wide(*wargs, opts, None)
 
-    def defer():
-        return l.mrec_sparse_lazy_adam_wide_defer(*wargs, C.cast(fin, C.c_void_p), None)
+    def defer(opts=None):
+        return l.mrec_sparse_lazy_adam_wide_defer(*wargs, C.cast(fin, C.c_void_p), opts, None)
 
-    def seg():
-        return _seg(l, n=16)
+    def seg(opts=None):
+        return _seg(l, opts, n=16)
 
-    def ftrl():
-        return _ftrl(l)
+    def ftrl(opts=None):
+        return _ftrl(l, opts)
 
-    def adam():
-        return _adam(l)
+    def adam(opts=None):
+        return _adam(l, opts)
 
     calls = (wide, defer, seg, ftrl, adam)
     plain = tuple(f() for f in calls)
     assert EUNSUPPORTED not in plain
     for f in (wide, defer, seg, ftrl):                                # the folded wide forms, a segment sum, an FTRL apply
-        assert _arm(l) == 0
-        assert f() == EUNSUPPORTED, f.__name__
-        assert tuple(g() for g in calls) == plain, f.__name__         # disarmed by the refusal: every call after it is plain
-    # widths the clip cannot run at: refused by the armed call, before it looks at its pointers
+        assert f(_rec()) == EUNSUPPORTED, f.__name__
+        assert tuple(g() for g in calls) == plain, f.__name__         # every call after the refusal is plain
+    # widths the clip cannot run at: refused before the call looks at its pointers
     for D in (6, 260):
         assert _adam(l, D=D) == EINVAL                                # plain: null pointers
-        assert _arm(l) == 0
-        assert _adam(l, D=D) == EUNSUPPORTED
+        assert _adam(l, _rec(), D=D) == EUNSUPPORTED
         assert _adam(l, D=D) == EINVAL and tuple(g() for g in calls) == plain
-    assert _arm(l) == 0 and _adam(l, D=256) == EINVAL                 # the widest row is supported
-    # a separately armed max_norm on top of it: refused like today, and both are disarmed
-    assert _arm(l) == 0
-    assert l.mrec_sparse_apply_next_max_norm(1.0) == 0
-    assert adam() == EUNSUPPORTED
+    assert _adam(l, _rec(), D=256) == EINVAL                          # the widest row is supported
+    # the plain max_norm: LazyAdam entries only, and not beside pool = L
+    for f in (seg, ftrl):
+        assert f(C.byref(ops.ApplyOpts(max_norm=1.0))) == EUNSUPPORTED, f.__name__
+    assert adam(C.byref(ops.ApplyOpts(max_norm=1.0, pool=4))) == EUNSUPPORTED
     assert _seg(l) == EINVAL and tuple(g() for g in calls) == plain
-    # ... and the old combination is what it was
-    assert l.mrec_sparse_apply_next_pool_fields(3, _i32(LENS), _f32(SC)) == 0
-    assert l.mrec_sparse_apply_next_max_norm(1.0) == 0
-    assert adam() == EUNSUPPORTED
-    assert tuple(g() for g in calls) == plain
 
 
 def test_python_wrappers_check_max_norm_on_the_host():
@@ -230,13 +225,18 @@ def test_python_wrappers_check_max_norm_on_the_host():
             ops._pooled(Plan, None, (3, 5, 4), None, 1.0, c)
     with pytest.raises(ValueError):
         ops._pooled(Plan, None, None, None, 1.0, 0.5)                 # pool_max_norm goes with pool= or fields=
-    arm, rows, gs = ops._pooled(Plan, None, (3, 5, 4), (1.0, 0.5, 0.25), 1.0, 0.5)
-    assert arm[0] == "mrec_sparse_apply_next_pool_fields_clip" and arm[1] == 3 and arm[4] == 0.5 and rows[0] == 6 and gs == 1.0
-    arm, rows, gs = ops._pooled(Plan, 4, None, None, 0.25, 0.5)       # pool=L: F = 1, field_scale = {grad_scale}
-    assert arm[0] == "mrec_sparse_apply_next_pool_fields_clip" and arm[1] == 1 and list(arm[2]) == [4] and list(arm[3]) == [0.25]
+    rec, rows, gs = ops._pooled(Plan, None, (3, 5, 4), (1.0, 0.5, 0.25), 1.0, 0.5)
+    assert (rec.struct_bytes, rec.pool, rec.n_fields, rec.max_norm) == (C.sizeof(ops.ApplyOpts), 1, 3, 0.5) and rows[0] == 6 and gs == 1.0
+    assert rec.field_len[:3] == [3, 5, 4] and rec.field_scale[:3] == [1.0, 0.5, 0.25] and not rec.const_state and not rec.const_ids
+    rec, rows, gs = ops._pooled(Plan, 4, None, None, 0.25, 0.5)       # pool=L: F = 1, field_scale = {grad_scale}
+    assert (rec.pool, rec.n_fields, rec.max_norm) == (1, 1, 0.5) and rec.field_len[:1] == [4] and rec.field_scale[:1] == [0.25]
     assert rows[0] == 6 and gs == 1.0
-    assert ops._pooled(Plan, 4, None, None, 0.25)[0] == ("mrec_sparse_apply_next_pool", 4)      # without it: today's arms
-    assert ops._pooled(Plan, None, (3, 5, 4), None, 1.0)[0][0] == "mrec_sparse_apply_next_pool_fields"
+    rec, rows, gs = ops._pooled(Plan, 4, None, None, 0.25)            # without it: pool = L, scaled by the call's grad_scale
+    assert (rec.pool, rec.n_fields, rec.max_norm, bool(rec.field_len), bool(rec.field_scale)) == (4, 0, 0.0, False, False)
+    assert rows[0] == 6 and gs == 0.25
+    rec, rows, gs = ops._pooled(Plan, None, (3, 5, 4), None, 1.0)
+    assert (rec.pool, rec.n_fields, rec.max_norm) == (1, 3, 0.0) and rec.field_len[:3] == [3, 5, 4] and rec.field_scale[:3] == [1.0] * 3
+    assert ops._pooled(Plan, None, None, None, 0.5) == (None, None, 0.5)      # the plain apply: no record
     # the classes: everything about max_norm is checked before the device
     for opt in ("ftrl", "adam"):
         with pytest.raises(ValueError, match="max_norm"):

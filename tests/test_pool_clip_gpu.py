@@ -1,5 +1,5 @@
 """max_norm over multi-hot fields on the GPU: the clip instantiations of the pooled lookups (mrec_gather_pool_fields_clip,
-mrec_gather_pool_fields_keyed_clip), the pooled apply under the clip (mrec_sparse_apply_next_pool_fields_clip) and max_norm on
+mrec_gather_pool_fields_keyed_clip), the pooled apply under the clip (mrec_apply_opts_t's fields form with max_norm) and max_norm on
 MultiHotEmbedding, MultiHotWideDeep and MultiHotHashEmbedding.
 
   lookup: bit for bit against ops.gather_rows(max_norm=c) -- an existing, separately tested kernel -- pooled on the host
@@ -9,7 +9,7 @@ MultiHotEmbedding, MultiHotWideDeep and MultiHotHashEmbedding.
     test_max_norm_gpu.py::test_sparse_lazy_adam_clip_matches_oracle; one clip decision per row in the forward and the backward;
   classes: against the ops calls, eager and captured; the wide half untouched by the clip; the hash table against MapTensorGet rows
     and against the dense sibling;
-  refusals: nothing is launched, nothing stays armed.
+  refusals: nothing is launched, and the call after one is the plain call.
 Tables hold a zero row, a row of norm exactly c and rows within a few ulps of c; ids include -1 and V."""
 import os
 import sys
@@ -479,9 +479,10 @@ def test_widths_the_clip_cannot_run_at_are_refused(dev, D):
         MultiHotEmbedding(50, D, lens, device=dev, max_norm=C)
 
 
-def test_clip_arm_refusals_launch_nothing_and_disarm(dev):
-    """an FTRL apply and the folded wide forms under the clip arm, invalid max_norm values, and the old max_norm= + fields=
-    combination: tables untouched, and the next plain call is the never-armed call"""
+def test_clip_arm_refusals_launch_nothing_and_disarm(dev, monkeypatch):
+    """an FTRL apply, a segment sum and the folded wide forms under the pooled clip's record, invalid max_norm values, and the old
+    max_norm= + fields= combination: tables untouched, and the next plain call is the plain call.  ops gives these calls no such
+    record: they are handed it (mrec_apply_opts_t) here."""
     from mindrec_amd import _lib, ops
     import ctypes
     lens, D = (3, 5, 4), 64
@@ -489,8 +490,11 @@ def test_clip_arm_refusals_launch_nothing_and_disarm(dev):
     F = len(lens)
     n = plan.n
 
-    def arm(c=C):
-        _lib.call("mrec_sparse_apply_next_pool_fields_clip", F, (ctypes.c_int32 * F)(*lens), (ctypes.c_float * F)(1.0, 1.0, 1.0), c)
+    def clipped(fn, *args, c=C, **kwargs):
+        rec = ops.ApplyOpts(n_fields=F, field_len=(ctypes.c_int32 * F)(*lens), field_scale=(ctypes.c_float * F)(1.0, 1.0, 1.0), max_norm=c)
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, "_opts_ptr", lambda _: ctypes.byref(rec))
+            return fn(*args, **kwargs)
 
     never = [T(a, dev) for a in st]
     ops.sparse_lazy_adam_(*never, plan, tgb)
@@ -504,17 +508,15 @@ def test_clip_arm_refusals_launch_nothing_and_disarm(dev):
     fnever = [T(a, dev) for a in fst]
     ops.sparse_ftrl_(*fnever, plan, tgb)
     ts = [T(a, dev) for a in fst]
-    arm()
     with pytest.raises(_lib.MrecError) as e:
-        ops.sparse_ftrl_(*ts, plan, tgb)
+        clipped(ops.sparse_ftrl_, *ts, plan, tgb)
     assert e.value.code == -3
     _untouched(ts, fst)
     ops.sparse_ftrl_(*ts, plan, tgb)
     _same_t(ts, fnever, "the next plain FTRL call")
     # a segment sum
-    arm()
     with pytest.raises(_lib.MrecError) as e:
-        ops.segment_sum(plan, tgb)
+        clipped(ops.segment_sum, plan, tgb)
     assert e.value.code == -3
     plain_is_plain([T(a, dev) for a in st])
     # the folded wide apply (fused rows [p | w accum linear pad | m | v | pad]), launched and deferred
@@ -534,9 +536,8 @@ def test_clip_arm_refusals_launch_nothing_and_disarm(dev):
     wide(wnever)
     for defer in (False, True):
         tb = T(buf, dev)
-        arm()
         with pytest.raises(_lib.MrecError) as e:
-            wide(tb, defer=defer)
+            clipped(wide, tb, defer=defer)
         assert e.value.code == -3
         _untouched([tb], [buf])
         wide(tb)                                                           # plain again
@@ -548,9 +549,10 @@ def test_clip_arm_refusals_launch_nothing_and_disarm(dev):
             ops.sparse_lazy_adam_(*ts, plan, tgs, fields=lens, pool_max_norm=c)
         with pytest.raises(ValueError):
             ops.gather_pool_fields(ts[0], ids, lens, max_norm=c)
-        with pytest.raises(_lib.MrecError) as e:
-            arm(c)
-        assert e.value.code == -1
+        if c != 0.0:                                                       # (in the record itself, 0.0 is "no clip")
+            with pytest.raises(_lib.MrecError) as e:
+                clipped(ops.sparse_lazy_adam_, *ts, plan, tgs, fields=lens, c=c)
+            assert e.value.code == -1
         _untouched(ts, st)
         plain_is_plain(ts)
     # the old combination: max_norm= with fields=, still MREC_EUNSUPPORTED

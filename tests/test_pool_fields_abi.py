@@ -1,6 +1,7 @@
-"""The fields form of the multi-hot entry points (mrec_gather_pool_fields, mrec_sparse_apply_next_pool_fields) on a machine without a
-GPU: declared, exported and bound; argument errors come back before any HIP call (null device pointers everywhere); a refused or
-invalid arm leaves nothing armed; the Python wrappers check the tuple of bag lengths on the host and refuse CPU tensors."""
+"""The fields form of the multi-hot entry points (mrec_gather_pool_fields, the n_fields / field_len / field_scale members of
+mrec_apply_opts_t) on a machine without a GPU: declared, exported and bound; argument errors come back before any HIP call (null device
+pointers everywhere); a refused or invalid record changes nothing for the call after it (nothing is armed: there is no state); the
+Python wrappers check the tuple of bag lengths on the host and refuse CPU tensors."""
 import ctypes as C
 import os
 import re
@@ -9,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = -1, -3
-NEW = ("mrec_gather_pool_fields", "mrec_sparse_apply_next_pool_fields")
+NEW = ("mrec_gather_pool_fields",)
 MAX_FIELDS, MAX_BAG = 64, 4096
 
 
@@ -31,6 +32,8 @@ def test_new_symbols_declared_exported_and_bound():
         assert name in _lib.EXPORTED, f"{name} is not in the binding table"
         assert getattr(l, name).argtypes is not None
     assert f"MREC_POOL_MAX_FIELDS {MAX_FIELDS}" in text and f"MREC_POOL_MAX_BAG {MAX_BAG}" in text
+    for member in ("int32_t n_fields;", "const int32_t* field_len;", "const float* field_scale;", "} mrec_apply_opts_t;"):
+        assert member in text
     assert (ops.MAX_FIELDS, ops.MAX_BAG) == (MAX_FIELDS, MAX_BAG)
 
 
@@ -65,54 +68,64 @@ def test_gather_pool_fields_argument_errors_before_any_hip_call():
     assert l.mrec_gather_pool_fields(None, 10, 8, 8, None, 4, 5, 3, None, None, 1, None, 0, 0, None) == EINVAL      # no lengths
 
 
-def _seg(l, n=1 << 30, gs=1.0):
-    return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, gs, 4, None, None, 0, None)
+def _rec(F, lens, sc, **members):
+    """the record of a fields apply (lens / sc: ctypes arrays or None), by reference"""
+    from mindrec_amd import ops
+    return C.byref(ops.ApplyOpts(n_fields=F, field_len=lens, field_scale=sc, **members))
+
+
+def _seg(l, opts=None, n=1 << 30, gs=1.0):
+    return l.mrec_segment_sum_f32(None, None, None, n, None, 4, None, gs, 4, None, None, 0, opts, None)
 
 
 def test_next_pool_fields_refuses_and_leaves_nothing_armed():
-    """What 'armed' means is visible without a GPU: an armed segment sum over n * Ls >= 2^32 positions is refused as unsupported
-    before it looks at its (null) pointers, a plain one gets as far as the pointers."""
+    """What the fields form means is visible without a GPU: a segment sum with it over n * Ls >= 2^32 positions is refused as
+    unsupported before it looks at its (null) pointers, a plain one gets as far as the pointers; and the call with opts = NULL right
+    after any of them is the plain call."""
     from mindrec_amd import _lib
     l = _lib.lib()
-    arm = l.mrec_sparse_apply_next_pool_fields
     lens, sc = _i32((1, 2, 1)), _f32((1.0, 0.5, 1.0))                # Ls = 4: n * Ls = 2^32
     assert _seg(l) == EINVAL                                         # plain: null pointers
-    assert arm(3, lens, sc) == 0
-    assert _seg(l) == EUNSUPPORTED                                   # armed
+    assert _seg(l, _rec(3, lens, sc)) == EUNSUPPORTED                # the fields form
     assert _seg(l) == EINVAL                                         # ... for that one call
+    assert _seg(l, n=0) == 0                                         # (nothing to do: a call that only a bad record can fail)
     bad = [(0, lens, sc, EINVAL), (-2, lens, sc, EINVAL), (3, None, sc, EINVAL), (3, lens, None, EINVAL),
            (3, _i32((1, 0, 1)), sc, EINVAL), (3, lens, _f32((1.0, float("nan"), 1.0)), EINVAL),
            (3, lens, _f32((1.0, float("inf"), 1.0)), EINVAL), (2, _i32((MAX_BAG, 1)), sc, EUNSUPPORTED),
            (MAX_FIELDS + 1, _i32((1,) * (MAX_FIELDS + 1)), _f32((1.0,) * (MAX_FIELDS + 1)), EUNSUPPORTED)]
     for F, a, b, code in bad:
-        assert arm(3, lens, sc) == 0
-        assert arm(F, a, b) == code
-        assert _seg(l) == EINVAL                                     # nothing armed: the earlier arm is gone too
-    assert arm(MAX_FIELDS, _i32((1,) * MAX_FIELDS), _f32((1.0,) * MAX_FIELDS)) == 0
-    assert _seg(l, n=1 << 26) == EUNSUPPORTED and _seg(l, n=1 << 26) == EINVAL      # Ls = 64: 2^26 * 64 = 2^32
+        assert _seg(l, _rec(F, a, b), n=0) == code                   # the record is answered first, whatever else the call holds
+        assert _seg(l, _rec(F, a, b)) == code
+        assert _seg(l) == EINVAL and _seg(l, n=0) == 0               # the plain call after it
+    big = _rec(MAX_FIELDS, _i32((1,) * MAX_FIELDS), _f32((1.0,) * MAX_FIELDS))
+    assert _seg(l, big, n=1 << 26) == EUNSUPPORTED and _seg(l, n=1 << 26) == EINVAL      # Ls = 64: 2^26 * 64 = 2^32
 
 
 def test_armed_call_takes_grad_scale_one_only():
+    """the fields form has one scale per contribution, the field's: the call's own grad_scale must be 1"""
     from mindrec_amd import _lib
     l = _lib.lib()
     lens, sc = _i32((1, 2, 1)), _f32((1.0, 0.5, 1.0))
-    assert l.mrec_sparse_apply_next_pool_fields(3, lens, sc) == 0
-    assert _seg(l, n=16, gs=0.5) == EINVAL                           # (indistinguishable here from the null pointers, but it must disarm)
+    assert _seg(l, n=0, gs=0.5) == 0
+    assert _seg(l, _rec(3, lens, sc), n=0, gs=0.5) == EINVAL         # refused for its grad_scale, whatever else the call holds
+    assert _seg(l, _rec(3, lens, sc), n=16, gs=0.5) == EINVAL
     assert _seg(l) == EINVAL
-    assert l.mrec_sparse_apply_next_pool_fields(3, lens, sc) == 0
-    assert _seg(l, gs=0.5) == EINVAL                                 # refused for its grad_scale BEFORE the range check ...
-    assert _seg(l) == EINVAL                                         # ... and disarmed
+    assert _seg(l, _rec(3, lens, sc), gs=0.5) == EINVAL              # refused for its grad_scale BEFORE the range check ...
+    assert _seg(l, _rec(3, lens, sc)) == EUNSUPPORTED                # ... which is what the same record meets at grad_scale 1
+    assert _seg(l) == EINVAL and _seg(l, n=0, gs=0.5) == 0           # the plain call after it
 
 
 def test_the_two_pooled_arms_replace_each_other():
+    """pool = L and the fields form are two forms of the same thing: a record holds one of them"""
     from mindrec_amd import _lib
     l = _lib.lib()
     lens, sc = _i32((1, 2, 1)), _f32((1.0, 0.5, 1.0))
-    assert l.mrec_sparse_apply_next_pool_fields(3, lens, sc) == 0
-    assert l.mrec_sparse_apply_next_pool(1) == 0                     # the plain apply: disarms the fields form
-    assert _seg(l) == EINVAL
-    assert l.mrec_sparse_apply_next_pool(4) == 0
-    assert l.mrec_sparse_apply_next_pool_fields(1, _i32((1,)), _f32((1.0,))) == 0      # Ls = 1: in range where pool = 4 is not
+    assert _seg(l, _rec(3, lens, sc, pool=4), n=0) == EINVAL         # both
+    assert _seg(l, _rec(3, lens, sc, pool=1), n=0) == 0              # pool = 1 is no pool: the fields form alone
+    assert _seg(l, _rec(0, None, None, pool=1)) == EINVAL            # neither: the plain apply (null pointers)
+    assert _seg(l, _rec(0, None, None, pool=1), n=0) == 0
+    assert _seg(l, _rec(0, None, None, pool=4)) == EUNSUPPORTED      # pool = 4: out of range at n = 2^30 ...
+    assert _seg(l, _rec(1, _i32((1,)), _f32((1.0,)))) == EINVAL      # ... where Ls = 1 is in range (null pointers)
     assert _seg(l) == EINVAL and _seg(l) == EINVAL
 
 
@@ -124,27 +137,28 @@ def test_next_pool_fields_refused_for_the_folded_wide_apply_and_max_norm():
     fin = (C.c_ubyte * 448)()
     lens, sc = _i32((1, 2, 1)), _f32((1.0, 0.5, 1.0))
 
-    def wide():
-        return l.mrec_sparse_lazy_adam_wide(*wargs, None)
+    def wide(opts=None):
+        return l.mrec_sparse_lazy_adam_wide(*wargs, opts, None)
 
-    def defer():
-        return l.mrec_sparse_lazy_adam_wide_defer(*wargs, C.cast(fin, C.c_void_p), None)
+    def defer(opts=None):
+        return l.mrec_sparse_lazy_adam_wide_defer(*wargs, C.cast(fin, C.c_void_p), opts, None)
 
-    def adam():
-        return l.mrec_sparse_lazy_adam_f32_i32(None, None, None, 10, 4, 4, None, None, None, None, 16, None, 4, None, 1e-3, 0.9, 0.999, 1e-8,
-                                               0.9, 0.999, 1.0, 0, None, 0, None)
+    def adam(opts=None, D=4):
+        return l.mrec_sparse_lazy_adam_f32_i32(None, None, None, 10, D, D, None, None, None, None, 16, None, D, None, 1e-3, 0.9, 0.999, 1e-8,
+                                               0.9, 0.999, 1.0, 0, None, 0, opts, None)
 
     plain = (wide(), defer(), adam())
     assert EUNSUPPORTED not in plain
     for call in (wide, defer):
-        assert l.mrec_sparse_apply_next_pool_fields(3, lens, sc) == 0
-        assert call() == EUNSUPPORTED
-        assert _seg(l) == EINVAL                                     # disarmed by the refusal: the call after it is plain
+        assert call(_rec(3, lens, sc)) == EUNSUPPORTED
+        assert _seg(l) == EINVAL                                     # the call after the refusal is plain
         assert call() == plain[0 if call is wide else 1]
-    assert l.mrec_sparse_apply_next_pool_fields(3, lens, sc) == 0
-    assert l.mrec_sparse_apply_next_max_norm(1.0) == 0
-    assert adam() == EUNSUPPORTED                                    # max_norm and fields together
-    assert _seg(l) == EINVAL and (wide(), defer(), adam()) == plain  # ... disarms both
+    # max_norm beside the fields form is the pooled clip (tests/test_pool_clip_abi.py): a LazyAdam apply takes it, at a width the clip
+    # can run at; max_norm beside pool = L is refused
+    assert adam(_rec(3, lens, sc, max_norm=1.0)) == EINVAL           # (null pointers)
+    assert adam(_rec(3, lens, sc, max_norm=1.0), D=6) == EUNSUPPORTED
+    assert adam(_rec(0, None, None, pool=4, max_norm=1.0)) == EUNSUPPORTED
+    assert _seg(l) == EINVAL and (wide(), defer(), adam()) == plain  # ... and plain calls after them
 
 
 def test_fields_tuple_is_checked_on_the_host():

@@ -1,6 +1,6 @@
 """Multi-hot fields of UNEQUAL bag length on the GPU: the fields lookup (mrec_gather_pool_fields) bit for bit against its host
 restatement (tests/_pool_fields_ref.py) and against the one-length kernel field by field; the fields apply
-(mrec_sparse_apply_next_pool_fields) bit for bit against the restated contributions pushed through the apply's order of additions
+(the fields form of mrec_apply_opts_t) bit for bit against the restated contributions pushed through the apply's order of additions
 (tests/_pool_ref.sums), against pool=L where the lengths are equal, and -- independently of every restatement -- against the plain
 apply on the explicitly expanded gradient where the field scales are powers of two; MultiHotEmbedding with a tuple `bag`, eager and
 captured, and the one-update-per-step property the fields form exists for.  Every comparison is on raw bits, over all rows."""

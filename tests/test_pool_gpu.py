@@ -1,5 +1,5 @@
 """Multi-hot fields on the GPU: the pooled lookup (ops.gather_pool, which runs mrec_gather_pool_fields with one field, and the C entry
-mrec_gather_pool itself) bit for bit against its host restatement (tests/_pool_ref.py), the pooled sparse apply (mrec_sparse_apply_next_pool) bit for bit against the restatement of the apply's order of additions (tests/
+mrec_gather_pool itself) bit for bit against its host restatement (tests/_pool_ref.py), the pooled sparse apply (mrec_apply_opts_t.pool) bit for bit against the restatement of the apply's order of additions (tests/
 _apply_order.py) AND against the plain apply on the explicitly expanded gradient, the arming rules, and MultiHotEmbedding's training
 loop, eager and captured.  Every comparison is on raw bits, over all rows (touched and untouched)."""
 import os
@@ -344,10 +344,16 @@ def test_a_pooled_call_arms_one_call_only(dev):
     assert not torch.equal(scratch[0], never[0])
 
 
-def test_refused_combinations_launch_nothing_and_disarm(dev):
-    """pool with max_norm, with constant columns armed, and on the folded wide apply: MREC_EUNSUPPORTED, tables untouched, and the
-    next plain call is the never-armed call"""
+def test_refused_combinations_launch_nothing_and_disarm(dev, monkeypatch):
+    """pool with max_norm, with constant columns, and on the folded wide apply: MREC_EUNSUPPORTED, tables untouched, and the next
+    plain call is the plain call.  ops has no keyword for the last two: the call is handed their record (mrec_apply_opts_t) here."""
+    import ctypes
     from mindrec_amd import _lib, ops
+
+    def with_record(rec, fn, *args, **kwargs):
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, "_opts_ptr", lambda _: ctypes.byref(rec))
+            return fn(*args, **kwargs)
     D, L, F = 64, 8, 8
     V, n, ids, st, tgs, tgb, trs = _arming_case(dev, D, L)
     tid = T(ids, dev)
@@ -373,13 +379,13 @@ def test_refused_combinations_launch_nothing_and_disarm(dev):
     assert e.value.code == -3
     untouched(ts, st)
     plain_is_plain(ts)
-    # constant columns armed
+    # constant columns in the same record
     ts = [T(a, dev) for a in st]
     ids2 = tid.reshape(-1, F).contiguous()
     state = ops.const_cols_detect(ids2, V)
-    _lib.call("mrec_sparse_apply_next_const_cols", ops._ptr(state), ops._ptr(ids2), 4, ids2.shape[0])
+    rec = ops.ApplyOpts(pool=L, const_state=ops._ptr(state), const_ids=ops._ptr(ids2), const_id_bytes=4, const_B=ids2.shape[0])
     with pytest.raises(_lib.MrecError) as e:
-        ops.sparse_lazy_adam_(*ts, plan, tgs, trs, pool=L, **kw)
+        with_record(rec, ops.sparse_lazy_adam_, *ts, plan, tgs, trs, pool=L, **kw)
     assert e.value.code == -3
     untouched(ts, st)
     plain_is_plain(ts)
@@ -398,9 +404,8 @@ def test_refused_combinations_launch_nothing_and_disarm(dev):
     wide(wnever)
     for defer in (False, True):
         tb = T(buf, dev)
-        _lib.call("mrec_sparse_apply_next_pool", L)
         with pytest.raises(_lib.MrecError) as e:
-            wide(tb, defer=defer)
+            with_record(ops.ApplyOpts(pool=L), wide, tb, defer=defer)
         assert e.value.code == -3
         untouched([tb], [buf])
         wide(tb)                                                              # plain again
