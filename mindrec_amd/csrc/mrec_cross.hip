@@ -629,7 +629,8 @@ int launch_fwd(const float* x0, const float* w, const float* b, int L, int64_t B
     int64_t blocks = mrec_cdiv(B, 2 * (FWD_NT / 64));            // 16 waves x 2 rows per pass
     if (blocks > 256) blocks = 256;
     if constexpr (NPL % 4 == 0) {
-        if (lds > 0 && lds <= kMaxLds) {
+        // stage_rows4 holds its pieces in a register array sized for LMAX layers: a deeper stack reads w / b from global memory
+        if (lds > 0 && lds <= kMaxLds && L <= LMAX) {
             int rc = set_lds(k_cross_fwd4<NPL, true>, lds);
             if (rc != MREC_OK) return rc;
             k_cross_fwd4<NPL, true><<<(unsigned)blocks, FWD_NT, lds, st>>>(x0, w, b, L, B, D, out);

@@ -1110,13 +1110,17 @@ def scatter_rows_(table, rows, vals):
 
 
 # ---- DCN-v1 cross layers ---------------------------------------------------------------------
-def cross_layers(x0, w, b):
-    """CrossLayer x L (deep_and_cross.py:139-149, 300-306).  x0 [B,D], w/b [L,D] -> [B,D]."""
-    _need_cuda(x0, w, b)
+def cross_layers(x0, w, b, out=None):
+    """CrossLayer x L (deep_and_cross.py:139-149, 300-306).  x0 [B,D], w/b [L,D] -> [B,D].
+    out: a contiguous float32 tensor of x0's shape to write into (a view of a larger buffer)."""
+    _need_cuda(x0, w, b, out)
     x0 = x0.contiguous(); w = w.contiguous(); b = b.contiguous()
     B, D = x0.shape
     L = w.shape[0]
-    out = torch.empty_like(x0)
+    if out is None:
+        out = torch.empty_like(x0)
+    elif out.shape != x0.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise TypeError("cross_layers: out must be a contiguous float32 tensor of x0's shape")
     _lib.call("mrec_cross_layers_f32", _ptr(x0), _ptr(w), _ptr(b), L, B, D, _ptr(out), _stream())
     return out
 

@@ -472,6 +472,13 @@ def test_cross_layers(dev, oracle, B, D, L):
     scale = np.abs(rdw).max()
     assert np.abs(dw.cpu().numpy() - rdw).max() <= 2e-5 * max(scale, 1) * np.sqrt(B)
     assert np.abs(db.cpu().numpy() - rdb).max() <= 2e-5 * max(np.abs(rdb).max(), 1) * np.sqrt(B)
+    # and to the bar of tests/test_cross_sweep_gpu.py: within 4x of what the same closed form gives in fp32 on the host, both
+    # measured against the float64 gradient
+    import _cross_ref as CR
+    _, *g64 = CR.cross_f64(x0, w, b, dy)
+    for name, got, r64, c32 in zip(("dx0", "dw", "db"), (dx0, dw, db), g64, CR.cross_bwd_closed_f32(x0, w, b, dy)):
+        e, ec = CR.row_rel(got.cpu().numpy(), r64), CR.row_rel(c32, r64)
+        assert e <= max(4 * ec, 16 * 2.0 ** -24), (name, e, ec)
     # dx0 += ...: onto another branch's gradient, the same sum to the bit
     base = rng.standard_normal((B, D)).astype(np.float32)
     acc = T(base, dev)
