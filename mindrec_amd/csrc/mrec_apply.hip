@@ -1204,12 +1204,94 @@ inline int apply_opts(const mrec_apply_opts_t* r, float gscale, bool adam, bool 
 
 struct ApplyWs { float* carry_head; float* carry_tail; int* owners; int* n_owners; float* dummy; float* cpart; };
 
+// THE layout of the apply's workspace: its regions and their element counts for n index entries and rows of D columns (the folded
+// wide form asks with D + 4: its wide lane's columns ride in the carry rows).  The size query runs it over a counting arena, the
+// apply over the caller's bytes -- the size answered is the size consumed, by construction.
+inline ApplyWs apply_ws_carve(MrecArena& a, int64_t n, int32_t D) {
+    if (n < 1) n = 1;
+    const size_t nsw = (size_t)mrec_cdiv(n, AW_MIN);                       // windows, at the narrowest window of any form
+    const size_t nch = (size_t)(mrec_cdiv(n, 64) < kConstLG ? mrec_cdiv(n, 64) : kConstLG);      // the hot columns' 64-sample chunks
+    const size_t Dc = D > 256 ? 256 : D;                                   // columns of one launch pair (apply_impl's column blocks)
+    ApplyWs w;
+    w.carry_head = a.take<float>(nsw * Dc);
+    w.carry_tail = a.take<float>(nsw * Dc);
+    w.owners = a.take<int>(nsw);
+    w.n_owners = a.take<int>(1);
+    w.dummy = a.take<float>(2048 * 16);
+    w.cpart = a.take<float>(nch * kConstMax * Dc);
+    return w;
+}
+
 size_t apply_ws_bytes(int64_t n, int32_t D) {
-    const size_t nsw = (size_t)mrec_cdiv(n ? n : 1, AW_MIN);
-    const int Dc = D > 256 ? 256 : D;
-    const size_t nch = (size_t)mrec_cdiv(n ? n : 1, 64) < (size_t)kConstLG ? (size_t)mrec_cdiv(n ? n : 1, 64) : (size_t)kConstLG;
-    return mrec_align_up(nsw * Dc * 4, 256) * 2 + mrec_align_up(nsw * 4, 256) + 256 + 2048 * 64 +
-           mrec_align_up(nch * kConstMax * Dc * 4, 256);
+    MrecArena count;
+    apply_ws_carve(count, n, D);
+    return count.off;
+}
+
+// What apply_cols() works out for one column block, as that block's kernels take it.
+template <class K, class GT>
+struct ApplyLaunch {
+    int64_t V, ld; const K* uniq; const int* spos; const int* sseg; const int* seg_offsets; int n; const GT* g; int64_t ldg;
+    const float* rscale; float gscale; ApplyGeom gm; ApplyWs w; WideArgs wa; StepState* ss; const int64_t* nv;
+    int nsw; unsigned blocks, lblocks;      // windows; workgroups of the windows' launch and of k_apply_long
+    hipStream_t st; hipEvent_t ev1;         // ev1: recorded between the two launches (mrec_profile_next_apply)
+};
+
+// The plain form at VEC columns per lane: the windows (under pool / fields the pooled windows, k_apply_main_fields; UpdAdamClip
+// there is the record's max_norm over its fields form), then the runs that cross them.
+template <int VEC, class K, class Upd, class GT>
+int launch_plain(const Upd& upd, const ApplyLaunch<K, GT>& a, const FieldArgs* fields) {
+    if (!fields)
+        k_apply_main<VEC, K, Upd, GT><<<a.blocks, 256, 0, a.st>>>(upd, a.V, a.ld, a.uniq, a.spos, a.sseg, a.n, a.g, a.ldg, a.rscale, a.gscale,
+                                                                 a.gm, a.w.carry_head, a.w.carry_tail, a.w.owners, a.seg_offsets, a.wa, a.ss);
+    else if (fields->F == 1 && fields->Ls > 1)
+        k_apply_main_fields<VEC, K, Upd, GT, true><<<a.blocks, 256, 0, a.st>>>(upd, a.V, a.ld, a.uniq, a.spos, a.sseg, a.n, a.g, a.ldg, a.rscale,
+                                                                              a.gm, a.w.carry_head, a.w.carry_tail, a.w.owners, a.seg_offsets, *fields);
+    else
+        k_apply_main_fields<VEC, K, Upd, GT, false><<<a.blocks, 256, 0, a.st>>>(upd, a.V, a.ld, a.uniq, a.spos, a.sseg, a.n, a.g, a.ldg, a.rscale,
+                                                                               a.gm, a.w.carry_head, a.w.carry_tail, a.w.owners, a.seg_offsets, *fields);
+    if (a.ev1) MREC_HIP_CHECK(hipEventRecord(a.ev1, a.st));
+    k_apply_long<VEC, K, Upd><<<a.lblocks, 256, 0, a.st>>>(upd, a.V, a.ld, a.uniq, a.sseg, a.seg_offsets, a.n, a.gm, a.w.carry_head,
+                                                          a.w.carry_tail, a.w.owners, a.nsw, a.wa, a.ss);
+    return MREC_OK;
+}
+
+// The finishing pass of a folded wide apply as a record: what k_apply_long and k_apply_const_finish would have been launched with.
+template <class K, class Upd, class GT>
+void fill_finish(ApplyFinish* f, const Upd& upd, const ApplyLaunch<K, GT>& a, const ConstCols& cc) {
+    f->upd = upd; f->V = a.V; f->ld = a.ld; f->uniq = a.uniq; f->key_bytes = (int)sizeof(K); f->sseg = a.sseg; f->seg_offsets = a.seg_offsets;
+    f->n = a.n; f->gm = a.gm; f->carry_head = a.w.carry_head; f->carry_tail = a.w.carry_tail; f->owners = a.w.owners; f->nsw = a.nsw;
+    f->wa = a.wa; f->ss = a.ss; f->nv = a.nv; f->lblocks = a.lblocks; f->magic = kFinishMagic;
+    f->cc = cc; f->cfin = cc.mask ? (unsigned)kConstMax : 0u;
+    if constexpr (Upd::kClip) f->clip = upd.clip; else f->clip = 0.0f;
+}
+
+// The folded wide form (float4 lanes and the wide lane; LazyAdam, plain or behind max_norm): the windows -- with the hot columns'
+// chunk sums in front where the batch has any (HOT: 32-bit keys and no max_norm, cc is empty otherwise) -- then the finishing
+// pass, launched here or handed back in *defer.
+template <class K, class Upd, class GT>
+int launch_wide(const Upd& upd, const ApplyLaunch<K, GT>& a, const ConstCols& cc, ApplyFinish* defer) {
+    if constexpr (sizeof(K) == 4 && std::is_same<Upd, UpdAdam>::value) {
+        if (cc.mask)
+            k_apply_main<4, K, Upd, GT, true, true><<<a.blocks + cc.cblocks, 256, 0, a.st>>>(upd, a.V, a.ld, a.uniq, a.spos, a.sseg, a.n, a.g, a.ldg,
+                                                         a.rscale, a.gscale, a.gm, a.w.carry_head, a.w.carry_tail, a.w.owners, a.seg_offsets,
+                                                         a.wa, a.ss, a.nv, cc);
+    }
+    if (!cc.mask)
+        k_apply_main<4, K, Upd, GT, true><<<a.blocks, 256, 0, a.st>>>(upd, a.V, a.ld, a.uniq, a.spos, a.sseg, a.n, a.g, a.ldg, a.rscale, a.gscale,
+                                                                     a.gm, a.w.carry_head, a.w.carry_tail, a.w.owners, a.seg_offsets, a.wa, a.ss,
+                                                                     a.nv, cc);
+    if (a.ev1) MREC_HIP_CHECK(hipEventRecord(a.ev1, a.st));
+    if (defer) {
+        fill_finish(defer, upd, a, cc);
+        return MREC_OK;
+    }
+    k_apply_long<4, K, Upd, true><<<a.lblocks, 256, 0, a.st>>>(upd, a.V, a.ld, a.uniq, a.sseg, a.seg_offsets, a.n, a.gm, a.w.carry_head,
+                                                              a.w.carry_tail, a.w.owners, a.nsw, a.wa, a.ss, a.nv);
+    if constexpr (std::is_same<Upd, UpdAdam>::value) {
+        if (cc.mask) k_apply_const_finish<K><<<kConstMax, 256, 0, a.st>>>(upd, a.V, a.ld, a.gm, a.wa, cc, a.ss);
+    }
+    return MREC_OK;
 }
 
 // One launch pair over columns [c0, c0+Dc) of every array.
@@ -1218,12 +1300,15 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
                const int* seg_offsets, int64_t n, const GT* g, int64_t ldg, const float* rscale, float gscale,
                int Dc, int vec, const ApplyWs& w, hipStream_t st, const ApplyOpts& o, const WideArgs* wide = nullptr, StepState* ss = nullptr,
                const int64_t* nv = nullptr) {
-    const FieldArgs* fields = o.fa.F ? &o.fa : nullptr;
-    ApplyGeom gm;
+    const bool folded = vec == 4 && wide;
+    ApplyLaunch<K, GT> a{};
+    a.V = V; a.ld = ld; a.uniq = uniq; a.spos = spos; a.sseg = sseg; a.seg_offsets = seg_offsets; a.n = (int)n; a.g = g; a.ldg = ldg;
+    a.rscale = rscale; a.gscale = gscale; a.w = w; a.ss = ss; a.nv = nv; a.st = st;
+    ApplyGeom& gm = a.gm;
     gm.D = Dc + (wide ? 4 : 0);
     gm.lpr = Dc / vec + (wide ? 1 : 0);
     gm.G = 64 / gm.lpr;
-    WideArgs wa{};
+    WideArgs& wa = a.wa;
     if (wide) {
         wa = *wide;
         wa.magic = (unsigned)(((uint64_t)1 << 32) / (uint64_t)wa.F + 1);       // pos / F = umulhi(pos, magic) while pos * F < 2^32
@@ -1231,33 +1316,19 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
         if ((uint64_t)n * (uint64_t)wa.F >= ((uint64_t)1 << 32) || (uint64_t)n * (uint64_t)wa.gws >= ((uint64_t)1 << 32)) return MREC_EUNSUPPORTED;
     }
     const int64_t nsw = mrec_cdiv(n, vec == 4 ? ACfg<4>::AW : ACfg<1>::AW);
-    unsigned blocks = (unsigned)mrec_cdiv(nsw, (int64_t)4 * gm.G);
-    if (blocks > MREC_APPLY_MAXB) blocks = MREC_APPLY_MAXB;
-    const unsigned lblocks = (unsigned)mrec_cdiv(nsw, (int64_t)(16 * gm.G < 256 ? 16 * gm.G : 256));      // k_apply_long: 4 windows per lane-group, 4 G lane-groups, 256 at most
-    const hipEvent_t ev0 = t_prof_start, ev1 = t_prof_stop;
+    a.nsw = (int)nsw;
+    a.blocks = (unsigned)mrec_cdiv(nsw, (int64_t)4 * gm.G);
+    if (a.blocks > MREC_APPLY_MAXB) a.blocks = MREC_APPLY_MAXB;
+    a.lblocks = (unsigned)mrec_cdiv(nsw, (int64_t)(16 * gm.G < 256 ? 16 * gm.G : 256));      // k_apply_long: 4 windows per lane-group, 4 G lane-groups, 256 at most
+    const hipEvent_t ev0 = t_prof_start;
+    a.ev1 = t_prof_stop;
     t_prof_start = t_prof_stop = nullptr;
-    // the pooled windows (fields; refused before this for the folded wide forms; UpdAdamClip with fields is the record's max_norm over
-    // its fields form): k_apply_main_fields, else k_apply_main
-#define MREC_APPLY_MAIN(VECN)                                                                                                          \
-    do {                                                                                                                               \
-        if (!fields)                                                                                                                   \
-            k_apply_main<VECN, K, Upd, GT><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,      \
-                                                                  w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss);          \
-        else {                                                                                                                         \
-            if (fields->F == 1 && fields->Ls > 1)                                                                                      \
-                k_apply_main_fields<VECN, K, Upd, GT, true><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gm,  \
-                                                                                   w.carry_head, w.carry_tail, w.owners, seg_offsets, *fields); \
-            else                                                                                                                       \
-                k_apply_main_fields<VECN, K, Upd, GT, false><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gm, \
-                                                                                    w.carry_head, w.carry_tail, w.owners, seg_offsets, *fields); \
-        }                                                                                                                              \
-    } while (0)
     if (ev0) MREC_HIP_CHECK(hipEventRecord(ev0, st));
-    if (nv && !(vec == 4 && wide)) return MREC_EUNSUPPORTED;
+    if (nv && !folded) return MREC_EUNSUPPORTED;
     // constant columns (the record's const_* members): the batch is B = n / F samples of F fields, ids of the table's key width,
     // LazyAdam on the fused rows -- anything else runs every column through the windows
     ConstCols cc = o.cc;
-    if (!(vec == 4 && wide && std::is_same<Upd, UpdAdam>::value && sizeof(K) == 4 && !nv && cc.mask && cc.ids0 && wa.F >= 1 && wa.F <= 64 &&
+    if (!(folded && std::is_same<Upd, UpdAdam>::value && sizeof(K) == 4 && !nv && cc.mask && cc.ids0 && wa.F >= 1 && wa.F <= 64 &&
           n % wa.F == 0 && cc.B == (int)(n / wa.F) && cc.B > 0 && cc.B <= 64 * kConstLG && wa.gws == 1 && cc.id_bytes == (int)sizeof(K)))
         cc = ConstCols{};
     if (cc.mask) {
@@ -1266,57 +1337,21 @@ int apply_cols(Upd upd, int64_t V, int64_t ld, const K* uniq, const int* spos, c
         cc.nlg = (int)mrec_cdiv((int64_t)cc.B, (int64_t)cc.rr);                                      // chunks
         cc.cblocks = (unsigned)mrec_cdiv((int64_t)cc.nlg * kConstMax, (int64_t)4 * gm.G);      // (room for kConstMax columns: how many there are is known on the device)
     }
-    if (vec == 4 && wide) {
-      if constexpr (!IsAdam<Upd>::value) {
-        return MREC_EUNSUPPORTED;                  // (the wide lane rides LazyAdam only: no such instantiation of the other updaters)
-      } else {
-        if constexpr (sizeof(K) == 4 && std::is_same<Upd, UpdAdam>::value) {      // (no HOT variant behind max_norm: cc is empty there)
-            if (cc.mask)
-                k_apply_main<4, K, Upd, GT, true, true><<<blocks + cc.cblocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale,
-                                                             gscale, gm, w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss, nv, cc);
-        }
-        if (!cc.mask)
-            k_apply_main<4, K, Upd, GT, true><<<blocks, 256, 0, st>>>(upd, V, ld, uniq, spos, sseg, (int)n, g, ldg, rscale, gscale, gm,
-                                                             w.carry_head, w.carry_tail, w.owners, seg_offsets, wa, ss, nv, cc);
-        if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
-        if (o.defer) {
-            if constexpr (IsAdam<Upd>::value) {
-                ApplyFinish* f = o.defer;
-                f->upd = upd; f->V = V; f->ld = ld; f->uniq = uniq; f->key_bytes = (int)sizeof(K); f->sseg = sseg; f->seg_offsets = seg_offsets;
-                f->n = (int)n; f->gm = gm; f->carry_head = w.carry_head; f->carry_tail = w.carry_tail; f->owners = w.owners; f->nsw = (int)nsw;
-                f->wa = wa; f->ss = ss; f->nv = nv; f->lblocks = lblocks; f->magic = kFinishMagic;
-                f->cc = cc; f->cfin = cc.mask ? (unsigned)kConstMax : 0u;
-                if constexpr (Upd::kClip) f->clip = upd.clip; else f->clip = 0.0f;
-            } else {
-                return MREC_EUNSUPPORTED;
-            }
-        } else {
-            k_apply_long<4, K, Upd, true><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
-                                                                  w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss, nv);
-            if constexpr (std::is_same<Upd, UpdAdam>::value) {
-                if (cc.mask) k_apply_const_finish<K><<<kConstMax, 256, 0, st>>>(upd, V, ld, gm, wa, cc, ss);
-            }
-        }
-      }
+    const FieldArgs* fields = o.fa.F ? &o.fa : nullptr;      // (the pooled form; refused before this for the folded wide form)
+    int rc;
+    if (folded) {
+        if constexpr (IsAdam<Upd>::value) rc = launch_wide(upd, a, cc, o.defer);
+        else rc = MREC_EUNSUPPORTED;               // (the wide lane rides LazyAdam only: no such instantiation of the other updaters)
     } else if (vec == 4) {
-        MREC_APPLY_MAIN(4);
-        if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
-        k_apply_long<4, K, Upd><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
-                                                        w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss);
+        rc = launch_plain<4>(upd, a, fields);
     } else if constexpr (Upd::kClip) {
-        return MREC_EUNSUPPORTED;                  // (max_norm: float4 rows only, refused by apply_impl before any launch)
+        rc = MREC_EUNSUPPORTED;                    // (max_norm: float4 rows only, refused by apply_impl before any launch)
     } else if (vec == 2) {
-        MREC_APPLY_MAIN(2);
-        if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
-        k_apply_long<2, K, Upd><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
-                                                        w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss);
+        rc = launch_plain<2>(upd, a, fields);
     } else {
-        MREC_APPLY_MAIN(1);
-        if (ev1) MREC_HIP_CHECK(hipEventRecord(ev1, st));
-        k_apply_long<1, K, Upd><<<lblocks, 256, 0, st>>>(upd, V, ld, uniq, sseg, seg_offsets, (int)n, gm,
-                                                        w.carry_head, w.carry_tail, w.owners, (int)nsw, wa, ss);
+        rc = launch_plain<1>(upd, a, fields);
     }
-#undef MREC_APPLY_MAIN
+    if (rc != MREC_OK) return rc;
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
@@ -1334,19 +1369,9 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
     if (!spos || !sseg || !seg_offsets || !g || !ws) return MREC_EINVAL;
     for (int i = 0; i < Upd::NS; ++i) if (!upd.s[i]) return MREC_EINVAL;
     if (n > (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    if (ws_bytes < apply_ws_bytes(n, D + (wide ? 4 : 0))) return MREC_EWORKSPACE;
-    const size_t nsw = (size_t)mrec_cdiv(n, AW_MIN);
-    const int Dc_max = (D > 256 ? 256 : D) + (wide ? 4 : 0);
     MrecArena a(ws, ws_bytes);
-    ApplyWs w;
-    w.carry_head = a.take<float>(nsw * Dc_max);
-    w.carry_tail = a.take<float>(nsw * Dc_max);
-    w.owners = a.take<int>(nsw);
-    w.n_owners = a.take<int>(1);
-    w.dummy = a.take<float>(2048 * 16);
-    const size_t nch = (size_t)mrec_cdiv(n, 64) < (size_t)kConstLG ? (size_t)mrec_cdiv(n, 64) : (size_t)kConstLG;
-    w.cpart = a.take<float>(nch * kConstMax * Dc_max);
-    if (!a.ok) return MREC_EWORKSPACE;
+    const ApplyWs w = apply_ws_carve(a, n, D + (wide ? 4 : 0));
+    if (!a.ok) return MREC_EWORKSPACE;      // (fewer bytes than mrec_sparse_apply_workspace_bytes answers for this n and width)
     bool aligned = (ld % 4 == 0) && (ldg % 4 == 0) && ((((uintptr_t)g) & (4 * sizeof(GT) - 1)) == 0);
     for (int i = 0; i < Upd::NS; ++i) aligned = aligned && al16(upd.s[i]);
     bool aligned8 = (ld % 2 == 0) && (ldg % 2 == 0) && ((((uintptr_t)g) & (2 * sizeof(GT) - 1)) == 0);
@@ -1364,47 +1389,6 @@ int apply_impl(Upd upd, int64_t V, int64_t ld, int32_t D, const K* uniq, const i
         if (rc != MREC_OK) return rc;
     }
     return MREC_OK;
-}
-
-template <class K, class GT = float>
-int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const K* uniq,
-                   const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const GT* g,
-                   int64_t ldg, const float* rscale, float lr, float b1, float b2, float eps, float b1_pow,
-                   float b2_pow, float gscale, int nesterov, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream,
-                   const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr, ApplyFinish* defer = nullptr) {
-    ApplyOpts o;
-    if (const int rc = apply_opts(opts, gscale, true, wide != nullptr, o)) return rc;
-    o.defer = defer;
-    if (o.clip > 0.0f && (D % 4 || D > (wide ? 252 : 256))) return MREC_EUNSUPPORTED;      // (a width the clip cannot run at)
-    if (!uniq && n > 0) return MREC_EINVAL;
-    UpdAdam u;
-    u.s[0] = p; u.s[1] = m; u.s[2] = v;
-    u.h.lr_t = lr * sqrtf(1.0f - b2_pow) / (1.0f - b1_pow);
-    u.h.b1 = b1; u.h.b2 = b2; u.h.omb1 = 1.0f - b1; u.h.omb2 = 1.0f - b2; u.h.eps = eps; u.h.gscale = gscale;
-    u.h.nesterov = nesterov;
-    if (o.clip > 0.0f) {
-        UpdAdamClip uc;
-        static_cast<UpdAdam&>(uc) = u;
-        uc.clip = o.clip;
-        return apply_impl<K, UpdAdamClip, GT>(uc, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                              stream, o, wide, ss, nv);
-    }
-    return apply_impl<K, UpdAdam, GT>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes,
-                                  stream, o, wide, ss, nv);
-}
-
-template <class K>
-int ftrl_impl(float* var, float* accum, float* linear, int64_t V, int64_t ld, int32_t D, const K* uniq,
-              const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const float* g,
-              int64_t ldg, const float* rscale, float lr, float l1, float l2, float lr_power, float gscale, void* ws,
-              size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    ApplyOpts o;
-    if (const int rc = apply_opts(opts, gscale, false, false, o)) return rc;
-    if (!uniq && n > 0) return MREC_EINVAL;
-    UpdFtrl u;
-    u.s[0] = var; u.s[1] = accum; u.s[2] = linear;
-    u.h = FtrlH{lr, l1, l2, lr_power, gscale};
-    return apply_impl<K, UpdFtrl>(u, V, ld, D, uniq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes, stream, o);
 }
 
 }  // namespace
@@ -1654,16 +1638,45 @@ MREC_API int mrec_sparse_apply_workspace_bytes(int64_t n, int32_t D, size_t* out
     return MREC_OK;
 }
 
-MREC_API int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets,
-                                  int64_t n, const float* g, int64_t ldg, const float* row_scale, float grad_scale,
-                                  int32_t D, float* out, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
+// (key width, gradient kind) -> <K, GT>, each decided in ONE place: uniq_bytes 4 / 8 -> int32_t / int64_t, g_kind 0 / 1 / 2 -> float /
+// bf16_t / f16_t; f gets the typed pointer(s).  An updater asks for the axes it has kernels for and no others -- LazyAdam both, FTRL
+// the key, the segment sum the gradient -- so the instantiations are those of the entries below and nothing else.
+template <class F>
+int by_key(const void* uniq, int uniq_bytes, F&& f) {
+    if (uniq_bytes == 4) return f((const int32_t*)uniq);
+    if (uniq_bytes == 8) return f((const int64_t*)uniq);
+    return MREC_EINVAL;
+}
+template <class F>
+int by_grad(const void* g, int g_kind, F&& f) {
+    if (g_kind == 0) return f((const float*)g);
+    if (g_kind == 1) return f((const bf16_t*)g);
+    if (g_kind == 2) return f((const f16_t*)g);
+    return MREC_EINVAL;
+}
+// (the gradient outside, the key inside: the order in which the compiler lays the kernels out, so that two builds compare byte for byte)
+template <class F>
+int by_key_grad(const void* uniq, int uniq_bytes, const void* g, int g_kind, F&& f) {
+    return by_grad(g, g_kind, [&](auto* gp) { return by_key(uniq, uniq_bytes, [&](auto* uq) { return f(uq, gp); }); });
+}
+
+// UnsortedSegmentSum: rows are group numbers, and there are at most n groups
+static int segment_sum_impl(const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const void* g, int g_kind,
+                     int64_t ldg, const float* rscale, float gscale, int32_t D, float* out, void* ws, size_t ws_bytes,
+                     const mrec_apply_opts_t* opts, void* stream) {
     UpdStore u;
     u.s[0] = out;
     ApplyOpts o;
-    if (const int rc = apply_opts(opts, grad_scale, false, false, o)) return rc;
-    // rows are group numbers; there are at most n groups
-    return apply_impl<int32_t, UpdStore>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, g,
-                                         ldg, row_scale, grad_scale, ws, ws_bytes, stream, o);
+    if (const int rc = apply_opts(opts, gscale, false, false, o)) return rc;
+    return by_grad(g, g_kind, [&](auto* gp) {
+        return apply_impl(u, n, D, D, (const int32_t*)nullptr, spos, sseg, seg_offsets, n, gp, ldg, rscale, gscale, ws, ws_bytes, stream, o);
+    });
+}
+
+MREC_API int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets,
+                                  int64_t n, const float* g, int64_t ldg, const float* row_scale, float grad_scale,
+                                  int32_t D, float* out, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
+    return segment_sum_impl(sorted_pos, sorted_seg, seg_offsets, n, g, 0, ldg, row_scale, grad_scale, D, out, ws, ws_bytes, opts, stream);
 }
 
 /* ... over 16-bit row gradients (g_kind 1: bf16, 2: IEEE half), widened exactly and summed in fp32: what a rank of a row-sharded
@@ -1671,79 +1684,47 @@ MREC_API int mrec_segment_sum_f32(const int32_t* sorted_pos, const int32_t* sort
 MREC_API int mrec_segment_sum_g16(const int32_t* sorted_pos, const int32_t* sorted_seg, const int32_t* seg_offsets,
                                   int64_t n, const void* g, int32_t g_kind, int64_t ldg, const float* row_scale, float grad_scale,
                                   int32_t D, float* out, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    UpdStore u;
-    u.s[0] = out;
+    return segment_sum_impl(sorted_pos, sorted_seg, seg_offsets, n, g, g_kind == 0 ? -1 : g_kind, ldg, row_scale, grad_scale, D, out, ws,
+                            ws_bytes, opts, stream);      // (kind 0 is mrec_segment_sum_f32's: MREC_EINVAL here, as any other)
+}
+
+static int lazy_adam_impl(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const void* uniq, int uniq_bytes,
+                   const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const void* g, int g_kind,
+                   int64_t ldg, const float* rscale, float lr, float b1, float b2, float eps, float b1_pow,
+                   float b2_pow, float gscale, int nesterov, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream,
+                   const WideArgs* wide = nullptr, StepState* ss = nullptr, const int64_t* nv = nullptr, ApplyFinish* defer = nullptr) {
     ApplyOpts o;
-    if (const int rc = apply_opts(opts, grad_scale, false, false, o)) return rc;
-    if (g_kind == 1)
-        return apply_impl<int32_t, UpdStore, bf16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const bf16_t*)g,
-                                                     ldg, row_scale, grad_scale, ws, ws_bytes, stream, o);
-    if (g_kind == 2)
-        return apply_impl<int32_t, UpdStore, f16_t>(u, n, D, D, (const int32_t*)nullptr, sorted_pos, sorted_seg, seg_offsets, n, (const f16_t*)g,
-                                                    ldg, row_scale, grad_scale, ws, ws_bytes, stream, o);
-    return MREC_EINVAL;
+    if (const int rc = apply_opts(opts, gscale, true, wide != nullptr, o)) return rc;
+    o.defer = defer;
+    if (o.clip > 0.0f && (D % 4 || D > (wide ? 252 : 256))) return MREC_EUNSUPPORTED;      // (a width the clip cannot run at)
+    if (!uniq && n > 0) return MREC_EINVAL;
+    UpdAdamClip uc;
+    uc.s[0] = p; uc.s[1] = m; uc.s[2] = v;
+    uc.h = adam_hyper(lr, b1, b2, eps, b1_pow, b2_pow, gscale, nesterov);
+    uc.clip = o.clip;
+    const UpdAdam& u = uc;
+    return by_key_grad(uniq, uniq_bytes, g, g_kind, [&](auto* uq, auto* gp) {
+        if (o.clip > 0.0f) return apply_impl(uc, V, ld, D, uq, spos, sseg, seg_offsets, n, gp, ldg, rscale, gscale, ws, ws_bytes, stream, o, wide, ss, nv);
+        return apply_impl(u, V, ld, D, uq, spos, sseg, seg_offsets, n, gp, ldg, rscale, gscale, ws, ws_bytes, stream, o, wide, ss, nv);
+    });
 }
 
-MREC_API int mrec_sparse_lazy_adam_f32_i32(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
-                                           const int32_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
-                                           const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
-                                           const float* row_scale, float lr, float b1, float b2, float eps,
-                                           float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                           size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return lazy_adam_impl<int32_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg, row_scale,
-                                   lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream);
-}
-MREC_API int mrec_sparse_lazy_adam_f32_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
-                                           const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
-                                           const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
-                                           const float* row_scale, float lr, float b1, float b2, float eps,
-                                           float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                           size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return lazy_adam_impl<int64_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg, row_scale,
-                                   lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream);
-}
-
-MREC_API int mrec_sparse_lazy_adam_bf16g_i32(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
-                                             const int32_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
-                                             const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
-                                             const float* row_scale, float lr, float b1, float b2, float eps,
-                                             float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                             size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return lazy_adam_impl<int32_t, bf16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
-                                           (const bf16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                           nesterov, ws, ws_bytes, opts, stream);
-}
-MREC_API int mrec_sparse_lazy_adam_bf16g_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
-                                             const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
-                                             const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
-                                             const float* row_scale, float lr, float b1, float b2, float eps,
-                                             float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                             size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return lazy_adam_impl<int64_t, bf16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
-                                           (const bf16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                           nesterov, ws, ws_bytes, opts, stream);
-}
-
-MREC_API int mrec_sparse_lazy_adam_f16g_i32(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
-                                            const int32_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
-                                            const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
-                                            const float* row_scale, float lr, float b1, float b2, float eps,
-                                            float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                            size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return lazy_adam_impl<int32_t, f16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
-                                          (const f16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                          nesterov, ws, ws_bytes, opts, stream);
-}
-MREC_API int mrec_sparse_lazy_adam_f16g_i64(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D,
-                                            const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
-                                            const int32_t* seg_offsets, int64_t n, const uint16_t* g, int64_t ldg,
-                                            const float* row_scale, float lr, float b1, float b2, float eps,
-                                            float b1_pow, float b2_pow, float grad_scale, int nesterov, void* ws,
-                                            size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return lazy_adam_impl<int64_t, f16_t>(p, m, v, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n,
-                                          (const f16_t*)g, ldg, row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale,
-                                          nesterov, ws, ws_bytes, opts, stream);
-}
+// The six typed LazyAdam entries: one signature but for the types of uniq and g, which each hands on as (uniq_bytes, g_kind).
+#define MREC_LAZY_ADAM_ENTRY(NAME, KT, GABI, GKIND)                                                                                   \
+    MREC_API int NAME(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const KT* uniq, const int32_t* sorted_pos,     \
+                      const int32_t* sorted_seg, const int32_t* seg_offsets, int64_t n, const GABI* g, int64_t ldg,                   \
+                      const float* row_scale, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow, float grad_scale, \
+                      int nesterov, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {                         \
+        return lazy_adam_impl(p, m, v, V, ld, D, uniq, (int)sizeof(KT), sorted_pos, sorted_seg, seg_offsets, n, g, GKIND, ldg,       \
+                              row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream);          \
+    }
+MREC_LAZY_ADAM_ENTRY(mrec_sparse_lazy_adam_f32_i32, int32_t, float, 0)
+MREC_LAZY_ADAM_ENTRY(mrec_sparse_lazy_adam_f32_i64, int64_t, float, 0)
+MREC_LAZY_ADAM_ENTRY(mrec_sparse_lazy_adam_bf16g_i32, int32_t, uint16_t, 1)
+MREC_LAZY_ADAM_ENTRY(mrec_sparse_lazy_adam_bf16g_i64, int64_t, uint16_t, 1)
+MREC_LAZY_ADAM_ENTRY(mrec_sparse_lazy_adam_f16g_i32, int32_t, uint16_t, 2)
+MREC_LAZY_ADAM_ENTRY(mrec_sparse_lazy_adam_f16g_i64, int64_t, uint16_t, 2)
+#undef MREC_LAZY_ADAM_ENTRY
 
 /* LazyAdam on the deep columns + FTRL on the wide record of the same fused rows, one pass (see include/mrec.h); defer: the finishing
  * pass is handed back in *defer instead of launched */
@@ -1757,20 +1738,11 @@ static int lazy_adam_wide(float* p, float* m, float* v, int64_t V, int64_t ld, i
     WideArgs wa;
     wa.gw = gw; wa.F = F; wa.wcol = wide_col; wa.magic = 0; wa.dummy = nullptr; wa.gws = (unsigned)gw_stride;
     wa.h = FtrlH{ftrl_lr, l1, l2, lr_power, grad_scale};
-#define MREC_WIDE_CALL(KT, GT)                                                                                          \
-    return lazy_adam_impl<KT, GT>(p, m, v, V, ld, D, (const KT*)uniq, sorted_pos, sorted_seg, seg_offsets, n, (const GT*)g, ldg, \
-                                  row_scale, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream, &wa, \
-                                  (StepState*)step_state, n_valid_dev, defer)
-    if (uniq_bytes == 4) {
-        if (g_kind == 0) { MREC_WIDE_CALL(int32_t, float); }
-        if (g_kind == 1) { MREC_WIDE_CALL(int32_t, bf16_t); }
-        MREC_WIDE_CALL(int32_t, f16_t);
-    }
-    if (g_kind == 0) { MREC_WIDE_CALL(int64_t, float); }
-    if (g_kind == 1) { MREC_WIDE_CALL(int64_t, bf16_t); }
-    MREC_WIDE_CALL(int64_t, f16_t);
-#undef MREC_WIDE_CALL
+    return lazy_adam_impl(p, m, v, V, ld, D, uniq, uniq_bytes, sorted_pos, sorted_seg, seg_offsets, n, g, g_kind, ldg, row_scale, lr, b1,
+                          b2, eps, b1_pow, b2_pow, grad_scale, nesterov, ws, ws_bytes, opts, stream, &wa, (StepState*)step_state,
+                          n_valid_dev, defer);
 }
+
 
 MREC_API int mrec_sparse_lazy_adam_wide(float* p, float* m, float* v, int64_t V, int64_t ld, int32_t D, const void* uniq,
                                         int32_t uniq_bytes, const int32_t* sorted_pos, const int32_t* sorted_seg,
@@ -1835,8 +1807,7 @@ MREC_API int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, cons
     DenseAdamSlabArgs a;
     a.p = (float4*)p; a.m = (float4*)m; a.v = (float4*)v; a.g = (const float4*)g; a.n4 = n / 4; a.shadow = (uint2*)shadow16;
     a.ss = (const StepState*)step_state;
-    a.h.lr_t = lr * sqrtf(1.0f - b2_pow) / (1.0f - b1_pow);
-    a.h.b1 = b1; a.h.b2 = b2; a.h.omb1 = 1.0f - b1; a.h.omb2 = 1.0f - b2; a.h.eps = eps; a.h.gscale = grad_scale; a.h.nesterov = nesterov;
+    a.h = adam_hyper(lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov);
     a.f1.idx = -1;
     a.f1.h = FtrlH{1.0f, 0.0f, 0.0f, -0.5f, grad_scale};
     if (one && one->index >= 0) {
@@ -1865,19 +1836,34 @@ MREC_API int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, cons
     return MREC_OK;
 }
 
+static int ftrl_impl(float* var, float* accum, float* linear, int64_t V, int64_t ld, int32_t D, const void* uniq, int uniq_bytes,
+              const int32_t* spos, const int32_t* sseg, const int32_t* seg_offsets, int64_t n, const float* g,
+              int64_t ldg, const float* rscale, float lr, float l1, float l2, float lr_power, float gscale, void* ws,
+              size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
+    ApplyOpts o;
+    if (const int rc = apply_opts(opts, gscale, false, false, o)) return rc;
+    if (!uniq && n > 0) return MREC_EINVAL;
+    UpdFtrl u;
+    u.s[0] = var; u.s[1] = accum; u.s[2] = linear;
+    u.h = FtrlH{lr, l1, l2, lr_power, gscale};
+    return by_key(uniq, uniq_bytes, [&](auto* uq) {
+        return apply_impl(u, V, ld, D, uq, spos, sseg, seg_offsets, n, g, ldg, rscale, gscale, ws, ws_bytes, stream, o);
+    });
+}
+
 MREC_API int mrec_sparse_ftrl_f32_i32(float* var, float* accum, float* linear, int64_t V, int64_t ld, int32_t D,
                                       const int32_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                       const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                       const float* row_scale, float lr, float l1, float l2, float lr_power,
                                       float grad_scale, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return ftrl_impl<int32_t>(var, accum, linear, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg,
-                              row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, opts, stream);
+    return ftrl_impl(var, accum, linear, V, ld, D, uniq, 4, sorted_pos, sorted_seg, seg_offsets, n, g, ldg,
+                     row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, opts, stream);
 }
 MREC_API int mrec_sparse_ftrl_f32_i64(float* var, float* accum, float* linear, int64_t V, int64_t ld, int32_t D,
                                       const int64_t* uniq, const int32_t* sorted_pos, const int32_t* sorted_seg,
                                       const int32_t* seg_offsets, int64_t n, const float* g, int64_t ldg,
                                       const float* row_scale, float lr, float l1, float l2, float lr_power,
                                       float grad_scale, void* ws, size_t ws_bytes, const mrec_apply_opts_t* opts, void* stream) {
-    return ftrl_impl<int64_t>(var, accum, linear, V, ld, D, uniq, sorted_pos, sorted_seg, seg_offsets, n, g, ldg,
-                              row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, opts, stream);
+    return ftrl_impl(var, accum, linear, V, ld, D, uniq, 8, sorted_pos, sorted_seg, seg_offsets, n, g, ldg,
+                     row_scale, lr, l1, l2, lr_power, grad_scale, ws, ws_bytes, opts, stream);
 }

@@ -22,18 +22,21 @@ extern int g_mrec_last_hip_error;
 
 static inline size_t mrec_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Bump allocator over the caller's workspace; every block 256-B aligned.
+// Bump allocator over the caller's workspace; every block 256-B aligned.  Without a workspace (the default constructor) it only
+// counts: every take() answers nullptr and `off` ends as the bytes the same takes need of a real one -- so a layout is written once,
+// as the takes that carve it, and its size query runs those takes.
 struct MrecArena {
     char* base;
     size_t cap;
     size_t off;
     bool ok;
+    MrecArena() : base(nullptr), cap(SIZE_MAX), off(0), ok(true) {}
     MrecArena(void* ws, size_t bytes) : base((char*)ws), cap(bytes), off(0), ok(true) {}
     template <class T>
     T* take(size_t count) {
         size_t b = mrec_align_up(count * sizeof(T), 256);
         if (off + b > cap) { ok = false; off += b; return nullptr; }
-        T* p = (T*)(base + off);
+        T* p = base ? (T*)(base + off) : nullptr;
         off += b;
         return p;
     }

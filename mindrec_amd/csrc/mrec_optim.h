@@ -6,6 +6,16 @@
 
 struct AdamH { float lr_t, b1, b2, omb1, omb2, eps, gscale; int nesterov; };
 
+// An Adam entry's scalars as the kernels take them (host side).  lr_t in exactly these fp32 operations, in this order: the oracle and
+// k_step_advance spell the same ones, and tests compare the results bit for bit.
+static inline AdamH adam_hyper(float lr, float b1, float b2, float eps, float b1_pow, float b2_pow, float gscale, int nesterov) {
+    AdamH h;
+    h.lr_t = lr * sqrtf(1.0f - b2_pow) / (1.0f - b1_pow);
+    h.b1 = b1; h.b2 = b2; h.omb1 = 1.0f - b1; h.omb2 = 1.0f - b2; h.eps = eps; h.gscale = gscale;
+    h.nesterov = nesterov;
+    return h;
+}
+
 __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, const AdamH& h) {
     const float mn = h.b1 * m + h.omb1 * g;
     const float vn = h.b2 * v + h.omb2 * (g * g);

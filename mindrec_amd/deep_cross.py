@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .wide_deep_mlp import _flat_views
 
 
 @dataclass
@@ -47,17 +48,6 @@ class DeepCrossConfig:
     fp32_matmul: str = "x3"       # the DenseLayers' fp32 MatMuls: "x3" = three-part bf16 operands on the 16-bit matrix instruction
                                   # (fp32-class accuracy at 6/16 of the fp32-MFMA time, csrc/mrec_gemm_x3.hip); "exact" = the
                                   # fp32-input matrix instruction (a k-ordered chain of fmaf per output, csrc/mrec_gemm_f32.hip)
-
-
-def _flat_views(shapes, device):
-    n = sum(int(np.prod(s)) for s in shapes)
-    flat = torch.zeros(n, dtype=torch.float32, device=device)
-    views, off = [], 0
-    for s in shapes:
-        k = int(np.prod(s))
-        views.append(flat[off:off + k].view(s))
-        off += k
-    return flat, views
 
 
 class DeepCrossEngine:

@@ -546,9 +546,38 @@ def _row_scale(plan, row_scale):
     return rs
 
 
-def _apply_ws(plan, D, dev):
-    nb = _lib.query_bytes("mrec_sparse_apply_workspace_bytes", plan.n, D)
-    return workspace("apply", nb, dev)
+_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # a float type as the library's entries name it (g_kind and the like)
+
+
+class _Apply:
+    """What the sparse-apply wrappers share, checked and resolved in their common order: the state tables `what` (one shape and row
+    stride; none: a segment sum, whose width is g's), pool= / fields= (_pooled), the gradient rows (_grads), row_scale and the
+    workspace (of D + ws_cols columns).  Holds the pieces of the call in the entries' argument order -- table (pointers, V, ld, D),
+    uniq, index (sorted_pos, sorted_seg, seg_offsets, n), g, kind, ldg, rs, ws (pointer, bytes) -- beside opts and grad_scale as
+    _pooled resolved them, and the tensors behind the pointers (g2, rs_t, ws_t), alive as long as it is."""
+
+    def __init__(self, plan, tables, what, g, row_scale, grad_scale, allow_bf16=True, ws_cols=0, pool=None, fields=None, field_scale=None,
+                 pool_max_norm=None):
+        if tables:
+            V, D, ld = _table(tables[0])
+            for t in tables[1:]:
+                if _table(t) != (V, D, ld):
+                    raise ValueError(f"{what} must share shape and row stride")
+            self.table = tuple(_ptr(t) for t in tables) + (V, ld, D)
+        self.opts, rows, self.grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm)
+        if not tables:
+            D = g.shape[-1]
+            F = len(fields) if fields is not None else 1
+            if F > 1 and g.dim() == 2 and g.shape[0] * sum(fields) == plan.n and D % F == 0:
+                D //= F                           # g as the lookup's result has it, [B, F * D]: the same memory as [B * F, D]
+        self.D = D
+        self.g2, self.ldg = _grads(plan, g, D, allow_bf16=allow_bf16, rows=rows)
+        self.rs_t = _row_scale(plan, row_scale)
+        self.ws_t = workspace("apply", _lib.query_bytes("mrec_sparse_apply_workspace_bytes", plan.n, D + ws_cols),
+                              tables[0].device if tables else g.device)
+        self.uniq = _ptr(plan.uniq_buf) if tables else None
+        self.index = (_ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n)
+        self.g, self.kind, self.rs, self.ws = _ptr(self.g2), _KIND[self.g2.dtype], _ptr(self.rs_t), (_ptr(self.ws_t), self.ws_t.numel())
 
 
 def apply_window(D, aligned=True):
@@ -564,22 +593,13 @@ def segment_sum(plan, g, row_scale=None, grad_scale=1.0, pool=None, fields=None,
     [B, F * D] gradient seen as [B * F, D], and position i = b * Ls + s, s in field f, contributes (g[b * F + f] * row_scale[i]) *
     field_scale[f]; field_scale (one float per field) takes the place of grad_scale, without it every field's scale is grad_scale."""
     _need_cuda(g, row_scale)
-    opts, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
-    D = g.shape[-1]
-    F = len(fields) if fields is not None else 1
-    if F > 1 and g.dim() == 2 and g.shape[0] * sum(fields) == plan.n and D % F == 0:
-        D //= F                           # g as the lookup's result has it, [B, F * D]: the same memory as [B * F, D]
-    g2, ldg = _grads(plan, g, D, allow_bf16=True, rows=rows)
-    rs = _row_scale(plan, row_scale)
-    out = torch.empty((max(plan.n, 1), D), dtype=torch.float32, device=g.device)
-    ws = _apply_ws(plan, D, g.device)
-    if g2.dtype == torch.float32:
-        _lib.call("mrec_segment_sum_f32", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                  _ptr(g2), ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(), _opts_ptr(opts), _stream())
+    a = _Apply(plan, (), None, g, row_scale, grad_scale, pool=pool, fields=fields, field_scale=field_scale)
+    out = torch.empty((max(plan.n, 1), a.D), dtype=torch.float32, device=g.device)
+    tail = (a.ldg, a.rs, a.grad_scale, a.D, _ptr(out), *a.ws, _opts_ptr(a.opts), _stream())
+    if a.kind == 0:
+        _lib.call("mrec_segment_sum_f32", *a.index, a.g, *tail)
     else:       # 16-bit row gradients (what the mixed-precision MLP backward produces): widened exactly, summed in fp32
-        _lib.call("mrec_segment_sum_g16", _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n,
-                  _ptr(g2), 1 if g2.dtype == torch.bfloat16 else 2, ldg, _ptr(rs), grad_scale, D, _ptr(out), _ptr(ws), ws.numel(),
-                  _opts_ptr(opts), _stream())
+        _lib.call("mrec_segment_sum_g16", *a.index, a.g, a.kind, *tail)
     return out
 
 
@@ -596,27 +616,19 @@ def sparse_lazy_adam_(p, m, v, plan, g, row_scale=None, lr=3.5e-4, beta1=0.9, be
     whose completed row sums go through the clip's Jacobian as under max_norm (the record's max_norm beside its fields form);
     D % 4 == 0, D <= 256.  max_norm= stays the plain apply's and is refused with pool= or fields=."""
     _need_cuda(p, m, v, g, row_scale)
-    V, D, ld = _table(p)
-    for t in (m, v):
-        if _table(t) != (V, D, ld):
-            raise ValueError("p, m, v must share shape and row stride")
-    opts, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale, pool_max_norm)
-    g2, ldg = _grads(plan, g, D, allow_bf16=True, rows=rows)
-    rs = _row_scale(plan, row_scale)
-    ws = _apply_ws(plan, D, p.device)
-    sfx = _suffix(plan.uniq_buf)
-    fn = {torch.float32: "mrec_sparse_lazy_adam_f32_", torch.bfloat16: "mrec_sparse_lazy_adam_bf16g_",
-          torch.float16: "mrec_sparse_lazy_adam_f16g_"}[g2.dtype]
+    a = _Apply(plan, (p, m, v), "p, m, v", g, row_scale, grad_scale, pool=pool, fields=fields, field_scale=field_scale,
+               pool_max_norm=pool_max_norm)
+    fn = f"mrec_sparse_lazy_adam_{('f32', 'bf16g', 'f16g')[a.kind]}_{_suffix(plan.uniq_buf)}"
+    opts = a.opts
     if max_norm is not None:
         c = _max_norm(max_norm)
         if opts is None:
             opts = ApplyOpts()
         elif opts.n_fields:      # the record holds ONE max_norm, and beside fields= it is pool_max_norm's: MREC_EUNSUPPORTED, as ever
-            raise _lib.MrecError(fn + sfx, -3, "(max_norm= with fields=: the pooled apply takes pool_max_norm=)")
+            raise _lib.MrecError(fn, -3, "(max_norm= with fields=: the pooled apply takes pool_max_norm=)")
         opts.max_norm = c
-    _lib.call(fn + sfx, _ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), _ptr(plan.sorted_pos), _ptr(plan.sorted_seg),
-              _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale,
-              int(use_nesterov), _ptr(ws), ws.numel(), _opts_ptr(opts), _stream())
+    _lib.call(fn, *a.table, a.uniq, *a.index, a.g, a.ldg, a.rs, lr, beta1, beta2, eps, beta1_power, beta2_power, a.grad_scale,
+              int(use_nesterov), *a.ws, _opts_ptr(opts), _stream())
 
 
 class ApplyFinish(C.Structure):      # mrec_apply_finish_t
@@ -675,12 +687,7 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
     by the same launch instead of through the index (a different, fixed order of additions for those rows).  max_norm: as
     sparse_lazy_adam_ for the deep columns (the wide record's FTRL is not clipped; D <= 252); not with const_cols."""
     _need_cuda(p, m, v, g, row_scale, gw)
-    V, D, ld = _table(p)
-    for t in (m, v):
-        if _table(t) != (V, D, ld):
-            raise ValueError("p, m, v must share shape and row stride")
-    g2, ldg = _grads(plan, g, D, allow_bf16=True)
-    rs = _row_scale(plan, row_scale)
+    a = _Apply(plan, (p, m, v), "p, m, v", g, row_scale, grad_scale, ws_cols=4)      # (the wide lane's four columns ride in the carry rows)
     if gw.dtype != torch.float32 or gw.numel() * F != plan.n:
         raise TypeError("gw must be float32 with one value per sample (n / F)")
     if gw.dim() == 2 and gw.shape[1] == 1:
@@ -689,13 +696,9 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
         gws = 1
     else:
         raise TypeError("gw must be contiguous, or an [n, 1] column view")
-    nb = _lib.query_bytes("mrec_sparse_apply_workspace_bytes", max(plan.n, 1), D + 4)
-    ws = workspace("apply", nb, p.device)
-    kind = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[g2.dtype]
-    args = (_ptr(p), _ptr(m), _ptr(v), V, ld, D, _ptr(plan.uniq_buf), plan.uniq_buf.element_size(),
-            _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), kind, ldg, _ptr(rs), lr,
-            beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), _ptr(gw), int(gws), int(F), int(wide_col),
-            ftrl_lr, l1, l2, lr_power, _ptr(ws), ws.numel(), _ptr(step_state.buf) if step_state is not None else None,
+    args = (*a.table, a.uniq, plan.uniq_buf.element_size(), *a.index, a.g, a.kind, a.ldg, a.rs, lr,
+            beta1, beta2, eps, beta1_power, beta2_power, a.grad_scale, int(use_nesterov), _ptr(gw), int(gws), int(F), int(wide_col),
+            ftrl_lr, l1, l2, lr_power, *a.ws, _ptr(step_state.buf) if step_state is not None else None,
             _ptr(getattr(plan, "n_valid_dev", None)))
     opts = keep_cc = None
     if max_norm is not None and const_cols is not None and const_cols[0] is not None:
@@ -715,7 +718,7 @@ def sparse_lazy_adam_wide_(p, m, v, plan, g, row_scale, gw, F, wide_col, lr=3.5e
         # finish=...) runs it as the first workgroups of the dense net's Adam launch.  The record points into `ws`, the plan and
         # the tables: run the finish before any of them is reused.
         fin = ApplyFinish()
-        fin.keep = (ws, plan, p, g2, rs, gw, keep_cc)
+        fin.keep = (a.ws_t, plan, p, a.g2, a.rs_t, gw, keep_cc)
         _lib.call("mrec_sparse_lazy_adam_wide_defer", *args, C.byref(fin), _opts_ptr(opts), _stream())
         return fin
     _lib.call("mrec_sparse_lazy_adam_wide", *args, _opts_ptr(opts), _stream())
@@ -727,18 +730,10 @@ def sparse_ftrl_(var, accum, linear, plan, g, row_scale=None, lr=5e-2, l1=1e-8, 
     """nn.FTRL sparse apply (wide_and_deep.py:423-430): in place on var, accum, linear.  pool=L, fields=(L_0, ..) / field_scale: as
     sparse_lazy_adam_."""
     _need_cuda(var, accum, linear, g, row_scale)
-    V, D, ld = _table(var)
-    for t in (accum, linear):
-        if _table(t) != (V, D, ld):
-            raise ValueError("var, accum, linear must share shape and row stride")
-    opts, rows, grad_scale = _pooled(plan, pool, fields, field_scale, grad_scale)
-    g2, ldg = _grads(plan, g, D, rows=rows)
-    rs = _row_scale(plan, row_scale)
-    ws = _apply_ws(plan, D, var.device)
-    sfx = _suffix(plan.uniq_buf)
-    _lib.call(f"mrec_sparse_ftrl_f32_{sfx}", _ptr(var), _ptr(accum), _ptr(linear), V, ld, D, _ptr(plan.uniq_buf),
-              _ptr(plan.sorted_pos), _ptr(plan.sorted_seg), _ptr(plan.seg_offsets), plan.n, _ptr(g2), ldg, _ptr(rs), lr, l1,
-              l2, lr_power, grad_scale, _ptr(ws), ws.numel(), _opts_ptr(opts), _stream())
+    a = _Apply(plan, (var, accum, linear), "var, accum, linear", g, row_scale, grad_scale, allow_bf16=False, pool=pool, fields=fields,
+               field_scale=field_scale)
+    _lib.call(f"mrec_sparse_ftrl_f32_{_suffix(plan.uniq_buf)}", *a.table, a.uniq, *a.index, a.g, a.ldg, a.rs, lr, l1, l2, lr_power,
+              a.grad_scale, *a.ws, _opts_ptr(a.opts), _stream())
 
 
 def _flat_same(*ts):
@@ -1584,9 +1579,6 @@ class Dropout:
 
 def _drop_ref(d):
     return C.cast(C.pointer(d._c), C.c_void_p) if d is not None else None
-
-
-_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 def dropout_(x, drop, out=None):
