@@ -480,6 +480,19 @@ int mrec_dense_adam_rows_l2_f32(float* p, float* m, float* v, int64_t V, int32_t
                                 const int64_t* n_uniq_dev, const float* sums, float lr, float b1, float b2, float eps, float b1_pow,
                                 float b2_pow, float grad_scale, int nesterov, float l2_scaled, double* sumsq, int sumsq_accumulate,
                                 const void* step_state, void* ws, size_t ws_bytes, void* stream);
+/* max_norm where the optimizer is dense -- the bprop of mrec_gather_rows_clip_* in front of mrec_dense_adam_rows_l2_f32 (the tables of
+ * DeepFM and Deep&Cross behind an EmbeddingLookup(max_norm=c)).  Every occurrence of a row shares the row's Jacobian, so clipping the
+ * summed gradient is exact: `sums` [>= U, D] (contiguous, as mrec_segment_sum_* leaves them; group g belongs to row uniq_rows[g]) is
+ * rewritten IN PLACE, G <- (c / n) (G - (x.G / n^2) x) where n = |x| > c and x = p[uniq_rows[g]] -- so the call must run BEFORE the
+ * optimizer that updates p -- and left as it is where n <= c (a tie is not clipped, a zero row never is).  n^2, the decision and the
+ * arithmetic are those of mrec_apply_opts_t.max_norm below: the decision is, bit for bit, the one the lookup took for that row.
+ * Only groups g < min(U, *n_uniq_dev) are touched (n_uniq_dev: device count, nullable: all U), and a group whose row lies outside
+ * [0, V) (the -1 of an un-admitted key) is left alone; unclipped groups are not written.  p: [V, ld >= D], row stride ld.
+ * max_norm not a finite number > 0, a null p / uniq_rows / sums, U < 0, V < 0 or ld < D: MREC_EINVAL; D % 4 != 0, D > 256 or rows that
+ * are not 16-byte aligned: MREC_EUNSUPPORTED -- all before any launch; U == 0: MREC_OK without one.  One launch, no workspace, no
+ * atomics, no synchronisation: capturable. */
+int mrec_clip_group_sums_f32(const float* p, int64_t V, int64_t ld, int32_t D, const int32_t* uniq_rows, int64_t U,
+                             const int64_t* n_uniq_dev, float* sums, float max_norm, void* stream);
 /* Both of the above with ONE element of the buffer under FTRL instead of Adam: Wide&Deep's `wide_b` (models/wide_deep/src/
  * wide_and_deep.py:161-163) is a member of the FTRL optimizer's parameter list -- TrainStepWrap sorts by `"wide" in params.name`
  * (:407-411) and MindSpore names the Parameter held in the attribute `wide_b` "<prefix>.wide_b" [EXT: Cell.update_parameters_name

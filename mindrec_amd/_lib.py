@@ -218,6 +218,7 @@ _SIGS = {
     "mrec_dense_adam_rows_l2_workspace_bytes": [_i64, _i32, _vp],
     "mrec_dense_adam_rows_l2_f32": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _f32, _vp, _int,
                                     _vp, _vp, _sz, _vp],
+    "mrec_clip_group_sums_f32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
     "mrec_crc32c_host": [C.c_char_p, _sz, _vp],
     "mrec_auc_ws_bytes": [_i64, _szp],
     "mrec_auc_counts": [_vp, _vp, _i64, _vp, _vp, _sz, _vp],

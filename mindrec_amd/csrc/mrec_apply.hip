@@ -309,20 +309,7 @@ template <> struct IsAdam<UpdAdamClip> : std::true_type {};
 // lanes ds = 0 .. nd - 1 of the lane-group (lane0 = hardware lane of ds 0) hold row x (= p) and the sum g; every one of them calls
 template <class Upd>
 __device__ __forceinline__ void clip_grad(const Upd& u, Vf<4>& g, const Vf<4>& x, int ds, int nd, int lane0) {
-    const float n2 = mrec_row_sumsq(x.v, ds, nd, lane0);
-    float d = x.v.x * g.v.x;
-    d = d + x.v.y * g.v.y;
-    d = d + x.v.z * g.v.z;
-    d = d + x.v.w * g.v.w;
-    d = mrec_group_sum(d, ds, nd, lane0);
-    float s;
-    if (mrec_clip_scale(n2, u.clip, &s)) {
-        const float t = d / n2;
-        g.v.x = s * (g.v.x - t * x.v.x);
-        g.v.y = s * (g.v.y - t * x.v.y);
-        g.v.z = s * (g.v.z - t * x.v.z);
-        g.v.w = s * (g.v.w - t * x.v.w);
-    }
+    mrec_clip_jacobian(g.v, x.v, u.clip, ds, nd, lane0);
 }
 
 template <class Upd>

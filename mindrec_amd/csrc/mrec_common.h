@@ -130,3 +130,26 @@ __device__ __forceinline__ bool mrec_clip_scale(float n2, float c, float* scale)
     *scale = c / n;
     return n > c;
 }
+// the clip's Jacobian over a completed gradient sum: lanes ds = 0 .. nd - 1 of the lane-group hold row x (the pre-update p, what the
+// lookup read) and the sum g, and every one of them calls; g becomes (c / n) (g - (x.g / n^2) x) where n = |x| > c -- n^2 in
+// mrec_row_sumsq's order and the decision mrec_clip_scale's, so it is the lookup's -- and stays as it is otherwise.  True where
+// the row was clipped.  One body for the sparse apply (clip_grad, mrec_apply.hip) and the dense optimizers' group sums
+// (k_clip_group_sums, mrec_gather.hip).
+__device__ __forceinline__ bool mrec_clip_jacobian(float4& g, const float4& x, float c, int ds, int nd, int lane0) {
+    const float n2 = mrec_row_sumsq(x, ds, nd, lane0);
+    float d = x.x * g.x;
+    d = d + x.y * g.y;
+    d = d + x.z * g.z;
+    d = d + x.w * g.w;
+    d = mrec_group_sum(d, ds, nd, lane0);
+    float s;
+    const bool hit = mrec_clip_scale(n2, c, &s);
+    if (hit) {
+        const float t = d / n2;
+        g.x = s * (g.x - t * x.x);
+        g.y = s * (g.y - t * x.y);
+        g.z = s * (g.z - t * x.z);
+        g.w = s * (g.w - t * x.w);
+    }
+    return hit;
+}

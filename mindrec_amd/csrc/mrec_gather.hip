@@ -651,6 +651,35 @@ __global__ __launch_bounds__(256) void k_rows_to_groups(const int* __restrict__ 
     }
 }
 
+// max_norm in front of a DENSE optimizer (the bprop of mrec_gather_rows_clip_* where nn.Adam sweeps the whole table: DeepFM, Deep&Cross):
+// every occurrence of a row shares the row's Jacobian, so the step's group sums [U, D] (mrec_segment_sum_*) go through it once per
+// group, in place, before the optimizer reads them -- G <- (c / n) (G - (x.G / n^2) x) where n = |x| > c, x = p[uniq[g]] at its
+// pre-update value (mrec_clip_jacobian: the sparse apply's arithmetic and the lookup's decision, bit for bit).  The lookup's geometry:
+// a lane-group of nd = D / 4 lanes holds a row, one float4 per lane, 64 / nd groups per wave.  A group past min(U, *n_uniq_dev)
+// or whose row is outside [0, V) (the -1 of an un-admitted key) loads nothing and stores nothing; an unclipped group stores nothing
+// either, so its sum stays bit for bit.  Whole lane-groups take or skip every branch together and every lane of a live wave reaches the
+// butterfly (its partners are lanes of its own lane-group); the spare lanes behind the last group leave at the top: nobody reads them.
+__global__ __launch_bounds__(256) void k_clip_group_sums(const float* __restrict__ p, int64_t V, int64_t ld, const int* __restrict__ uniq,
+                                                         int64_t U, const int64_t* __restrict__ n_uniq_dev, float* __restrict__ sums, int D,
+                                                         RowGeom gm, float c) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    int64_t n = U;
+    if (n_uniq_dev) { const int64_t x = *n_uniq_dev; n = x < 0 ? 0 : (x < U ? x : U); }
+    const int64_t g = ((int64_t)blockIdx.x * 4 + wave) * gm.G + grp;
+    const int64_t r = g < n ? (int64_t)uniq[g] : -1;
+    const bool ok = r >= 0 && r < V;
+    const int col = sub * 4;
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f), G = x;
+    if (ok) {
+        x = *(const float4*)(p + r * ld + col);
+        G = *(const float4*)(sums + g * D + col);
+    }
+    const bool hit = mrec_clip_jacobian(G, x, c, sub, gm.lpr, lane - sub);      // (a zero row -- every skipped group -- is never clipped)
+    if (ok && hit) *(float4*)(sums + g * D + col) = G;
+}
+
 template <bool SH>
 __global__ __launch_bounds__(256) void k_dense_adam4_g16(float4* __restrict__ p, float4* __restrict__ m,
                                                          float4* __restrict__ v, const uint2* __restrict__ g,
@@ -1268,6 +1297,23 @@ MREC_API int mrec_dense_adam_rows_l2_f32(float* p, float* m, float* v, int64_t V
     if (v4) k_dense_adam_rows_l2<4><<<gr, 256, 0, st>>>(p, m, v, V, D, row_group, sums, h, l2_scaled, partial, (const StepState*)step_state);
     else k_dense_adam_rows_l2<1><<<gr, 256, 0, st>>>(p, m, v, V, D, row_group, sums, h, l2_scaled, partial, (const StepState*)step_state);
     if (sumsq) k_sumsq_finish<<<1, 256, 0, st>>>(partial, (int)gr, sumsq, sumsq_accumulate);
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+/* max_norm in front of a dense optimizer (see include/mrec.h): one launch, no workspace; everything is checked before it. */
+MREC_API int mrec_clip_group_sums_f32(const float* p, int64_t V, int64_t ld, int32_t D, const int32_t* uniq_rows, int64_t U,
+                                      const int64_t* n_uniq_dev, float* sums, float max_norm, void* stream) {
+    const int rc = clip_check(max_norm, D, 256);
+    if (rc != MREC_OK) return rc;
+    if (V < 0 || U < 0 || ld < D) return MREC_EINVAL;
+    if (!p || !uniq_rows || !sums) return MREC_EINVAL;
+    if (ld % 4 || !al16(p) || !al16(sums)) return MREC_EUNSUPPORTED;
+    RowGeom gm{D / 4, 64 / (D / 4)};
+    const int64_t blocks = mrec_cdiv(U, (int64_t)4 * gm.G);
+    if (blocks > 0x7FFFFFFF) return MREC_EUNSUPPORTED;
+    if (U == 0 || V == 0) return MREC_OK;
+    k_clip_group_sums<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, V, ld, uniq_rows, U, n_uniq_dev, sums, D, gm, max_norm);
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }

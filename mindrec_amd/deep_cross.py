@@ -21,7 +21,7 @@ engine (tests/) runs a torch restatement of the same math.
 """
 import contextlib
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -48,6 +48,10 @@ class DeepCrossConfig:
     fp32_matmul: str = "x3"       # the DenseLayers' fp32 MatMuls: "x3" = three-part bf16 operands on the 16-bit matrix instruction
                                   # (fp32-class accuracy at 6/16 of the fp32-MFMA time, csrc/mrec_gemm_x3.hip); "exact" = the
                                   # fp32-input matrix instruction (a k-ordered chain of fmaf per output, csrc/mrec_gemm_f32.hip)
+    max_norm: Optional[float] = None   # nn.EmbeddingLookup(max_norm=c) (embedding.py:156-161,202-205): every looked-up row is clipped to norm
+                                  # c before the mask multiply, and the table's gradient goes through the clip's Jacobian
+                                  # (ops.clip_group_sums_ in front of the dense Adam).  emb_dim % 4 == 0, emb_dim <= 256: the default
+                                  # emb_dim = 30 cannot clip
 
 
 class DeepCrossEngine:
@@ -61,6 +65,7 @@ class DeepCrossEngine:
         if not self._gpu and not self._allow_cpu:
             raise RuntimeError("DeepCrossEngine runs on an MI355X (no CPU fallback)")
         V, D, dev = cfg.vocab_size, cfg.emb_dim, self.device
+        self._max_norm = ops.engine_max_norm(cfg.max_norm, D, "DeepCrossEngine", "; the default emb_dim = 30 cannot clip: use 28 or 32")
         X = cfg.field_size * D
         with (torch.cuda.device(dev) if self._gpu else contextlib.nullcontext()):
             self.table = torch.empty((V, D), dtype=torch.float32, device=dev)
@@ -126,9 +131,14 @@ class DeepCrossEngine:
     def _train_step_generic(self, ids, wts, label):
         raise self._unsupported("training step")
 
+    def _clip_kw(self):
+        """{"max_norm": c} for the lookup when cfg.max_norm is set, {} otherwise (the calls are then exactly the ones of an engine
+        without the field)"""
+        return {} if self._max_norm is None else {"max_norm": self._max_norm}
+
     def predict(self, ids, wts):
         B, Fd = ids.shape
-        emb = self.k.gather_rows(self.table, ids, wts).view(B, Fd * self.cfg.emb_dim)
+        emb = self.k.gather_rows(self.table, ids, wts, **self._clip_kw()).view(B, Fd * self.cfg.emb_dim)
         with torch.no_grad():
             logit = self.forward(emb)
         return logit, torch.sigmoid(logit)
@@ -174,7 +184,7 @@ class DeepCrossEngine:
         # the critical chain (mindrec_amd/wide_deep.py, _front)
         main = torch.cuda.current_stream()
         fork = main.record_event() if self._side is not None else None
-        emb = k.gather_rows(self.table, ids, wts).view(B, X)
+        emb = k.gather_rows(self.table, ids, wts, **self._clip_kw()).view(B, X)
         plan = None
         if self._side is not None:
             self._side.wait_event(fork)
@@ -225,6 +235,8 @@ class DeepCrossEngine:
         else:
             main.wait_stream(self._side)
         sums = k.segment_sum(plan, g.view(B * Fd, D), wts)
+        if self._max_norm is not None:                # the bprop of the clipped lookup, at the rows' pre-update values: one more node
+            k.clip_group_sums_(sums, plan, self.table, self._max_norm)
         kw = dict(lr=cfg.learning_rate, beta1=float(self.beta1), beta2=float(self.beta2), eps=cfg.eps, beta1_power=0.0, beta2_power=0.0,
                   grad_scale=1.0 / cfg.loss_scale, step_state=self._state)
         # nn.Adam over the whole table; its gradient (the bprop of Gather) is nonzero on the touched rows only: looked up per row

@@ -17,7 +17,7 @@ mlp_dtype="fp32" keeps a torch restatement (library GEMMs) -- the form the oracl
 """
 import contextlib
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -44,6 +44,10 @@ class DeepFMConfig:
                                   # deepfm.py:135-145); "bf16" runs the same kernels, "fp32" the fp32 kernels (ops.x3_* / ops.dense32_*)
     graphs: str = "mlp"           # "mlp": the dense net's step replays as HIP graphs (16-bit net), "none": kernel by kernel
     fp32_matmul: str = "x3"       # fp32 net: "x3" three-part bf16 operands on the 16-bit matrix instruction, "exact" the fp32-input one
+    max_norm: Optional[float] = None   # nn.EmbeddingLookup(max_norm=c) of the [V, D] table (embedding.py:156-161,202-205): every looked-up
+                                  # row is clipped to norm c before the mask multiply, and the table's gradient goes through the clip's
+                                  # Jacobian (ops.clip_group_sums_ in front of the dense Adam; the hash engine: the clipped LazyAdam).
+                                  # The [V, 1] linear weights are never clipped; emb_dim % 4 == 0, emb_dim <= 256
 
 
 class _DeepFMNet(DenseNetMixin):
@@ -128,6 +132,7 @@ class DeepFMEngine(_DeepFMNet):
         if not self._gpu and not self._allow_cpu:
             raise RuntimeError("DeepFMEngine runs on an MI355X (no CPU fallback)")
         V, D, dev = cfg.data_vocab_size, cfg.data_emb_dim, self.device
+        self._max_norm = ops.engine_max_norm(cfg.max_norm, D, "DeepFMEngine")
         with (torch.cuda.device(dev) if self._gpu else contextlib.nullcontext()):
             self.V_l2 = torch.empty((V, D), dtype=torch.float32, device=dev)
             self.k.fill_normal_(self.V_l2, cfg.seed, cfg.init_sigma)
@@ -140,9 +145,14 @@ class DeepFMEngine(_DeepFMNet):
         cfg = self.cfg
         B, Fd = ids.shape
         D = cfg.data_emb_dim
-        vx = self.k.gather_rows(self.V_l2, ids, wts)                     # [B, F, D], mask fused
+        vx = self.k.gather_rows(self.V_l2, ids, wts, **self._clip_kw())  # [B, F, D], (clip,) mask fused
         linear = self.k.wide_sum(self.W_l2, ids, wts)                    # [B]
         return vx, linear
+
+    def _clip_kw(self):
+        """{"max_norm": c} for the V table's lookup when cfg.max_norm is set, {} otherwise (the calls are then exactly the ones of an
+        engine without the field)"""
+        return {} if self._max_norm is None else {"max_norm": self._max_norm}
 
     def predict(self, ids, wts):
         with torch.no_grad():
@@ -188,8 +198,12 @@ class DeepFMEngine(_DeepFMNet):
             # nn.Adam over the WHOLE table, the gradient nonzero on the touched rows only: the group sums are looked up per row inside
             # the Adam kernel's one pass (no [V, D] gradient is zeroed, scattered into and read back)
             m, v = self.state[name]
-            self.k.dense_adam_rows_l2_(table, m, v, plan, self.k.segment_sum(plan, g, scale), cfg.l2_coef * sens, sumsq=self._sumsq,
-                                       accumulate=i > 0, **kw)
+            sums = self.k.segment_sum(plan, g, scale)
+            if name == "V" and self._max_norm is not None:
+                # the bprop of the clipped lookup: the group sums through the clip's Jacobian at the rows' pre-update values.  The L2
+                # term (and sumsq) stay on the raw table: the loss's L2 is over the parameters, not the looked-up rows
+                self.k.clip_group_sums_(sums, plan, table, self._max_norm)
+            self.k.dense_adam_rows_l2_(table, m, v, plan, sums, cfg.l2_coef * sens, sumsq=self._sumsq, accumulate=i > 0, **kw)
         loss = log_loss.detach() + (self._sumsq * (cfg.l2_coef * 0.5)).to(torch.float32).view(())
         self._dense_adam(1.0 / sens)
         return loss
@@ -211,13 +225,18 @@ class DeepFMHashEngine(_DeepFMNet):
     One Unique serves both tables (same keys, as wide_and_deep.py:300-302)."""
 
     def __init__(self, cfg: DeepFMConfig, device, key_dtype=torch.int64, capacity=1 << 22, permit_filter_value=1,
-                 evict_filter_value=None, rank=0, world=1, comm=None, shard_capacity_factor=1.25):
+                 evict_filter_value=None, rank=0, world=1, comm=None, shard_capacity_factor=1.25, max_norm=None):
         """rank / world > 1: both hash tables are sharded by key -- owner = hash(key) mod world, the raw keys travel, every owner
         keeps its own key index, admission counters and optimizer state -- over the fixed-capacity exchange of
         mindrec_amd/wide_deep_shard.py (static message shapes, no host round trip); the dense net is data parallel with one
-        all-reduce(mean).  comm: collectives provider (default: torch.distributed, i.e. RCCL on device tensors)."""
+        all-reduce(mean).  comm: collectives provider (default: torch.distributed, i.e. RCCL on device tensors).
+        max_norm=c (or cfg.max_norm): HashEmbeddingLookup(max_norm=c) on V -- the clipped lookup and the clipped LazyAdam
+        (ops.sparse_lazy_adam_(max_norm=c)); W is never clipped.  One GPU only."""
         from .experimental import MAX_SIZE, MapParameter
         self.cfg, self.device = cfg, torch.device(device)
+        self._max_norm = ops.engine_max_norm(cfg.max_norm if max_norm is None else max_norm, cfg.data_emb_dim, "DeepFMHashEngine")
+        if self._max_norm is not None and int(world) > 1:
+            raise ValueError("max_norm is not supported with key shards (world > 1)")
         if self.device.type != "cuda":
             raise RuntimeError("DeepFMHashEngine runs on an MI355X (no CPU fallback)")
         self.rank, self.world, self.cap_factor = int(rank), int(world), float(shard_capacity_factor)
@@ -241,6 +260,10 @@ class DeepFMHashEngine(_DeepFMNet):
             from .wide_deep_shard import OverflowGuard
             n = self.dense_flat.numel()
             self._guard = OverflowGuard(self.dense_grad_full[n:n + 1], self.cap_factor)
+
+    def _clip_kw(self):
+        """{"max_norm": c} for V's lookup and apply when max_norm is set, {} otherwise (the calls are then exactly the plain ones)"""
+        return {} if self._max_norm is None else {"max_norm": self._max_norm}
 
     def _lookup(self, keys, insert):
         flat = self.V._keys(keys)
@@ -320,7 +343,7 @@ class DeepFMHashEngine(_DeepFMNet):
                 vx, linear, _ = self._shard_lookup(keys, wts, train=False)      # (a collective: every rank calls predict)
             else:
                 _, _, pos_v, _, pos_w = self._lookup(keys, insert=True)
-                vx = ops.gather_rows(self.V.values, pos_v.view(B, Fd), wts)
+                vx = ops.gather_rows(self.V.values, pos_v.view(B, Fd), wts, **self._clip_kw())
                 linear = ops.wide_sum(self.W.values, pos_w.view(B, Fd), wts)
             fm, _ = ops.fm_forward(vx)
             logit = (linear + fm).view(-1, 1) + self._mlp(vx.view(B, -1))
@@ -339,15 +362,15 @@ class DeepFMHashEngine(_DeepFMNet):
             self._guard.probe()
             return loss
         d, rows_v, pos_v, rows_w, pos_w = self._lookup(keys, insert=True)
-        vx = ops.gather_rows(self.V.values, pos_v.view(B, Fd), wts)             # [B, F, D], mask fused
+        vx = ops.gather_rows(self.V.values, pos_v.view(B, Fd), wts, **self._clip_kw())      # [B, F, D], (clip,) mask fused
         linear = ops.wide_sum(self.W.values, pos_w.view(B, Fd), wts)             # [B]
         loss, g_vx, g_lin = self._net_step(vx, None, linear, label)
         kw = self._adam_kw(1.0 / cfg.loss_scale)
         plan = ops.group_by_inverse(d)
-        for t, rows_u, g, scale in ((self.V, rows_v, g_vx.view(B * Fd, D), wts),
-                                    (self.W, rows_w, (g_lin.view(B, 1) * wts).view(B * Fd, 1), None)):
+        for t, rows_u, g, scale, clip in ((self.V, rows_v, g_vx.view(B * Fd, D), wts, self._clip_kw()),
+                                          (self.W, rows_w, (g_lin.view(B, 1) * wts).view(B * Fd, 1), None, {})):
             plan.uniq_buf = t.admitted_rows(rows_u)               # groups -> table rows, un-admitted keys -> -1 (skipped)
-            ops.sparse_lazy_adam_(t.values, t.slots["moment1"]["table"], t.slots["moment2"]["table"], plan, g, scale, **kw)
+            ops.sparse_lazy_adam_(t.values, t.slots["moment1"]["table"], t.slots["moment2"]["table"], plan, g, scale, **kw, **clip)
         self._dense_adam(1.0 / cfg.loss_scale)
         return loss.detach()
 

@@ -83,9 +83,10 @@ def _max_norm_of(c):
 
 
 def _refuse_max_norm(owner, what):
-    """No lowering drops a lookup's max_norm: the engines other than Wide&Deep's have no clip."""
+    """No lowering drops a lookup's max_norm: the Deep&Cross and DeepFM lowerings do not hand it to their engines' configs
+    (DeepCrossConfig.max_norm / DeepFMConfig.max_norm are reached by building the engine directly)."""
     if any(_lookup_table(x) and _max_norm_of(x) is not None for x in owner.cells()):
-        raise LoweringRefused(f"max_norm on an embedding lookup of a {what} model: no engine mode clips its rows")
+        raise LoweringRefused(f"max_norm on an embedding lookup of a {what} model is not lowered: the step runs primitive by primitive")
 
 
 def _chain(layers, width_in):

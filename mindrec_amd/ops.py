@@ -178,6 +178,18 @@ def _max_norm(max_norm):
     return c
 
 
+def engine_max_norm(max_norm, emb_dim, who, note=""):
+    """An engine's max_norm at construction: None stays None; else the float the clipped lookup and its backward take, refused where
+    they would refuse it -- a value that is not a finite number > 0, a row width that is not a multiple of 4 or wider than 256."""
+    if max_norm is None:
+        return None
+    if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float, np.number)) or not (math.isfinite(max_norm) and max_norm > 0):
+        raise ValueError(f"{who}: max_norm must be a finite number > 0, got {max_norm!r}")
+    if emb_dim % 4 or emb_dim > 256:
+        raise ValueError(f"{who}: max_norm needs emb_dim % 4 == 0 and emb_dim <= 256 (emb_dim={emb_dim}{note})")
+    return float(max_norm)
+
+
 def _pool(pool):
     """pool=L as the C entry point takes it: an integer bag length >= 1 (None: the plain apply)."""
     L = int(pool)
@@ -814,6 +826,23 @@ def dense_adam_rows_l2_(p, m, v, plan, sums, l2_scaled=0.0, sumsq=None, accumula
     _lib.call("mrec_dense_adam_rows_l2_f32", _ptr(p), _ptr(m), _ptr(v), V, D, _ptr(uniq), U, _ptr(plan.n_uniq_dev), _ptr(sums), lr, beta1,
               beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), float(l2_scaled), _ptr(sumsq), int(bool(accumulate)),
               C.c_void_p(step_state.buf.data_ptr()) if step_state is not None else None, _ptr(ws), ws.numel(), _stream())
+
+
+def clip_group_sums_(sums, plan, p, max_norm):
+    """The bprop of gather_rows(p, ..., max_norm=c) for a DENSE optimizer: `sums` [>= U, D] (ops.segment_sum over the plan's groups)
+    goes through the clip's Jacobian in place -- each group's sum G becomes (c / n)(G - (x.G / n^2) x) where n = |x| > c, x = the
+    group's row of p, and stays bit for bit otherwise -- and is returned.  Every occurrence of a row shares the row's Jacobian, so
+    clipping the summed gradient is exact.  The call must run BEFORE the optimizer that updates p (dense_adam_rows_l2_): x is the row
+    the step's lookup read, and the clip decision is that lookup's, bit for bit.  Groups past the plan's device count and groups
+    whose row is outside [0, V) are left alone.  D % 4 == 0, D <= 256, 16-byte aligned rows."""
+    _need_cuda(sums, p)
+    V, D, ld = _table(p)
+    uniq = plan.uniq_buf if plan.uniq_buf.dtype == torch.int32 else plan.uniq_buf.to(torch.int32)
+    U = uniq.numel()
+    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[1] != D or sums.shape[0] < U or not sums.is_contiguous():
+        raise TypeError("clip_group_sums_: sums must be contiguous float32 [>= U, D]")
+    _lib.call("mrec_clip_group_sums_f32", _ptr(p), V, ld, D, _ptr(uniq), U, _ptr(plan.n_uniq_dev), _ptr(sums), _max_norm(max_norm), _stream())
+    return sums
 
 
 def dense_ftrl_(var, accum, linear, g, lr=5e-2, l1=1e-8, l2=1e-8, lr_power=-0.5, grad_scale=1.0):
