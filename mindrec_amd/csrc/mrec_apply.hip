@@ -1135,8 +1135,6 @@ __global__ __launch_bounds__(256) void k_finish_dense_adam_clip(ApplyFinish f, D
                                 (int64_t)(blockIdx.x - front) * 256 + threadIdx.x, (int64_t)(gridDim.x - front) * 256);
 }
 
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 thread_local hipEvent_t t_prof_start = nullptr, t_prof_stop = nullptr;
 // What an mrec_apply_opts_t asks of ONE apply, decoded: fa.F == 0: not pooled; clip == 0: no max_norm; cc.mask == nullptr: no constant
 // columns; defer: the finishing pass is handed back, not launched (mrec_sparse_lazy_adam_wide_defer fills it in, not the record).
@@ -1781,30 +1779,13 @@ MREC_API int mrec_dense_adam_slabs_finish_f32(float* p, float* m, float* v, cons
     if (n > 0 && (!p || !m || !v || !g || (nseg > 0 && (!slabs || !starts || !lens || !splits)) || (shadow_kind && !shadow16))) return MREC_EINVAL;
     if (n % 4 || !al16(p) || !al16(m) || !al16(v) || !al16(g) || (shadow16 && (((uintptr_t)shadow16) & 7))) return MREC_EUNSUPPORTED;
     SlabSegs sg;
-    sg.n = nseg;
-    for (int q = 0; q < nseg; ++q) {
-        if (!slabs[q] || starts[q] < 0 || lens[q] <= 0 || starts[q] % 4 || lens[q] % 4 || starts[q] + lens[q] > n || splits[q] <= 0 ||
-            !al16(slabs[q]))
-            return MREC_EINVAL;
-        sg.part[q] = (const float4*)slabs[q];
-        sg.start4[q] = starts[q] / 4;
-        sg.len4[q] = lens[q] / 4;
-        sg.S[q] = splits[q];
-    }
+    if (const int rc = slab_segs_from(nseg, slabs, starts, lens, splits, n, sg, nullptr)) return rc;
     DenseAdamSlabArgs a;
     a.p = (float4*)p; a.m = (float4*)m; a.v = (float4*)v; a.g = (const float4*)g; a.n4 = n / 4; a.shadow = (uint2*)shadow16;
     a.ss = (const StepState*)step_state;
     a.h = adam_hyper(lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov);
-    a.f1.idx = -1;
-    a.f1.h = FtrlH{1.0f, 0.0f, 0.0f, -0.5f, grad_scale};
-    if (one && one->index >= 0) {
-        if (one->index >= n || !(one->lr > 0.0f) || one->l1 < 0.0f || one->l2 < 0.0f || one->lr_power > 0.0f) return MREC_EINVAL;
-        a.f1.idx = one->index;
-        a.f1.h = FtrlH{one->lr, one->l1, one->l2, one->lr_power, grad_scale};
-    }
-    int64_t ab = mrec_cdiv(a.n4, 256);
-    if (ab > 256 * 16) ab = 256 * 16;
-    const unsigned grid = fp->lblocks + fp->cfin + (unsigned)ab;
+    if (const int rc = ftrl1_from(one, n, grad_scale, &a.f1)) return rc;
+    const unsigned grid = fp->lblocks + fp->cfin + (a.n4 > 0 ? stream_grid(a.n4) : 0u);      // (an empty dense buffer: the finishing pass alone)
     if (grid == 0) return MREC_OK;
     hipStream_t st = (hipStream_t)stream;
 #define MREC_FIN(KT)                                                                                      \

@@ -44,9 +44,22 @@ struct MrecArena {
 
 static inline int64_t mrec_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// Grid of a grid-stride kernel of 256-thread workgroups: one thread per item, capped at 4096 workgroups.
+static inline unsigned stream_grid(int64_t work_items) {
+    int64_t b = mrec_cdiv(work_items, 256);
+    if (b > 256 * 16) b = 256 * 16;
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
+
 constexpr int kWave = 64;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// fp32 -> bf16, round to nearest even
+__device__ __forceinline__ uint16_t f2bf(float x) { __bf16 b = (__bf16)x; return __builtin_bit_cast(uint16_t, b); }
 
 __host__ __device__ __forceinline__ uint64_t mrec_mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
@@ -99,6 +112,17 @@ __device__ __forceinline__ int block_excl_scan_256(int x, int* smem, int* total)
 }
 
 // ---- max_norm (nn.ClipByNorm over a looked-up row) ----------------------------------------------------------------------
+/* max_norm: finite and > 0 (else MREC_EINVAL); D % 4 == 0 and D <= max_d (else MREC_EUNSUPPORTED) -- checked before any launch */
+static inline int clip_check(float max_norm, int32_t D, int32_t max_d) {
+    if (!(max_norm > 0.0f) || !(max_norm <= 3.402823466e38f)) return MREC_EINVAL;
+    if (D <= 0) return MREC_EINVAL;
+    if (D % 4 || D > max_d) return MREC_EUNSUPPORTED;
+    return MREC_OK;
+}
+
+// Lane-group geometry shared by the row kernels: lpr lanes per row, G = 64/lpr groups per wave.
+namespace { struct RowGeom { int lpr; int G; }; }
+
 // A row of D = 4 nd columns sits in nd consecutive lanes of a lane-group, four columns each; `lane0` is the hardware lane of deep
 // lane 0 and `ds` this lane's deep lane number (the wide lane, where a group has one, passes any ds and ignores the result; it is
 // never read).  mrec_group_sum adds one value per deep lane in an order fixed by the deep lane numbers alone -- a butterfly over
@@ -134,7 +158,7 @@ __device__ __forceinline__ bool mrec_clip_scale(float n2, float c, float* scale)
 // lookup read) and the sum g, and every one of them calls; g becomes (c / n) (g - (x.g / n^2) x) where n = |x| > c -- n^2 in
 // mrec_row_sumsq's order and the decision mrec_clip_scale's, so it is the lookup's -- and stays as it is otherwise.  True where
 // the row was clipped.  One body for the sparse apply (clip_grad, mrec_apply.hip) and the dense optimizers' group sums
-// (k_clip_group_sums, mrec_gather.hip).
+// (k_clip_group_sums, mrec_dense_optim.hip).
 __device__ __forceinline__ bool mrec_clip_jacobian(float4& g, const float4& x, float c, int ds, int nd, int lane0) {
     const float n2 = mrec_row_sumsq(x, ds, nd, lane0);
     float d = x.x * g.x;

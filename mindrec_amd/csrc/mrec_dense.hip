@@ -14,8 +14,6 @@ namespace {
 
 using mgemm::Args;
 
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 int g_cu_count = 0;
 int cu_count() {
     if (g_cu_count == 0) {

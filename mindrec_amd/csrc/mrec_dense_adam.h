@@ -1,24 +1,32 @@
 // mrec_dense_adam.h -- the dense Adam over a flat buffer whose gradient is partly fp32 slabs (the dense net's optimizer step),
-// as a device body shared by its own kernel (mrec_gather.hip) and by the launch that also finishes the sparse apply's
-// window-crossing runs (k_finish_dense_adam, mrec_apply.hip).
+// as a device body shared by its own kernel (launched from mrec_dense_optim.hip) and by the launch that also finishes the sparse
+// apply's window-crossing runs (k_finish_dense_adam, mrec_apply.hip) -- and the host prologue the entries of both files share.
 #pragma once
 #include "mrec_common.h"
 #include "mrec_optim.h"
 
 namespace {
 
-__device__ __forceinline__ uint16_t f2bf(float x) { __bf16 b = (__bf16)x; return __builtin_bit_cast(uint16_t, b); }
-
 // One element of a dense buffer may belong to FTRL instead of Adam (Ftrl1: its index, or -1): Wide&Deep's `wide_b`, which
 // TrainStepWrap hands to the FTRL optimizer with the wide table (wide_and_deep.py:407-411) while it lives in the dense net's flat
 // buffer here -- its `m` word is FTRL's accum, its `v` word FTRL's linear.  A uniform compare per vector; no second launch.
 struct Ftrl1 { int64_t idx; FtrlH h; };
 
+// (host) mrec_ftrl1_t -> Ftrl1: no record, or a negative index, is "no FTRL element"; a record that names one is checked whole
+inline int ftrl1_from(const mrec_ftrl1_t* one, int64_t n, float grad_scale, Ftrl1* out) {
+    out->idx = -1;
+    out->h = FtrlH{1.0f, 0.0f, 0.0f, -0.5f, grad_scale};
+    if (!one || one->index < 0) return MREC_OK;
+    if (one->index >= n || !(one->lr > 0.0f) || one->l1 < 0.0f || one->l2 < 0.0f || one->lr_power > 0.0f) return MREC_EINVAL;
+    out->idx = one->index;
+    out->h = FtrlH{one->lr, one->l1, one->l2, one->lr_power, grad_scale};
+    return MREC_OK;
+}
+
 __device__ __forceinline__ void adam_or_ftrl(float& p, float& m, float& v, float g, const AdamH& h, bool ftrl, const FtrlH& fh) {
     if (ftrl) ftrl_elem(p, m, v, g, fh);
     else adam_elem(p, m, v, g, h);
 }
-
 
 // The same, for the hand-written MFMA weight-gradient kernel (mrec_dense.hip): its split slabs are fp32 partial
 // sums (never rounded), added here in slab order.  SHK: 0 = no shadow, 1 = bf16 shadow, 2 = fp16 shadow.
@@ -28,6 +36,27 @@ struct SlabSegs {
     int S[16];
     int n;
 };
+
+// (host) the caller's segment arrays -> SlabSegs: every segment a non-empty run of whole float4s inside [0, n), its slabs 16-byte
+// aligned, at least one of them (else MREC_EINVAL; nseg <= 16 and the arrays themselves are the entry's to check).  *total4
+// (nullable): the float4s of all segments together.
+inline int slab_segs_from(int32_t nseg, const float* const* slabs, const int64_t* starts, const int64_t* lens, const int32_t* splits,
+                          int64_t n, SlabSegs& sg, int64_t* total4) {
+    sg.n = nseg;
+    int64_t t4 = 0;
+    for (int q = 0; q < nseg; ++q) {
+        if (!slabs[q] || starts[q] < 0 || lens[q] <= 0 || starts[q] % 4 || lens[q] % 4 || starts[q] + lens[q] > n || splits[q] <= 0 ||
+            !al16(slabs[q]))
+            return MREC_EINVAL;
+        sg.part[q] = (const float4*)slabs[q];
+        sg.start4[q] = starts[q] / 4;
+        sg.len4[q] = lens[q] / 4;
+        sg.S[q] = splits[q];
+        t4 += lens[q] / 4;
+    }
+    if (total4) *total4 = t4;
+    return MREC_OK;
+}
 
 __device__ __forceinline__ unsigned pack_shadow2(float lo, float hi, int shk) {
     if (shk == 2) {

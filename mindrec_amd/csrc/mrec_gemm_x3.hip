@@ -29,7 +29,6 @@ using mgemm::Args;
 constexpr uint32_t kCodeP = 2u | (1u << 2) | (0u << 4) | (1u << 6) | (0u << 8) | (0u << 10);
 constexpr uint32_t kCodeQ = 0u | (1u << 2) | (2u << 4) | (0u << 6) | (1u << 8) | (0u << 10);
 
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 inline int64_t up64(int64_t x) { return (x + 63) / 64 * 64; }
 
 __device__ __forceinline__ void split3(float x, uint16_t& a, uint16_t& b, uint16_t& c) {

@@ -6,7 +6,6 @@
 namespace {
 
 __device__ __forceinline__ float bf2f(uint16_t x) { return __uint_as_float(((unsigned)x) << 16); }
-__device__ __forceinline__ uint16_t f2bf(float x) { __bf16 b = (__bf16)x; return __builtin_bit_cast(uint16_t, b); }
 
 struct bf8 { uint4 u; };   // 8 bf16
 

@@ -791,6 +791,21 @@ def dense_adam_(p, m, v, g, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_p
               _stream())
 
 
+def _sumsq(sumsq):
+    if sumsq is not None and (sumsq.dtype != torch.float64 or sumsq.numel() != 1):
+        raise TypeError("sumsq must be a float64 [1] device tensor")
+    return _ptr(sumsq)
+
+
+def _group_sums(who, plan, sums, D):
+    """(the plan's group rows as int32, U) once `sums` is seen to hold a row of D per group"""
+    uniq = plan.uniq_buf if plan.uniq_buf.dtype == torch.int32 else plan.uniq_buf.to(torch.int32)
+    U = uniq.numel()
+    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[1] != D or sums.shape[0] < U or not sums.is_contiguous():
+        raise TypeError(f"{who}: sums must be contiguous float32 [>= U, D]")
+    return uniq, U
+
+
 def dense_adam_l2_(p, m, v, g, l2_scaled, sumsq=None, accumulate=False, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_power=0.9,
                    beta2_power=0.999, grad_scale=1.0, use_nesterov=False):
     """nn.Adam over a whole table whose loss carries l2_coef * sum(p^2) / 2 (wide_and_deep.py:356-360; deepfm.py:252-259): `g` holds
@@ -798,11 +813,10 @@ def dense_adam_l2_(p, m, v, g, l2_scaled, sumsq=None, accumulate=False, lr=3.5e-
     before the update in `sumsq` (float64 [1] device tensor; accumulate=True: added onto it) -- one pass instead of four."""
     _need_cuda(p, m, v, g, sumsq)
     n = _flat_same(p, m, v, g)
-    if sumsq is not None and (sumsq.dtype != torch.float64 or sumsq.numel() != 1):
-        raise TypeError("sumsq must be a float64 [1] device tensor")
+    sq = _sumsq(sumsq)
     ws = workspace("adam_l2", _lib.query_bytes("mrec_dense_adam_l2_workspace_bytes", n), p.device)
     _lib.call("mrec_dense_adam_l2_f32", _ptr(p), _ptr(m), _ptr(v), _ptr(g), n, lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale,
-              int(use_nesterov), float(l2_scaled), _ptr(sumsq), int(bool(accumulate)), _ptr(ws), ws.numel(), _stream())
+              int(use_nesterov), float(l2_scaled), sq, int(bool(accumulate)), _ptr(ws), ws.numel(), _stream())
 
 
 def dense_adam_rows_l2_(p, m, v, plan, sums, l2_scaled=0.0, sumsq=None, accumulate=False, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
@@ -816,15 +830,11 @@ def dense_adam_rows_l2_(p, m, v, plan, sums, l2_scaled=0.0, sumsq=None, accumula
     for t in (p, m, v):
         if _table(t) != (V, D, D) or t.dtype != torch.float32:
             raise TypeError("dense_adam_rows_l2_: p, m, v must be contiguous float32 [V, D] tables")
-    uniq = plan.uniq_buf if plan.uniq_buf.dtype == torch.int32 else plan.uniq_buf.to(torch.int32)
-    U = uniq.numel()
-    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[1] != D or sums.shape[0] < U or not sums.is_contiguous():
-        raise TypeError("dense_adam_rows_l2_: sums must be contiguous float32 [>= U, D]")
-    if sumsq is not None and (sumsq.dtype != torch.float64 or sumsq.numel() != 1):
-        raise TypeError("sumsq must be a float64 [1] device tensor")
+    uniq, U = _group_sums("dense_adam_rows_l2_", plan, sums, D)
+    sq = _sumsq(sumsq)
     ws = workspace(f"adam_rows:{V}:{D}", _lib.query_bytes("mrec_dense_adam_rows_l2_workspace_bytes", V, D), p.device)
     _lib.call("mrec_dense_adam_rows_l2_f32", _ptr(p), _ptr(m), _ptr(v), V, D, _ptr(uniq), U, _ptr(plan.n_uniq_dev), _ptr(sums), lr, beta1,
-              beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), float(l2_scaled), _ptr(sumsq), int(bool(accumulate)),
+              beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov), float(l2_scaled), sq, int(bool(accumulate)),
               C.c_void_p(step_state.buf.data_ptr()) if step_state is not None else None, _ptr(ws), ws.numel(), _stream())
 
 
@@ -837,10 +847,7 @@ def clip_group_sums_(sums, plan, p, max_norm):
     whose row is outside [0, V) are left alone.  D % 4 == 0, D <= 256, 16-byte aligned rows."""
     _need_cuda(sums, p)
     V, D, ld = _table(p)
-    uniq = plan.uniq_buf if plan.uniq_buf.dtype == torch.int32 else plan.uniq_buf.to(torch.int32)
-    U = uniq.numel()
-    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[1] != D or sums.shape[0] < U or not sums.is_contiguous():
-        raise TypeError("clip_group_sums_: sums must be contiguous float32 [>= U, D]")
+    uniq, U = _group_sums("clip_group_sums_", plan, sums, D)
     _lib.call("mrec_clip_group_sums_f32", _ptr(p), V, ld, D, _ptr(uniq), U, _ptr(plan.n_uniq_dev), _ptr(sums), _max_norm(max_norm), _stream())
     return sums
 
@@ -1785,6 +1792,17 @@ def sum_slabs(slabs, out):
     return out
 
 
+def _slab_args(slabs):
+    """slabs = [(start, tensor [S, ...] fp32)] as the slab-segment entries take them: the arrays (slabs, starts, lens, splits)"""
+    k = max(len(slabs), 1)
+    ptrs, starts, lens, splits = (C.c_void_p * k)(), (C.c_int64 * k)(), (C.c_int64 * k)(), (C.c_int32 * k)()
+    for q, (start, part) in enumerate(slabs):
+        if part.dtype != torch.float32 or not part.is_contiguous():
+            raise TypeError("slabs must be contiguous float32 [S, ...]")
+        ptrs[q], starts[q], lens[q], splits[q] = part.data_ptr(), int(start), part[0].numel(), part.shape[0]
+    return ptrs, starts, lens, splits
+
+
 def sum_slab_segments_(g, slabs):
     """g[start : start + len] = tensor.sum(0) in slab order for every (start, tensor [S, ...]) of `slabs`, ONE launch."""
     _need_cuda(g)
@@ -1793,16 +1811,7 @@ def sum_slab_segments_(g, slabs):
         return
     if k > 16:
         raise ValueError("at most 16 slab segments")
-    ptrs = (C.c_void_p * k)()
-    starts = (C.c_int64 * k)()
-    lens = (C.c_int64 * k)()
-    splits = (C.c_int32 * k)()
-    for q, (start, part) in enumerate(slabs):
-        if part.dtype != torch.float32 or not part.is_contiguous():
-            raise TypeError("slabs must be contiguous float32 [S, ...]")
-        ptrs[q], starts[q], lens[q], splits[q] = part.data_ptr(), int(start), part[0].numel(), part.shape[0]
-    _lib.call("mrec_dense_sum_slab_segments_f32", _ptr(g), g.numel(), k, C.cast(ptrs, C.c_void_p), C.cast(starts, C.c_void_p),
-              C.cast(lens, C.c_void_p), C.cast(splits, C.c_void_p), _stream())
+    _lib.call("mrec_dense_sum_slab_segments_f32", _ptr(g), g.numel(), k, *_slab_args(slabs), _stream())
 
 
 def dense_adam_slabs_(p, m, v, g, slabs, shadow16=None, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, beta1_power=0.9,
@@ -1822,17 +1831,9 @@ def dense_adam_slabs_(p, m, v, g, slabs, shadow16=None, lr=1e-3, beta1=0.9, beta
         if shadow16.dtype not in _DT16 or shadow16.numel() != n or not shadow16.is_contiguous():
             raise TypeError("shadow16 must be a contiguous bfloat16 / float16 tensor of the parameter's size")
         kind = 1 if shadow16.dtype == torch.bfloat16 else 2
-    ptrs = (C.c_void_p * max(k, 1))()
-    starts = (C.c_int64 * max(k, 1))()
-    lens = (C.c_int64 * max(k, 1))()
-    splits = (C.c_int32 * max(k, 1))()
-    for q, (start, part) in enumerate(slabs):
-        if part.dtype != torch.float32 or not part.is_contiguous():
-            raise TypeError("slabs must be contiguous float32 [S, ...]")
-        ptrs[q], starts[q], lens[q], splits[q] = part.data_ptr(), int(start), part[0].numel(), part.shape[0]
+    segs = _slab_args(slabs)
     f = _ftrl1(ftrl1) if ftrl1 is not None else None
-    args = (_ptr(p), _ptr(m), _ptr(v), _ptr(g), _ptr(shadow16), kind, n, k,
-            C.cast(ptrs, C.c_void_p), C.cast(starts, C.c_void_p), C.cast(lens, C.c_void_p), C.cast(splits, C.c_void_p),
+    args = (_ptr(p), _ptr(m), _ptr(v), _ptr(g), _ptr(shadow16), kind, n, k, *segs,
             lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov),
             _ptr(step_state.buf) if step_state is not None else None, C.cast(C.pointer(f), C.c_void_p) if f is not None else None)
     if finish is not None:        # + the finishing pass of a deferred sparse apply, as the first workgroups of this launch
