@@ -1625,13 +1625,7 @@ MREC_API int mrec_sparse_apply_workspace_bytes(int64_t n, int32_t D, size_t* out
 
 // (key width, gradient kind) -> <K, GT>, each decided in ONE place: uniq_bytes 4 / 8 -> int32_t / int64_t, g_kind 0 / 1 / 2 -> float /
 // bf16_t / f16_t; f gets the typed pointer(s).  An updater asks for the axes it has kernels for and no others -- LazyAdam both, FTRL
-// the key, the segment sum the gradient -- so the instantiations are those of the entries below and nothing else.
-template <class F>
-int by_key(const void* uniq, int uniq_bytes, F&& f) {
-    if (uniq_bytes == 4) return f((const int32_t*)uniq);
-    if (uniq_bytes == 8) return f((const int64_t*)uniq);
-    return MREC_EINVAL;
-}
+// the key, the segment sum the gradient -- so the instantiations are those of the entries below and nothing else.  (by_key: mrec_common.h)
 template <class F>
 int by_grad(const void* g, int g_kind, F&& f) {
     if (g_kind == 0) return f((const float*)g);

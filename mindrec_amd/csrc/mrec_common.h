@@ -54,6 +54,26 @@ static inline unsigned stream_grid(int64_t work_items) {
     return (unsigned)b;
 }
 
+// Host type dispatch: an argument that selects a template parameter is decided in ONE place, and f -- a generic lambda -- gets the typed
+// pointer.  by_key: the width of an id / key 4 / 8 -> const int32_t* / const int64_t*.  by_out: the kind of a lookup's output rows
+// 0 / 1 / 2 -> float* / bf16o_t* / f16o_t* (fp32, bf16, IEEE half: tags; the kernels' vstore overloads round, once, to nearest even).
+// Where both are nested, the kernels are laid out in the code object in the order of the nesting: keep it and two builds compare byte
+// for byte.
+namespace { struct bf16o_t { uint16_t v; }; struct f16o_t { uint16_t v; }; }
+template <class F>
+static inline int by_key(const void* ids, int id_bytes, F&& f) {
+    if (id_bytes == 4) return f((const int32_t*)ids);
+    if (id_bytes == 8) return f((const int64_t*)ids);
+    return MREC_EINVAL;
+}
+template <class F>
+static inline int by_out(void* out, int out_kind, F&& f) {
+    if (out_kind == 0) return f((float*)out);
+    if (out_kind == 1) return f((bf16o_t*)out);
+    if (out_kind == 2) return f((f16o_t*)out);
+    return MREC_EINVAL;
+}
+
 constexpr int kWave = 64;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

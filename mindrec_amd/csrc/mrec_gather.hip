@@ -36,8 +36,7 @@ __device__ __forceinline__ Vf<4> vzero(Vf<4>*) { Vf<4> r; r.v = make_float4(0.f,
 __device__ __forceinline__ Vf<1> vzero(Vf<1>*) { Vf<1> r; r.v = 0.f; return r; }
 
 // bf16 output rows (round-to-nearest-even, the cast the reference applies to the masked embeddings
-// before its mixed-precision MLP, wide_and_deep.py:113-133): halves the gather's write stream.
-struct bf16o_t { uint16_t v; };
+// before its mixed-precision MLP, wide_and_deep.py:113-133): halves the gather's write stream.  (the tag bf16o_t: mrec_common.h)
 __device__ __forceinline__ void vstore(bf16o_t* p, const Vf<4>& x) {
     uint2 u;
     u.x = (unsigned)f2bf(x.v.x) | ((unsigned)f2bf(x.v.y) << 16);
@@ -46,8 +45,7 @@ __device__ __forceinline__ void vstore(bf16o_t* p, const Vf<4>& x) {
 }
 __device__ __forceinline__ void vstore(bf16o_t* p, const Vf<1>& x) { p->v = f2bf(x.v); }
 
-// ... and IEEE half output rows (the reference's own mixed-precision dtype)
-struct f16o_t { uint16_t v; };
+// ... and IEEE half output rows (the reference's own mixed-precision dtype; f16o_t)
 __device__ __forceinline__ unsigned f2h2(float lo, float hi) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const h2 v = {(_Float16)lo, (_Float16)hi};
@@ -491,18 +489,46 @@ __global__ __launch_bounds__(256) void k_move_rows(const float* __restrict__ src
     }
 }
 
-template <class K, class OT = bf16o_t>
-int gather_bf16_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t n,
-                     const float* row_scale, uint16_t* out, void* stream, int wcol = 0, float* wprod = nullptr, int64_t ldo = 0,
-                     int64_t ldw = 2, GatherDrop gd = GatherDrop{}, int ids_stride = 1, int rs_stride = 1, bool skip_invalid = false,
-                     StepState* ss = nullptr, float clip = 0.0f) {
-    constexpr int ob = (int)sizeof(OT);                    // bytes per output element (2: bf16 / f16, 4: fp32 rows + the wide lane)
+// What a row lookup is asked for.  The members without an initialiser are every entry's; an entry fills in those of the rest that differ.
+struct GatherArgs {
+    const float* table;
+    int64_t V, ld;
+    int32_t D;
+    const void* ids;                     // const K*
+    int64_t n;
+    const float* row_scale;
+    void* out;                           // OT*
+    void* stream;
+    int wcol = 0;                        // the wide word's column (it must be D) ...
+    float* wprod = nullptr;              // ... and where its products go, ldw floats apart (nullptr: no wide word)
+    int64_t ldo = 0, ldw = 2;            // ldo: elements between output rows (0: D)
+    GatherDrop gd{};
+    int ids_stride = 1, rs_stride = 1;
+    bool skip_invalid = false;
+    StepState* ss = nullptr;
+    float clip = 0.0f;                   // max_norm (0: none)
+};
+
+// The one launch path of the row lookups: K the id type, OT the output rows' (float, bf16o_t, f16o_t).  Its order of checks is every
+// entry's, so no entry checks anything of its own in front: the entries without a wide word, strides or ldo pass the first two tests by
+// construction and meet n / D / V / ld first, as they always did.
+template <class K, class OT>
+int gather_run(const GatherArgs& a) {
+    constexpr int ob = (int)sizeof(OT);                    // bytes per output element (2: bf16 / f16, 4: fp32 rows)
     const int oa = ob == 2 ? 7 : 15;                       // alignment of an output row's 4-element quad
+    const float *table = a.table, *row_scale = a.row_scale;
+    const K* ids = (const K*)a.ids;
+    OT* out = (OT*)a.out;
+    float* wprod = a.wprod;
+    const int64_t V = a.V, ld = a.ld, n = a.n, ldo = a.ldo, ldw = a.ldw;
+    const int32_t D = a.D;
+    const int ids_stride = a.ids_stride, rs_stride = a.rs_stride;
+    const bool skip_invalid = a.skip_invalid;
+    const float clip = a.clip;
     if ((ldo != 0 && (ldo < D || ldo % 4)) || (wprod && (ldw < 2 || ldw % 2)) || ids_stride < 1 || rs_stride < 1) return MREC_EINVAL;
-    if (wprod && (wcol != D || D % 4 || D > 252 || ld % 4 || ld < D + 4 || !al16(table) || (((uintptr_t)out) & oa) || (((uintptr_t)wprod) & 7)))
+    if (wprod && (a.wcol != D || D % 4 || D > 252 || ld % 4 || ld < D + 4 || !al16(table) || (((uintptr_t)out) & oa) || (((uintptr_t)wprod) & 7)))
         return MREC_EUNSUPPORTED;       // the wide word must sit right behind the deep columns of 16-byte aligned rows
-    if (ob == 4 && !wprod) return MREC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)a.stream;
     if (n < 0 || D <= 0 || V < 0 || ld < D) return MREC_EINVAL;
     if (n == 0) return MREC_OK;
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
@@ -514,69 +540,43 @@ int gather_bf16_impl(const float* table, int64_t V, int64_t ld, int32_t D, const
                      ldo_e % 8 == 0 && al16(out) && (!wprod || al16(wprod)) && al16(ids) && (!row_scale || al16(row_scale)) &&
                      !no_w16;
     if (clip > 0.0f && !vec) return MREC_EUNSUPPORTED;
+    // what the kernels without float4 rows serve: dense output rows, unit strides, no wide word, every position written
+    const bool plain = !wprod && ldo == 0 && ids_stride == 1 && rs_stride == 1 && !skip_invalid;
+    const int lpr = vec ? D / 4 + (wprod ? 1 : 0) : D;     // lanes per row: a float4 each (and the wide lane), or a column each
+    const RowGeom gm{lpr, 64 / lpr};
+    const auto blocks = [&](int rows_in_flight) { return (unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * rows_in_flight); };
     if (w16) {
         if constexpr (ob == 2) {
-            const int lpr = D / 4 + (wprod ? 1 : 0);
-            RowGeom gm{lpr, 64 / lpr};
             if (clip > 0.0f)
-                k_gather_rows_w16<K, OT, float><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * 4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, (OT*)out,
-                                                                                                          D, gm, wprod, ldo_e, gd, ss, clip);
+                k_gather_rows_w16<K, OT, float><<<blocks(4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, out, D, gm, wprod, ldo_e, a.gd, a.ss, clip);
             else
-                k_gather_rows_w16<K, OT><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * 4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, (OT*)out,
-                                                                                                     D, gm, wprod, ldo_e, gd, ss);
+                k_gather_rows_w16<K, OT><<<blocks(4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, out, D, gm, wprod, ldo_e, a.gd, a.ss);
         }
     } else if (vec && clip > 0.0f) {
-        const int lpr = D / 4 + (wprod ? 1 : 0);
-        RowGeom gm{lpr, 64 / lpr};
-        k_gather_rows<4, K, OT, float><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * GB), 256, 0, st>>>(
-            table, V, ld, ids, n, row_scale, (OT*)out, D, gm, wprod, ldo, ldw, gd, ids_stride, rs_stride, skip_invalid, ss, clip);
+        k_gather_rows<4, K, OT, float><<<blocks(GB), 256, 0, st>>>(table, V, ld, ids, n, row_scale, out, D, gm, wprod, ldo, ldw, a.gd, ids_stride,
+                                                                  rs_stride, skip_invalid, a.ss, clip);
     } else if (vec) {
-        const int lpr = D / 4 + (wprod ? 1 : 0);
-        RowGeom gm{lpr, 64 / lpr};
-        k_gather_rows<4, K, OT><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * GB), 256, 0, st>>>(
-            table, V, ld, ids, n, row_scale, (OT*)out, D, gm, wprod, ldo, ldw, gd, ids_stride, rs_stride, skip_invalid, ss);
-    } else if (D <= 64 && !wprod && ldo == 0 && ids_stride == 1 && rs_stride == 1 && !skip_invalid) {
-        RowGeom gm{D, 64 / D};
-        k_gather_rows<1, K, OT><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * GB), 256, 0, st>>>(
-            table, V, ld, ids, n, row_scale, (OT*)out, D, gm);
+        k_gather_rows<4, K, OT><<<blocks(GB), 256, 0, st>>>(table, V, ld, ids, n, row_scale, out, D, gm, wprod, ldo, ldw, a.gd, ids_stride, rs_stride,
+                                                           skip_invalid, a.ss);
+    } else if (plain && D <= 64) {
+        k_gather_rows<1, K, OT><<<blocks(GB), 256, 0, st>>>(table, V, ld, ids, n, row_scale, out, D, gm);
+    } else if (plain && ob == 4) {                         // any other fp32 row: a wave per row
+        if constexpr (ob == 4) k_gather_rows_generic<K><<<(unsigned)mrec_cdiv(n, 4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, out, D);
     } else {
         return MREC_EUNSUPPORTED;
     }
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
+template <class K, class OT>
+int gather_run(const K*, OT*, const GatherArgs& a) { return gather_run<K, OT>(a); }      // (<K, OT> from by_key's and by_out's pointers)
 
-template <class K>
-int gather_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t n,
-                const float* row_scale, float* out, void* stream, bool skip_invalid = false, float clip = 0.0f) {
-    hipStream_t st = (hipStream_t)stream;
-    if (n < 0 || D <= 0 || V < 0 || ld < D) return MREC_EINVAL;
-    if (n == 0) return MREC_OK;
-    if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
-    if (!table || !ids || !out) return MREC_EINVAL;
-    const bool vec = (D % 4 == 0) && (D <= 256) && (ld % 4 == 0) && al16(table) && al16(out);
-    if (clip > 0.0f) {
-        if (!vec) return MREC_EUNSUPPORTED;
-        RowGeom gm{D / 4, 64 / (D / 4)};
-        k_gather_rows<4, K, float, float><<<(unsigned)mrec_cdiv(n, (int64_t)4 * gm.G * GB), 256, 0, st>>>(
-            table, V, ld, ids, n, row_scale, out, D, gm, nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, clip);
-    } else if (vec) {
-        RowGeom gm{D / 4, 64 / (D / 4)};
-        const int64_t rows_per_block = (int64_t)4 * gm.G * GB;
-        k_gather_rows<4, K><<<(unsigned)mrec_cdiv(n, rows_per_block), 256, 0, st>>>(table, V, ld, ids, n, row_scale,
-                                                                                  out, D, gm, nullptr, 0, 2, GatherDrop{}, 1, 1, skip_invalid);
-    } else if (skip_invalid) {
-        return MREC_EUNSUPPORTED;
-    } else if (D <= 64) {
-        RowGeom gm{D, 64 / D};
-        const int64_t rows_per_block = (int64_t)4 * gm.G * GB;
-        k_gather_rows<1, K><<<(unsigned)mrec_cdiv(n, rows_per_block), 256, 0, st>>>(table, V, ld, ids, n, row_scale,
-                                                                                  out, D, gm);
-    } else {
-        k_gather_rows_generic<K><<<(unsigned)mrec_cdiv(n, 4), 256, 0, st>>>(table, V, ld, ids, n, row_scale, out, D);
-    }
-    MREC_LAUNCH_CHECK();
-    return MREC_OK;
+// ... with max_norm, judged before anything else
+template <class K, class OT>
+int gather_clip(GatherArgs a, float max_norm) {
+    if (const int rc = clip_check(max_norm, a.D, 256)) return rc;
+    a.clip = max_norm;
+    return gather_run<K, OT>(a);
 }
 
 template <class K>
@@ -671,61 +671,90 @@ MREC_API int mrec_fill_normal_f32(float* out, int64_t nrows, int32_t D, int64_t 
 
 MREC_API int mrec_gather_rows_f32_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids,
                                       int64_t n, const float* row_scale, float* out, void* stream) {
-    return gather_impl<int32_t>(table, V, ld, D, ids, n, row_scale, out, stream);
+    return gather_run<int32_t, float>({table, V, ld, D, ids, n, row_scale, out, stream});
 }
 MREC_API int mrec_gather_rows_f32_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids,
                                       int64_t n, const float* row_scale, float* out, void* stream) {
-    return gather_impl<int64_t>(table, V, ld, D, ids, n, row_scale, out, stream);
+    return gather_run<int64_t, float>({table, V, ld, D, ids, n, row_scale, out, stream});
 }
 /* ... leaving the rows of ids outside [0, V) ALONE instead of writing zeros (MapTensorGet over new keys: mrec_map_lookup_out has
  * written their default rows into `out` already; 16-byte aligned rows, D % 4 == 0, D <= 256). */
 MREC_API int mrec_gather_rows_f32_skip_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids,
                                            int64_t n, float* out, void* stream) {
-    return gather_impl<int32_t>(table, V, ld, D, ids, n, nullptr, out, stream, true);
+    GatherArgs a{table, V, ld, D, ids, n, nullptr, out, stream};
+    a.skip_invalid = true;
+    return gather_run<int32_t, float>(a);
 }
 
 MREC_API int mrec_gather_rows_bf16_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids,
                                        int64_t n, const float* row_scale, uint16_t* out, void* stream) {
-    return gather_bf16_impl<int32_t>(table, V, ld, D, ids, n, row_scale, out, stream);
+    return gather_run<int32_t, bf16o_t>({table, V, ld, D, ids, n, row_scale, out, stream});
 }
 MREC_API int mrec_gather_rows_bf16_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids,
                                        int64_t n, const float* row_scale, uint16_t* out, void* stream) {
-    return gather_bf16_impl<int64_t>(table, V, ld, D, ids, n, row_scale, out, stream);
+    return gather_run<int64_t, bf16o_t>({table, V, ld, D, ids, n, row_scale, out, stream});
 }
 
 MREC_API int mrec_gather_rows_f16_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids,
                                       int64_t n, const float* row_scale, uint16_t* out, void* stream) {
-    return gather_bf16_impl<int32_t, f16o_t>(table, V, ld, D, ids, n, row_scale, out, stream);
+    return gather_run<int32_t, f16o_t>({table, V, ld, D, ids, n, row_scale, out, stream});
 }
 MREC_API int mrec_gather_rows_f16_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids,
                                       int64_t n, const float* row_scale, uint16_t* out, void* stream) {
-    return gather_bf16_impl<int64_t, f16o_t>(table, V, ld, D, ids, n, row_scale, out, stream);
+    return gather_run<int64_t, f16o_t>({table, V, ld, D, ids, n, row_scale, out, stream});
 }
 
-#define MREC_GATHER_CLIP(NAME, KT, IMPL_CALL)                                                                                      \
-    MREC_API int NAME(const float* table, int64_t V, int64_t ld, int32_t D, const KT* ids, int64_t n, const float* row_scale,      \
-                      void* out, float max_norm, void* stream) {                                                                  \
-        const int rc = clip_check(max_norm, D, 256);                                                                              \
-        if (rc != MREC_OK) return rc;                                                                                             \
-        return IMPL_CALL;                                                                                                         \
-    }
-MREC_GATHER_CLIP(mrec_gather_rows_clip_f32_i32, int32_t, (gather_impl<int32_t>(table, V, ld, D, ids, n, row_scale, (float*)out, stream, false, max_norm)))
-MREC_GATHER_CLIP(mrec_gather_rows_clip_f32_i64, int64_t, (gather_impl<int64_t>(table, V, ld, D, ids, n, row_scale, (float*)out, stream, false, max_norm)))
-MREC_GATHER_CLIP(mrec_gather_rows_clip_bf16_i32, int32_t, (gather_bf16_impl<int32_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream, 0,
-                                                                                    nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
-MREC_GATHER_CLIP(mrec_gather_rows_clip_bf16_i64, int64_t, (gather_bf16_impl<int64_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream, 0,
-                                                                                    nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
-MREC_GATHER_CLIP(mrec_gather_rows_clip_f16_i32, int32_t, (gather_bf16_impl<int32_t, f16o_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream,
-                                                                                           0, nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
-MREC_GATHER_CLIP(mrec_gather_rows_clip_f16_i64, int64_t, (gather_bf16_impl<int64_t, f16o_t>(table, V, ld, D, ids, n, row_scale, (uint16_t*)out, stream,
-                                                                                           0, nullptr, 0, 2, GatherDrop{}, 1, 1, false, nullptr, max_norm)))
-#undef MREC_GATHER_CLIP
+/* ... with max_norm (out: float / bf16 / f16 rows, by the entry's name) */
+MREC_API int mrec_gather_rows_clip_f32_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, int64_t n,
+                                           const float* row_scale, void* out, float max_norm, void* stream) {
+    return gather_clip<int32_t, float>({table, V, ld, D, ids, n, row_scale, out, stream}, max_norm);
+}
+MREC_API int mrec_gather_rows_clip_f32_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids, int64_t n,
+                                           const float* row_scale, void* out, float max_norm, void* stream) {
+    return gather_clip<int64_t, float>({table, V, ld, D, ids, n, row_scale, out, stream}, max_norm);
+}
+MREC_API int mrec_gather_rows_clip_bf16_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, int64_t n,
+                                            const float* row_scale, void* out, float max_norm, void* stream) {
+    return gather_clip<int32_t, bf16o_t>({table, V, ld, D, ids, n, row_scale, out, stream}, max_norm);
+}
+MREC_API int mrec_gather_rows_clip_bf16_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids, int64_t n,
+                                            const float* row_scale, void* out, float max_norm, void* stream) {
+    return gather_clip<int64_t, bf16o_t>({table, V, ld, D, ids, n, row_scale, out, stream}, max_norm);
+}
+MREC_API int mrec_gather_rows_clip_f16_i32(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, int64_t n,
+                                           const float* row_scale, void* out, float max_norm, void* stream) {
+    return gather_clip<int32_t, f16o_t>({table, V, ld, D, ids, n, row_scale, out, stream}, max_norm);
+}
+MREC_API int mrec_gather_rows_clip_f16_i64(const float* table, int64_t V, int64_t ld, int32_t D, const int64_t* ids, int64_t n,
+                                           const float* row_scale, void* out, float max_norm, void* stream) {
+    return gather_clip<int64_t, f16o_t>({table, V, ld, D, ids, n, row_scale, out, stream}, max_norm);
+}
 
+/* what mrec_gather_rows_wide_ex and mrec_gather_rows_wide_clip (clip = max_norm) do: their own arguments judged, then the record */
 static int gather_wide_ex_impl(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
                                int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out,
                                int32_t out_kind, int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw,
-                               const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, void* stream, float clip);
-
+                               const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, void* stream, float clip) {
+    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || id_stride < 1 || id_stride > (1 << 20) || scale_stride < 1 ||
+        scale_stride > (1 << 20))
+        return MREC_EINVAL;
+    if (!wide_prod || wide_col < 0 || wide_col >= ld) return MREC_EINVAL;
+    GatherArgs a{table, V, ld, D, ids, n, row_scale, out, stream};
+    if (drop) {
+        if (out_kind == 0 || fields <= 0 || n % fields || !drop_from(drop, (int64_t)fields * D, &a.gd.d)) return MREC_EINVAL;
+        a.gd.F = fields;
+    }
+    a.wcol = wide_col;
+    a.wprod = wide_prod;
+    a.ldo = ldo == D ? 0 : ldo;
+    a.ldw = ldw;
+    a.ids_stride = (int)id_stride;
+    a.rs_stride = (int)scale_stride;
+    a.skip_invalid = (flags & MREC_GATHER_SKIP_INVALID) != 0;
+    a.ss = (StepState*)step_state;
+    a.clip = clip;
+    return by_key(ids, id_bytes, [&](auto* kp) { return by_out(out, out_kind, [&](auto* op) { return gather_run(kp, op, a); }); });
+}
 /* Gather + the wide branch's products in one pass (see include/mrec.h): out_kind 0 = fp32, 1 = bf16, 2 = f16 rows. */
 MREC_API int mrec_gather_rows_wide_ex(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
                                       int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out,
@@ -740,38 +769,9 @@ MREC_API int mrec_gather_rows_wide_clip(const float* table, int64_t V, int64_t l
                                         int32_t out_kind, int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw,
                                         const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, float max_norm,
                                         void* stream) {
-    const int rc = clip_check(max_norm, D, 252);
-    if (rc != MREC_OK) return rc;
+    if (const int rc = clip_check(max_norm, D, 252)) return rc;
     return gather_wide_ex_impl(table, V, ld, D, ids, id_bytes, id_stride, n, row_scale, scale_stride, out, out_kind, ldo, wide_col, wide_prod,
                                ldw, drop, fields, flags, step_state, stream, max_norm);
-}
-static int gather_wide_ex_impl(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
-                                      int64_t id_stride, int64_t n, const float* row_scale, int64_t scale_stride, void* out,
-                                      int32_t out_kind, int64_t ldo, int32_t wide_col, float* wide_prod, int64_t ldw,
-                                      const mrec_dropout_t* drop, int32_t fields, uint32_t flags, void* step_state, void* stream, float clip) {
-    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || id_stride < 1 || id_stride > (1 << 20) || scale_stride < 1 ||
-        scale_stride > (1 << 20))
-        return MREC_EINVAL;
-    if (!wide_prod || wide_col < 0 || wide_col >= ld) return MREC_EINVAL;
-    GatherDrop gd{};
-    if (drop) {
-        if (out_kind == 0 || fields <= 0 || n % fields || !drop_from(drop, (int64_t)fields * D, &gd.d)) return MREC_EINVAL;
-        gd.F = fields;
-    }
-    if (ldo == D) ldo = 0;
-    const int is = (int)id_stride, rs = (int)scale_stride;
-    const bool skip = (flags & MREC_GATHER_SKIP_INVALID) != 0;
-#define MREC_GW(KT, OT) return gather_bf16_impl<KT, OT>(table, V, ld, D, (const KT*)ids, n, row_scale, (uint16_t*)out, stream, wide_col, \
-                                                        wide_prod, ldo, ldw, gd, is, rs, skip, (StepState*)step_state, clip)
-    if (id_bytes == 4) {
-        if (out_kind == 0) { MREC_GW(int32_t, float); }
-        if (out_kind == 1) { MREC_GW(int32_t, bf16o_t); }
-        MREC_GW(int32_t, f16o_t);
-    }
-    if (out_kind == 0) { MREC_GW(int64_t, float); }
-    if (out_kind == 1) { MREC_GW(int64_t, bf16o_t); }
-    MREC_GW(int64_t, f16o_t);
-#undef MREC_GW
 }
 MREC_API int mrec_gather_rows_wide(const float* table, int64_t V, int64_t ld, int32_t D, const void* ids, int32_t id_bytes,
                                    int64_t n, const float* row_scale, void* out, int32_t out_kind, int64_t ldo, int32_t wide_col,

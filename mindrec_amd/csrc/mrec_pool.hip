@@ -62,9 +62,7 @@ __device__ __forceinline__ void vtouch(Vf<1>& r) { asm volatile("" : "+v"(r.v));
 __device__ __forceinline__ Vf<4> vzero(Vf<4>*) { Vf<4> r; r.v = make_float4(0.f, 0.f, 0.f, 0.f); return r; }
 __device__ __forceinline__ Vf<1> vzero(Vf<1>*) { Vf<1> r; r.v = 0.f; return r; }
 
-// output rows: fp32, bf16 or IEEE half (round-to-nearest-even, once), as the lookup's (mrec_gather.hip)
-struct bf16o_t { uint16_t v; };
-struct f16o_t { uint16_t v; };
+// output rows: fp32, bf16 or IEEE half (round-to-nearest-even, once), as the lookup's (mrec_gather.hip; the tags: mrec_common.h)
 __device__ __forceinline__ unsigned f2h2(float lo, float hi) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const h2 v = {(_Float16)lo, (_Float16)hi};
@@ -160,20 +158,25 @@ __global__ __launch_bounds__(256) void k_gather_pool_fields(const float* __restr
     }
 }
 
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// The launch of all three pooled kernels: float4 lanes (vec) where the rows, and the 4-element quads of every field's output block, are
+// aligned (D % 4 == 0: f * D too), else a column per lane; lpr lanes per bag, at most a wave; four waves of G bags per workgroup.
+struct PoolLaunch { bool vec; PoolGeom gm; unsigned blocks; };
+inline PoolLaunch pool_launch(int32_t D, int64_t ld, int64_t ldo, const void* table, const void* out, size_t out_bytes, int64_t B, int32_t F) {
+    const uintptr_t oa = out_bytes == 2 ? 7 : 15;
+    PoolLaunch p;
+    p.vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
+    const int cols = p.vec ? D / 4 : D;
+    p.gm.lpr = cols < 64 ? cols : 64;
+    p.gm.G = 64 / p.gm.lpr;
+    p.blocks = (unsigned)mrec_cdiv(B * F, (int64_t)4 * p.gm.G);
+    return p;
+}
 
 template <class K, class OT>
 int pool_impl(const float* table, int64_t V, int64_t ld, int32_t D, const K* ids, int64_t B, int32_t F, int32_t Ls, int32_t maxL,
               const PoolFields& pf, const float* mask, int32_t mode, OT* out, int64_t ldo, hipStream_t st) {
-    // float4 lanes where the rows, and the 4-element quads of every field's output block, are aligned (D % 4 == 0: f * D too)
-    const uintptr_t oa = sizeof(OT) == 2 ? 7 : 15;
-    const bool vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
-    const int cols = vec ? D / 4 : D;
-    PoolGeom gm;
-    gm.lpr = cols < 64 ? cols : 64;
-    gm.G = 64 / gm.lpr;
+    const auto [vec, gm, blocks] = pool_launch(D, ld, ldo, table, out, sizeof(OT), B, F);
     const int64_t nbags = B * F;
-    const unsigned blocks = (unsigned)mrec_cdiv(nbags, (int64_t)4 * gm.G);
 #define MREC_POOL_LAUNCH1(VECN, PBN, ONE)                                                                                             \
     k_gather_pool_fields<VECN, PBN, K, OT, ONE><<<blocks, 256, 0, st>>>(table, V, ld, ids, mask, (unsigned)nbags, (unsigned)F, (int)Ls,       \
                                                                        (int)mode, out, ldo, (int)D, gm, pf)
@@ -200,16 +203,9 @@ int pool_run(const float* table, int64_t V, int64_t ld, int32_t D, const void* i
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!table || !ids || !out) return MREC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-#define MREC_POOL(KT, OT) return pool_impl<KT, OT>(table, V, ld, D, (const KT*)ids, B, F, Ls, maxL, pf, mask, mode, (OT*)out, ldo, st)
-    if (id_bytes == 4) {
-        if (out_kind == 0) { MREC_POOL(int32_t, float); }
-        if (out_kind == 1) { MREC_POOL(int32_t, bf16o_t); }
-        MREC_POOL(int32_t, f16o_t);
-    }
-    if (out_kind == 0) { MREC_POOL(int64_t, float); }
-    if (out_kind == 1) { MREC_POOL(int64_t, bf16o_t); }
-    MREC_POOL(int64_t, f16o_t);
-#undef MREC_POOL
+    return by_key(ids, id_bytes, [&](auto* ip) {
+        return by_out(out, out_kind, [&](auto* op) { return pool_impl(table, V, ld, D, ip, B, F, Ls, maxL, pf, mask, mode, op, ldo, st); });
+    });
 }
 
 // ===== the KEYED form: the pooled lookup over the rows of a hash table (MapParameter) ==================================================
@@ -301,14 +297,8 @@ template <class K, class OT>
 int pool_keyed_impl(const float* table, int64_t V, int64_t ld, int32_t D, const int32_t* ids, const K* keys, int64_t B, int32_t F,
                     int32_t Ls, int32_t maxL, const PoolFields& pf, const float* mask, int32_t mode, const MapDefault& dv, OT* out,
                     int64_t ldo, hipStream_t st) {
-    const uintptr_t oa = sizeof(OT) == 2 ? 7 : 15;       // (pool_impl's choice of lanes)
-    const bool vec = D % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && al16(table) && (((uintptr_t)out) & oa) == 0;
-    const int cols = vec ? D / 4 : D;
-    PoolGeom gm;
-    gm.lpr = cols < 64 ? cols : 64;
-    gm.G = 64 / gm.lpr;
+    const auto [vec, gm, blocks] = pool_launch(D, ld, ldo, table, out, sizeof(OT), B, F);
     const int64_t nbags = B * F;
-    const unsigned blocks = (unsigned)mrec_cdiv(nbags, (int64_t)4 * gm.G);
 #define MREC_POOLK_LAUNCH1(VECN, PBN, ONE)                                                                                            \
     k_gather_pool_fields_keyed<VECN, PBN, K, OT, ONE><<<blocks, 256, 0, st>>>(table, V, ld, ids, keys, mask, (unsigned)nbags, (unsigned)F,    \
                                                                              (int)Ls, (int)mode, out, ldo, (int)D, gm, dv, pf)
@@ -408,18 +398,16 @@ __global__ __launch_bounds__(256) void k_gather_pool_fields_clip(const float* __
     if (w < nbags) vstore(ob + col, acc);
 }
 
-/* max_norm: finite and > 0 (else MREC_EINVAL) -- mrec_gather.hip's clip_check, first half */
+/* max_norm: finite and > 0 (else MREC_EINVAL) -- clip_check's first half (mrec_common.h) */
 inline bool pool_clip_ok(float max_norm) { return max_norm > 0.0f && max_norm <= 3.402823466e38f; }
 
 template <class I, class KEY, class OT>
 int pool_clip_impl(const float* table, int64_t V, int64_t ld, int32_t D, const I* ids, const KEY* keys, int64_t B, int32_t F, int32_t Ls,
                    int32_t maxL, const PoolFields& pf, const float* mask, int32_t mode, const MapDefault& dv, float c, OT* out, int64_t ldo,
                    hipStream_t st) {
-    PoolGeom gm;
-    gm.lpr = D / 4;                                      // (D % 4 == 0, D <= 256: checked by pool_clip_run)
-    gm.G = 64 / gm.lpr;
+    const auto [vec, gm, blocks] = pool_launch(D, ld, ldo, table, out, sizeof(OT), B, F);      // (float4 rows, D <= 256: lpr == D / 4)
+    (void)vec;                                           // (true: checked by pool_clip_run)
     const int64_t nbags = B * F;
-    const unsigned blocks = (unsigned)mrec_cdiv(nbags, (int64_t)4 * gm.G);
 #define MREC_POOLC_LAUNCH1(PBN, ONE)                                                                                                  \
     k_gather_pool_fields_clip<PBN, I, KEY, OT, ONE><<<blocks, 256, 0, st>>>(table, V, ld, ids, keys, mask, (unsigned)nbags, (unsigned)F,     \
                                                                            (int)Ls, (int)mode, out, ldo, (int)D, gm, c, dv, pf)
@@ -437,25 +425,16 @@ int pool_clip_run(const float* table, int64_t V, int64_t ld, int32_t D, const vo
                   const MapDefault& dv, float c, void* out, int32_t out_kind, int64_t ldo, void* stream) {
     if (B * F > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;      // (bags are numbered in 32 bits)
     // float4 rows in one column block, or nothing: a row's norm is one lane-group's
-    const uintptr_t oa = out_kind == 0 ? 15 : 7;
-    if (D % 4 != 0 || D > 256 || ld % 4 != 0 || ldo % 4 != 0 || !al16(table) || (((uintptr_t)out) & oa) != 0) return MREC_EUNSUPPORTED;
+    if (!pool_launch(D, ld, ldo, table, out, out_kind == 0 ? 4 : 2, B, F).vec || D > 256) return MREC_EUNSUPPORTED;
     if (B == 0) return MREC_OK;
     if (V == 0) return MREC_EINVAL;      // rows are read unconditionally at clamped addresses: an empty table has no valid one
     if (!table || !ids || !out || (key_bytes && !keys)) return MREC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-#define MREC_POOLC(IT, KT, OT) return pool_clip_impl<IT, KT, OT>(table, V, ld, D, (const IT*)ids, (const KT*)keys, B, F, Ls, maxL, pf, mask, mode, dv, c, (OT*)out, ldo, st)
-#define MREC_POOLC_OUT(IT, KT)                                 \
-    do {                                                       \
-        if (out_kind == 0) { MREC_POOLC(IT, KT, float); }      \
-        if (out_kind == 1) { MREC_POOLC(IT, KT, bf16o_t); }    \
-        MREC_POOLC(IT, KT, f16o_t);                            \
-    } while (0)
-    if (key_bytes == 4) MREC_POOLC_OUT(int32_t, int32_t);
-    if (key_bytes == 8) MREC_POOLC_OUT(int32_t, int64_t);
-    if (id_bytes == 4) MREC_POOLC_OUT(int32_t, void);
-    MREC_POOLC_OUT(int64_t, void);
-#undef MREC_POOLC_OUT
-#undef MREC_POOLC
+    const auto run = [&](auto* ip, auto* kp) {      // (the keyed forms first, then the dense ones: the kernels' order in the code object)
+        return by_out(out, out_kind, [&](auto* op) { return pool_clip_impl(table, V, ld, D, ip, kp, B, F, Ls, maxL, pf, mask, mode, dv, c, op, ldo, st); });
+    };
+    if (key_bytes) return by_key(keys, key_bytes, [&](auto* kp) { return run((const int32_t*)ids, kp); });
+    return by_key(ids, id_bytes, [&](auto* ip) { return run(ip, (const void*)nullptr); });
 }
 
 // the bags of a sample from the caller's lengths: what both fields entries check, in this order
@@ -521,16 +500,9 @@ MREC_API int mrec_gather_pool_fields_keyed(const float* table, int64_t V, int64_
     if (!table || !rows || !keys || !out) return MREC_EINVAL;
     const MapDefault dv{seed, sigma, fill};
     hipStream_t st = (hipStream_t)stream;
-#define MREC_POOLK(KT, OT) return pool_keyed_impl<KT, OT>(table, V, ld, D, rows, (const KT*)keys, B, F, Ls, maxL, pf, mask, mode, dv, (OT*)out, ldo, st)
-    if (key_bytes == 4) {
-        if (out_kind == 0) { MREC_POOLK(int32_t, float); }
-        if (out_kind == 1) { MREC_POOLK(int32_t, bf16o_t); }
-        MREC_POOLK(int32_t, f16o_t);
-    }
-    if (out_kind == 0) { MREC_POOLK(int64_t, float); }
-    if (out_kind == 1) { MREC_POOLK(int64_t, bf16o_t); }
-    MREC_POOLK(int64_t, f16o_t);
-#undef MREC_POOLK
+    return by_key(keys, key_bytes, [&](auto* kp) {
+        return by_out(out, out_kind, [&](auto* op) { return pool_keyed_impl(table, V, ld, D, rows, kp, B, F, Ls, maxL, pf, mask, mode, dv, op, ldo, st); });
+    });
 }
 
 /* ... with max_norm: every looked-up row is clipped (nn.ClipByNorm) before its mask product */

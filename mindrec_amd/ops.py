@@ -13,7 +13,8 @@ import torch
 from . import _lib
 
 _WS = {}
-_DT16 = {torch.bfloat16: "bf16", torch.float16: "f16"}
+_DT16 = {torch.bfloat16: "bf16", torch.float16: "f16"}      # the 16-bit float types as the entries' names spell them
+_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # a float type as the entries' arguments name it (out_kind, g_kind ..)
 _WS_RETIRED = []      # outgrown workspaces stay referenced: a captured HIP graph may still hold their addresses
 
 
@@ -254,27 +255,29 @@ def gather_rows(table, ids, row_scale=None, out=None, out_dtype=torch.float32, m
     _need_cuda(table, ids, row_scale)
     V, D, ld = _table(table)
     sfx = _suffix(ids)
-    flat = ids.reshape(-1).contiguous()
-    n = flat.numel()
-    if row_scale is not None:
-        row_scale = row_scale.reshape(-1).contiguous()
-        if row_scale.dtype != torch.float32 or row_scale.numel() != n:
-            raise TypeError("row_scale must be float32 with one value per id")
-    if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+    flat, n, row_scale = _flat_ids(ids, row_scale)
+    if out_dtype not in _KIND:
         raise TypeError("gather_rows out_dtype must be float32, bfloat16 or float16")
     if out is None:
         out = torch.empty((n, D), dtype=out_dtype, device=table.device)
-    fn = {torch.float32: "mrec_gather_rows_f32_", torch.bfloat16: "mrec_gather_rows_bf16_",
-          torch.float16: "mrec_gather_rows_f16_"}[out.dtype]
-    if max_norm is not None:
-        _lib.call(fn.replace("mrec_gather_rows_", "mrec_gather_rows_clip_") + sfx, _ptr(table), V, ld, D, _ptr(flat), n, _ptr(row_scale),
-                  _ptr(out), _max_norm(max_norm), _stream())
-        return out.view(tuple(ids.shape) + (D,))
-    _lib.call(fn + sfx, _ptr(table), V, ld, D, _ptr(flat), n, _ptr(row_scale), _ptr(out), _stream())
+    clip = () if max_norm is None else (_max_norm(max_norm),)
+    _lib.call(_GATHER_ROWS[out.dtype, bool(clip)] + sfx, _ptr(table), V, ld, D, _ptr(flat), n, _ptr(row_scale), _ptr(out), *clip, _stream())
     return out.view(tuple(ids.shape) + (D,))
 
 
-_OUT_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+# (output type, with max_norm) -> the row lookup's entry, less its id suffix
+_GATHER_ROWS = {(dt, clip): f"mrec_gather_rows_{'clip_' if clip else ''}{name}_"
+                for dt, name in ((torch.float32, "f32"), *_DT16.items()) for clip in (False, True)}
+
+
+def _flat_ids(ids, row_scale=None):
+    """(ids flattened and contiguous, their number, row_scale likewise): what every row lookup makes of its ids and their weights"""
+    flat = ids.reshape(-1).contiguous()
+    if row_scale is not None:
+        row_scale = row_scale.reshape(-1).contiguous()
+        if row_scale.dtype != torch.float32 or row_scale.numel() != flat.numel():
+            raise TypeError("row_scale must be float32 with one value per id")
+    return flat, flat.numel(), row_scale
 
 
 def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype, keyed=None, max_norm=None):
@@ -289,10 +292,10 @@ def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype, keyed=None, 
         raise ValueError(f"{who} mode must be 'sum' or 'mean', got {mode!r}")
     B, F = ids.shape[0], len(lens)
     if out is None:
-        if out_dtype not in _OUT_KIND:
+        if out_dtype not in _KIND:
             raise TypeError(f"{who} out_dtype must be float32, bfloat16 or float16")
         out = torch.empty((B, F * D), dtype=out_dtype, device=table.device)
-    elif out.dtype not in _OUT_KIND or out.dim() != 2 or tuple(out.shape) != (B, F * D) or out.stride(1) != 1:
+    elif out.dtype not in _KIND or out.dim() != 2 or tuple(out.shape) != (B, F * D) or out.stride(1) != 1:
         raise TypeError(f"{who} out must be a [{B}, {F * D}] float32 / bfloat16 / float16 tensor with unit column stride")
     ldo = out.stride(0) if B > 1 else F * D
     ids = ids.contiguous()
@@ -302,10 +305,10 @@ def _gather_pool(who, table, ids, lens, mask, mode, out, out_dtype, keyed=None, 
         keys = keys.contiguous()
         _lib.call("mrec_gather_pool_fields_keyed" + tail, _ptr(table), V, ld, D, _ptr(ids), _ptr(keys), keys.element_size(), B, F,
                   (C.c_int32 * F)(*lens), _ptr(mask), 1 if mode == "mean" else 0, C.c_uint64(seed), sigma, fill, _ptr(out),
-                  _OUT_KIND[out.dtype], ldo, *clip, _stream())
+                  _KIND[out.dtype], ldo, *clip, _stream())
         return out
     _lib.call("mrec_gather_pool_fields" + tail, _ptr(table), V, ld, D, _ptr(ids), 4 if sfx == "i32" else 8, B, F, (C.c_int32 * F)(*lens),
-              _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _OUT_KIND[out.dtype], ldo, *clip, _stream())
+              _ptr(mask), 1 if mode == "mean" else 0, _ptr(out), _KIND[out.dtype], ldo, *clip, _stream())
     return out
 
 
@@ -385,15 +388,10 @@ def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.
     is not; D <= 252."""
     _need_cuda(table, ids, row_scale, out)
     V, D, ld = _table(table)
-    flat = ids.reshape(-1).contiguous()
-    n = flat.numel()
-    if row_scale is not None:
-        row_scale = row_scale.reshape(-1).contiguous()
-        if row_scale.dtype != torch.float32 or row_scale.numel() != n:
-            raise TypeError("row_scale must be float32 with one value per id")
+    flat, n, row_scale = _flat_ids(ids, row_scale)
     if out_dtype not in _DT16:
         raise TypeError("gather_rows_wide writes bfloat16 or float16 rows")
-    kind = 1 if out_dtype == torch.bfloat16 else 2
+    kind = _KIND[out_dtype]
     if packed_words:
         if max_norm is not None:
             raise ValueError("max_norm: not on a shard's packed answer message")
@@ -408,7 +406,7 @@ def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.
         out = torch.empty((n, D), dtype=out_dtype, device=table.device)
     wprod = torch.empty((max(n, 1), 2), dtype=torch.float32, device=table.device)[:n]      # (product, pad) pairs
     args = (_ptr(table), V, ld, D, _ptr(flat), flat.element_size(), 1, n, _ptr(row_scale), 1, _ptr(out),
-            1 if out.dtype == torch.bfloat16 else 2, D, int(wide_col), _ptr(wprod), 2, _drop_ref(drop),
+            _KIND[out.dtype] if out.dtype in _DT16 else 2, D, int(wide_col), _ptr(wprod), 2, _drop_ref(drop),
             ids.shape[-1] if drop is not None else 0, 0, _ptr(step_state.buf) if step_state is not None else None)
     if max_norm is not None:
         _lib.call("mrec_gather_rows_wide_clip", *args, _max_norm(max_norm), _stream())
@@ -422,10 +420,10 @@ def gather_rows_skip_(table, rows, out):
     front has written them: KeyIndex.lookup(out=...))."""
     _need_cuda(table, rows, out)
     V, D, ld = _table(table)
-    flat = rows.reshape(-1).contiguous()
-    if flat.dtype != torch.int32 or out.dtype != torch.float32 or out.numel() != flat.numel() * D or not out.is_contiguous():
+    flat, n, _ = _flat_ids(rows)
+    if flat.dtype != torch.int32 or out.dtype != torch.float32 or out.numel() != n * D or not out.is_contiguous():
         raise TypeError("gather_rows_skip_: int32 rows, contiguous float32 [n, D] out")
-    _lib.call("mrec_gather_rows_f32_skip_i32", _ptr(table), V, ld, D, _ptr(flat), flat.numel(), _ptr(out), _stream())
+    _lib.call("mrec_gather_rows_f32_skip_i32", _ptr(table), V, ld, D, _ptr(flat), n, _ptr(out), _stream())
     return out
 
 
@@ -437,9 +435,9 @@ def gather_rows_pinned(host_table, ids):
     _need_cuda(ids)
     V, D, ld = _table(host_table)
     sfx = _suffix(ids)
-    flat = ids.reshape(-1).contiguous()
-    out = torch.empty((flat.numel(), D), dtype=torch.float32, device=ids.device)
-    _lib.call("mrec_gather_rows_f32_" + sfx, _ptr(host_table), V, ld, D, _ptr(flat), flat.numel(), None, _ptr(out), _stream())
+    flat, n, _ = _flat_ids(ids)
+    out = torch.empty((n, D), dtype=torch.float32, device=ids.device)
+    _lib.call(_GATHER_ROWS[torch.float32, False] + sfx, _ptr(host_table), V, ld, D, _ptr(flat), n, None, _ptr(out), _stream())
     return out
 
 
@@ -558,7 +556,6 @@ def _row_scale(plan, row_scale):
     return rs
 
 
-_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # a float type as the library's entries name it (g_kind and the like)
 
 
 class _Apply:
@@ -1331,7 +1328,7 @@ def gather_rows_req(table, rows, rows_stride, wts, wts_stride, n_slots, wide_col
     msg = out if out is not None else torch.empty((max(n_slots, 1), W), dtype=torch.float32, device=table.device)[:n_slots]
     if msg.dtype != torch.float32 or tuple(msg.shape) != (n_slots, W) or not msg.is_contiguous():
         raise TypeError("gather_rows_req: out must be a contiguous float32 [n_slots, W] tensor")
-    kind = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[act_dtype]
+    kind = _KIND[act_dtype]
     ldo = W if kind == 0 else 2 * W
     _lib.call("mrec_gather_rows_wide_ex", _ptr(table), V, ld, D, _ptr(rows), rows.element_size(), int(rows_stride), n_slots, _ptr(wts),
               int(wts_stride), _ptr(msg), kind, ldo, int(wide_col), C.c_void_p(msg.data_ptr() + 4 * Dw), W, None, 0, 1, None, _stream())
@@ -1830,7 +1827,7 @@ def dense_adam_slabs_(p, m, v, g, slabs, shadow16=None, lr=1e-3, beta1=0.9, beta
     if shadow16 is not None:
         if shadow16.dtype not in _DT16 or shadow16.numel() != n or not shadow16.is_contiguous():
             raise TypeError("shadow16 must be a contiguous bfloat16 / float16 tensor of the parameter's size")
-        kind = 1 if shadow16.dtype == torch.bfloat16 else 2
+        kind = _KIND[shadow16.dtype]
     segs = _slab_args(slabs)
     f = _ftrl1(ftrl1) if ftrl1 is not None else None
     args = (_ptr(p), _ptr(m), _ptr(v), _ptr(g), _ptr(shadow16), kind, n, k, *segs,
@@ -2074,7 +2071,7 @@ def fm_forward(vx, add=None, out16=None):
     fm = torch.empty(B, dtype=torch.float32, device=vx.device)
     cs = torch.empty((B, D), dtype=torch.float32, device=vx.device)
     _lib.call("mrec_fm_fwd_add16_f32", _ptr(vx), B, F_, D, _ptr(add), _ptr(fm), _ptr(cs), _ptr(out16),
-              0 if out16 is None else (1 if out16.dtype == torch.bfloat16 else 2), _stream())
+              0 if out16 is None else _KIND[out16.dtype], _stream())
     return fm, cs
 
 
@@ -2086,7 +2083,7 @@ def fm_backward_mix(g16, vx, colsum, dout):
     if g16.dtype not in _DT16 or g16.numel() != vx.numel() or not g16.is_contiguous():
         raise TypeError("fm_backward_mix: g16 must be a contiguous bfloat16 / float16 tensor of vx's size")
     out = torch.empty_like(vx)
-    _lib.call("mrec_fm_bwd_mix_f32", _ptr(vx.contiguous()), _ptr(colsum), _ptr(dout.contiguous()), _ptr(g16), 1 if g16.dtype == torch.bfloat16 else 2,
+    _lib.call("mrec_fm_bwd_mix_f32", _ptr(vx.contiguous()), _ptr(colsum), _ptr(dout.contiguous()), _ptr(g16), _KIND[g16.dtype],
               B, F_, D, _ptr(out), _stream())
     return out
 

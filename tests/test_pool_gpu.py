@@ -91,7 +91,7 @@ def test_mrec_gather_pool_entry_bitwise(dev, D, L):
         tid = T(ids, dev)
         out = torch.empty((B, D), dtype=odt, device=dev)
         _lib.call("mrec_gather_pool", ops._ptr(tt), V, D, D, ops._ptr(tid), ids.itemsize, B, L, ops._ptr(tm), 1 if mode == "mean" else 0,
-                  ops._ptr(out), ops._OUT_KIND[odt], 0, ops._stream())
+                  ops._ptr(out), ops._KIND[odt], 0, ops._stream())
         _same(_bits(out), P.gather_pool(table, ids, mask, mode, _KIND[odt]), f"mrec_gather_pool D={D} L={L} {mode} {odt}")
 
 
