@@ -44,6 +44,14 @@ struct MrecArena {
 
 static inline int64_t mrec_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Slots of an open-addressing table over n keys at load <= 0.5: the power of two >= max(1024, 2 n).  The Unique's and the lookup's
+// scratch tables and the key index's slot array (KeyIndex.n_slots in ops.py restates it).
+static inline uint64_t scratch_cap(int64_t n) {
+    uint64_t cap = 1024;
+    while (cap < (uint64_t)n * 2) cap <<= 1;
+    return cap;
+}
+
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // Grid of a grid-stride kernel of 256-thread workgroups: one thread per item, capped at 4096 workgroups.
@@ -129,6 +137,55 @@ __device__ __forceinline__ int block_excl_scan_256(int x, int* smem, int* total)
     __syncthreads();
     *total = tot;
     return base + incl - x;
+}
+
+// Decoupled look-back over per-tile counts (one status word per tile: flag << 30 | value; flag 1 = the tile's own count,
+// 2 = inclusive prefix).  Tiles are dispatched in index order and only ever wait for lower-numbered tiles, so the wait always
+// ends.  The words are zero when the kernel starts, and whoever runs BEHIND the scanning kernel clears them again, which is what
+// keeps a primed workspace primed: k_radix_hist / k_dedup_inv behind k_dedup_rank, k_map_finish behind k_map_place; k_map_evict's
+// are zeroed by a memset in front of it.
+constexpr unsigned kFlagA = 1u << 30, kFlagP = 2u << 30, kFlagMask = 3u << 30;
+
+__device__ __forceinline__ int lookback_excl(unsigned* status, int tile) {
+    const int l = lane_id();
+    int excl = 0;
+    for (int base = tile - 1;; base -= 64) {
+        const int idx = base - l;
+        unsigned st;
+        do {
+            st = (idx >= 0) ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kFlagP;
+        } while (__any((st & kFlagMask) == 0));
+        const uint64_t pm = __ballot((st & kFlagMask) == kFlagP);
+        const int firstp = pm ? __ffsll((long long)pm) - 1 : 63; // nearest predecessor with an inclusive prefix (the virtual
+        int c = (l <= firstp) ? (int)(st & ~kFlagMask) : 0;      // tiles below 0 carry one); none in this round: add all 64
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+        excl += c;
+        if (pm) break;
+    }
+    return excl;
+}
+
+// One 256-thread workgroup per tile, c = this thread's flagged items: returns their rank among all tiles' (exclusive), *tile_total
+// = the tile's count; afterwards *s_excl (shared) holds the count of all lower tiles, so the last tile knows the grand total.
+__device__ __forceinline__ int tile_excl_scan_256(int c, unsigned* status, int* sm, int* s_excl, int* tile_total) {
+    int tot;
+    const int pre = block_excl_scan_256(c, sm, &tot);
+    if (threadIdx.x < 64) {
+        const int t = blockIdx.x;
+        int excl = 0;
+        if (t == 0) {
+            if (threadIdx.x == 0) __hip_atomic_store(&status[0], kFlagP | (unsigned)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            if (threadIdx.x == 0) __hip_atomic_store(&status[t], kFlagA | (unsigned)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            excl = lookback_excl(status, t);
+            if (threadIdx.x == 0) __hip_atomic_store(&status[t], kFlagP | (unsigned)(excl + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (threadIdx.x == 0) *s_excl = excl;
+    }
+    __syncthreads();
+    *tile_total = tot;
+    return *s_excl + pre;
 }
 
 // ---- max_norm (nn.ClipByNorm over a looked-up row) ----------------------------------------------------------------------

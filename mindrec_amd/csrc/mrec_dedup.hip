@@ -117,33 +117,8 @@ __global__ __launch_bounds__(DB) void k_dedup_insert(const K* __restrict__ ids, 
 // the scattered 4- and 8-byte pair writes cost more than the table's atomics, and a hot id puts all its copies in ONE bucket
 // -- 16384 LDS atomics on one slot by one workgroup.)
 //
-// Decoupled look-back over the tiles' first-occurrence counts (one status word per tile: flag << 30 | value; flag 1 = the
-// tile's own count, 2 = inclusive prefix).  Tiles are dispatched in index order and only ever wait for lower-numbered
-// tiles, so the wait always ends.  The words are zero when the kernel starts: the NEXT kernel of the chain clears them again
-// (k_radix_hist / k_dedup_inv), which is what keeps a primed workspace primed.
-constexpr unsigned kFlagA = 1u << 30, kFlagP = 2u << 30, kFlagMask = 3u << 30;
-
-__device__ __forceinline__ int lookback_excl(unsigned* status, int tile) {
-    const int l = lane_id();
-    int excl = 0;
-    for (int base = tile - 1;; base -= 64) {
-        const int idx = base - l;
-        unsigned st;
-        do {
-            st = (idx >= 0) ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kFlagP;
-        } while (__any((st & kFlagMask) == 0));
-        const uint64_t pm = __ballot((st & kFlagMask) == kFlagP);
-        const int firstp = pm ? __ffsll((long long)pm) - 1 : 63; // nearest predecessor with an inclusive prefix (the virtual
-        int c = (l <= firstp) ? (int)(st & ~kFlagMask) : 0;      // tiles below 0 carry one); none in this round: add all 64
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-        excl += c;
-        if (pm) break;
-    }
-    return excl;
-}
-
-// Numbers the first occurrences in position order in ONE pass (flag + count + scan + rank).  The scratch table is left as
+// Numbers the first occurrences in position order in ONE pass (flag + count + the look-back scan of mrec_common.h over the tiles'
+// first-occurrence counts + rank).  The scratch table is left as
 // it is -- a slot keeps the first position of its key, which is how a duplicate finds its group afterwards
 // (inv[slots[sidx[j]]]) -- and is cleared by a 4-MB memset at the head of the next call: handing the slots back one by
 // one, and keeping a rank per slot for the duplicates, were 850 k random 4-byte writes per call, a third of this kernel.
@@ -180,6 +155,8 @@ __global__ __launch_bounds__(DB) void k_dedup_rank(const K* __restrict__ ids, co
         c += first[k];
     }
     int tot;
+    // (tile_excl_scan_256 of mrec_common.h, written out: as a call the compiler lays this kernel's blocks out differently, and the
+    // plan runs in every step)
     const int pre = block_excl_scan_256(c, sm, &tot);
     if (threadIdx.x < 64) {
         const int t = blockIdx.x;
@@ -336,8 +313,7 @@ int dedup_impl(const K* ids, int64_t n, K* uniq, int32_t* inv, int64_t* n_uniq_d
     }
     if (!ids || !uniq || !inv || !ws) return MREC_EINVAL;
     if (n >= (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    uint64_t cap = 1024;
-    while (cap < (uint64_t)n * 2) cap <<= 1;
+    const uint64_t cap = scratch_cap(n);
     const int nblk = (int)mrec_cdiv(n, DT);
     MrecArena a(ws, ws_bytes);
     int* slots = a.take<int>(cap);
@@ -379,8 +355,7 @@ __global__ __launch_bounds__(256) void k_seg_offsets(const int* __restrict__ sse
 MREC_API int mrec_dedup_workspace_bytes(int64_t n, size_t* out) {
     if (!out || n < 0) return MREC_EINVAL;
     if (n >= (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    uint64_t cap = 1024;
-    while (cap < (uint64_t)n * 2) cap <<= 1;
+    const uint64_t cap = scratch_cap(n);
     size_t b = 0;
     b += mrec_align_up(cap * 4, 256) * 2;
     b += mrec_align_up((size_t)(n ? n : 1) * 4, 256);
@@ -399,15 +374,36 @@ MREC_API int mrec_dedup_i64(const int64_t* ids, int64_t n, int64_t* uniq, int32_
     return dedup_impl<int64_t>(ids, n, uniq, inv, n_uniq_dev, ws, ws_bytes, stream);
 }
 
+// The radix passes' workspace over n keys, as the takes that carve it (ws == nullptr: the arena only counts -- the size query), and
+// how the passes split the keys' bits (group numbers are < n).
+struct RadixWs {
+    int *hist, *hscan, *totals, *tk, *tv;
+    size_t bytes;
+    bool ok;
+    RadixWs(void* ws, size_t ws_bytes, int64_t n) {
+        const size_t nblk = (size_t)mrec_cdiv(n, RT);
+        MrecArena a(ws, ws_bytes);
+        hist = a.take<int>(nblk * RNB);
+        hscan = a.take<int>(nblk * RNB);
+        totals = a.take<int>(RNB);
+        tk = a.take<int>(n);
+        tv = a.take<int>(n);
+        bytes = a.off;
+        ok = a.ok;
+    }
+};
+struct RadixPlan { int passes, pbits; };
+static RadixPlan radix_plan(int64_t n) {
+    int bits = 1;
+    while (((int64_t)1 << bits) < n) ++bits;
+    const int passes = (bits + RMAXB - 1) / RMAXB;
+    return {passes, (bits + passes - 1) / passes};
+}
+
 MREC_API int mrec_group_workspace_bytes(int64_t n, size_t* out) {
     if (!out || n < 0) return MREC_EINVAL;
     if (n > (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    const size_t nn = (size_t)(n ? n : 1);
-    size_t b = 0;
-    b += mrec_align_up((size_t)mrec_cdiv(nn, RT) * RNB * 4, 256) * 2;
-    b += mrec_align_up((size_t)RNB * 4, 256);
-    b += mrec_align_up(nn * 4, 256) * 2;
-    *out = b;
+    *out = RadixWs(nullptr, SIZE_MAX, n ? n : 1).bytes;
     return MREC_OK;
 }
 
@@ -421,25 +417,16 @@ static int group_impl(const int32_t* inv, int64_t n, int32_t* sorted_pos, int32_
     }
     if (!inv || !sorted_pos || !sorted_seg || !ws) return MREC_EINVAL;
     if (n > (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    const int nblk = (int)mrec_cdiv(n, RT);
-    MrecArena a(ws, ws_bytes);
-    int* hist = a.take<int>((size_t)nblk * RNB);
-    int* hscan = a.take<int>((size_t)nblk * RNB);
-    int* totals = a.take<int>(RNB);
-    int* tk = a.take<int>(n);
-    int* tv = a.take<int>(n);
-    if (!a.ok) return MREC_EWORKSPACE;
-    int bits = 1;
-    while (((int64_t)1 << bits) < n) ++bits;  // group numbers are < n
-    const int passes = (bits + RMAXB - 1) / RMAXB;
-    const int pbits = (bits + passes - 1) / passes;
+    const RadixWs r(ws, ws_bytes, n);
+    if (!r.ok) return MREC_EWORKSPACE;
+    const auto [passes, pbits] = radix_plan(n);
     const int* kin = inv;
     const int* vin = nullptr;
     for (int p = 0; p < passes; ++p) {
         const bool to_user = ((passes - 1 - p) % 2) == 0;
-        int* kout = to_user ? sorted_seg : tk;
-        int* vout = to_user ? sorted_pos : tv;
-        radix_pass(kin, vin, (int)n, p * pbits, pbits, hist, hscan, totals, nullptr, kout, vout, st);
+        int* kout = to_user ? sorted_seg : r.tk;
+        int* vout = to_user ? sorted_pos : r.tv;
+        radix_pass(kin, vin, (int)n, p * pbits, pbits, r.hist, r.hscan, r.totals, nullptr, kout, vout, st);
         kin = kout;
         vin = vout;
     }
@@ -453,9 +440,14 @@ MREC_API int mrec_group_by_inverse(const int32_t* inv, int64_t n, int32_t* sorte
     return group_impl(inv, n, sorted_pos, sorted_seg, seg_offsets, ws, ws_bytes, stream);
 }
 
-// Unique + inverted index in one call (what a training step needs): the inverse rides on the first
-// radix histogram, saving a pass and a launch over mrec_dedup_* followed by mrec_group_by_inverse.
-static size_t plan_extra_bytes(int64_t n) { return mrec_align_up((size_t)(n ? n : 1) * 4, 256) * 2 + 256; }
+// The plan's workspace is two parts: *db bytes for the Unique (its own workspace, then first_pos, dup_pos and the two duplicate
+// counts of dedup_impl's plan form), *gb for the radix passes behind it.  The codes are the two size queries'.
+static int plan_split(int64_t n, size_t* db, size_t* gb) {
+    int rc = mrec_dedup_workspace_bytes(n, db);
+    if (rc != MREC_OK) return rc;
+    *db += mrec_align_up((size_t)(n ? n : 1) * 4, 256) * 2 + 256;
+    return mrec_group_workspace_bytes(n, gb);
+}
 
 // Unique + inverted index in one call (what a training step needs).  First occurrences leave the rank kernel already in
 // group order; only the DUPLICATE positions are sorted by group (their count lives on the device: the radix kernels run
@@ -469,10 +461,7 @@ static int plan_impl(const K* ids, int64_t n, K* uniq, int32_t* inv, int64_t* n_
     // n_uniq_dev is then two words, [1] = the number of entries of the index proper (valid positions)
     const int gkey = skipneg ? (int)(n - 1) : -1;
     size_t db = 0, gb = 0;
-    int rc = mrec_dedup_workspace_bytes(n, &db);
-    if (rc != MREC_OK) return rc;
-    db += plan_extra_bytes(n);
-    rc = mrec_group_workspace_bytes(n, &gb);
+    int rc = plan_split(n, &db, &gb);
     if (rc != MREC_OK) return rc;
     if (n > 0 && (!ws || ws_bytes < db + gb)) return MREC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -487,18 +476,10 @@ static int plan_impl(const K* ids, int64_t n, K* uniq, int32_t* inv, int64_t* n_
     DedupScratch sc{};
     rc = dedup_impl<K>(ids, n, uniq, inv, n_uniq_dev, ws, db, stream, &sc, primed, skipneg);
     if (rc != MREC_OK) return rc;
-    const int nblk = (int)mrec_cdiv(n, RT);
-    MrecArena a((char*)ws + db, gb);
-    int* hist = a.take<int>((size_t)nblk * RNB);
-    int* hscan = a.take<int>((size_t)nblk * RNB);
-    int* totals = a.take<int>(RNB);
-    int* tk = a.take<int>(n);
-    int* tv = a.take<int>(n);
-    if (!a.ok) return MREC_EWORKSPACE;
-    int bits = 1;
-    while (((int64_t)1 << bits) < n) ++bits;  // group numbers are < n
-    const int passes = (bits + RMAXB - 1) / RMAXB;
-    const int pbits = (bits + passes - 1) / passes;
+    const RadixWs r((char*)ws + db, gb, n);
+    if (!r.ok) return MREC_EWORKSPACE;
+    int *const hist = r.hist, *const hscan = r.hscan, *const totals = r.totals, *const tk = r.tk, *const tv = r.tv;
+    const auto [passes, pbits] = radix_plan(n);
     // ping-pong between A = the caller's (sorted_seg, sorted_pos), free until the placement kernel writes them, and
     // B = (tk, tv); the last pass lands in B.  The generated keys of pass 0 live in the key array pass 0 does not write.
     const bool first_to_b = ((passes - 1) % 2) == 0;
@@ -530,10 +511,7 @@ static int plan_impl(const K* ids, int64_t n, K* uniq, int32_t* inv, int64_t* n_
 
 MREC_API int mrec_sparse_plan_workspace_bytes(int64_t n, size_t* out) {
     size_t db = 0, gb = 0;
-    int rc = mrec_dedup_workspace_bytes(n, &db);
-    if (rc != MREC_OK) return rc;
-    db += plan_extra_bytes(n);
-    rc = mrec_group_workspace_bytes(n, &gb);
+    const int rc = plan_split(n, &db, &gb);
     if (rc != MREC_OK) return rc;
     *out = db + gb;
     return MREC_OK;

@@ -52,14 +52,10 @@ __device__ __forceinline__ int64_t eff_n(int64_t n, const int64_t* n_dev) {
     return nd < n ? (nd < 0 ? 0 : nd) : n;
 }
 
-__global__ __launch_bounds__(HB) void k_map_find(MapDev m, const int64_t* __restrict__ keys, int64_t n_max,
-                                                 const int64_t* __restrict__ n_dev, int* __restrict__ rows_out,
-                                                 int* __restrict__ slot_out, uint8_t* __restrict__ miss) {
-    const int64_t i = (int64_t)blockIdx.x * HB + threadIdx.x;
-    if (i >= n_max) return;
-    if (i >= eff_n(n_max, n_dev)) { miss[i] = 0; rows_out[i] = -1; return; }
-    const int64_t key = keys[i];
-    uint32_t s = mrec_hash_key(key) & m.mask;
+// ---- what the kernels below do to the index, each said once ---------------------------------------------------------------
+// The row of `key` (hsh = mrec_hash_key(key)) and the slot that holds it, or -1 and -1.
+__device__ __forceinline__ int map_find(const MapDev& m, int64_t key, uint32_t hsh, int* slot_out) {
+    uint32_t s = hsh & m.mask;
     int row = -1, slot = -1;
     // bounded: a slot array without an empty slot (it cannot arise while the rebuild below keeps
     // live + tombstones <= 0.7 S, but a probe must never depend on that) ends as a miss, not a hang
@@ -69,6 +65,68 @@ __global__ __launch_bounds__(HB) void k_map_find(MapDev m, const int64_t* __rest
         if (r >= 0 && m.slot[s].key == key) { row = r; slot = (int)s; break; }
         s = (s + 1) & m.mask;
     }
+    *slot_out = slot;
+    return row;
+}
+
+// Miss number r of a call (ranked in the order of first appearance) -> its row: fresh rows in order, then the free list from its
+// top, then -1 (the table is full).  hwm / nfree: the two counters as they stood before the call.
+__device__ __forceinline__ int map_row_for_rank(const MapDev& m, int64_t r, int64_t hwm, int64_t nfree) {
+    const int64_t fresh = m.C - hwm;
+    int row = -1;
+    if (r < fresh) row = (int)(hwm + r);
+    else if (r - fresh < nfree) row = m.free_list[nfree - 1 - (r - fresh)];
+    return row;
+}
+
+// A row leaves the index (its slot is the caller's: erase knows it, evict walks to it): dead, entry `at_free` of the free list,
+// its key entry `at_log` of the erased-keys log while the log has room.
+__device__ __forceinline__ void map_release_row(const MapDev& m, int row, int64_t key, int64_t at_free, int64_t at_log) {
+    m.row_live[row] = 0;
+    m.free_list[at_free] = row;
+    if (at_log < m.C) m.erased_log[at_log] = key;
+}
+
+// n rows left in one call (one thread, behind every map_release_row of the call).
+// Erase leaves tombstones, and an insert only takes one back when its probe happens to pass it: under
+// insert / erase churn the EMPTY slots (the only thing that ends a miss probe) would run out.  Once
+// tombstones exceed S / 5 (live <= S / 2, so live + tombstones <= 0.7 S always holds) the slot array is
+// rebuilt from the row side (row_key / row_live), which empties every tombstone.
+__device__ __forceinline__ void map_commit_freed(const MapDev& m, int64_t n, int64_t S) {
+    m.counters[C_FREE] += n;
+    m.counters[C_LIVE] -= n;
+    const int64_t nlog = m.counters[C_NLOG] + n;
+    m.counters[C_NLOG] = nlog < m.C ? nlog : m.C;
+    const int64_t tomb = m.counters[C_TOMB] + n;
+    const bool rebuild = tomb * 5 > S;
+    m.counters[C_REBUILD] = rebuild ? 1 : 0;
+    m.counters[C_TOMB] = rebuild ? 0 : tomb;
+    if (rebuild) m.counters[C_NREBUILD] += 1;
+}
+
+// Two counters as they stood before this kernel changes them: read by every tile BEFORE it publishes its count, so the last
+// tile -- whose look-back ends only after all others published -- can commit the new values.
+// (the two loads have RETURNED before anything behind this is issued -- what the ordering above needs; a release fence in their place
+// also wrote back whatever the workgroup's CU had dirtied in L2: MREC_MAP_FENCE=1 keeps it for A/B builds)
+__device__ __forceinline__ void map_counters_before(const MapDev& m, int a, int b, int64_t* va, int64_t* vb) {
+    int64_t x = m.counters[a], y = m.counters[b];
+#if defined(MREC_MAP_FENCE) && MREC_MAP_FENCE
+    __threadfence();
+#else
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(x), "+v"(y) : : "memory");
+#endif
+    *va = x;
+    *vb = y;
+}
+
+__global__ __launch_bounds__(HB) void k_map_find(MapDev m, const int64_t* __restrict__ keys, int64_t n_max,
+                                                 const int64_t* __restrict__ n_dev, int* __restrict__ rows_out,
+                                                 int* __restrict__ slot_out, uint8_t* __restrict__ miss) {
+    const int64_t i = (int64_t)blockIdx.x * HB + threadIdx.x;
+    if (i >= n_max) return;
+    if (i >= eff_n(n_max, n_dev)) { miss[i] = 0; rows_out[i] = -1; return; }
+    int slot;
+    const int row = map_find(m, keys[i], mrec_hash_key(keys[i]), &slot);
     rows_out[i] = row;
     if (slot_out) slot_out[i] = slot;
     miss[i] = (row < 0);
@@ -123,36 +181,23 @@ __global__ __launch_bounds__(HB) void k_map_insert(MapDev m, const int64_t* __re
     const int64_t i = (int64_t)blockIdx.x * HB + threadIdx.x;
     if (i >= n) return;
     if (!miss[i]) { if (is_new) is_new[i] = 0; return; }
-    const int64_t hwm = m.counters[C_HWM];
-    const int64_t nfree = m.counters[C_FREE];
-    const int64_t fresh = m.C - hwm;
-    const int64_t r = rank[i];
-    int row;
-    if (r < fresh) row = (int)(hwm + r);
-    else if (r - fresh < nfree) row = m.free_list[nfree - 1 - (r - fresh)];
-    else {
-        rows_out[i] = -1;
-        if (is_new) is_new[i] = 0;
-        atomicAdd((unsigned long long*)n_dropped_call, 1ull);
-        return;
-    }
     const int64_t key = keys[i];
-    uint32_t s = mrec_hash_key(key) & m.mask;
+    const int row = map_row_for_rank(m, rank[i], m.counters[C_HWM], m.counters[C_FREE]);
     bool placed = false;
-    // live keys <= C <= S / 2, so a negative slot exists; bounded all the same
-    for (uint32_t it = 0; it <= m.mask; ++it) {
+    uint32_t s = mrec_hash_key(key) & m.mask;
+    // claim a negative slot (empty or tombstone) on the key's probe path: live keys <= C <= S / 2, so one exists; bounded all the
+    // same.  k_map_place holds the same loop (see there why they stay two); it looks at a slot again after a lost CAS where this one
+    // steps on: slots only move negative -> row inside these kernels, so the lost slot holds a row >= 0 and both end at the same slot
+    for (uint32_t it = 0; row >= 0 && it <= m.mask; ++it) {
         const int cur = __hip_atomic_load(&m.slot[s].row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur < 0) {
-            const int old = atomicCAS(&m.slot[s].row, cur, row);
-            if (old == cur) {
-                if (cur == -2) atomicAdd((unsigned long long*)n_tomb_reused, 1ull);
-                placed = true;
-                break;
-            }
+        if (cur < 0 && atomicCAS(&m.slot[s].row, cur, row) == cur) {
+            if (cur == -2) atomicAdd((unsigned long long*)n_tomb_reused, 1ull);
+            placed = true;
+            break;
         }
         s = (s + 1) & m.mask;
     }
-    if (!placed) {
+    if (!placed) {      // the table is full
         rows_out[i] = -1;
         if (is_new) is_new[i] = 0;
         atomicAdd((unsigned long long*)n_dropped_call, 1ull);
@@ -185,28 +230,11 @@ __global__ __launch_bounds__(HB) void k_map_erase(MapDev m, int64_t n, const int
                                                   const int* __restrict__ rank) {
     const int64_t i = (int64_t)blockIdx.x * HB + threadIdx.x;
     if (i >= n || miss[i]) return;
-    const int64_t nfree = m.counters[C_FREE], nlog = m.counters[C_NLOG];
     m.slot[slots[i]].row = -2;
-    m.row_live[rows[i]] = 0;
-    m.free_list[nfree + rank[i]] = rows[i];
-    if (nlog + rank[i] < m.C) m.erased_log[nlog + rank[i]] = m.row_key[rows[i]];
+    map_release_row(m, rows[i], m.row_key[rows[i]], m.counters[C_FREE] + rank[i], m.counters[C_NLOG] + rank[i]);
 }
 
-// Erase leaves tombstones, and an insert only takes one back when its probe happens to pass it: under
-// insert / erase churn the EMPTY slots (the only thing that ends a miss probe) would run out.  Once
-// tombstones exceed S / 5 (live <= S / 2, so live + tombstones <= 0.7 S always holds) the slot array is
-// rebuilt from the row side (row_key / row_live), which empties every tombstone.
-__global__ void k_map_commit_erase(MapDev m, const int64_t* n_found, int64_t S) {
-    m.counters[C_FREE] += *n_found;
-    m.counters[C_LIVE] -= *n_found;
-    const int64_t nlog = m.counters[C_NLOG] + *n_found;
-    m.counters[C_NLOG] = nlog < m.C ? nlog : m.C;
-    const int64_t tomb = m.counters[C_TOMB] + *n_found;
-    const bool rebuild = tomb * 5 > S;
-    m.counters[C_REBUILD] = rebuild ? 1 : 0;
-    m.counters[C_TOMB] = rebuild ? 0 : tomb;
-    if (rebuild) m.counters[C_NREBUILD] += 1;
-}
+__global__ void k_map_commit_erase(MapDev m, const int64_t* n_found, int64_t S) { map_commit_freed(m, *n_found, S); }
 
 __global__ __launch_bounds__(HB) void k_map_rebuild_clear(MapDev m, int64_t S) {
     if (!m.counters[C_REBUILD]) return;
@@ -249,7 +277,6 @@ __global__ __launch_bounds__(HB) void k_map_export(MapDev m, const int* __restri
 //           positions of new keys, the admission mask.  With an output (mrec_map_lookup_out) every position of a key that was
 //           DROPPED because the table is full reads the key's default row, as an un-admitted key does: no table row is written.
 constexpr int kEmptyPos = 0x7f7f7f7f;
-constexpr unsigned kMFlagA = 1u << 30, kMFlagP = 2u << 30, kMFlagMask = 3u << 30;
 constexpr uint32_t F_INSERT = 1u, F_UNIQUE = 2u, F_TRAIN = 4u, F_PRIMED = 8u, F_SKIP_PAD = 16u;
 
 struct MapTab { float* rows; int64_t ld; int D; float sigma; float fill; uint64_t seed; };
@@ -273,47 +300,6 @@ struct LookupWs {
     int* rows_gather;  // [n]   row per position for the gather BEHIND this call: -1 where `out` is written here
 };
 
-__device__ __forceinline__ int map_lookback(unsigned* status, int tile) {
-    const int l = lane_id();
-    int excl = 0;
-    for (int base = tile - 1;; base -= 64) {
-        const int idx = base - l;
-        unsigned st;
-        do {
-            st = (idx >= 0) ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kMFlagP;
-        } while (__any((st & kMFlagMask) == 0));
-        const uint64_t pm = __ballot((st & kMFlagMask) == kMFlagP);
-        const int firstp = pm ? __ffsll((long long)pm) - 1 : 63;
-        int c = (l <= firstp) ? (int)(st & ~kMFlagMask) : 0;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-        excl += c;
-        if (pm) break;
-    }
-    return excl;
-}
-
-// tile-exclusive rank of this thread's flagged items among all tiles; *total_out (last tile, thread 0 only) = grand total
-__device__ __forceinline__ int map_tile_scan(int c, unsigned* status, int* sm, int* s_excl, int* tile_total) {
-    int tot;
-    const int pre = block_excl_scan_256(c, sm, &tot);
-    if (threadIdx.x < 64) {
-        const int t = blockIdx.x;
-        int excl = 0;
-        if (t == 0) {
-            if (threadIdx.x == 0) __hip_atomic_store(&status[0], kMFlagP | (unsigned)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            if (threadIdx.x == 0) __hip_atomic_store(&status[t], kMFlagA | (unsigned)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            excl = map_lookback(status, t);
-            if (threadIdx.x == 0) __hip_atomic_store(&status[t], kMFlagP | (unsigned)(excl + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (threadIdx.x == 0) *s_excl = excl;
-    }
-    __syncthreads();
-    *tile_total = tot;
-    return *s_excl + pre;
-}
-
 template <class K>
 __global__ __launch_bounds__(HB) void k_map_probe(MapDev m, const K* __restrict__ keys, int64_t n_max,
                                                   const int64_t* __restrict__ n_dev, uint32_t flags, int step,
@@ -329,14 +315,8 @@ __global__ __launch_bounds__(HB) void k_map_probe(MapDev m, const K* __restrict_
         return;
     }
     const uint32_t hsh = mrec_hash_key(key);
-    uint32_t s = hsh & m.mask;
-    int row = -1;
-    for (uint32_t it = 0; it <= m.mask; ++it) {
-        const int r = m.slot[s].row;
-        if (r == -1) break;
-        if (r >= 0 && m.slot[s].key == key) { row = r; break; }
-        s = (s + 1) & m.mask;
-    }
+    int slot;
+    const int row = map_find(m, key, hsh, &slot);
     rows_out[i] = row;
     if (w.rows_gather) w.rows_gather[i] = row;       // (a miss stays -1 where the finishing kernel writes the output row itself)
     if (row >= 0) {
@@ -373,16 +353,8 @@ __global__ __launch_bounds__(HB) void k_map_place(MapDev m, const K* __restrict_
     __shared__ int sm[8];
     __shared__ int s_excl;
     if (w.words[1] == 0) return;                  // no key of this call was missing
-    // the row counters as they stood before this call: read by every tile BEFORE it publishes its count, so the last
-    // tile -- whose look-back ends only after all others published -- can commit the new values
-    int64_t hwm0 = m.counters[C_HWM], nfree0 = m.counters[C_FREE];
-    // (the two loads have RETURNED before anything below is issued -- what the ordering above needs; a release fence in their place
-    // also wrote back whatever the workgroup's CU had dirtied in L2: MREC_MAP_FENCE=1 keeps it for A/B builds)
-#if defined(MREC_MAP_FENCE) && MREC_MAP_FENCE
-    __threadfence();
-#else
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(hwm0), "+v"(nfree0) : : "memory");
-#endif
+    int64_t hwm0, nfree0;
+    map_counters_before(m, C_HWM, C_FREE, &hwm0, &nfree0);
     const int64_t eff = eff_n(n_max, n_dev);
     const int64_t base = (int64_t)blockIdx.x * HT + threadIdx.x * HI;
     bool first[HI];
@@ -397,17 +369,17 @@ __global__ __launch_bounds__(HB) void k_map_place(MapDev m, const K* __restrict_
         c += f;
     }
     int tot;
-    int r = map_tile_scan(c, w.status, sm, &s_excl, &tot);
+    int r = tile_excl_scan_256(c, w.status, sm, &s_excl, &tot);
     const int64_t fresh = m.C - hwm0;
 #pragma unroll
     for (int k = 0; k < HI; ++k) {
         if (!first[k]) continue;
         const int64_t i = base + k;
         const int64_t key = (int64_t)keys[i];
-        int row = -1;
-        if (r < fresh) row = (int)(hwm0 + r);
-        else if (r - fresh < nfree0) row = m.free_list[nfree0 - 1 - (r - fresh)];
+        int row = map_row_for_rank(m, r, hwm0, nfree0);
         if (row >= 0) {
+            // claim a negative slot (empty or tombstone) on the key's probe path; k_map_insert holds the same loop, and the two stay
+            // two: as one helper it moved this kernel's instruction stream, which the lookup chain's step path may not
             uint32_t s = mrec_hash_key(key) & m.mask;
             bool placed = false;
             for (uint32_t it = 0; it <= m.mask; ++it) {
@@ -568,12 +540,8 @@ __global__ __launch_bounds__(HB) void k_map_evict(MapDev m, int step, int64_t th
                                                   int64_t* __restrict__ n_evicted, int64_t S) {
     __shared__ int sm[8];
     __shared__ int s_excl;
-    int64_t nfree0 = m.counters[C_FREE], nlog0 = m.counters[C_NLOG];
-#if defined(MREC_MAP_FENCE) && MREC_MAP_FENCE
-    __threadfence();
-#else
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(nfree0), "+v"(nlog0) : : "memory");      // (as k_map_place: returned before anything below is issued)
-#endif
+    int64_t nfree0, nlog0;
+    map_counters_before(m, C_FREE, C_NLOG, &nfree0, &nlog0);
     const int64_t base = (int64_t)blockIdx.x * HT + threadIdx.x * HI;
     bool dead[HI];
     int c = 0;
@@ -584,7 +552,7 @@ __global__ __launch_bounds__(HB) void k_map_evict(MapDev m, int step, int64_t th
         c += dead[k];
     }
     int tot;
-    int rk = map_tile_scan(c, status, sm, &s_excl, &tot);
+    int rk = tile_excl_scan_256(c, status, sm, &s_excl, &tot);
 #pragma unroll
     for (int k = 0; k < HI; ++k) {
         if (!dead[k]) continue;
@@ -597,22 +565,13 @@ __global__ __launch_bounds__(HB) void k_map_evict(MapDev m, int step, int64_t th
             if (cur == (int)r) { m.slot[s].row = -2; break; }
             s = (s + 1) & m.mask;
         }
-        m.row_live[r] = 0;
-        m.free_list[nfree0 + rk] = (int)r;
-        if (nlog0 + rk < m.C) m.erased_log[nlog0 + rk] = key;
+        map_release_row(m, (int)r, key, nfree0 + rk, nlog0 + rk);
         ++rk;
     }
-    if ((int)blockIdx.x == ntiles - 1 && threadIdx.x == 0) {
+    if ((int)blockIdx.x == ntiles - 1 && threadIdx.x == 0) {      // (the counters still stand as every tile read them)
         const int64_t M = (int64_t)s_excl + tot;
         *n_evicted = M;
-        m.counters[C_FREE] = nfree0 + M;
-        m.counters[C_LIVE] -= M;
-        m.counters[C_NLOG] = (nlog0 + M < m.C) ? nlog0 + M : m.C;
-        const int64_t tomb = m.counters[C_TOMB] + M;
-        const bool rebuild = tomb * 5 > S;
-        m.counters[C_REBUILD] = rebuild ? 1 : 0;
-        m.counters[C_TOMB] = rebuild ? 0 : tomb;
-        if (rebuild) m.counters[C_NREBUILD] += 1;
+        map_commit_freed(m, M, S);
     }
 }
 
@@ -638,14 +597,8 @@ __global__ __launch_bounds__(HB) void k_map_log_flags(MapDev m, uint8_t* __restr
     bool gone = false;
     if (j < m.counters[C_NLOG]) {
         const int64_t key = m.erased_log[j];
-        uint32_t s = mrec_hash_key(key) & m.mask;
-        gone = true;
-        for (uint32_t it = 0; it <= m.mask; ++it) {
-            const int r = m.slot[s].row;
-            if (r == -1) break;
-            if (r >= 0 && m.slot[s].key == key) { gone = false; break; }
-            s = (s + 1) & m.mask;
-        }
+        int slot;
+        gone = map_find(m, key, mrec_hash_key(key), &slot) < 0;
     }
     f[j] = gone;
 }
@@ -690,12 +643,6 @@ __global__ __launch_bounds__(HB) void k_put_reset(const int* __restrict__ rows, 
     if (i < n && rows[i] >= 0) winner[rows[i]] = -1;
 }
 
-size_t map_ws_bytes(int64_t n) {
-    const size_t nn = (size_t)(n ? n : 1);
-    return mrec_align_up(nn * 4, 256) * 3 + mrec_align_up(nn, 256) + mrec_align_up((size_t)mrec_cdiv(nn, HT) * 4, 256) +
-           512;
-}
-
 }  // namespace
 
 struct mrec_map {
@@ -703,56 +650,46 @@ struct mrec_map {
     uint64_t S;
 };
 
-static void map_layout(int64_t C, uint64_t* S_out, size_t off[10], size_t* total) {
-    uint64_t S = 1024;
-    while (S < (uint64_t)C * 2) S <<= 1;
-    size_t o = 0;
-    off[0] = o; o += mrec_align_up(S * sizeof(MapSlot), 256);
-    off[1] = o;                                   // (unused)
-    off[2] = o; o += mrec_align_up((size_t)C * 8, 256);
-    off[3] = o; o += mrec_align_up((size_t)C, 256);
-    off[4] = o; o += mrec_align_up((size_t)C * 4, 256);
-    off[5] = o; o += mrec_align_up(C_NCOUNTERS * 8, 256);
-    off[6] = o; o += mrec_align_up((size_t)C * 4, 256);
-    off[7] = o; o += mrec_align_up((size_t)C * 4, 256);
-    off[8] = o; o += mrec_align_up((size_t)C, 256);
-    off[9] = o; o += mrec_align_up((size_t)C * 8, 256);
-    *S_out = S;
-    *total = o;
+// The index's memory over C rows as the takes that carve it, from `mem` (nullptr: sizes only); the bytes it needs, or 0 for a
+// capacity no index has.
+static size_t map_layout(MapDev* d, void* mem, int64_t C) {
+    if (C <= 0 || C > (int64_t(1) << 30)) return 0;
+    const uint64_t S = scratch_cap(C);
+    MrecArena a(mem, SIZE_MAX);
+    d->slot = a.take<MapSlot>(S);
+    d->row_key = a.take<int64_t>(C);
+    d->row_live = a.take<uint8_t>(C);
+    d->free_list = a.take<int>(C);
+    d->counters = a.take<int64_t>(C_NCOUNTERS);
+    d->hits = a.take<int>(C);
+    d->last_step = a.take<int>(C);
+    d->dirty = a.take<uint8_t>(C);
+    d->erased_log = a.take<int64_t>(C);
+    d->C = C;
+    d->mask = (uint32_t)(S - 1);
+    return a.off;
 }
 
 MREC_API int mrec_map_bytes(int64_t capacity_rows, size_t* out) {
-    if (!out || capacity_rows <= 0 || capacity_rows > (int64_t(1) << 30)) return MREC_EINVAL;
-    uint64_t S; size_t off[10];
-    map_layout(capacity_rows, &S, off, out);
+    MapDev d;
+    const size_t total = map_layout(&d, nullptr, capacity_rows);
+    if (!out || !total) return MREC_EINVAL;
+    *out = total;
     return MREC_OK;
 }
 
 MREC_API int mrec_map_create(mrec_map_t** out, void* mem, size_t mem_bytes, int64_t capacity_rows, void* stream) {
-    if (!out || !mem || capacity_rows <= 0 || capacity_rows > (int64_t(1) << 30)) return MREC_EINVAL;
+    MapDev d;
+    const size_t total = map_layout(&d, mem, capacity_rows);
+    if (!out || !mem || !total) return MREC_EINVAL;
     if (((uintptr_t)mem) & 255) return MREC_EINVAL;
-    uint64_t S; size_t off[10], total;
-    map_layout(capacity_rows, &S, off, &total);
     if (mem_bytes < total) return MREC_EWORKSPACE;
-    char* b = (char*)mem;
-    mrec_map* h = new mrec_map;
-    h->S = S;
-    h->d.slot = (MapSlot*)(b + off[0]);
-    h->d.row_key = (int64_t*)(b + off[2]);
-    h->d.row_live = (uint8_t*)(b + off[3]);
-    h->d.free_list = (int*)(b + off[4]);
-    h->d.counters = (int64_t*)(b + off[5]);
-    h->d.hits = (int*)(b + off[6]);
-    h->d.last_step = (int*)(b + off[7]);
-    h->d.dirty = (uint8_t*)(b + off[8]);
-    h->d.erased_log = (int64_t*)(b + off[9]);
-    h->d.C = capacity_rows;
-    h->d.mask = (uint32_t)(S - 1);
+    mrec_map* h = new mrec_map{d, (uint64_t)d.mask + 1};
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(h->d.slot, 0xFF, S * sizeof(MapSlot), st);        // row = -1: empty
+    hipError_t e = hipMemsetAsync(h->d.slot, 0xFF, h->S * sizeof(MapSlot), st);        // row = -1: empty
     if (e == hipSuccess) e = hipMemsetAsync(h->d.row_live, 0, (size_t)capacity_rows, st);
     if (e == hipSuccess) e = hipMemsetAsync(h->d.counters, 0, C_NCOUNTERS * 8, st);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d.hits, 0, off[9] - off[6], st);        // hits, last_step, dirty
+    if (e == hipSuccess) e = hipMemsetAsync(h->d.hits, 0, (char*)h->d.erased_log - (char*)h->d.hits, st);        // hits, last_step, dirty
     if (e != hipSuccess) { g_mrec_last_hip_error = (int)e; delete h; return MREC_EHIP; }
     *out = h;
     return MREC_OK;
@@ -773,10 +710,46 @@ MREC_API int mrec_map_tracking_dev(const mrec_map_t* h, int32_t** hits, int32_t*
     return MREC_OK;
 }
 
+// The workspace of find_or_insert and erase over n keys as the takes that carve it (ws == nullptr: the arena only counts); erase also
+// keeps the rows and slots it found.
+struct FindWs {
+    int *rank, *slots, *blocksum, *rows;
+    uint8_t* miss;
+    int64_t* words;      // find_or_insert: [0] = misses, [1] = dropped in this call, [2] = tombstones taken back; erase: [0] = keys found
+    size_t bytes;
+    bool ok;
+    FindWs(void* ws, size_t ws_bytes, int64_t n, bool erase) {
+        MrecArena a(ws, ws_bytes);
+        rank = a.take<int>(n);
+        slots = a.take<int>(n);
+        miss = a.take<uint8_t>(n);
+        blocksum = a.take<int>(mrec_cdiv(n, HT));
+        words = a.take<int64_t>(3);
+        rows = erase ? a.take<int>(n) : nullptr;
+        bytes = a.off;
+        ok = a.ok;
+    }
+};
+
+// (erase's carve and 256 bytes nobody takes: the answer callers have sized their buffers by)
 MREC_API int mrec_map_workspace_bytes(int64_t n, size_t* out) {
     if (!out || n < 0) return MREC_EINVAL;
-    *out = map_ws_bytes(n);
+    *out = FindWs(nullptr, SIZE_MAX, n ? n : 1, true).bytes + 256;
     return MREC_OK;
+}
+
+// rank[i] = the exclusive rank of every element whose flag != 0 (invert: == 0) among n, *total_dev = their count
+static void rank_flags(const uint8_t* flags, int64_t n, int invert, int* blocksum, int* rank, int64_t* total_dev, hipStream_t st) {
+    const int nblk = (int)mrec_cdiv(n, HT);
+    k_flag_count<<<nblk, HB, 0, st>>>(flags, n, invert, blocksum);
+    k_flag_rank<<<nblk, HB, 0, st>>>(flags, n, invert, blocksum, nblk, rank, total_dev);
+}
+
+// behind a commit that may have asked for a rebuild: both return at once unless it did (grid-stride, so the idle launch is small)
+static void launch_rebuild(mrec_map* h, hipStream_t st) {
+    const unsigned gr = (unsigned)(mrec_cdiv((int64_t)h->S, HB) < 2048 ? mrec_cdiv((int64_t)h->S, HB) : 2048);
+    k_map_rebuild_clear<<<gr, HB, 0, st>>>(h->d, (int64_t)h->S);
+    k_map_rebuild_insert<<<gr, HB, 0, st>>>(h->d);
 }
 
 MREC_API int mrec_map_find_or_insert(mrec_map_t* h, const int64_t* keys, int64_t n, const int64_t* n_dev, int insert,
@@ -786,23 +759,15 @@ MREC_API int mrec_map_find_or_insert(mrec_map_t* h, const int64_t* keys, int64_t
     if (n == 0) return MREC_OK;
     if (!keys || !rows_out || !ws) return MREC_EINVAL;
     if (n > (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    MrecArena a(ws, ws_bytes);
-    int* rank = a.take<int>(n);
-    int* slots = a.take<int>(n);
-    uint8_t* miss = a.take<uint8_t>(n);
-    const int nblk = (int)mrec_cdiv(n, HT);
-    int* blocksum = a.take<int>(nblk);
-    int64_t* words = a.take<int64_t>(3);  // [0] = misses, [1] = dropped in this call, [2] = tombstones taken back
-    if (!a.ok) return MREC_EWORKSPACE;
-    (void)slots;
+    const FindWs w(ws, ws_bytes, n, false);
+    if (!w.ok) return MREC_EWORKSPACE;
     const unsigned g = (unsigned)mrec_cdiv(n, HB);
-    k_map_find<<<g, HB, 0, st>>>(h->d, keys, n, n_dev, rows_out, nullptr, miss);
+    k_map_find<<<g, HB, 0, st>>>(h->d, keys, n, n_dev, rows_out, nullptr, w.miss);
     if (insert) {
-        MREC_HIP_CHECK(hipMemsetAsync(words, 0, 24, st));
-        k_flag_count<<<nblk, HB, 0, st>>>(miss, n, 0, blocksum);
-        k_flag_rank<<<nblk, HB, 0, st>>>(miss, n, 0, blocksum, nblk, rank, words);
-        k_map_insert<<<g, HB, 0, st>>>(h->d, keys, n, miss, rank, rows_out, is_new_out, words + 1, words + 2);
-        k_map_commit_insert<<<1, 1, 0, st>>>(h->d, words, words + 1, words + 2);
+        MREC_HIP_CHECK(hipMemsetAsync(w.words, 0, 24, st));
+        rank_flags(w.miss, n, 0, w.blocksum, w.rank, w.words, st);
+        k_map_insert<<<g, HB, 0, st>>>(h->d, keys, n, w.miss, w.rank, rows_out, is_new_out, w.words + 1, w.words + 2);
+        k_map_commit_insert<<<1, 1, 0, st>>>(h->d, w.words, w.words + 1, w.words + 2);
     } else if (is_new_out) {
         MREC_HIP_CHECK(hipMemsetAsync(is_new_out, 0, (size_t)n, st));
     }
@@ -816,25 +781,14 @@ MREC_API int mrec_map_erase(mrec_map_t* h, const int64_t* keys, int64_t n, void*
     if (n == 0) return MREC_OK;
     if (!keys || !ws) return MREC_EINVAL;
     if (n > (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    MrecArena a(ws, ws_bytes);
-    int* rank = a.take<int>(n);
-    int* slots = a.take<int>(n);
-    uint8_t* miss = a.take<uint8_t>(n);
-    const int nblk = (int)mrec_cdiv(n, HT);
-    int* blocksum = a.take<int>(nblk);
-    int64_t* words = a.take<int64_t>(2);  // [0] = keys found
-    int* rows = a.take<int>(n);
-    if (!a.ok) return MREC_EWORKSPACE;
+    const FindWs w(ws, ws_bytes, n, true);
+    if (!w.ok) return MREC_EWORKSPACE;
     const unsigned g = (unsigned)mrec_cdiv(n, HB);
-    k_map_find<<<g, HB, 0, st>>>(h->d, keys, n, nullptr, rows, slots, miss);
-    k_flag_count<<<nblk, HB, 0, st>>>(miss, n, 1, blocksum);
-    k_flag_rank<<<nblk, HB, 0, st>>>(miss, n, 1, blocksum, nblk, rank, words);
-    k_map_erase<<<g, HB, 0, st>>>(h->d, n, rows, slots, miss, rank);
-    k_map_commit_erase<<<1, 1, 0, st>>>(h->d, words, (int64_t)h->S);
-    // both return at once unless the commit asked for a rebuild (grid-stride, so the idle launch is small)
-    const unsigned gr = (unsigned)(mrec_cdiv((int64_t)h->S, HB) < 2048 ? mrec_cdiv((int64_t)h->S, HB) : 2048);
-    k_map_rebuild_clear<<<gr, HB, 0, st>>>(h->d, (int64_t)h->S);
-    k_map_rebuild_insert<<<gr, HB, 0, st>>>(h->d);
+    k_map_find<<<g, HB, 0, st>>>(h->d, keys, n, nullptr, w.rows, w.slots, w.miss);
+    rank_flags(w.miss, n, 1, w.blocksum, w.rank, w.words, st);
+    k_map_erase<<<g, HB, 0, st>>>(h->d, n, w.rows, w.slots, w.miss, w.rank);
+    k_map_commit_erase<<<1, 1, 0, st>>>(h->d, w.words, (int64_t)h->S);
+    launch_rebuild(h, st);
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
@@ -846,89 +800,99 @@ MREC_API int mrec_map_export(mrec_map_t* h, int64_t* keys_out, int32_t* rows_out
     const int64_t C = h->d.C;
     MrecArena a(ws, ws_bytes);
     int* rank = a.take<int>(C);
-    const int nblk = (int)mrec_cdiv(C, HT);
-    int* blocksum = a.take<int>(nblk);
+    int* blocksum = a.take<int>(mrec_cdiv(C, HT));
     if (!a.ok) return MREC_EWORKSPACE;
-    k_flag_count<<<nblk, HB, 0, st>>>(h->d.row_live, C, 0, blocksum);
-    k_flag_rank<<<nblk, HB, 0, st>>>(h->d.row_live, C, 0, blocksum, nblk, rank, n_out_dev);
+    rank_flags(h->d.row_live, C, 0, blocksum, rank, n_out_dev, st);
     k_map_export<<<(unsigned)mrec_cdiv(C, HB), HB, 0, st>>>(h->d, rank, keys_out, rows_out);
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
 
 // ---- MapTensorGet chain -----------------------------------------------------------------------------------------
-static uint64_t lookup_cap(int64_t n) {
-    uint64_t cap = 1024;
-    while (cap < (uint64_t)(n ? n : 1) * 2) cap <<= 1;
-    return cap;
+// the chain's workspace over n keys as the takes that carve it (ws == nullptr: the arena only counts)
+static MrecArena lookup_carve(LookupWs* w, void* ws, size_t ws_bytes, int64_t n) {
+    const uint64_t cap = scratch_cap(n);
+    MrecArena a(ws, ws_bytes);
+    w->slots = a.take<int>(cap);
+    w->srank = a.take<int>(cap);
+    w->sidx = a.take<int>(n);
+    w->newrow = a.take<int>(n);
+    w->newkey = a.take<int64_t>(n);
+    w->status = (unsigned*)a.take<int>(mrec_cdiv(n, HT));
+    w->words = a.take<int64_t>(2);      // [0] new keys, [1] "some key was missing"
+    w->smask = (uint32_t)(cap - 1);
+    w->newpos = a.take<int>(n);
+    return a;
 }
 MREC_API int mrec_map_lookup_workspace_bytes(int64_t n, size_t* out) {
     if (!out || n < 0) return MREC_EINVAL;
     if (n >= (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    const size_t nn = (size_t)(n ? n : 1);
-    const uint64_t cap = lookup_cap(n);
-    *out = mrec_align_up(cap * 4, 256) * 2 + mrec_align_up(nn * 4, 256) * 3 + mrec_align_up(nn * 8, 256) +
-           mrec_align_up((size_t)mrec_cdiv(nn, HT) * 4, 256) + 256;
+    LookupWs w;
+    *out = lookup_carve(&w, nullptr, SIZE_MAX, n ? n : 1).off;
     return MREC_OK;
 }
 
+// What mrec_map_lookup and mrec_map_lookup_out take; with_out: the second, whose output arguments are then judged too.
+struct MapLookupArgs {
+    mrec_map* h; const void* keys; int32_t key_bytes; int64_t n; const int64_t* n_dev; uint32_t flags; int64_t step; int32_t permit;
+    const mrec_map_table_t* tables; int32_t n_tables; int32_t* rows_out; int32_t* rows_adm; void* ws; size_t ws_bytes; void* stream;
+    bool with_out; float* out; int64_t ldo; int32_t out_table; int32_t* rows_gather;
+};
+
 template <class K>
-static int map_lookup_impl(mrec_map* h, const K* keys, int64_t n, const int64_t* n_dev, uint32_t flags, int64_t step,
-                           int32_t permit, const mrec_map_table_t* tables, int32_t n_tables, int32_t* rows_out,
-                           int32_t* rows_adm, void* ws, size_t ws_bytes, hipStream_t st, float* out = nullptr, int64_t ldo = 0,
-                           int32_t out_table = 0, int32_t* rows_gather = nullptr) {
+static int map_lookup_impl(const MapLookupArgs& q, const K* keys) {
+    mrec_map* h = q.h;
+    const int64_t n = q.n;
+    const uint32_t flags = q.flags;
+    hipStream_t st = (hipStream_t)q.stream;
     MapTabs tabs;
-    tabs.n = n_tables;
-    for (int t = 0; t < n_tables; ++t) {
-        if (!tables[t].rows || tables[t].D <= 0 || tables[t].ld < tables[t].D) return MREC_EINVAL;
-        tabs.t[t] = MapTab{tables[t].rows, tables[t].ld, tables[t].D, tables[t].sigma, tables[t].fill, tables[t].seed};
+    tabs.n = q.n_tables;
+    for (int t = 0; t < q.n_tables; ++t) {
+        const mrec_map_table_t& tb = q.tables[t];
+        if (!tb.rows || tb.D <= 0 || tb.ld < tb.D) return MREC_EINVAL;
+        tabs.t[t] = MapTab{tb.rows, tb.ld, tb.D, tb.sigma, tb.fill, tb.seed};
     }
     const int ntiles = (int)mrec_cdiv(n, HT);
-    const uint64_t cap = lookup_cap(n);
-    MrecArena a(ws, ws_bytes);
     LookupWs w;
-    w.slots = a.take<int>(cap);
-    w.srank = a.take<int>(cap);
-    w.sidx = a.take<int>(n);
-    w.newrow = a.take<int>(n);
-    w.newkey = a.take<int64_t>(n);
-    w.status = (unsigned*)a.take<int>(ntiles);
-    w.words = a.take<int64_t>(2);
-    w.smask = (uint32_t)(cap - 1);
-    w.newpos = a.take<int>(n);
-    w.out = out; w.ldo = ldo; w.out_tab = out_table; w.rows_gather = rows_gather;
-    if (!a.ok) return MREC_EWORKSPACE;
+    if (!lookup_carve(&w, q.ws, q.ws_bytes, n).ok) return MREC_EWORKSPACE;
+    w.out = q.out; w.ldo = q.ldo; w.out_tab = q.out_table; w.rows_gather = q.rows_gather;
     const bool inserting = (flags & F_INSERT) != 0;
     if (inserting && !(flags & F_PRIMED)) {
-        MREC_HIP_CHECK(hipMemsetAsync(w.slots, 0x7f, cap * sizeof(int), st));      // (also for unique keys: "primed" must hold for any later call)
+        MREC_HIP_CHECK(hipMemsetAsync(w.slots, 0x7f, ((size_t)w.smask + 1) * sizeof(int), st));      // (also for unique keys: "primed" must hold for any later call)
         MREC_HIP_CHECK(hipMemsetAsync(w.status, 0, (size_t)ntiles * sizeof(int), st));
     }
-    if (inserting) MREC_HIP_CHECK(hipMemsetAsync(w.words, 0, 16, st));     // [0] new keys, [1] "some key was missing"
+    if (inserting) MREC_HIP_CHECK(hipMemsetAsync(w.words, 0, 16, st));
     const unsigned g = (unsigned)mrec_cdiv(n, HB);
-    k_map_probe<K><<<g, HB, 0, st>>>(h->d, keys, n, n_dev, flags, (int)step, rows_out, w);
-    if (inserting) k_map_place<K><<<ntiles, HB, 0, st>>>(h->d, keys, n, n_dev, flags, (int)step, rows_out, w, ntiles);
-    if (inserting || rows_adm) {
+    k_map_probe<K><<<g, HB, 0, st>>>(h->d, keys, n, q.n_dev, flags, (int)q.step, q.rows_out, w);
+    if (inserting) k_map_place<K><<<ntiles, HB, 0, st>>>(h->d, keys, n, q.n_dev, flags, (int)q.step, q.rows_out, w, ntiles);
+    if (inserting || q.rows_adm) {
         const unsigned gf = g < 2048 ? g : 2048;
-        k_map_finish<K><<<gf, HB, 0, st>>>(h->d, tabs, keys, n, n_dev, flags, permit, rows_out, rows_adm, w, ntiles);
+        k_map_finish<K><<<gf, HB, 0, st>>>(h->d, tabs, keys, n, q.n_dev, flags, q.permit, q.rows_out, q.rows_adm, w, ntiles);
     }
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
 
+// One order of checks for both entries.  Where they differ the record says so: mrec_map_lookup takes no table at all (n_tables == 0),
+// mrec_map_lookup_out needs the one its output rows belong to, and its output arguments join each rung of the ladder.
+static int map_lookup_run(const MapLookupArgs& q) {
+    if (!q.h || q.n < 0 || (q.key_bytes != 4 && q.key_bytes != 8) || q.n_tables < (q.with_out ? 1 : 0) || q.n_tables > 8 ||
+        (q.n_tables > 0 && !q.tables) || q.step < 0 || q.step > 0x7fffffff)
+        return MREC_EINVAL;
+    if (q.with_out && (q.out_table < 0 || q.out_table >= q.n_tables)) return MREC_EINVAL;
+    if (q.n == 0) return MREC_OK;
+    if (!q.keys || !q.rows_out || !q.ws) return MREC_EINVAL;
+    if (q.with_out && (!q.out || !q.rows_gather || q.ldo < q.tables[q.out_table].D)) return MREC_EINVAL;
+    if (q.n >= (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
+    if (q.with_out && ((q.ldo % 4) || !al16(q.out))) return MREC_EUNSUPPORTED;
+    return by_key(q.keys, q.key_bytes, [&](auto* keys) { return map_lookup_impl(q, keys); });
+}
+
 MREC_API int mrec_map_lookup(mrec_map_t* h, const void* keys, int32_t key_bytes, int64_t n, const int64_t* n_dev, uint32_t flags,
                              int64_t step, int32_t permit, const mrec_map_table_t* tables, int32_t n_tables,
                              int32_t* rows_out, int32_t* rows_admitted_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || n < 0 || (key_bytes != 4 && key_bytes != 8) || n_tables < 0 || n_tables > 8 || (n_tables > 0 && !tables) ||
-        step < 0 || step > 0x7fffffff)
-        return MREC_EINVAL;
-    if (n == 0) return MREC_OK;
-    if (!keys || !rows_out || !ws) return MREC_EINVAL;
-    if (n >= (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    if (key_bytes == 4)
-        return map_lookup_impl<int32_t>(h, (const int32_t*)keys, n, n_dev, flags, step, permit, tables, n_tables, rows_out,
-                                        rows_admitted_out, ws, ws_bytes, (hipStream_t)stream);
-    return map_lookup_impl<int64_t>(h, (const int64_t*)keys, n, n_dev, flags, step, permit, tables, n_tables, rows_out,
-                                    rows_admitted_out, ws, ws_bytes, (hipStream_t)stream);
+    return map_lookup_run({h, keys, key_bytes, n, n_dev, flags, step, permit, tables, n_tables, rows_out, rows_admitted_out, ws, ws_bytes,
+                           stream, false, nullptr, 0, 0, nullptr});
 }
 
 /* MapTensorGet with insertion, the lookup's OUTPUT included for new keys: as mrec_map_lookup, and the kernel that generates the
@@ -939,18 +903,8 @@ MREC_API int mrec_map_lookup_out(mrec_map_t* h, const void* keys, int32_t key_by
                                  int64_t step, int32_t permit, const mrec_map_table_t* tables, int32_t n_tables,
                                  int32_t* rows_out, int32_t* rows_admitted_out, float* out, int64_t ldo, int32_t out_table,
                                  int32_t* rows_gather, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || n < 0 || (key_bytes != 4 && key_bytes != 8) || n_tables <= 0 || n_tables > 8 || !tables || step < 0 || step > 0x7fffffff ||
-        out_table < 0 || out_table >= n_tables)
-        return MREC_EINVAL;
-    if (n == 0) return MREC_OK;
-    if (!keys || !rows_out || !ws || !out || !rows_gather || ldo < tables[out_table].D) return MREC_EINVAL;
-    if (n >= (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
-    if ((ldo % 4) || (((uintptr_t)out) & 15)) return MREC_EUNSUPPORTED;
-    if (key_bytes == 4)
-        return map_lookup_impl<int32_t>(h, (const int32_t*)keys, n, n_dev, flags, step, permit, tables, n_tables, rows_out,
-                                        rows_admitted_out, ws, ws_bytes, (hipStream_t)stream, out, ldo, out_table, rows_gather);
-    return map_lookup_impl<int64_t>(h, (const int64_t*)keys, n, n_dev, flags, step, permit, tables, n_tables, rows_out,
-                                    rows_admitted_out, ws, ws_bytes, (hipStream_t)stream, out, ldo, out_table, rows_gather);
+    return map_lookup_run({h, keys, key_bytes, n, n_dev, flags, step, permit, tables, n_tables, rows_out, rows_admitted_out, ws, ws_bytes,
+                           stream, true, out, ldo, out_table, rows_gather});
 }
 
 MREC_API int mrec_map_fill_missing(const void* keys, int32_t key_bytes, const int32_t* rows, int64_t n, float* out, int64_t ldo,
@@ -960,10 +914,11 @@ MREC_API int mrec_map_fill_missing(const void* keys, int32_t key_bytes, const in
     if (!keys || !rows || !out) return MREC_EINVAL;
     MapTab tb{nullptr, 0, table->D, table->sigma, table->fill, table->seed};
     const unsigned g = (unsigned)(mrec_cdiv(n, HB) < 2048 ? mrec_cdiv(n, HB) : 2048);
-    if (key_bytes == 4) k_map_fill_missing<int32_t><<<g, HB, 0, (hipStream_t)stream>>>((const int32_t*)keys, rows, n, out, ldo, tb);
-    else k_map_fill_missing<int64_t><<<g, HB, 0, (hipStream_t)stream>>>((const int64_t*)keys, rows, n, out, ldo, tb);
-    MREC_LAUNCH_CHECK();
-    return MREC_OK;
+    return by_key(keys, key_bytes, [&](auto* k) -> int {
+        k_map_fill_missing<<<g, HB, 0, (hipStream_t)stream>>>(k, rows, n, out, ldo, tb);
+        MREC_LAUNCH_CHECK();
+        return MREC_OK;
+    });
 }
 
 MREC_API int mrec_map_evict(mrec_map_t* h, int64_t step, int64_t threshold, int64_t* n_evicted_dev, void* ws, size_t ws_bytes,
@@ -974,9 +929,7 @@ MREC_API int mrec_map_evict(mrec_map_t* h, int64_t step, int64_t threshold, int6
     if (ws_bytes < (size_t)ntiles * 4) return MREC_EWORKSPACE;
     MREC_HIP_CHECK(hipMemsetAsync(ws, 0, (size_t)ntiles * 4, st));
     k_map_evict<<<ntiles, HB, 0, st>>>(h->d, (int)step, threshold, (unsigned*)ws, ntiles, n_evicted_dev, (int64_t)h->S);
-    const unsigned gr = (unsigned)(mrec_cdiv((int64_t)h->S, HB) < 2048 ? mrec_cdiv((int64_t)h->S, HB) : 2048);
-    k_map_rebuild_clear<<<gr, HB, 0, st>>>(h->d, (int64_t)h->S);
-    k_map_rebuild_insert<<<gr, HB, 0, st>>>(h->d);
+    launch_rebuild(h, st);
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }
@@ -988,19 +941,16 @@ MREC_API int mrec_map_export_dirty(mrec_map_t* h, int64_t* keys_out, int32_t* ro
     const int64_t C = h->d.C;
     MrecArena a(ws, ws_bytes);
     int* rank = a.take<int>(C);
-    const int nblk = (int)mrec_cdiv(C, HT);
-    int* blocksum = a.take<int>(nblk);
+    int* blocksum = a.take<int>(mrec_cdiv(C, HT));
     uint8_t* f = a.take<uint8_t>(C);
-    int64_t* words = a.take<int64_t>(2);
+    int64_t* words = a.take<int64_t>(2);      // [0] = modified rows, [1] = erased keys
     if (!a.ok) return MREC_EWORKSPACE;
     const unsigned g = (unsigned)mrec_cdiv(C, HB);
     k_map_dirty_flags<<<g, HB, 0, st>>>(h->d, f);
-    k_flag_count<<<nblk, HB, 0, st>>>(f, C, 0, blocksum);
-    k_flag_rank<<<nblk, HB, 0, st>>>(f, C, 0, blocksum, nblk, rank, words);
+    rank_flags(f, C, 0, blocksum, rank, words, st);
     k_map_export_flagged<<<g, HB, 0, st>>>(h->d, f, rank, keys_out, rows_out, status_out);
     k_map_log_flags<<<g, HB, 0, st>>>(h->d, f);
-    k_flag_count<<<nblk, HB, 0, st>>>(f, C, 0, blocksum);
-    k_flag_rank<<<nblk, HB, 0, st>>>(f, C, 0, blocksum, nblk, rank, words + 1);
+    rank_flags(f, C, 0, blocksum, rank, words + 1, st);
     k_map_export_log<<<g, HB, 0, st>>>(h->d, f, rank, words, words + 1, keys_out, rows_out, status_out, n_out_dev);
     if (clear) k_map_clear_dirty<<<g, HB, 0, st>>>(h->d);
     MREC_LAUNCH_CHECK();
