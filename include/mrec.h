@@ -605,6 +605,11 @@ typedef struct mrec_transpose {
 } mrec_transpose_t;
 int mrec_dense_operand_copies(int32_t n_t, const mrec_transpose_t* t, const uint16_t* tail_w2, const uint16_t* tail_w3, int32_t K2,
                               int32_t N2, int32_t N3, uint16_t* tail_packed, void* stream);
+/* Read-only: the tile configuration a launch of this shape runs in on this device, by the very rule the launches use.
+ * op 0 = forward, 1 = bprop/input, 2 = bprop/weight (also the weight-gradient side of mrec_dense_bwd_*).  *rows_out = 256
+ * (256 x 256 output tiles) or 128 (128 x 256).  Touches no device memory; without a device the rule assumes 256 CUs.
+ * M, K, N > 0, else MREC_EINVAL. */
+int mrec_dense_tile_rows(int32_t op, int64_t M, int32_t K, int32_t N, int32_t* rows_out);
 /* bprop with respect to the layer's input, fused with the ReLU and BiasAdd bprops of the layer BELOW:
  *   dx[m, k] = h[m, k] > 0 ? sum_n dy[m, n] * w[k, n] : 0      (h nullable: no mask -- the first layer's input)
  *   db[k]    = sum_m dx[m, k]                                  (db nullable; sums of the rounded dx, fp32, fixed order)

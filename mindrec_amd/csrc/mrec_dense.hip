@@ -29,6 +29,7 @@ int cu_count() {
 // Tile configuration: the 256 x 256 tile when its workgroups fill the chip, else the 128 x 256 one (twice the
 // workgroups, half the time per K-tile: the narrow layers are bound by the latency of one workgroup's K loop).
 inline int pick_mr(int64_t blocks_256) { return blocks_256 * 4 >= (int64_t)cu_count() * 3 ? 8 : 4; }
+inline int fwd_mr(int64_t M, int32_t N) { return pick_mr(mrec_cdiv(M, 256) * mrec_cdiv(N, 256)); }
 int bwd_input_mr(int64_t M, int32_t K);
 int bwd_mr(int64_t M, int32_t K, int32_t N);
 
@@ -81,7 +82,7 @@ int fwd_impl(const uint16_t* x, int64_t ldx, const uint16_t* w, const float* bia
     if (M * ldx * 2 >= (int64_t(1) << 31) || (int64_t)K * N * 2 >= (int64_t(1) << 31) || M > (int64_t(1) << 30)) return MREC_EUNSUPPORTED;
     // (128 x 256 tiles for layer 0 of the reference's net too -- 512 workgroups instead of exactly one round of 256, to lose less
     // to the plan kernels that take CUs beside it -- was measured: 0.674 vs 0.654 ms/step)
-    const int mr = pick_mr(mrec_cdiv(M, 256) * mrec_cdiv(N, 256));
+    const int mr = fwd_mr(M, N);
     Args a{};
     a.P = x; a.Q = w; a.C = y; a.bias = bias;
     a.ldp = ldx; a.ldq = WT ? K : N; a.ldc = ldy;
@@ -293,6 +294,14 @@ MREC_API int mrec_dense_bwd_input_f16(const uint16_t* dy, int64_t lddy, const ui
                                       int32_t K, int32_t N, uint16_t* dx, int64_t lddx, float* db, void* ws, size_t ws_bytes,
                                       const mrec_dropout_t* drop_in, void* stream) {
     return bwd_input_impl<true>(dy, lddy, w, h, M, K, N, dx, lddx, db, ws, ws_bytes, drop_in, stream);
+}
+
+/* P-side rows of the tile configuration a launch of this shape runs in (see include/mrec.h) */
+MREC_API int mrec_dense_tile_rows(int32_t op, int64_t M, int32_t K, int32_t N, int32_t* rows_out) {
+    if (!rows_out || op < 0 || op > 2 || M <= 0 || K <= 0 || N <= 0) return MREC_EINVAL;
+    const int mr = op == 0 ? fwd_mr(M, N) : op == 1 ? bwd_input_mr(M, K) : bwd_mr(M, K, N);
+    *rows_out = mr * 32;
+    return MREC_OK;
 }
 
 MREC_API int mrec_dense_bwd_weight_slabs(int64_t M, int32_t K, int32_t N, int32_t* S_out) {

@@ -1707,6 +1707,19 @@ def dense_bwd_input(dy, w, h=None, db_out=None, out=None, db_slabs=None, drop_in
     return dx
 
 
+def dense_tile_rows(op, M, K, N):
+    """Rows of the output tile (256 or 128) the library runs this shape in on this device: op "fwd" / "bwd_input" /
+    "bwd_weight" (or 0 / 1 / 2).  dense_bwd runs its two halves in the bwd_input and bwd_weight configurations."""
+    names = {"fwd": 0, "bwd_input": 1, "bwd_weight": 2}
+    if isinstance(op, str):
+        if op not in names:
+            raise ValueError(f'dense_tile_rows: op must be "fwd", "bwd_input" or "bwd_weight" (or 0 / 1 / 2), not {op!r}')
+        op = names[op]
+    r = C.c_int32(0)
+    _lib.call("mrec_dense_tile_rows", int(op), M, K, N, C.byref(r))
+    return int(r.value)
+
+
 def dense_bwd_bias_slabs(M, K, N, fused=True):
     """Rows of the bias-gradient slabs [T, K] dense_bwd (fused) / dense_bwd_input leave behind for this shape."""
     t = C.c_int32(0)
