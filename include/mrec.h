@@ -1039,7 +1039,8 @@ int mrec_profile_next_apply(void* start, void* stop);
  *                form 1: C[M, K] = P[M, N] . Q[K, N]^T       P = parts of dy [M, N], Q = parts of w [K, N]
  *                form 2: C[S][K, N] = P[M, K]^T . Q[M, N]    P = parts of x [M, K],  Q = parts of dy [M, N]; S batch slabs of
  *                        fp32 partial sums (slab s at C + s * K * ldc), added up by mrec_dense_adam_slabs_* / mrec_dense_sum_slabs_f32
- *   C is fp32 with row stride ldc (even; 16-byte stores when ldc % 4 == 0).
+ *   C is fp32 with row stride ldc (even; 16-byte stores when ldc % 4 == 0, except the last two columns of a width that is 2 mod 4:
+ *   nothing outside the [rows, width] window of C is written, so C may be a column window of a wider buffer).
  *   mrec_x3_bias_relu: y = relu?(acc + bias) in place (BiasAdd + ReLU) and, parts_out != NULL, y's parts image in the same pass.
  *   mrec_x3_mask_colsum: dx = (h > 0 ? acc : 0) * scale in place (scale: 1 / keep of a Dropout on the layer's input, else 1) (the ReLU bprop of the layer below; h nullable), colsum [ceil(M / 64), K]
  *   (nullable) = column sums of dx per 64 rows (that layer's BiasAdd bprop), and dx's parts image. */
@@ -1047,6 +1048,11 @@ int mrec_x3_parts_elems(int64_t rows, int64_t cols, int64_t* out);
 int mrec_x3_split(const float* x, int64_t ldx, int64_t R, int32_t C, uint16_t* parts, void* stream);
 int mrec_x3_gemm(int form, const uint16_t* Pparts, const uint16_t* Qparts, int64_t M, int32_t K, int32_t N, float* C, int64_t ldc,
                  int32_t S, void* stream);
+/* Read-only: the tile configuration mrec_x3_gemm (and the fused forms mrec_x3_gemm_fwd = form 0, mrec_x3_gemm_dgrad's one-launch
+ * form = form 1, both with S = 1) runs this shape in, by the very rule the launches use: *rows_out = 256 (256 x 256 output tiles) or
+ * 128 (128 x 256).  Touches no device memory.  MREC_EINVAL, and nothing written, on the form / M / K / N / S mrec_x3_gemm refuses
+ * (forms 0 and 1: S != 1; form 2: an S that leaves a slab without a share of the 6 * ceil(M / 64) reduction tiles). */
+int mrec_x3_tile_rows(int form, int64_t M, int32_t K, int32_t N, int32_t S, int32_t* rows_out);
 int mrec_x3_bias_relu(float* acc, int64_t ld, int64_t M, int32_t N, const float* bias, int relu, uint16_t* parts_out, void* stream);
 /* the slab count mrec_x3_gemm's form 2 runs fastest with (a 256 x 256 tile x slab per CU); any S <= 6 * ceil(M / 64) whose slabs are
  * all non-empty is accepted */

@@ -115,6 +115,7 @@ _SIGS = {
     "mrec_x3_parts_elems": [_i64, _i64, _vp],
     "mrec_x3_split": [_vp, _i64, _i64, _i32, _vp, _vp],
     "mrec_x3_gemm": [_int, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp],
+    "mrec_x3_tile_rows": [_int, _i64, _i32, _i32, _i32, C.POINTER(C.c_int32)],
     "mrec_x3_bias_relu": [_vp, _i64, _i64, _i32, _vp, _int, _vp, _vp],
     "mrec_x3_wgrad_slabs": [_i64, _i32, _i32, _vp],
     "mrec_x3_gemm_fwd": [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp],

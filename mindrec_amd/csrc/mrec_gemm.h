@@ -642,9 +642,10 @@ __device__ __forceinline__ void gemm256_body(const Args& a, const int bid, const
                     const int q = q0 + ni * 16;
                     if (q < a.Qext) {
                         float* dst = C + (int64_t)p * a.ldc + q;
-                        if ((a.ldc & 3) == 0) {
+                        if ((a.ldc & 3) == 0 && q + 4 <= a.Qext) {
                             *(f32x4_t*)dst = acc[mi][ni];
-                        } else {            // rows that are only 8-byte aligned (Deep&Cross's 1170-column input gradient)
+                        } else {            // rows that are only 8-byte aligned (Deep&Cross's 1170-column input gradient), or the last
+                                            // two columns of a width that is 2 mod 4
                             typedef float f32x2_t __attribute__((ext_vector_type(2)));
                             *(f32x2_t*)dst = f32x2_t{acc[mi][ni][0], acc[mi][ni][1]};
                             if (q + 2 < a.Qext) *(f32x2_t*)(dst + 2) = f32x2_t{acc[mi][ni][2], acc[mi][ni][3]};
@@ -719,7 +720,7 @@ __device__ __forceinline__ void gemm256_body(const Args& a, const int bid, const
 #pragma unroll
                     for (int r = 0; r < 4; ++r) cs[mi / 4][ni][r] += v[r];
                     float* dst = C + (int64_t)p * a.ldc + q;
-                    if (v16) {
+                    if (v16 && q + 4 <= a.Qext) {
                         *(f32x4_t*)dst = v;
                     } else {
                         *(f32x2_t*)dst = f32x2_t{v[0], v[1]};

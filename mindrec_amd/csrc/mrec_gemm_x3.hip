@@ -224,7 +224,30 @@ struct X3Epi {                // the fused output end (EPI_X3); mode 0: plain fp
 };
 int x3_gemm(int form, const uint16_t* Pparts, const uint16_t* Qparts, int64_t M, int32_t K, int32_t N, float* C, int64_t ldc, int32_t S,
             const X3Epi& e, void* stream);
+
+// Rows of the output tile a launch of this form and shape runs in (256 or 128); 0: arguments x3_gemm refuses (forms 0 and 1 take
+// S = 1 only; form 2 any S whose slabs all get a share of the 6 * ceil(M / 64) reduction tiles).
+// 256- or 128-row tiles: whichever fills the 256 CUs in fewer tile-times (a 128-row tile costs ~0.55 of a 256-row one; the input
+// gradient into 1170 columns is 320 big tiles = two rounds at 62 %, or 640 small ones = 2.5 rounds of half the length)
+int x3_tile_rows(int form, int64_t M, int32_t K, int32_t N, int32_t S) {
+    if (form < 0 || form > 2 || M <= 0 || K <= 0 || N <= 0 || S <= 0 || (form != 2 && S != 1)) return 0;
+    const int64_t Ttot = 6 * (up64(form == 0 ? K : form == 1 ? N : M) / 64);
+    if (S > 1 && mrec_cdiv(Ttot, S) * (S - 1) >= Ttot) return 0;
+    const int64_t Pext = form == 2 ? K : M, Qext = form == 1 ? K : N;
+    const int64_t t8 = mrec_cdiv(Pext, 256) * mrec_cdiv(Qext, 256) * S, t4 = mrec_cdiv(Pext, 128) * mrec_cdiv(Qext, 256) * S;
+    int rows = (double)mrec_cdiv(t4, 256) * 0.55 < (double)mrec_cdiv(t8, 256) ? 128 : 256;
+    static const int force_mr = [] { const char* e = getenv("MREC_X3_MR"); return e ? atoi(e) : 0; }();      // (tools/probes/x3_bench.py)
+    if (force_mr == 4 || force_mr == 8) rows = force_mr * 32;
+    return rows;
+}
 }  // namespace
+
+MREC_API int mrec_x3_tile_rows(int form, int64_t M, int32_t K, int32_t N, int32_t S, int32_t* rows_out) {
+    const int rows = x3_tile_rows(form, M, K, N, S);
+    if (!rows_out || !rows) return MREC_EINVAL;
+    *rows_out = rows;
+    return MREC_OK;
+}
 
 MREC_API int mrec_x3_gemm(int form, const uint16_t* Pparts, const uint16_t* Qparts, int64_t M, int32_t K, int32_t N, float* C, int64_t ldc,
                           int32_t S, void* stream) {
@@ -285,7 +308,8 @@ MREC_API int mrec_x3_gemm_dgrad(const uint16_t* dyparts, const uint16_t* wparts,
 namespace {
 int x3_gemm(int form, const uint16_t* Pparts, const uint16_t* Qparts, int64_t M, int32_t K, int32_t N, float* C, int64_t ldc, int32_t S,
             const X3Epi& e, void* stream) {
-    if (form < 0 || form > 2 || M <= 0 || K <= 0 || N <= 0 || !Pparts || !Qparts || !C || S <= 0) return MREC_EINVAL;
+    const int rows = x3_tile_rows(form, M, K, N, S);
+    if (!rows || !Pparts || !Qparts || !C) return MREC_EINVAL;
     if (!al16(Pparts) || !al16(Qparts) || (((uintptr_t)C) & 7) || ldc % 2) return MREC_EUNSUPPORTED;
     const int64_t Mp = up64(M), Kp = up64(K), Np = up64(N);
     Args a{};
@@ -293,10 +317,10 @@ int x3_gemm(int form, const uint16_t* Pparts, const uint16_t* Qparts, int64_t M,
     int64_t partP, partQ, red;                    // elements per part of P / Q; the reduction extent (padded)
     if (form == 0) {          // P = x parts [Mp][Kp], Q = w parts [Kp][Np]
         a.ldp = Kp; a.ldq = Np; a.Pext = (int)M; a.Qext = N; red = Kp; partP = Mp * Kp; partQ = Kp * Np;
-        if (ldc < N || S != 1) return MREC_EINVAL;
+        if (ldc < N) return MREC_EINVAL;
     } else if (form == 1) {   // P = dy parts [Mp][Np], Q = w parts [Kp][Np] (rows = outputs)
         a.ldp = Np; a.ldq = Np; a.Pext = (int)M; a.Qext = K; red = Np; partP = Mp * Np; partQ = Kp * Np;
-        if (ldc < K || S != 1) return MREC_EINVAL;
+        if (ldc < K) return MREC_EINVAL;
     } else {                  // P = x parts [Mp][Kp] (reduction over rows), Q = dy parts [Mp][Np]
         a.ldp = Kp; a.ldq = Np; a.Pext = K; a.Qext = N; red = Mp; partP = Mp * Kp; partQ = Mp * Np;
         if (ldc < N) return MREC_EINVAL;
@@ -311,13 +335,7 @@ int x3_gemm(int form, const uint16_t* Pparts, const uint16_t* Qparts, int64_t M,
     a.rangeP = 3 * partP * 2; a.rangeQ = 3 * partQ * 2;
     const int Ttot = 6 * a.seg_tiles;
     a.kt_per_slab = (Ttot + S - 1) / S;
-    if ((int64_t)a.kt_per_slab * (S - 1) >= Ttot && S > 1) return MREC_EINVAL;
-    // 256- or 128-row tiles: whichever fills the 256 CUs in fewer tile-times (a 128-row tile costs ~0.55 of a 256-row one; the input
-    // gradient into 1170 columns is 320 big tiles = two rounds at 62 %, or 640 small ones = 2.5 rounds of half the length)
-    const int64_t t8 = mrec_cdiv(a.Pext, 256) * mrec_cdiv(a.Qext, 256) * S, t4 = mrec_cdiv(a.Pext, 128) * mrec_cdiv(a.Qext, 256) * S;
-    int mr = (double)mrec_cdiv(t4, 256) * 0.55 < (double)mrec_cdiv(t8, 256) ? 4 : 8;
-    static const int force_mr = [] { const char* e = getenv("MREC_X3_MR"); return e ? atoi(e) : 0; }();      // (tools/probes/x3_bench.py)
-    if (force_mr == 4 || force_mr == 8) mr = force_mr;
+    const int mr = rows / 32;
     a.nTp = (int)mrec_cdiv(a.Pext, mr * 32); a.nTq = (int)mrec_cdiv(a.Qext, 256);
     const unsigned grid = (unsigned)(a.nTp * a.nTq * S);
     hipStream_t st = (hipStream_t)stream;

@@ -1953,6 +1953,14 @@ def x3_slabs(M, S):
     return S
 
 
+def x3_tile_rows(form, M, K, N, S=1):
+    """Rows of the output tile (256 or 128) x3_gemm runs this form (0 / 1 / 2) and shape in; x3_fwd runs in form 0's configuration,
+    x3_dgrad's one-launch form in form 1's.  MrecError (MREC_EINVAL) on what x3_gemm refuses, a slab count form 2 cannot take included."""
+    r = C.c_int32(0)
+    _lib.call("mrec_x3_tile_rows", int(form), int(M), int(K), int(N), int(S), C.byref(r))
+    return int(r.value)
+
+
 def x3_split(x, out=None):
     """fp32 [R, C] -> its parts image bf16 [3][Rp][Cp] (x = x1 + x2 + x3, zero padded to multiples of 64)."""
     _need_cuda(x, out)
