@@ -697,6 +697,22 @@ int mrec_head_fwd_bwd_wide(int32_t f16, const uint16_t* h4, const float* w5, con
                            float* dlogit, uint16_t* dh4, float* dw5, float* db4, float* db5, float* dwide_bias, float* loss,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* The same head for ANY last hidden width K5 % 8 == 0, 8 <= K5 <= 2048 (the entries above: K5 / 8 a power of two <= 64, and
+ * they keep refusing every other width) -- e.g. the 1024 -> 1 end of benchmarks/wide_deep/default_config.yaml and of
+ * models/wide_and_deep_multitable/src/wide_and_deep.py:158.  Same arithmetic, operation for operation; what a row gets (logit,
+ * dlogit, dh4) depends on K5 alone, never on B or on where the row sits in the batch; the batch sums are per-workgroup partial rows
+ * in ws added in workgroup order: no float atomics, the same bits on every run.
+ *   kind: activations h4 / dh4 [B, K5] as 0 bfloat16, 1 IEEE half, 2 float32; contiguous rows, 16-byte aligned.
+ *   Exactly one of wide [B] / wide_prod [B, F, 2] (then F > 0 and wide_bias, as mrec_head_fwd_bwd_wide: added in field order).
+ *   dwide_bias (nullable): receives the value db5 gets.  ws: mrec_head_workspace_bytes(B, K5).
+ * Decided before any launch, in this order: MREC_EINVAL (B, K5 <= 0, kind, dh_scale < 1, a products form without F or bias, both or
+ * neither wide form, a null pointer), MREC_EUNSUPPORTED (K5 % 8 != 0 or K5 > 2048), MREC_EINVAL (h4 / dh4 misaligned),
+ * MREC_EWORKSPACE. */
+int mrec_head_fwd_bwd_any(int32_t kind, const void* h4, const float* w5, const float* b5, const float* wide, const float* wide_prod,
+                          int32_t F, const float* wide_bias, const float* label, int64_t B, int32_t K5, float dscale, float dh_scale,
+                          float* logit, float* dlogit, void* dh4, float* dw5, float* db4, float* db5, float* dwide_bias, float* loss,
+                          void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the tail of the dense net in one launch -------------------------------------------------
  * dense_layer_3, dense_layer_4 (512 -> 256 -> 128, wide_and_deep.py:176-199), the output head above and the input-gradient
  * bprops back through both layers, for 64 samples per workgroup with every intermediate in LDS -- five latency-bound launches

@@ -8,6 +8,7 @@
 //  k_head_fwd_bwd    : logit = h4 . W5 + b5 + wide;  loss terms;  dlogit = (sigmoid(logit) - y) * scale;
 //                      dh4 = dlogit * W5 masked by h4 > 0;  dW5 += h4 * dlogit;  db5 += dlogit
 //                      -- forward AND backward of the output layer and the loss in one pass over h4.
+//  k_head_any        : the same arithmetic for every K5 % 8 == 0 up to 2048 (k_head_fwd_bwd: K5 / 8 a power of two <= 64).
 //
 // It reduces over the batch with per-block partials written to a workspace and a second tiny kernel
 // that adds the partials in block order: bitwise reproducible, no float atomics.
@@ -175,6 +176,161 @@ __global__ __launch_bounds__(MB) void k_head_finish(const float* __restrict__ pa
     } else *loss = s * inv_B;
 }
 
+// ---- the same head at any K5 = 8 C, C <= 256 chunks of 8 values a row ------------------------------------------------------------
+// A row belongs to a group of G = min(64, pow2ceil(C)) adjacent lanes; lane cg owns the chunks cg, cg + G, .. (NC = ceil(C / G) <= 4
+// of them, those at or past C absent: they load zeros, add nothing and store nothing).  What a row gets -- the lane's products
+// added chunk by chunk, then a fixed xor tree over the group -- depends on K5 alone, not on the row-group or block that met the
+// row.  The raw bits of the NEXT pass's row are loaded before this pass's arithmetic (a block has one row per group in flight
+// otherwise); they are widened twice, for the dot and for the bprop, instead of being held as 8 floats a chunk.
+template <int KIND> struct HeadQ { static constexpr int n = KIND == 2 ? 2 : 1; };      // 16-byte words of a chunk
+template <int KIND, int NC>
+__device__ __forceinline__ void head_load_row(const uint4* __restrict__ h4, int64_t r, bool valid, int C, int G, int cg,
+                                              uint4 (&raw)[NC][HeadQ<KIND>::n]) {
+    constexpr int Q = HeadQ<KIND>::n;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        const int c = cg + j * G;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            if (valid && c < C) raw[j][q] = h4[Q * (r * C + c) + q];
+            else raw[j][q] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+}
+template <int KIND> __device__ __forceinline__ void head_widen(const uint4 (&raw)[HeadQ<KIND>::n], float (&f)[8]) {
+    if (KIND == 2) {
+        const uint4 a = raw[0], b = raw[HeadQ<KIND>::n - 1];
+        f[0] = __uint_as_float(a.x); f[1] = __uint_as_float(a.y); f[2] = __uint_as_float(a.z); f[3] = __uint_as_float(a.w);
+        f[4] = __uint_as_float(b.x); f[5] = __uint_as_float(b.y); f[6] = __uint_as_float(b.z); f[7] = __uint_as_float(b.w);
+    } else {
+        unpack8t<KIND == 1>(raw[0], f);
+    }
+}
+
+template <int KIND, int NC>      // KIND as k_head_fwd_bwd's; NC chunks a lane
+__global__ __launch_bounds__(MB) void k_head_any(const uint4* __restrict__ h4, const float* __restrict__ w5,
+                                                 const float* __restrict__ b5, const float* __restrict__ wide,
+                                                 const float* __restrict__ label, int64_t B, int C, int G, int rows_per_block,
+                                                 float dscale, float* __restrict__ logit_out, float* __restrict__ dlogit_out,
+                                                 uint4* __restrict__ dh4, float* __restrict__ partial,
+                                                 const float* __restrict__ wprod, int F, const float* __restrict__ wide_bias,
+                                                 float dh_scale) {
+    constexpr int Q = HeadQ<KIND>::n;
+    __shared__ float red[MB][8];
+    __shared__ float red2[MB][2];
+    const int cg = threadIdx.x % G, rl = threadIdx.x / G, RP = MB / G;
+    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t r_end = (r_begin + rows_per_block < B) ? r_begin + rows_per_block : B;
+    float w[NC][8], accw[NC][8], accd[NC][8];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        const int c = cg + j * G;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            w[j][k] = c < C ? w5[c * 8 + k] : 0.0f;
+            accw[j][k] = 0.0f;
+            accd[j][k] = 0.0f;
+        }
+    }
+    const float bias = *b5;
+    float accb = 0.0f, accl = 0.0f;
+    uint4 cur[NC][Q], nxt[NC][Q];
+    head_load_row<KIND, NC>(h4, r_begin + rl, r_begin + rl < r_end, C, G, cg, cur);
+    // all threads of a block iterate together (the shuffles below need the G lanes of a row converged)
+    for (int64_t r0 = r_begin; r0 < r_end; r0 += RP) {
+        const int64_t r = r0 + rl;
+        const bool valid = r < r_end;
+        head_load_row<KIND, NC>(h4, r + RP, r + RP < r_end, C, G, cg, nxt);
+        float part = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            float fh[8];
+            head_widen<KIND>(cur[j], fh);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) part += fh[k] * w[j][k];
+        }
+        for (int d = G >> 1; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+        // the wide branch, as k_head_fwd_bwd takes it: per sample, or the per-field products added in FIELD ORDER + the bias
+        float wv = 0.0f;
+        if (wprod) {
+            const int lane_row0 = (threadIdx.x & 63) - cg;
+            float acc_w = 0.0f;
+            for (int f0 = 0; f0 < F; f0 += G) {
+                const int f = f0 + cg;
+                const float mine = (valid && f < F) ? wprod[2 * (r * F + f)] : 0.0f;
+                const int nf = (F - f0 < G) ? F - f0 : G;
+                for (int c = 0; c < nf; ++c) acc_w = acc_w + __shfl(mine, lane_row0 + c, 64);
+            }
+            wv = acc_w + *wide_bias;
+        } else if (valid) {
+            wv = wide[r];
+        }
+        if (valid) {
+            const float z = part + bias + wv;
+            const float y = label[r];
+            const float loss = fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
+            const float sg = 1.0f / (1.0f + expf(-z));
+            const float dl = (sg - y) * dscale;
+            if (cg == 0) {
+                logit_out[r] = z;
+                dlogit_out[r] = dl;
+                accl += loss;
+                accb += dl;
+            }
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const int c = cg + j * G;
+                if (c < C) {
+                    float fh[8], o[8];
+                    head_widen<KIND>(cur[j], fh);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        o[k] = fh[k] > 0.0f ? (dl * w[j][k]) * dh_scale : 0.0f;
+                        accw[j][k] += fh[k] * dl;
+                        accd[j][k] += o[k];
+                    }
+                    store8k<KIND>(dh4, r * C + c, o);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) cur[j][q] = nxt[j][q];
+        }
+    }
+    // the block's partial row [K5 dw5 | K5 db4 | db5 | loss]: the row groups added in group order, a chunk at a time
+    const int K5 = C * 8;
+    float* p = partial + (int64_t)blockIdx.x * (2 * K5 + 2);
+    red2[threadIdx.x][0] = accb;
+    red2[threadIdx.x][1] = accl;
+#pragma unroll
+    for (int t = 0; t < 2 * NC; ++t) {
+        const int j = t >> 1, c = cg + j * G;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) red[threadIdx.x][k] = (t & 1) ? accd[j][k] : accw[j][k];
+        __syncthreads();
+        if (rl == 0 && c < C) {
+            float s[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s[k] = red[cg][k];
+            for (int q = 1; q < RP; ++q) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s[k] += red[q * G + cg][k];
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) p[(t & 1) * K5 + c * 8 + k] = s[k];
+        }
+        if (t == 0 && threadIdx.x == 0) {
+            float sb = 0.0f, sl = 0.0f;
+            for (int q = 0; q < RP; ++q) { sb += red2[q * G][0]; sl += red2[q * G][1]; }
+            p[2 * K5] = sb;
+            p[2 * K5 + 1] = sl;
+        }
+        __syncthreads();
+    }
+}
+
 inline bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 inline int pick_blocks(int64_t B, int RP) {
     int64_t nb = 256;
@@ -247,6 +403,46 @@ MREC_API int mrec_head_fwd_bwd_wide(int32_t f16, const uint16_t* h4, const float
                                     float* loss, void* ws, size_t ws_bytes, void* stream) {
     return head_impl(f16 != 0 ? 1 : 0, h4, w5, b5, nullptr, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, loss, ws, ws_bytes,
                      stream, wide_prod, F, wide_bias, dwide_bias);
+}
+
+/* The head at any K5 % 8 == 0, 8 <= K5 <= 2048 (k_head_any; see include/mrec.h). */
+MREC_API int mrec_head_fwd_bwd_any(int32_t kind, const void* h4, const float* w5, const float* b5, const float* wide,
+                                   const float* wide_prod, int32_t F, const float* wide_bias, const float* label, int64_t B, int32_t K5,
+                                   float dscale, float dh_scale, float* logit, float* dlogit, void* dh4, float* dw5, float* db4, float* db5,
+                                   float* dwide_bias, float* loss, void* ws, size_t ws_bytes, void* stream) {
+    if (B <= 0 || K5 <= 0 || kind < 0 || kind > 2 || !(dh_scale >= 1.0f)) return MREC_EINVAL;
+    if (wide_prod && (F <= 0 || !wide_bias)) return MREC_EINVAL;
+    if ((wide != nullptr) == (wide_prod != nullptr)) return MREC_EINVAL;
+    if (!h4 || !w5 || !b5 || !label || !logit || !dlogit || !dh4 || !dw5 || !db4 || !db5 || !loss || !ws) return MREC_EINVAL;
+    if (K5 % 8 || K5 > 2048) return MREC_EUNSUPPORTED;
+    if ((((uintptr_t)h4 | (uintptr_t)dh4) & 15) != 0) return MREC_EINVAL;
+    const int C = K5 / 8;
+    int G = 1;
+    while (G < C && G < 64) G <<= 1;
+    const int NC = (int)mrec_cdiv(C, G), RP = MB / G;
+    const int nblk = pick_blocks(B, RP);                   // <= 256 of the workspace's 512 partial rows
+    if (ws_bytes < (size_t)nblk * (2 * K5 + 2) * sizeof(float)) return MREC_EWORKSPACE;
+    const int rows_per_block = (int)mrec_cdiv(mrec_cdiv(B, nblk), RP) * RP;
+    const int nb = (int)mrec_cdiv(B, rows_per_block);
+    hipStream_t st = (hipStream_t)stream;
+#define MREC_HEAD_ANY(KIND, NCH)                                                                                                       \
+    k_head_any<KIND, NCH><<<nb, MB, 0, st>>>((const uint4*)h4, w5, b5, wide, label, B, C, G, rows_per_block, dscale, logit, dlogit,    \
+                                             (uint4*)dh4, (float*)ws, wide_prod, F, wide_bias, dh_scale)
+#define MREC_HEAD_ANY_NC(KIND)                                                                                                         \
+    do {                                                                                                                               \
+        if (NC == 1) MREC_HEAD_ANY(KIND, 1);                                                                                           \
+        else if (NC == 2) MREC_HEAD_ANY(KIND, 2);                                                                                      \
+        else if (NC == 3) MREC_HEAD_ANY(KIND, 3);                                                                                      \
+        else MREC_HEAD_ANY(KIND, 4);                                                                                                   \
+    } while (0)
+    if (kind == 2) MREC_HEAD_ANY_NC(2);
+    else if (kind == 1) MREC_HEAD_ANY_NC(1);
+    else MREC_HEAD_ANY_NC(0);
+#undef MREC_HEAD_ANY_NC
+#undef MREC_HEAD_ANY
+    k_head_finish<<<(unsigned)mrec_cdiv(2 * K5 + 2, 32), MB, 0, st>>>((const float*)ws, nb, K5, 1.0f / (float)B, dw5, db4, db5, loss, dwide_bias);
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
 }
 
 // ---- Dropout as a pass of its own (spec: mrec_dropout.h): the first DenseLayer's input (the looked-up rows) and the fp32 net --

@@ -1499,6 +1499,40 @@ def head_fwd_bwd_wide(h4, w5, b5, wide_prod, wide_bias, label, dscale, dw5_out, 
     return loss, logit, dlogit, dh4
 
 
+def head_any_supported(K5):
+    """Widths of the second head kernel (csrc/mrec_mlp.hip: k_head_any): every multiple of 8 up to 2048."""
+    return K5 % 8 == 0 and 8 <= K5 <= 2048
+
+
+def head_fwd_bwd_any(h4, w5, b5, wide, label, dscale, dw5_out, db4_out, db5_out, dh_scale=1.0, wide_prod=None, wide_bias=None,
+                     dwide_bias_out=None):
+    """head_fwd_bwd / head_fwd_bwd_wide for any last hidden width head_any_supported() names, h4 bfloat16, float16 or float32.
+    The wide branch is `wide` [B], or (wide None) `wide_prod` [B, F, 2] + `wide_bias`, summed in field order inside the head.
+    Returns (loss [1], logit [B], dlogit [B], dh4 [B, K5] of h4's dtype)."""
+    _need_cuda(h4, w5, b5, wide, wide_prod, wide_bias, label)
+    B, K5 = h4.shape
+    dev = h4.device
+    if h4.dtype not in _DT16 and h4.dtype != torch.float32:
+        raise TypeError("h4 must be bfloat16, float16 or float32")
+    F = 0
+    if wide_prod is not None:
+        if (wide_prod.dtype != torch.float32 or wide_prod.dim() != 3 or wide_prod.shape[0] != B or wide_prod.shape[2] != 2
+                or not wide_prod.is_contiguous()):
+            raise TypeError("wide_prod must be the contiguous float32 [B, F, 2] tensor of gather_rows_wide")
+        F = wide_prod.shape[1]
+    logit = torch.empty(B, dtype=torch.float32, device=dev)
+    dlogit = torch.empty(B, dtype=torch.float32, device=dev)
+    dh4 = torch.empty_like(h4)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    nb = _lib.query_bytes("mrec_head_workspace_bytes", B, K5)
+    ws = workspace("head", nb, dev)
+    kind = 2 if h4.dtype == torch.float32 else int(h4.dtype == torch.float16)
+    _lib.call("mrec_head_fwd_bwd_any", kind, _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide.contiguous() if wide is not None else None),
+              _ptr(wide_prod), F, _ptr(wide_bias), _ptr(label.contiguous()), B, K5, float(dscale), float(dh_scale), _ptr(logit), _ptr(dlogit),
+              _ptr(dh4), _ptr(dw5_out), _ptr(db4_out), _ptr(db5_out), _ptr(dwide_bias_out), _ptr(loss), _ptr(ws), ws.numel(), _stream())
+    return loss, logit, dlogit, dh4
+
+
 # ---- the tail of the dense net in one launch (csrc/mrec_tail.hip: k_tail) -------------------------------------------------
 def tail_supported(B, K2, N2, N3):
     return bool(_lib.lib().mrec_tail_supported(int(B), int(K2), int(N2), int(N3)))

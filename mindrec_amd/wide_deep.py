@@ -294,7 +294,7 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
         if not cfg.sparse and (self._sharded or cfg.dynamic_embedding or cfg.host_cache_rows > 0):
             raise ValueError("sparse=False (dense gradients over the whole table) runs on one GPU with resident dense tables")
         self._fold_wide = bool(cfg.sparse and cfg.fold_wide and self._mfma and not self._sharded and cfg.fused_state and cfg.host_cache_rows == 0 and D <= 252
-                               and self.k.head_supported(dims[nl - 1]))
+                               and (self.k.head_supported(dims[nl - 1]) or ops.head_any_supported(dims[nl - 1])))
         with (torch.cuda.device(dev) if self._gpu else contextlib.nullcontext()):
             # deep table + Adam moments, wide table + FTRL accumulators: plain row-major fp32 in HBM
             R = self.local_rows

@@ -94,7 +94,8 @@ class DenseNetMixin:
         # The fp32 net (mlp_dtype "fp32": DenseLayer without casts) by hand as well: hidden layers on the fp32 matrix instruction
         # (ops.dense32_*), the output end as one pass (ops.head_fwd_bwd on fp32 activations); Dropout keeps the torch restatement.
         self._f32net = bool(self._gpu and self.k is ops and not self._mfma and getattr(self, "_amp", None) is None and nl >= 2
-                            and (self.k.head_supported(dims[nl - 1]) or self.k.dcn_head_supported(dims[nl - 1], 2)))
+                            and (self.k.head_supported(dims[nl - 1]) or self.k.dcn_head_supported(dims[nl - 1], 2)
+                                 or ops.head_any_supported(dims[nl - 1])))
         self._tail_packed, self._dense16_t = None, None
         self._tail_ok = bool(self._mfma and fused_tail and nl >= 4 and self.k.tail_supported(64, *self.dims[nl - 3:nl]))
         self._mlp_graph = None        # dict: captured MLP step + its static input / output tensors
@@ -199,8 +200,8 @@ class DenseNetMixin:
     def _unsupported(self, what):
         dt = {None: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}[getattr(self, "_amp", None)]
         return UnsupportedNet(f"MREC_EUNSUPPORTED: {what}: no hand-written HIP path for the {dt} dense net {self.dims} on {self.device} "
-                              f"(16-bit nets: every width a multiple of 8; the layer in front of the output a power of two times 8, <= 512; "
-                              f"head widths as above)")
+                              f"(16-bit nets: every width a multiple of 8, the layer in front of the output <= 2048; fp32 nets: that layer "
+                              f"a multiple of 4 up to 1024 or of 8 up to 2048)")
 
     def _mlp_generic(self, x):
         raise self._unsupported("inference forward")
@@ -282,7 +283,16 @@ class DenseNetMixin:
                 self.dense_grad[2 * (n - 3) + 1], self.dense_grad[2 * (n - 4) + 1], dwide_bias_out=self.wide_b_grad if prod else None,
                 drop_in=self._drop(n - 3, B), out=self._tail_out.setdefault((B, hs[-1].dtype, self._slot), {}))
             return {"hs": hs + [y2], "loss": loss.view(()), "g_wide": dlogit.view(-1), "dh": dz2, "tail": (dz4, dz3)}
-        if isinstance(wide, _WideProd):
+        if self.k is ops and not ops.head_supported(K5) and ops.head_any_supported(K5):
+            # a last hidden width that is no power of two times 8, or wider than 512: the head kernel for any multiple of 8 up to 2048
+            prod = isinstance(wide, _WideProd)
+            loss, _, dlogit, dh = ops.head_fwd_bwd_any(hs[-1], W5.detach().view(-1), b5.detach(), None if prod else wide, label.view(-1),
+                                                       self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
+                                                       self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1], dh_scale=dhs,
+                                                       wide_prod=wide.prod if prod else None, wide_bias=self.wide_b if prod else None,
+                                                       dwide_bias_out=self.wide_b_grad if prod else None)
+            loss = loss.view(())
+        elif isinstance(wide, _WideProd):
             loss, _, dlogit, dh = self.k.head_fwd_bwd_wide(hs[-1], W5.detach().view(-1), b5.detach(), wide.prod, self.wide_b,
                                                             label.view(-1), self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
                                                             self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1],
@@ -371,6 +381,12 @@ class DenseNetMixin:
                                                  wide, label.view(-1), self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
                                                  self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1],
                                                  dh_scale=drops[n - 1].scale if drops[n - 1] is not None else 1.0)
+        elif not k.dcn_head_supported(K5, 2):
+            # wider than the detour below reaches (1024 < K5 <= 2048): the head kernel for any multiple of 8
+            loss, _, dlogit, dh = k.head_fwd_bwd_any(hs[-1], self.dense[2 * (n - 1)].detach().view(-1), self.dense[2 * (n - 1) + 1].detach(),
+                                                     wide, label.view(-1), self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
+                                                     self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1],
+                                                     dh_scale=drops[n - 1].scale if drops[n - 1] is not None else 1.0)
         else:
             # a last hidden layer wider than the head kernel's 512 columns (the reference's benchmark net ends 1024 -> 1): the
             # output end of Deep&Cross does the same arithmetic over [h | c] . w3 -- with c = [wide, 0] and w3 = [W5 | 1, 0] that is
