@@ -713,6 +713,23 @@ int mrec_head_fwd_bwd_any(int32_t kind, const void* h4, const float* w5, const f
                           float* logit, float* dlogit, void* dh4, float* dw5, float* db4, float* db5, float* dwide_bias, float* loss,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* The evaluation forward of that head (PredictWithSigmoid, wide_and_deep.py:495-518): mrec_head_fwd_bwd_any's forward half and
+ * nothing of its backward.  logit[b] = h4[b,:].w5 + b5 + wide[b];  prob[b] = sigmoid(logit[b]);  with a label, *loss = mean_b
+ * BCE(logit, label).  The same lane geometry, products, reduction tree, field-order wide sum and expressions as
+ * mrec_head_fwd_bwd_any: logit is that entry's logit bit for bit, prob its dlogit at label 0 and dscale 1.  What a row gets depends
+ * on K5 and that row's inputs alone, never on B or on where the row sits in the batch.
+ *   kind, h4 [B, K5], the two wide forms: as mrec_head_fwd_bwd_any.  logit, prob: float32 [B].
+ *   label (nullable) [B] and loss (one float): both or neither.  With a label every workgroup leaves one partial loss sum in ws and a
+ *   second one-workgroup launch adds them in workgroup order and multiplies by 1 / B: no float atomics, the same bits on every run.
+ *   Without a label: one launch, ws is not used and may be NULL.  ws: mrec_head_predict_workspace_bytes(B).
+ * Decided before any launch, in this order: MREC_EINVAL (B, K5 <= 0, kind, a products form without F or bias, both or neither wide
+ * form, a null h4 / w5 / b5 / logit / prob, label and loss not both null or both set), MREC_EUNSUPPORTED (K5 % 8 != 0 or K5 > 2048),
+ * MREC_EINVAL (h4 misaligned), MREC_EWORKSPACE (with a label only). */
+int mrec_head_predict_workspace_bytes(int64_t B, size_t* out);
+int mrec_head_predict(int32_t kind, const void* h4, const float* w5, const float* b5, const float* wide, const float* wide_prod,
+                      int32_t F, const float* wide_bias, const float* label, int64_t B, int32_t K5, float* logit, float* prob,
+                      float* loss, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the tail of the dense net in one launch -------------------------------------------------
  * dense_layer_3, dense_layer_4 (512 -> 256 -> 128, wide_and_deep.py:176-199), the output head above and the input-gradient
  * bprops back through both layers, for 64 samples per workgroup with every intermediate in LDS -- five latency-bound launches

@@ -161,6 +161,8 @@ _SIGS = {
     "mrec_head_fwd_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "mrec_head_fwd_bwd_any": [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _sz, _vp],
+    "mrec_head_predict_workspace_bytes": [_i64, _szp],
+    "mrec_head_predict": [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp],
     "mrec_map_bytes": [_i64, _szp],
     "mrec_map_create": [C.POINTER(_vp), _vp, _sz, _i64, _vp],
     "mrec_map_destroy": [_vp],

@@ -9,6 +9,7 @@
 //                      dh4 = dlogit * W5 masked by h4 > 0;  dW5 += h4 * dlogit;  db5 += dlogit
 //                      -- forward AND backward of the output layer and the loss in one pass over h4.
 //  k_head_any        : the same arithmetic for every K5 % 8 == 0 up to 2048 (k_head_fwd_bwd: K5 / 8 a power of two <= 64).
+//  k_head_predict    : k_head_any's forward half for evaluation: logit, sigmoid(logit) and, with a label, the mean loss.
 //
 // It reduces over the batch with per-block partials written to a workspace and a second tiny kernel
 // that adds the partials in block order: bitwise reproducible, no float atomics.
@@ -331,6 +332,98 @@ __global__ __launch_bounds__(MB) void k_head_any(const uint4* __restrict__ h4, c
     }
 }
 
+// ---- the forward half of k_head_any: evaluation ------------------------------------------------------------------------------
+// Same lane geometry, same products in the same order per lane, same xor tree, same field-order wide sum and the same expressions
+// for z, the sigmoid and the loss term -- so a row's logit is k_head_any's bit for bit, and its prob is the `sg` k_head_any forms.
+// Nothing of the backward: no dh4, no dw5 / db4 / db5 accumulators, no red[MB][8].  label nullable: without it no loss term, no
+// partial and no LDS use; with it the workgroup leaves ONE partial (its row groups' sums added in group order).
+template <int KIND, int NC>      // KIND as k_head_fwd_bwd's; NC chunks a lane
+__global__ __launch_bounds__(MB) void k_head_predict(const uint4* __restrict__ h4, const float* __restrict__ w5,
+                                                     const float* __restrict__ b5, const float* __restrict__ wide,
+                                                     const float* __restrict__ label, int64_t B, int C, int G, int rows_per_block,
+                                                     float* __restrict__ logit_out, float* __restrict__ prob_out,
+                                                     float* __restrict__ partial, const float* __restrict__ wprod, int F,
+                                                     const float* __restrict__ wide_bias) {
+    constexpr int Q = HeadQ<KIND>::n;
+    __shared__ float red2[MB];
+    const int cg = threadIdx.x % G, rl = threadIdx.x / G, RP = MB / G;
+    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t r_end = (r_begin + rows_per_block < B) ? r_begin + rows_per_block : B;
+    float w[NC][8];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        const int c = cg + j * G;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[j][k] = c < C ? w5[c * 8 + k] : 0.0f;
+    }
+    const float bias = *b5;
+    float accl = 0.0f;
+    uint4 cur[NC][Q], nxt[NC][Q];
+    head_load_row<KIND, NC>(h4, r_begin + rl, r_begin + rl < r_end, C, G, cg, cur);
+    // all threads of a block iterate together (the shuffles below need the G lanes of a row converged)
+    for (int64_t r0 = r_begin; r0 < r_end; r0 += RP) {
+        const int64_t r = r0 + rl;
+        const bool valid = r < r_end;
+        head_load_row<KIND, NC>(h4, r + RP, r + RP < r_end, C, G, cg, nxt);
+        float part = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            float fh[8];
+            head_widen<KIND>(cur[j], fh);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) part += fh[k] * w[j][k];
+        }
+        for (int d = G >> 1; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+        // the wide branch, as k_head_any takes it: per sample, or the per-field products added in FIELD ORDER + the bias
+        float wv = 0.0f;
+        if (wprod) {
+            const int lane_row0 = (threadIdx.x & 63) - cg;
+            float acc_w = 0.0f;
+            for (int f0 = 0; f0 < F; f0 += G) {
+                const int f = f0 + cg;
+                const float mine = (valid && f < F) ? wprod[2 * (r * F + f)] : 0.0f;
+                const int nf = (F - f0 < G) ? F - f0 : G;
+                for (int c = 0; c < nf; ++c) acc_w = acc_w + __shfl(mine, lane_row0 + c, 64);
+            }
+            wv = acc_w + *wide_bias;
+        } else if (valid) {
+            wv = wide[r];
+        }
+        if (valid && cg == 0) {
+            const float z = part + bias + wv;
+            const float sg = 1.0f / (1.0f + expf(-z));
+            logit_out[r] = z;
+            prob_out[r] = sg;
+            if (label) {
+                const float y = label[r];
+                const float loss = fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
+                accl += loss;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) cur[j][q] = nxt[j][q];
+        }
+    }
+    if (!label) return;          // (uniform: a kernel argument)
+    red2[threadIdx.x] = accl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float sl = 0.0f;
+        for (int q = 0; q < RP; ++q) sl += red2[q * G];
+        partial[blockIdx.x] = sl;
+    }
+}
+
+// loss = (the workgroups' partials added in workgroup order, finish_column's order as k_head_finish) / B: one workgroup
+__global__ __launch_bounds__(MB) void k_head_predict_finish(const float* __restrict__ partial, int nblk, float inv_B,
+                                                            float* __restrict__ loss) {
+    __shared__ float sm[8][32];
+    const float s = finish_column(partial, nblk, 1, threadIdx.x & 31, sm);
+    if (threadIdx.x == 0) *loss = s * inv_B;
+}
+
 inline bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 inline int pick_blocks(int64_t B, int RP) {
     int64_t nb = 256;
@@ -441,6 +534,51 @@ MREC_API int mrec_head_fwd_bwd_any(int32_t kind, const void* h4, const float* w5
 #undef MREC_HEAD_ANY_NC
 #undef MREC_HEAD_ANY
     k_head_finish<<<(unsigned)mrec_cdiv(2 * K5 + 2, 32), MB, 0, st>>>((const float*)ws, nb, K5, 1.0f / (float)B, dw5, db4, db5, loss, dwide_bias);
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+/* The evaluation forward of the head at any K5 % 8 == 0, 8 <= K5 <= 2048 (k_head_predict; see include/mrec.h). */
+MREC_API int mrec_head_predict_workspace_bytes(int64_t B, size_t* out) {
+    if (!out || B < 0) return MREC_EINVAL;
+    *out = (size_t)256 * sizeof(float) + 256;          // one loss partial a workgroup, at most 256 of them
+    return MREC_OK;
+}
+
+MREC_API int mrec_head_predict(int32_t kind, const void* h4, const float* w5, const float* b5, const float* wide, const float* wide_prod,
+                               int32_t F, const float* wide_bias, const float* label, int64_t B, int32_t K5, float* logit, float* prob,
+                               float* loss, void* ws, size_t ws_bytes, void* stream) {
+    if (B <= 0 || K5 <= 0 || kind < 0 || kind > 2) return MREC_EINVAL;
+    if (wide_prod && (F <= 0 || !wide_bias)) return MREC_EINVAL;
+    if ((wide != nullptr) == (wide_prod != nullptr)) return MREC_EINVAL;
+    if (!h4 || !w5 || !b5 || !logit || !prob || (label != nullptr) != (loss != nullptr)) return MREC_EINVAL;
+    if (K5 % 8 || K5 > 2048) return MREC_EUNSUPPORTED;
+    if (((uintptr_t)h4 & 15) != 0) return MREC_EINVAL;
+    const int C = K5 / 8;
+    int G = 1;
+    while (G < C && G < 64) G <<= 1;
+    const int NC = (int)mrec_cdiv(C, G), RP = MB / G;
+    const int nblk = pick_blocks(B, RP);                   // <= 256
+    if (label && (!ws || ws_bytes < (size_t)nblk * sizeof(float))) return MREC_EWORKSPACE;
+    const int rows_per_block = (int)mrec_cdiv(mrec_cdiv(B, nblk), RP) * RP;
+    const int nb = (int)mrec_cdiv(B, rows_per_block);
+    hipStream_t st = (hipStream_t)stream;
+#define MREC_HEAD_PRED(KIND, NCH)                                                                                                      \
+    k_head_predict<KIND, NCH><<<nb, MB, 0, st>>>((const uint4*)h4, w5, b5, wide, label, B, C, G, rows_per_block, logit, prob,          \
+                                                 label ? (float*)ws : nullptr, wide_prod, F, wide_bias)
+#define MREC_HEAD_PRED_NC(KIND)                                                                                                        \
+    do {                                                                                                                               \
+        if (NC == 1) MREC_HEAD_PRED(KIND, 1);                                                                                          \
+        else if (NC == 2) MREC_HEAD_PRED(KIND, 2);                                                                                     \
+        else if (NC == 3) MREC_HEAD_PRED(KIND, 3);                                                                                     \
+        else MREC_HEAD_PRED(KIND, 4);                                                                                                  \
+    } while (0)
+    if (kind == 2) MREC_HEAD_PRED_NC(2);
+    else if (kind == 1) MREC_HEAD_PRED_NC(1);
+    else MREC_HEAD_PRED_NC(0);
+#undef MREC_HEAD_PRED_NC
+#undef MREC_HEAD_PRED
+    if (label) k_head_predict_finish<<<1, MB, 0, st>>>((const float*)ws, nb, 1.0f / (float)B, loss);
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }

@@ -1533,6 +1533,51 @@ def head_fwd_bwd_any(h4, w5, b5, wide, label, dscale, dw5_out, db4_out, db5_out,
     return loss, logit, dlogit, dh4
 
 
+def head_predict_supported(K5):
+    """Widths of the evaluation head (csrc/mrec_mlp.hip: k_head_predict): head_any_supported's."""
+    return head_any_supported(K5)
+
+
+def head_predict(h4, w5, b5, wide=None, wide_prod=None, wide_bias=None, label=None, out=None):
+    """The evaluation forward of head_fwd_bwd_any -- output layer + wide/deep add + sigmoid, and with `label` the mean sigmoid
+    cross-entropy -- in one pass over h4 [B, K5] (bfloat16, float16 or float32), nothing of the backward.  The wide branch is `wide` [B],
+    or `wide_prod` [B, F, 2] + `wide_bias`, summed in field order inside the kernel.  logit is head_fwd_bwd_any's bit for bit.
+    Returns (logit [B], prob [B]), with a label (logit, prob, loss [1]).  out: dict of persistent output tensors with those names
+    (filled on first use), so that a captured graph replays into fixed addresses."""
+    _need_cuda(h4, w5, b5, wide, wide_prod, wide_bias, label)
+    B, K5 = h4.shape
+    dev = h4.device
+    if h4.dtype not in _DT16 and h4.dtype != torch.float32:
+        raise TypeError("h4 must be bfloat16, float16 or float32")
+    F = 0
+    if wide_prod is not None:
+        if (wide_prod.dtype != torch.float32 or wide_prod.dim() != 3 or wide_prod.shape[0] != B or wide_prod.shape[2] != 2
+                or not wide_prod.is_contiguous()):
+            raise TypeError("wide_prod must be the contiguous float32 [B, F, 2] tensor of gather_rows_wide")
+        F = wide_prod.shape[1]
+    o = out if out is not None else {}
+
+    def buf(name, n):
+        t = o.get(name)
+        if t is None:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+            o[name] = t
+        elif t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device != dev:
+            raise TypeError(f"head_predict: out[{name!r}] must be a contiguous float32 [{n}] tensor on h4's device")
+        return t
+    logit, prob = buf("logit", B), buf("prob", B)
+    loss, ws, ws_bytes = None, None, 0
+    if label is not None:
+        loss = buf("loss", 1)
+        ws = workspace("head_predict", _lib.query_bytes("mrec_head_predict_workspace_bytes", B), dev)
+        ws_bytes = ws.numel()
+    kind = 2 if h4.dtype == torch.float32 else int(h4.dtype == torch.float16)
+    _lib.call("mrec_head_predict", kind, _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide.contiguous() if wide is not None else None),
+              _ptr(wide_prod), F, _ptr(wide_bias), _ptr(label.contiguous() if label is not None else None), B, K5, _ptr(logit), _ptr(prob),
+              _ptr(loss), _ptr(ws), ws_bytes, _stream())
+    return (logit, prob) if label is None else (logit, prob, loss)
+
+
 # ---- the tail of the dense net in one launch (csrc/mrec_tail.hip: k_tail) -------------------------------------------------
 def tail_supported(B, K2, N2, N3):
     return bool(_lib.lib().mrec_tail_supported(int(B), int(K2), int(N2), int(N3)))

@@ -386,6 +386,8 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
         self._front_graph = None      # one-GPU: the whole front of the step (lookups .. MLP backward) as one captured graph
         self._step_graph = None       # ... and, with the wide branch folded, the whole step
         self._sink_graphs = {}        # (sink size, batch shape, id dtype) -> that many whole steps as one graph (train_steps)
+        self._predict_graphs = {}     # (batch shape, id dtype, label given?) -> calls seen + the captured evaluation forward (predict_fused)
+        self._predict_capture = True  # cleared when a capture of the evaluation forward is refused
         self._step_state = None       # ops.StepState (device-side beta powers / step size), created on first use
         self._state_step = -1         # the step count the device-side state stands at
         self._dropout = bool(cfg.dropout_flag and cfg.dropout_keep_prob < 1.0)
@@ -427,15 +429,14 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             # both lookups in one pass over the fused rows; the per-sample sum of the wide products is taken by the head
             d0 = self._drop(0, B)                  # Dropout on the first layer's input rides the lookup (train_step only)
             self._emb_dropped = d0 is not None
-            emb, wprod = self.k.gather_rows_wide(self.deep, ids, wts, cfg.emb_dim, out=self._emb_out(B * Fd, cfg.emb_dim, self._amp), drop=d0,
-                                                 out_dtype=self._amp, step_state=self._step_state if self._dyn else None, **self._clip_kw())
+            emb, wprod = self._lookup_folded(ids, wts, drop=d0, out=self._emb_out(B * Fd, cfg.emb_dim, self._amp),
+                                             step_state=self._step_state if self._dyn else None)
             self._tock(ev)
-            return emb.view(B, Fd * cfg.emb_dim), _WideProd(wprod), None
+            return emb, wprod, None
         if self._mfma and torch.is_grad_enabled():
-            emb = self.k.gather_rows(self.deep, ids, wts, out=self._emb_out(B * Fd, cfg.emb_dim, self._amp),
-                                     out_dtype=self._amp, **self._clip_kw()).view(B, Fd * cfg.emb_dim)
+            emb = self._lookup_rows(ids, wts, out_dtype=self._amp, out=self._emb_out(B * Fd, cfg.emb_dim, self._amp))
         else:
-            emb = self.k.gather_rows(self.deep, ids, wts, **self._clip_kw()).view(B, Fd * cfg.emb_dim)
+            emb = self._lookup_rows(ids, wts)
         self._tock(ev)
         if defer_wide:
             return emb, (lambda: self.k.wide_sum(self.wide, ids, wts, self.wide_b)), None
@@ -443,6 +444,22 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
         wide = self.k.wide_sum(self.wide, ids, wts, self.wide_b)
         self._tock(ev)
         return emb, wide, None
+
+    # the two forms of the one-GPU lookup, named by whoever wants one: lookup() above chooses for the training step, predict_fused()
+    # for evaluation
+    def _lookup_folded(self, ids, wts, drop=None, out=None, step_state=None):
+        """Both lookups in one pass over the fused rows: (deep_in [B, F*D] in the net's 16-bit dtype, the wide branch's per-field
+        products).  drop: the first layer's Dropout rides the kernel; step_state: the kernel leaves its stamps there."""
+        B, Fd = ids.shape
+        emb, wprod = self.k.gather_rows_wide(self.deep, ids, wts, self.cfg.emb_dim, out=out, drop=drop, out_dtype=self._amp,
+                                             step_state=step_state, **self._clip_kw())
+        return emb.view(B, Fd * self.cfg.emb_dim), _WideProd(wprod)
+
+    def _lookup_rows(self, ids, wts, out_dtype=None, out=None):
+        """The deep table's lookup alone: deep_in [B, F*D], fp32 or (out_dtype) cast to 16 bits inside the kernel."""
+        B, Fd = ids.shape
+        kw = {} if out_dtype is None else {"out": out, "out_dtype": out_dtype}
+        return self.k.gather_rows(self.deep, ids, wts, **kw, **self._clip_kw()).view(B, Fd * self.cfg.emb_dim)
 
     def _clip_kw(self):
         """{"max_norm": c} for the deep table's lookup and apply when cfg.max_norm is set, {} otherwise (the calls are then exactly
@@ -463,6 +480,76 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
                 emb, wide, _ = self.lookup(ids, wts)
             logit = wide.view(-1, 1) + self.mlp(emb)
         return logit, torch.sigmoid(logit)
+
+    # ---- evaluation on the training step's kernels ----------------------------------------------------------------------------
+    @property
+    def fused_predict_supported(self):
+        """predict_fused runs here: one GPU, tables resident in HBM (dense or hashed).  Row shards and host-cached tables: predict."""
+        return bool(self._gpu and self.k is ops and not self._sharded and self.hb is None)
+
+    def _predict_chain(self, ids, wts, label):
+        """lookup -> hidden layers -> head, one stream, no side branch: the lookup form the net's training step uses (16-bit rows
+        with the wide branch folded in, or 16-bit / fp32 rows + wide_sum), never a Dropout, no step stamps; then mlp_predict."""
+        if self._fold_wide:
+            emb, wide = self._lookup_folded(ids, wts)
+        else:
+            emb = self._lookup_rows(ids, wts, out_dtype=self._amp if self._mfma else None)
+            wide = self.k.wide_sum(self.wide, ids, wts, self.wide_b)
+        return self.mlp_predict(emb, wide, label)
+
+    def predict_fused(self, ids, wts, label=None):
+        """predict() on the hand-written path end to end: the training lookup (16-bit rows written once, the wide branch folded
+        in), the hidden layers on the K-contiguous forward GEMMs, and one head launch for the output layer, the wide/deep add and
+        the sigmoid.  Returns (logit [B, 1], prob [B, 1]) as predict does and, with `label`, the batch's mean sigmoid cross-entropy
+        (0-d) as a third value.  Evaluation only: no Dropout whatever the engine is doing, and no step, optimizer or Dropout state
+        is read or written.
+        With HIP graphs on (graphs != "none") and dense resident tables, the chain replays as one captured graph from the third
+        call at a given (batch shape, label given?): THE RETURNED TENSORS ARE THEN STATIC BUFFERS WHICH THE NEXT CALL OVERWRITES --
+        copy what must outlive it (the metrics copy in update()).  dynamic_embedding engines translate their keys as predict does
+        and always run eagerly.  Row shards and host-cached tables raise ValueError (fused_predict_supported is False)."""
+        if not self.fused_predict_supported:
+            mode = ("row shards (world > 1)" if self._sharded else "the host cache (host_cache_rows > 0)" if self.hb is not None
+                    else "this device / op set")
+            raise ValueError(f"predict_fused is not supported with {mode}: use predict")
+        B = ids.shape[0]
+        if self.index is not None:
+            ids, _ = self._translate_keys(ids)          # MapTensorGet inserts default rows in eval too, as predict
+            return self._predict_out(self._predict_chain(ids, wts, label), B)
+        if not (self._graph_level >= 1 and self._predict_capture):
+            return self._predict_out(self._predict_chain(ids, wts, label), B)
+        key = (tuple(ids.shape), ids.dtype, label is not None)
+        st = self._predict_graphs.setdefault(key, {"calls": 0, "g": None})
+        st["calls"] += 1
+        if st["calls"] <= 2:                             # two eager calls first: every workspace exists by then
+            return self._predict_out(self._predict_chain(ids, wts, label), B)
+        g = st["g"]
+        if g is None:
+            try:
+                g = st["g"] = self._capture_predict(ids, wts, label)
+            except RuntimeError as e:          # capture refused: stay eager
+                import warnings
+                warnings.warn(f"HIP-graph capture of the evaluation forward failed, running it eagerly: {e}")
+                self._predict_capture = False
+                self._predict_graphs = {}
+                return self._predict_out(self._predict_chain(ids, wts, label), B)
+        ins = (ids, wts) if label is None else (ids, wts, label)
+        self.k.copy_many_(list(g["in"]), list(ins))       # one launch
+        g["graph"].replay()
+        return self._predict_out(g["out"], B)
+
+    def _capture_predict(self, ids, wts, label):
+        """The evaluation chain captured on static copies of these inputs: one graph, one stream."""
+        g = {"in": tuple(t.clone().contiguous() for t in ((ids, wts) if label is None else (ids, wts, label)))}
+        torch.cuda.synchronize(self.device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            g["out"] = self._predict_chain(g["in"][0], g["in"][1], g["in"][2] if label is not None else None)
+        g["graph"] = graph
+        return g
+
+    @staticmethod
+    def _predict_out(out, B):
+        return (out[0].view(B, 1), out[1].view(B, 1)) + ((out[2].view(()),) if len(out) == 3 else ())
 
     def _map_tables(self):
         """(tensor, sigma, fill, seed) of the six tables that share the key index's row numbering, with the values a row gets
@@ -804,6 +891,7 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             torch.cuda.synchronize(self.device)
         self._step_graph = self._front_graph = self._mlp_graph = None
         self._sink_graphs = {}
+        self._predict_graphs = {}
         if self._gpu:
             torch.cuda.synchronize(self.device)
 
@@ -829,7 +917,7 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
 
     def __del__(self):
         try:
-            if getattr(self, "_sink_graphs", None) or getattr(self, "_step_graph", None) is not None:
+            if getattr(self, "_sink_graphs", None) or getattr(self, "_step_graph", None) is not None or getattr(self, "_predict_graphs", None):
                 self.release_graphs()
         except Exception:      # noqa: BLE001  (interpreter shutdown)
             pass

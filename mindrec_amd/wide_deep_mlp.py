@@ -196,6 +196,32 @@ class DenseNetMixin:
             return self.k.dense32_fwd(h, self.dense[2 * (n - 1)].detach(), self.dense[2 * (n - 1) + 1].detach(), relu=False)
         return self._mlp_generic(x)
 
+    @torch.no_grad()
+    def mlp_predict(self, emb, wide, label=None):
+        """The evaluation forward on the training step's kernels: the hidden layers as the training forward runs them (16-bit
+        nets: both GEMM operands K-contiguous, the transposes _refresh_tail keeps current; no Dropout), then the output layer, the
+        wide/deep add, the sigmoid and -- with `label` -- the mean sigmoid cross-entropy as ONE pass over the last activation
+        (ops.head_predict).  emb: the looked-up rows in the net's dtype; wide: a _WideProd (summed inside the head) or a [B] tensor.
+        Returns (logit [B], prob [B]) or, with a label, (logit, prob, loss [1]).  No cast, add or sigmoid runs outside the kernels."""
+        n = len(self.dims) - 1
+        K5 = self.dims[n - 1]
+        if self.k is not ops or not (self._mfma or self._f32net) or not ops.head_predict_supported(K5):
+            raise self._unsupported("evaluation forward")
+        if emb.dtype != (self._amp if self._mfma else torch.float32):
+            raise TypeError(f"mlp_predict: the looked-up rows arrive in the net's dtype, got {emb.dtype}")
+        h = emb
+        if self._mfma:
+            for i in range(n - 1):
+                h = ops.dense_fwd(h, self.dense16[2 * i], self.dense[2 * i + 1].detach(), relu=True, wt=self._dense16_t.get(i))
+        else:
+            h = h.contiguous()
+            for i in range(n - 1):
+                h = ops.dense32_fwd(h, self.dense[2 * i].detach(), self.dense[2 * i + 1].detach(), relu=True)
+        prod = isinstance(wide, _WideProd)
+        return ops.head_predict(h, self.dense[2 * (n - 1)].detach().view(-1), self.dense[2 * (n - 1) + 1].detach(),
+                                wide=None if prod else wide.view(-1), wide_prod=wide.prod if prod else None,
+                                wide_bias=self.wide_b if prod else None, label=label.view(-1) if label is not None else None)
+
     # ---- hooks: nets without a HIP path.  The product refuses them; tests/_torch_net.py implements them for the oracle side ----
     def _unsupported(self, what):
         dt = {None: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}[getattr(self, "_amp", None)]

@@ -171,9 +171,12 @@ class EvalCallBack(Callback):
 class WideDeepRunner:
     """train(*batch) / eval(dataset) over a WideDeepEngine, with the reference's return conventions (module docstring)."""
 
-    def __init__(self, engine, metrics=None):
+    def __init__(self, engine, metrics=None, fused_eval=False):
+        """fused_eval=True: where the engine has it (engine.fused_predict_supported), eval() runs engine.predict_fused -- the
+        evaluation forward on the training step's kernels -- and reports the validation log-loss beside the metrics."""
         self.engine = engine
         self.metrics = dict(metrics or {})
+        self.fused_eval = bool(fused_eval)
 
     def __call__(self, ids, wts, label):
         loss = self.engine.train_step(ids, wts, label)
@@ -182,6 +185,8 @@ class WideDeepRunner:
     def eval(self, dataset, dataset_sink_mode=False):
         for m in self.metrics.values():
             m.clear()
+        if self.fused_eval and getattr(self.engine, "fused_predict_supported", False):
+            return self._eval_fused(dataset)
         for ids, wts, label in dataset:
             logit, prob = self.engine.predict(ids, wts)
             for m in self.metrics.values():
@@ -191,6 +196,26 @@ class WideDeepRunner:
             self.engine.check_shard_overflow()
         self.engine.check_cache()
         return {k: m.eval() for k, m in self.metrics.items()}
+
+    def _eval_fused(self, dataset):
+        """eval() over engine.predict_fused: the metrics see the same (logit, prob, label); "logloss" is the mean sigmoid
+        cross-entropy over every row seen -- the batch means weighted by their rows, added up in float64 on the device and read once
+        at the end.  (predict_fused hands out static buffers once its graph replays: the metrics copy in update(), the sum below is
+        queued on the stream in front of the next call.)"""
+        import torch
+        total, rows = None, 0
+        for ids, wts, label in dataset:
+            logit, prob, loss = self.engine.predict_fused(ids, wts, label)
+            for m in self.metrics.values():
+                m.update(logit, prob, label)
+            if total is None:
+                total = torch.zeros((), dtype=torch.float64, device=loss.device)
+            total.add_(loss, alpha=float(ids.shape[0]))
+            rows += int(ids.shape[0])
+        self.engine.check_cache()
+        out = {k: m.eval() for k, m in self.metrics.items()}
+        out["logloss"] = float(total) / rows if rows else float("nan")
+        return out
 
     def close(self):
         self.engine.close()
