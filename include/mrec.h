@@ -937,6 +937,20 @@ int mrec_fm_fwd_add16_f32(const float* vx, int64_t B, int32_t F, int32_t D, cons
                           int32_t kind16, void* stream);
 int mrec_fm_bwd_mix_f32(const float* vx, const float* colsum, const float* dout, const void* g16, int32_t g16_kind, int64_t B, int32_t F,
                         int32_t D, float* g_out, void* stream);
+/* The evaluation forward's lookup, one launch for mrec_gather_rows[_clip]_* -> mrec_wide_sum_f32_* -> mrec_fm_fwd_add16_f32 (forward
+ * only: no colsum, no workspace), every output that composition's bit for bit:
+ *   rows[b, f, :] = clip(V[ids_v[b, f], :]) * wts[b, f]   written once, rows_kind 0: fp32, 1: bf16, 2: f16 (rounded to nearest even);
+ *   lin_fm[b]     = sum_f W[ids_w[b, f]] * wts[b, f]  +  fm(b) over those rows before rounding (field order).
+ * V [Vrows, D] rows ld floats apart, W [Wrows, 1] rows ldw floats apart; ids_v / ids_w [B, F] of id_bytes 4 or 8, ids_w NULL: ids_v;
+ * an id outside its table reads as a zero row / weight.  max_norm 0: no clip; c > 0: every raw row is clipped to norm c before the
+ * weight (W never is).
+ *   MREC_EINVAL: a NULL pointer other than ids_w and stream; F <= 0, D <= 0, B < 0; rows_kind outside 0..2; id_bytes not 4 or 8;
+ *     max_norm negative or not finite; an empty table, ld < D or ldw < 1.
+ *   MREC_EUNSUPPORTED (then): D % 4 != 0 or D > 256; ld % 4 != 0; V not 16-byte aligned, rows not 16-byte (16-bit rows: 8-byte)
+ *     aligned.  B == 0: MREC_OK after these checks.  All of it before any launch. */
+int mrec_fm_lookup(const float* V, int64_t Vrows, int64_t ld, int32_t D, const float* W, int64_t Wrows, int64_t ldw, const void* ids_v,
+                   const void* ids_w, int32_t id_bytes, const float* wts, int64_t B, int32_t F, float max_norm, void* rows,
+                   int32_t rows_kind, float* lin_fm, void* stream);
 /* table[rows[i], :] += vals[i, :] for distinct rows (rows < 0 skipped): adds a segment-sum into a dense
  * [V, D] gradient that already holds the L2 term (deepfm.py:252-259). */
 int mrec_scatter_add_rows_f32(float* table, int64_t ld, int32_t D, const int32_t* rows, int64_t n,

@@ -73,6 +73,41 @@ class _DeepFMNet(DenseNetMixin):
         """DenseLayer x5 (deepfm.py:98-150): the 16-bit kernels' inference path, or the torch restatement."""
         return self.mlp(x)
 
+    # ---- evaluation on the training step's kernels ----------------------------------------------------------------------------
+    def _fused_refusal(self):
+        """None where predict_fused runs, else the reason it does not"""
+        if not (self._gpu and self.k is ops):
+            return "this device / op set"
+        if getattr(self, "world", 1) > 1:
+            return "key shards (world > 1)"
+        if self.cfg.data_emb_dim % 4:
+            return f"data_emb_dim = {self.cfg.data_emb_dim} (the one-launch lookup needs a multiple of 4)"
+        if not (self._mfma or self._f32net) or not ops.head_predict_supported(self.dims[-2]):
+            return f"the {self.cfg.mlp_dtype} dense net {self.dims} (no hand-written evaluation forward)"
+        return None
+
+    @property
+    def fused_predict_supported(self):
+        """predict_fused runs here: one GPU, the product's op set, data_emb_dim % 4 == 0, a dense net with a hand-written forward and
+        an output head ops.head_predict serves."""
+        return self._fused_refusal() is None
+
+    def _check_fused(self):
+        why = self._fused_refusal()
+        if why is not None:
+            raise ValueError(f"predict_fused is not supported with {why}: use predict")
+
+    def _fused_chain(self, V, W, ids_v, ids_w, wts, label):
+        """one lookup launch (ops.fm_lookup: the masked rows in the net's dtype, written once, and linear + fm) -> hidden layers ->
+        head: no fp32 [B, F, D] tensor, no cast, add or sigmoid outside the kernels; never a Dropout"""
+        B, Fd = ids_v.shape
+        rows, lin_fm = ops.fm_lookup(V, W, ids_v, wts, ids_w=ids_w, out_dtype=self._amp if self._mfma else torch.float32, **self._clip_kw())
+        return self.mlp_predict(rows.view(B, Fd * self.cfg.data_emb_dim), lin_fm, label)
+
+    @staticmethod
+    def _predict_out(out, B):
+        return (out[0].view(B, 1), out[1].view(B, 1)) + ((out[2].view(()),) if len(out) == 3 else ())
+
     def _net_step(self, vx, vx16, linear, label):
         """Forward + backward of everything behind the lookups: FM term, the dense net, the loss.  Returns (loss, g_vx fp32
         [B, F, D], g_linear [B]); dense gradients are left in the slabs / the flat gradient buffer for _dense_adam."""
@@ -140,6 +175,8 @@ class DeepFMEngine(_DeepFMNet):
             self.k.fill_normal_(self.W_l2, cfg.seed + 1, cfg.init_sigma)
             self.state = {n: (torch.zeros_like(t), torch.zeros_like(t)) for n, t in (("V", self.V_l2), ("W", self.W_l2))}
             self._init_net(cfg, [cfg.data_field_size * D] + list(cfg.deep_layer_dims) + [1])
+        self._predict_graphs = {}     # (ids shape, ids dtype, label given?) -> calls seen + the captured evaluation forward (predict_fused)
+        self._predict_capture = True  # cleared when a capture of the evaluation forward is refused
 
     def _forward(self, ids, wts):
         cfg = self.cfg
@@ -160,6 +197,65 @@ class DeepFMEngine(_DeepFMNet):
             fm, _ = self.k.fm_forward(vx)
             logit = (linear + fm).view(-1, 1) + self._mlp(vx.view(vx.shape[0], -1))
         return logit, torch.sigmoid(logit)
+
+    def _predict_chain(self, ids, wts, label):
+        return self._fused_chain(self.V_l2, self.W_l2, ids, None, wts, label)
+
+    def predict_fused(self, ids, wts, label=None):
+        """predict() on the hand-written path end to end: ONE lookup launch for the masked rows (in the net's dtype, written once),
+        the linear term and the FM term (ops.fm_lookup), the hidden layers on the training forward's GEMMs, and one head launch for
+        the output layer, the linear + fm + deep add and the sigmoid (DenseNetMixin.mlp_predict).  Returns (logit [B, 1], prob [B, 1])
+        as predict does and, with `label`, the batch's mean sigmoid cross-entropy (0-d) as a third value.  Evaluation only: no
+        Dropout, and no step, optimizer or plan state is read or written.
+        With HIP graphs on (cfg.graphs != "none") the chain replays as one captured graph from the third call at a given (ids shape,
+        ids dtype, label given?): THE RETURNED TENSORS ARE THEN STATIC BUFFERS WHICH THE NEXT CALL OVERWRITES -- copy what must
+        outlive it.  Raises ValueError where fused_predict_supported is False."""
+        self._check_fused()
+        B = ids.shape[0]
+        if not (self.cfg.graphs != "none" and self._predict_capture):
+            return self._predict_out(self._predict_chain(ids, wts, label), B)
+        key = (tuple(ids.shape), ids.dtype, label is not None)
+        st = self._predict_graphs.setdefault(key, {"calls": 0, "g": None})
+        st["calls"] += 1
+        if st["calls"] <= 2:                             # two eager calls first: every workspace exists by then
+            return self._predict_out(self._predict_chain(ids, wts, label), B)
+        g = st["g"]
+        if g is None:
+            try:
+                g = st["g"] = self._capture_predict(ids, wts, label)
+            except RuntimeError as e:          # capture refused: stay eager
+                import warnings
+                warnings.warn(f"HIP-graph capture of the evaluation forward failed, running it eagerly: {e}")
+                self._predict_capture = False
+                self._predict_graphs = {}
+                return self._predict_out(self._predict_chain(ids, wts, label), B)
+        ins = (ids, wts) if label is None else (ids, wts, label)
+        self.k.copy_many_(list(g["in"]), list(ins))       # one launch
+        g["graph"].replay()
+        return self._predict_out(g["out"], B)
+
+    def _capture_predict(self, ids, wts, label):
+        """The evaluation chain captured on static copies of these inputs: one graph, one stream."""
+        g = {"in": tuple(t.clone().contiguous() for t in ((ids, wts) if label is None else (ids, wts, label)))}
+        torch.cuda.synchronize(self.device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            g["out"] = self._predict_chain(g["in"][0], g["in"][1], g["in"][2] if label is not None else None)
+        g["graph"] = graph
+        return g
+
+    def release_graphs(self):
+        """Drops every captured HIP graph -- the dense net's training step and the evaluation forwards (they are re-captured on demand)."""
+        if self._gpu:
+            torch.cuda.synchronize(self.device)
+        self._mlp_graph = None
+        self._predict_graphs = {}
+        if self._gpu:
+            torch.cuda.synchronize(self.device)
+
+    def close(self):
+        """End of the engine's use: the captured graphs are released."""
+        self.release_graphs()
 
     def train_step(self, ids, wts, label):
         cfg = self.cfg
@@ -348,6 +444,17 @@ class DeepFMHashEngine(_DeepFMNet):
             fm, _ = ops.fm_forward(vx)
             logit = (linear + fm).view(-1, 1) + self._mlp(vx.view(B, -1))
         return logit, torch.sigmoid(logit)
+
+    def predict_fused(self, keys, wts, label=None):
+        """predict() on the hand-written path end to end (DeepFMEngine.predict_fused): the keys are looked up as predict looks them
+        up -- MapTensorGet inserts default rows in eval too --, then ONE lookup launch over V.values / W.values at the two tables'
+        row positions, the hidden layers and one head launch.  Returns (logit [B, 1], prob [B, 1]) and, with `label`, the batch's
+        mean sigmoid cross-entropy (0-d).  Always eager (the key lookup sizes its work on the host).  Key shards (world > 1) raise
+        ValueError, as every case where fused_predict_supported is False: use predict."""
+        self._check_fused()
+        B, Fd = keys.shape
+        _, _, pos_v, _, pos_w = self._lookup(keys, insert=True)
+        return self._predict_out(self._fused_chain(self.V.values, self.W.values, pos_v.view(B, Fd), pos_w.view(B, Fd), wts, label), B)
 
     def train_step(self, keys, wts, label):
         cfg = self.cfg

@@ -2175,6 +2175,47 @@ def fm_forward(vx, add=None, out16=None):
     return fm, cs
 
 
+def fm_lookup(table, wtable, ids, wts, ids_w=None, out_dtype=torch.float16, max_norm=None, out=None):
+    """The evaluation forward's lookup in one launch (csrc/mrec_fm.hip: k_fm_lookup): gather_rows(table, ids, wts[, max_norm]) ->
+    wide_sum(wtable, ids_w, wts) -> fm_forward(vx, add=linear, out16=...) without the fp32 [B, F, D] tensor in between.
+    table float32 [V, D] (D % 4 == 0, D <= 256, row stride % 4 == 0), wtable float32 [Vw, 1], ids [B, F] int32 / int64, wts float32
+    [B, F]; ids_w [B, F] of ids' dtype: the rows of wtable (None: ids).  Returns (rows [B, F, D] in out_dtype -- float32, bfloat16 or
+    float16 --, lin_fm [B] = linear + fm), both that composition's bit for bit.  max_norm=c: as gather_rows.  out: dict of persistent
+    output tensors "rows" and "lin_fm" (filled on first use), so that a captured graph replays into fixed addresses."""
+    _need_cuda(table, wtable, ids, wts, ids_w)
+    V, D, ld = _table(table)
+    _suffix(ids)
+    if ids.dim() != 2:
+        raise ValueError("ids must be [B, F]")
+    B, F = ids.shape
+    if wtable.dtype != torch.float32 or wtable.dim() != 2 or wtable.shape[1] != 1:
+        raise TypeError("wtable must be a float32 [V,1] table (any row stride)")
+    Vw, ldw = wtable.shape[0], (wtable.stride(0) if wtable.shape[0] > 1 else 1)
+    if wts.dtype != torch.float32 or tuple(wts.shape) != (B, F):
+        raise TypeError("wts must be float32 with one value per id")
+    if ids_w is not None and (ids_w.dtype != ids.dtype or tuple(ids_w.shape) != (B, F)):
+        raise TypeError("ids_w must have ids' dtype and shape")
+    if out_dtype not in _KIND:
+        raise TypeError("fm_lookup out_dtype must be float32, bfloat16 or float16")
+    dev = table.device
+    o = out if out is not None else {}
+
+    def buf(name, shape, dtype):
+        t = o.get(name)
+        if t is None:
+            t = o[name] = torch.empty(shape, dtype=dtype, device=dev)
+        elif t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise TypeError(f"fm_lookup: out[{name!r}] must be a contiguous {dtype} {list(shape)} tensor on the table's device")
+        return t
+    rows, lin_fm = buf("rows", (B, F, D), out_dtype), buf("lin_fm", (B,), torch.float32)
+    if B == 0:                     # (empty tensors have no address to hand over)
+        return rows, lin_fm
+    _lib.call("mrec_fm_lookup", _ptr(table), V, ld, D, _ptr(wtable), Vw, ldw, _ptr(ids.contiguous()),
+              _ptr(ids_w.contiguous() if ids_w is not None else None), ids.element_size(), _ptr(wts.contiguous()), B, F,
+              0.0 if max_norm is None else _max_norm(max_norm), _ptr(rows), _KIND[out_dtype], _ptr(lin_fm), _stream())
+    return rows, lin_fm
+
+
 def fm_backward_mix(g16, vx, colsum, dout):
     """fp32 [B, F, D]: widen(g16) + dout[b] * (colsum[b, d] - vx[b, f, d]) -- the FM gradient added to the 16-bit input gradient
     of the mixed-precision MLP, one pass."""
