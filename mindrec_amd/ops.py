@@ -2158,18 +2158,37 @@ def dcn_head_fwd_bwd(d2, c, w3, b3, label, dscale, dw3_out, db2_out, db3_out, ou
 
 
 # ---- DeepFM second-order term ------------------------------------------------------------------
-def fm_forward(vx, add=None, out16=None):
+def _fm_vx(who, vx):
+    if vx.dtype != torch.float32 or vx.dim() != 3:
+        raise TypeError(f"{who}: vx must be a float32 [B, F, D] tensor")
+    return vx.shape
+
+
+def _fm_out(who, name, t, shape, device):
+    """An output the caller owns: the kernels write it through its flat index"""
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise TypeError(f"{who}: {name} must be a contiguous float32 {list(shape)} tensor on vx's device")
+    return t
+
+
+def fm_forward(vx, add=None, out16=None, out=None):
     """vx [B, F, D] fp32 -> (fm_out [B], colsum [B, D]) (deepfm.py:221-228).  add [B] (the linear term): fm_out = add + fm.
-    out16 (bfloat16 / float16 [B, F, D], D % 4 == 0): receives vx rounded to 16 bits in the same pass (the dense net's input)."""
+    out16 (bfloat16 / float16 [B, F, D], D % 4 == 0): receives vx rounded to 16 bits in the same pass (the dense net's input).
+    out: dict of preallocated "fm" [B] and "colsum" [B, D] (contiguous float32; filled on first use)."""
     _need_cuda(vx, add, out16)
-    B, F_, D = vx.shape
+    B, F_, D = _fm_vx("fm_forward", vx)
     vx = vx.contiguous()
     if add is not None and (add.dtype != torch.float32 or add.numel() != B or not add.is_contiguous()):
         raise TypeError("fm_forward: add must be contiguous float32 [B]")
     if out16 is not None and (out16.dtype not in _DT16 or out16.numel() != vx.numel() or not out16.is_contiguous() or D % 4):
         raise TypeError("fm_forward: out16 must be a contiguous bfloat16 / float16 tensor of vx's size (D % 4 == 0)")
-    fm = torch.empty(B, dtype=torch.float32, device=vx.device)
-    cs = torch.empty((B, D), dtype=torch.float32, device=vx.device)
+    o = out if out is not None else {}
+    for name, shape in (("fm", (B,)), ("colsum", (B, D))):
+        if o.get(name) is None:
+            o[name] = torch.empty(shape, dtype=torch.float32, device=vx.device)
+        else:
+            _fm_out("fm_forward", f"out[{name!r}]", o[name], shape, vx.device)
+    fm, cs = o["fm"], o["colsum"]
     _lib.call("mrec_fm_fwd_add16_f32", _ptr(vx), B, F_, D, _ptr(add), _ptr(fm), _ptr(cs), _ptr(out16),
               0 if out16 is None else _KIND[out16.dtype], _stream())
     return fm, cs
@@ -2216,23 +2235,34 @@ def fm_lookup(table, wtable, ids, wts, ids_w=None, out_dtype=torch.float16, max_
     return rows, lin_fm
 
 
-def fm_backward_mix(g16, vx, colsum, dout):
+def _fm_bwd_operands(who, vx, colsum, dout):
+    B, F_, D = _fm_vx(who, vx)
+    if colsum.dtype != torch.float32 or tuple(colsum.shape) != (B, D) or not colsum.is_contiguous():
+        raise TypeError(f"{who}: colsum must be a contiguous float32 [B, D] tensor")
+    if dout.dtype != torch.float32 or dout.numel() != B:
+        raise TypeError(f"{who}: dout must be float32 with one value per sample")
+    return B, F_, D
+
+
+def fm_backward_mix(g16, vx, colsum, dout, out=None):
     """fp32 [B, F, D]: widen(g16) + dout[b] * (colsum[b, d] - vx[b, f, d]) -- the FM gradient added to the 16-bit input gradient
-    of the mixed-precision MLP, one pass."""
-    _need_cuda(g16, vx, colsum, dout)
-    B, F_, D = vx.shape
+    of the mixed-precision MLP, one pass.  out: the preallocated result (contiguous float32 of vx's shape)."""
+    _need_cuda(g16, vx, colsum, dout, out)
+    B, F_, D = _fm_bwd_operands("fm_backward_mix", vx, colsum, dout)
     if g16.dtype not in _DT16 or g16.numel() != vx.numel() or not g16.is_contiguous():
         raise TypeError("fm_backward_mix: g16 must be a contiguous bfloat16 / float16 tensor of vx's size")
-    out = torch.empty_like(vx)
+    out = torch.empty(vx.shape, dtype=torch.float32, device=vx.device) if out is None else _fm_out("fm_backward_mix", "out", out, vx.shape, vx.device)
     _lib.call("mrec_fm_bwd_mix_f32", _ptr(vx.contiguous()), _ptr(colsum), _ptr(dout.contiguous()), _ptr(g16), _KIND[g16.dtype],
               B, F_, D, _ptr(out), _stream())
     return out
 
 
 def fm_backward_(g, vx, colsum, dout):
-    """g[b,f,d] += dout[b] * (colsum[b,d] - vx[b,f,d]) in place."""
+    """g[b,f,d] += dout[b] * (colsum[b,d] - vx[b,f,d]) in place.  The kernels reach g and colsum through the flat index, so both must
+    be contiguous float32 (g of vx's shape, colsum [B, D]): anything else is refused, not updated at the wrong elements."""
     _need_cuda(g, vx, colsum, dout)
-    B, F_, D = vx.shape
+    B, F_, D = _fm_bwd_operands("fm_backward_", vx, colsum, dout)
+    _fm_out("fm_backward_", "g", g, vx.shape, vx.device)
     _lib.call("mrec_fm_bwd_f32", _ptr(vx.contiguous()), _ptr(colsum), _ptr(dout.contiguous()), B, F_, D, _ptr(g), _stream())
     return g
 
