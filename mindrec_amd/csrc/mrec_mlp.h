@@ -1,5 +1,6 @@
 // mrec_mlp.h -- helpers shared by the output-head kernels (mrec_mlp.hip) and the tail launch (mrec_tail.hip): 8-element 16-bit
-// pack / unpack in both 16-bit formats, and the fixed-order column sum of per-workgroup partial rows.
+// pack / unpack in both 16-bit formats, the sigmoid and the loss term of a logit, and the fixed-order column sum of per-workgroup
+// partial rows.
 #pragma once
 #include "mrec_common.h"
 
@@ -42,6 +43,11 @@ template <bool F16> __device__ __forceinline__ uint4 pack8t(const float (&f)[8])
 }
 
 constexpr int MB = 256;   // threads per block
+
+// the output end's two expressions of a logit z (label y), every head kernel's and the tail launch's
+__device__ __forceinline__ float sigmoid_of(float z) { return 1.0f / (1.0f + expf(-z)); }
+// SigmoidCrossEntropyWithLogits: max(z,0) - z*y + log(1 + exp(-|z|))
+__device__ __forceinline__ float sigmoid_xent(float z, float y) { return fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z))); }
 
 // out[c] = sum over blocks of partial[blk][c] in a fixed order.  A block owns 32 adjacent columns and
 // splits the partial rows over 8 row-groups; every thread keeps 8 independent loads in flight (a single

@@ -3,7 +3,7 @@
 // The hidden DenseLayers (models/wide_deep/src/wide_and_deep.py:113-133) run on the matrix cores (mrec_dense.hip; their
 // ReLU / BiasAdd bprops are GEMM epilogues there); what is left is the output end of the net, HBM-bound byte work that
 // MindSpore runs as separate primitives (the 128 -> 1 output layer, wide + deep add :315,
-// SigmoidCrossEntropyWithLogits + ReduceMean :352-354 and their bprops).  One kernel covers it:
+// SigmoidCrossEntropyWithLogits + ReduceMean :352-354 and their bprops).  Three kernels cover it:
 //
 //  k_head_fwd_bwd    : logit = h4 . W5 + b5 + wide;  loss terms;  dlogit = (sigmoid(logit) - y) * scale;
 //                      dh4 = dlogit * W5 masked by h4 > 0;  dW5 += h4 * dlogit;  db5 += dlogit
@@ -11,15 +11,21 @@
 //  k_head_any        : the same arithmetic for every K5 % 8 == 0 up to 2048 (k_head_fwd_bwd: K5 / 8 a power of two <= 64).
 //  k_head_predict    : k_head_any's forward half for evaluation: logit, sigmoid(logit) and, with a label, the mean loss.
 //
-// It reduces over the batch with per-block partials written to a workspace and a second tiny kernel
+// What a row gets is written ONCE, in the head_* functions below, and every kernel calls them: its workgroup's rows, the wide
+// term, the row dot's tree, the sums over a workgroup's row groups (sigmoid and loss term: mrec_mlp.h).  One host prologue
+// (head_geom, head_check, head_dispatch) gives all three the same launch geometry.
+// They reduce over the batch with per-block partials written to a workspace and a second tiny kernel
 // that adds the partials in block order: bitwise reproducible, no float atomics.
+#include <type_traits>
+
 #include "mrec_common.h"
 #include "mrec_dropout.h"
 #include "mrec_mlp.h"
 
 namespace {
 
-// Output head.  K5 = width of the last hidden layer (multiple of 8, K5/8 a power of two <= 64).
+// Output head.  K5 = 8 C = width of the last hidden layer.  A row belongs to a group of G adjacent lanes (a power of two <= 64),
+// a workgroup meets MB / G rows a pass.
 // partial layout per block: [K5] dW5 partials, [K5] column sums of dh4 (= bias gradient of the last
 // hidden layer), then db5 partial, then loss partial.
 // the row's 8 values of this lane: 16 bytes of 16-bit values, or 32 bytes of fp32 (KIND 2: the fp32 net)
@@ -40,6 +46,77 @@ template <int KIND> __device__ __forceinline__ void store8k(uint4* __restrict__ 
     }
 }
 
+// ---- what the head kernels share ------------------------------------------------------------------------------------------
+// the rows [r_begin, r_end) of this workgroup
+__device__ __forceinline__ void head_rows(int rows_per_block, int64_t B, int64_t& r_begin, int64_t& r_end) {
+    r_begin = (int64_t)blockIdx.x * rows_per_block;
+    r_end = (r_begin + rows_per_block < B) ? r_begin + rows_per_block : B;
+}
+
+// The wide branch of row r: either given per sample, or as the per-field products the fused lookup wrote ([B, F, 2]: product,
+// pad).  The G lanes of the row load the products side by side (one pass of loads, not F dependent ones), then every
+// lane adds them up in FIELD ORDER through shuffles -- ReduceSum over the fields, then + Wide_b: the same adds in the
+// same order as mrec_wide_sum / the CPU restatement.  (The G lanes of a row are converged here.)
+__device__ __forceinline__ float head_wide_term(const float* wprod, int F, const float* wide_bias,
+                                                const float* wide, int64_t r, bool valid, int cg, int G) {
+    float wv = 0.0f;
+    if (wprod) {
+        const int lane_row0 = (threadIdx.x & 63) - cg;           // first lane of this row's group
+        float acc_w = 0.0f;
+        for (int f0 = 0; f0 < F; f0 += G) {
+            const int f = f0 + cg;
+            const float mine = (valid && f < F) ? wprod[2 * (r * F + f)] : 0.0f;
+            const int nf = (F - f0 < G) ? F - f0 : G;
+            for (int c = 0; c < nf; ++c) acc_w = acc_w + __shfl(mine, lane_row0 + c, 64);
+        }
+        wv = acc_w + *wide_bias;
+    } else if (valid) {
+        wv = wide[r];
+    }
+    return wv;
+}
+
+// a lane's share of the row dot, added over the G lanes of the row (adjacent lanes): a fixed xor tree
+__device__ __forceinline__ float head_group_sum(float part, int G) {
+    for (int d = G >> 1; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+    return part;
+}
+
+// One [8 columns a lane] accumulator of the workgroup's partial row: every lane leaves its 8 sums in red, then the lanes of row
+// group 0 add the row groups' in group order (rows cg, G + cg, ..) and write dst[0..8) (own: this lane has columns there).
+// red is free again after the caller's next __syncthreads().
+__device__ __forceinline__ void head_block_sum(float (*red)[8], const float (&acc)[8], int cg, int rl, int G, int RP, bool own,
+                                               float* dst) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) red[threadIdx.x][k] = acc[k];
+    __syncthreads();
+    if (rl == 0 && own) {
+        float s[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[k] = red[cg][k];
+        for (int q = 1; q < RP; ++q) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s[k] += red[q * G + cg][k];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) dst[k] = s[k];
+    }
+}
+
+// the N per-row scalars the first lane of every row group left in red2 (db5 and loss; loss alone), added in group order from 0:
+// one thread's, after a barrier
+template <int N> __device__ __forceinline__ void head_block_scalars(const float (*red2)[N], int G, int RP, float* dst) {
+    float s[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) s[n] = 0.0f;
+    for (int q = 0; q < RP; ++q) {
+#pragma unroll
+        for (int n = 0; n < N; ++n) s[n] += red2[q * G][n];
+    }
+#pragma unroll
+    for (int n = 0; n < N; ++n) dst[n] = s[n];
+}
+
 template <int KIND>      // 0: bfloat16, 1: IEEE half, 2: fp32 activations
 __global__ __launch_bounds__(MB) void k_head_fwd_bwd(const uint4* __restrict__ h4, const float* __restrict__ w5,
                                                      const float* __restrict__ b5, const float* __restrict__ wide,
@@ -51,8 +128,8 @@ __global__ __launch_bounds__(MB) void k_head_fwd_bwd(const uint4* __restrict__ h
     __shared__ float red[MB][8];
     __shared__ float red2[MB][2];
     const int cg = threadIdx.x % CG, rl = threadIdx.x / CG, RP = MB / CG;
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r_end = (r_begin + rows_per_block < B) ? r_begin + rows_per_block : B;
+    int64_t r_begin, r_end;
+    head_rows(rows_per_block, B, r_begin, r_end);
     float w[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) w[k] = w5[cg * 8 + k];
@@ -60,7 +137,7 @@ __global__ __launch_bounds__(MB) void k_head_fwd_bwd(const uint4* __restrict__ h
     float accw[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float accd[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float accb = 0.0f, accl = 0.0f;
-    // all threads of a row-group iterate together (the shuffles below need the CG lanes of a row converged)
+    // all threads of a row-group iterate together (the shuffles of head_group_sum / head_wide_term need the CG lanes of a row converged)
     for (int64_t r0 = r_begin; r0 < r_end; r0 += RP) {
         const int64_t r = r0 + rl;
         const bool valid = r < r_end;
@@ -73,35 +150,13 @@ __global__ __launch_bounds__(MB) void k_head_fwd_bwd(const uint4* __restrict__ h
         float part = 0.0f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) part += fh[k] * w[k];
-        // reduce over the CG lanes of this row (CG is a power of two <= 64, lanes of a row are adjacent)
-        for (int d = CG >> 1; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
-        // the wide branch: either given per sample, or as the per-field products the fused lookup wrote ([B, F, 2]: product,
-        // pad).  The CG lanes of the row load the products side by side (one pass of loads, not F dependent ones), then every
-        // lane adds them up in FIELD ORDER through shuffles -- ReduceSum over the fields, then + Wide_b: the same adds in the
-        // same order as mrec_wide_sum / the CPU restatement.
-        float wv = 0.0f;
-        if (wprod) {
-            const int lane_row0 = (threadIdx.x & 63) - cg;           // first lane of this row's group
-            float acc_w = 0.0f;
-            for (int f0 = 0; f0 < F; f0 += CG) {
-                const int f = f0 + cg;
-                const float mine = (valid && f < F) ? wprod[2 * (r * F + f)] : 0.0f;
-                const int nf = (F - f0 < CG) ? F - f0 : CG;
-                for (int c = 0; c < nf; ++c) acc_w = acc_w + __shfl(mine, lane_row0 + c, 64);
-            }
-            wv = acc_w + *wide_bias;
-        } else if (valid) {
-            wv = wide[r];
-        }
-        float dl = 0.0f;
+        part = head_group_sum(part, CG);
+        const float wv = head_wide_term(wprod, F, wide_bias, wide, r, valid, cg, CG);
         if (valid) {
-            float wsum = wv;
-            const float z = part + bias + wsum;
+            const float z = part + bias + wv;
             const float y = label[r];
-            // SigmoidCrossEntropyWithLogits: max(z,0) - z*y + log(1 + exp(-|z|))
-            const float loss = fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
-            const float sg = 1.0f / (1.0f + expf(-z));
-            dl = (sg - y) * dscale;
+            const float loss = sigmoid_xent(z, y);
+            const float dl = (sigmoid_of(z) - y) * dscale;
             if (cg == 0) {
                 logit_out[r] = z;
                 dlogit_out[r] = dl;
@@ -119,45 +174,14 @@ __global__ __launch_bounds__(MB) void k_head_fwd_bwd(const uint4* __restrict__ h
             store8k<KIND>(dh4, r * CG + cg, o);
         }
     }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[threadIdx.x][k] = accw[k];
-    red2[threadIdx.x][0] = accb;
-    red2[threadIdx.x][1] = accl;
-    __syncthreads();
     const int K5 = CG * 8;
     float* p = partial + (int64_t)blockIdx.x * (2 * K5 + 2);
-    if (rl == 0) {
-        float s[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s[k] = red[cg][k];
-        for (int q = 1; q < RP; ++q) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s[k] += red[q * CG + cg][k];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) p[cg * 8 + k] = s[k];
-    }
-    if (threadIdx.x == 0) {
-        float sb = 0.0f, sl = 0.0f;
-        for (int q = 0; q < RP; ++q) { sb += red2[q * CG][0]; sl += red2[q * CG][1]; }
-        p[2 * K5] = sb;
-        p[2 * K5 + 1] = sl;
-    }
+    red2[threadIdx.x][0] = accb;
+    red2[threadIdx.x][1] = accl;
+    head_block_sum(red, accw, cg, rl, CG, RP, true, p + cg * 8);
+    if (threadIdx.x == 0) head_block_scalars<2>(red2, CG, RP, p + 2 * K5);
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[threadIdx.x][k] = accd[k];
-    __syncthreads();
-    if (rl == 0) {
-        float s[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s[k] = red[cg][k];
-        for (int q = 1; q < RP; ++q) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s[k] += red[q * CG + cg][k];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) p[K5 + cg * 8 + k] = s[k];
-    }
+    head_block_sum(red, accd, cg, rl, CG, RP, true, p + K5 + cg * 8);
 }
 
 __global__ __launch_bounds__(MB) void k_head_finish(const float* __restrict__ partial, int nblk, int K5, float inv_B,
@@ -207,6 +231,19 @@ template <int KIND> __device__ __forceinline__ void head_widen(const uint4 (&raw
         unpack8t<KIND == 1>(raw[0], f);
     }
 }
+// h4[r] . W5: the lane's products added chunk by chunk, then head_group_sum's tree (k_head_fwd_bwd: its one chunk, the same tree)
+template <int KIND, int NC>
+__device__ __forceinline__ float head_row_dot(const uint4 (&cur)[NC][HeadQ<KIND>::n], const float (&w)[NC][8], int G) {
+    float part = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        float fh[8];
+        head_widen<KIND>(cur[j], fh);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) part += fh[k] * w[j][k];
+    }
+    return head_group_sum(part, G);
+}
 
 template <int KIND, int NC>      // KIND as k_head_fwd_bwd's; NC chunks a lane
 __global__ __launch_bounds__(MB) void k_head_any(const uint4* __restrict__ h4, const float* __restrict__ w5,
@@ -220,8 +257,8 @@ __global__ __launch_bounds__(MB) void k_head_any(const uint4* __restrict__ h4, c
     __shared__ float red[MB][8];
     __shared__ float red2[MB][2];
     const int cg = threadIdx.x % G, rl = threadIdx.x / G, RP = MB / G;
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r_end = (r_begin + rows_per_block < B) ? r_begin + rows_per_block : B;
+    int64_t r_begin, r_end;
+    head_rows(rows_per_block, B, r_begin, r_end);
     float w[NC][8], accw[NC][8], accd[NC][8];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
@@ -237,41 +274,18 @@ __global__ __launch_bounds__(MB) void k_head_any(const uint4* __restrict__ h4, c
     float accb = 0.0f, accl = 0.0f;
     uint4 cur[NC][Q], nxt[NC][Q];
     head_load_row<KIND, NC>(h4, r_begin + rl, r_begin + rl < r_end, C, G, cg, cur);
-    // all threads of a block iterate together (the shuffles below need the G lanes of a row converged)
+    // all threads of a block iterate together (the shuffles of head_row_dot / head_wide_term need the G lanes of a row converged)
     for (int64_t r0 = r_begin; r0 < r_end; r0 += RP) {
         const int64_t r = r0 + rl;
         const bool valid = r < r_end;
         head_load_row<KIND, NC>(h4, r + RP, r + RP < r_end, C, G, cg, nxt);
-        float part = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            float fh[8];
-            head_widen<KIND>(cur[j], fh);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) part += fh[k] * w[j][k];
-        }
-        for (int d = G >> 1; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
-        // the wide branch, as k_head_fwd_bwd takes it: per sample, or the per-field products added in FIELD ORDER + the bias
-        float wv = 0.0f;
-        if (wprod) {
-            const int lane_row0 = (threadIdx.x & 63) - cg;
-            float acc_w = 0.0f;
-            for (int f0 = 0; f0 < F; f0 += G) {
-                const int f = f0 + cg;
-                const float mine = (valid && f < F) ? wprod[2 * (r * F + f)] : 0.0f;
-                const int nf = (F - f0 < G) ? F - f0 : G;
-                for (int c = 0; c < nf; ++c) acc_w = acc_w + __shfl(mine, lane_row0 + c, 64);
-            }
-            wv = acc_w + *wide_bias;
-        } else if (valid) {
-            wv = wide[r];
-        }
+        const float part = head_row_dot<KIND, NC>(cur, w, G);
+        const float wv = head_wide_term(wprod, F, wide_bias, wide, r, valid, cg, G);
         if (valid) {
             const float z = part + bias + wv;
             const float y = label[r];
-            const float loss = fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
-            const float sg = 1.0f / (1.0f + expf(-z));
-            const float dl = (sg - y) * dscale;
+            const float loss = sigmoid_xent(z, y);
+            const float dl = (sigmoid_of(z) - y) * dscale;
             if (cg == 0) {
                 logit_out[r] = z;
                 dlogit_out[r] = dl;
@@ -308,33 +322,15 @@ __global__ __launch_bounds__(MB) void k_head_any(const uint4* __restrict__ h4, c
 #pragma unroll
     for (int t = 0; t < 2 * NC; ++t) {
         const int j = t >> 1, c = cg + j * G;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) red[threadIdx.x][k] = (t & 1) ? accd[j][k] : accw[j][k];
-        __syncthreads();
-        if (rl == 0 && c < C) {
-            float s[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s[k] = red[cg][k];
-            for (int q = 1; q < RP; ++q) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) s[k] += red[q * G + cg][k];
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) p[(t & 1) * K5 + c * 8 + k] = s[k];
-        }
-        if (t == 0 && threadIdx.x == 0) {
-            float sb = 0.0f, sl = 0.0f;
-            for (int q = 0; q < RP; ++q) { sb += red2[q * G][0]; sl += red2[q * G][1]; }
-            p[2 * K5] = sb;
-            p[2 * K5 + 1] = sl;
-        }
+        head_block_sum(red, (t & 1) ? accd[j] : accw[j], cg, rl, G, RP, c < C, p + (t & 1) * K5 + c * 8);
+        if (t == 0 && threadIdx.x == 0) head_block_scalars<2>(red2, G, RP, p + 2 * K5);
         __syncthreads();
     }
 }
 
 // ---- the forward half of k_head_any: evaluation ------------------------------------------------------------------------------
-// Same lane geometry, same products in the same order per lane, same xor tree, same field-order wide sum and the same expressions
-// for z, the sigmoid and the loss term -- so a row's logit is k_head_any's bit for bit, and its prob is the `sg` k_head_any forms.
+// Same lane geometry and the same functions for a row's weights, dot, wide term, sigmoid and loss term -- so a row's logit is
+// k_head_any's bit for bit, and its prob is the sigmoid k_head_any forms.
 // Nothing of the backward: no dh4, no dw5 / db4 / db5 accumulators, no red[MB][8].  label nullable: without it no loss term, no
 // partial and no LDS use; with it the workgroup leaves ONE partial (its row groups' sums added in group order).
 template <int KIND, int NC>      // KIND as k_head_fwd_bwd's; NC chunks a lane
@@ -345,59 +341,36 @@ __global__ __launch_bounds__(MB) void k_head_predict(const uint4* __restrict__ h
                                                      float* __restrict__ partial, const float* __restrict__ wprod, int F,
                                                      const float* __restrict__ wide_bias) {
     constexpr int Q = HeadQ<KIND>::n;
-    __shared__ float red2[MB];
+    __shared__ float red2[MB][1];
     const int cg = threadIdx.x % G, rl = threadIdx.x / G, RP = MB / G;
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r_end = (r_begin + rows_per_block < B) ? r_begin + rows_per_block : B;
+    int64_t r_begin, r_end;
+    head_rows(rows_per_block, B, r_begin, r_end);
     float w[NC][8];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
         const int c = cg + j * G;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) w[j][k] = c < C ? w5[c * 8 + k] : 0.0f;
+        for (int k = 0; k < 8; ++k) w[j][k] = c < C ? w5[c * 8 + k] : 0.0f;      // (k_head_any's rows of W5)
     }
     const float bias = *b5;
     float accl = 0.0f;
     uint4 cur[NC][Q], nxt[NC][Q];
     head_load_row<KIND, NC>(h4, r_begin + rl, r_begin + rl < r_end, C, G, cg, cur);
-    // all threads of a block iterate together (the shuffles below need the G lanes of a row converged)
+    // all threads of a block iterate together (the shuffles of head_row_dot / head_wide_term need the G lanes of a row converged)
     for (int64_t r0 = r_begin; r0 < r_end; r0 += RP) {
         const int64_t r = r0 + rl;
         const bool valid = r < r_end;
         head_load_row<KIND, NC>(h4, r + RP, r + RP < r_end, C, G, cg, nxt);
-        float part = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            float fh[8];
-            head_widen<KIND>(cur[j], fh);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) part += fh[k] * w[j][k];
-        }
-        for (int d = G >> 1; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
-        // the wide branch, as k_head_any takes it: per sample, or the per-field products added in FIELD ORDER + the bias
-        float wv = 0.0f;
-        if (wprod) {
-            const int lane_row0 = (threadIdx.x & 63) - cg;
-            float acc_w = 0.0f;
-            for (int f0 = 0; f0 < F; f0 += G) {
-                const int f = f0 + cg;
-                const float mine = (valid && f < F) ? wprod[2 * (r * F + f)] : 0.0f;
-                const int nf = (F - f0 < G) ? F - f0 : G;
-                for (int c = 0; c < nf; ++c) acc_w = acc_w + __shfl(mine, lane_row0 + c, 64);
-            }
-            wv = acc_w + *wide_bias;
-        } else if (valid) {
-            wv = wide[r];
-        }
+        const float part = head_row_dot<KIND, NC>(cur, w, G);
+        const float wv = head_wide_term(wprod, F, wide_bias, wide, r, valid, cg, G);
         if (valid && cg == 0) {
             const float z = part + bias + wv;
-            const float sg = 1.0f / (1.0f + expf(-z));
+            const float sg = sigmoid_of(z);
             logit_out[r] = z;
             prob_out[r] = sg;
             if (label) {
                 const float y = label[r];
-                const float loss = fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
-                accl += loss;
+                accl += sigmoid_xent(z, y);
             }
         }
 #pragma unroll
@@ -407,13 +380,9 @@ __global__ __launch_bounds__(MB) void k_head_predict(const uint4* __restrict__ h
         }
     }
     if (!label) return;          // (uniform: a kernel argument)
-    red2[threadIdx.x] = accl;
+    red2[threadIdx.x][0] = accl;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        float sl = 0.0f;
-        for (int q = 0; q < RP; ++q) sl += red2[q * G];
-        partial[blockIdx.x] = sl;
-    }
+    if (threadIdx.x == 0) head_block_scalars<1>(red2, G, RP, partial + blockIdx.x);
 }
 
 // loss = (the workgroups' partials added in workgroup order, finish_column's order as k_head_finish) / B: one workgroup
@@ -424,11 +393,82 @@ __global__ __launch_bounds__(MB) void k_head_predict_finish(const float* __restr
     if (threadIdx.x == 0) *loss = s * inv_B;
 }
 
+// ---- host: one launch geometry, one argument check, one (kind, chunks a lane) dispatch ---------------------------------------
 inline bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-inline int pick_blocks(int64_t B, int RP) {
-    int64_t nb = 256;
-    while (nb > 1 && B / nb < 4 * RP) nb >>= 1;   // at least a few passes per block
-    return (int)nb;
+
+// C chunks of 8 values a row; G = min(64, pow2ceil(C)) lanes a row, NC chunks a lane, RP rows a pass; nblk workgroups budgeted (a
+// power of two <= 256, each with at least a few passes) of which nb are launched, rows_per_block rows (whole passes) each
+struct HeadGeom { int C, G, NC, RP, nblk, rows_per_block, nb; };
+inline HeadGeom head_geom(int64_t B, int K5) {
+    HeadGeom g;
+    g.C = K5 / 8;
+    g.G = 1;
+    while (g.G < g.C && g.G < 64) g.G <<= 1;
+    g.NC = (int)mrec_cdiv(g.C, g.G);
+    g.RP = MB / g.G;
+    int64_t nblk = 256;
+    while (nblk > 1 && B / nblk < 4 * g.RP) nblk >>= 1;   // at least a few passes per block
+    g.nblk = (int)nblk;
+    g.rows_per_block = (int)mrec_cdiv(mrec_cdiv(B, nblk), g.RP) * g.RP;
+    g.nb = (int)mrec_cdiv(B, g.rows_per_block);
+    return g;
+}
+
+// What an entry refuses, in the order every entry refuses it.  HEAD_TRAIN: the backward's outputs (outs: dlogit, dh4, dw5, db4, db5),
+// label, loss and the workspace are required, dh_scale >= 1, a workspace of nblk partial rows; without it (evaluation; outs: prob)
+// label and loss come together or not at all and only they want a workspace, of nblk floats.  HEAD_POW2: k_head_fwd_bwd's widths.
+enum { HEAD_TRAIN = 1, HEAD_POW2 = 2 };
+int head_check(int flags, int kind, const void* h4, const float* w5, const float* b5, const float* wide, const float* wprod, int F,
+               const float* wide_bias, const float* label, int64_t B, int K5, float dh_scale, const float* logit, bool outs,
+               const void* dh4, const float* loss, const void* ws, size_t ws_bytes, HeadGeom* g) {
+    const bool train = flags & HEAD_TRAIN;
+    if (B <= 0 || K5 <= 0 || kind < 0 || kind > 2 || (train && !(dh_scale >= 1.0f))) return MREC_EINVAL;
+    if (wprod && (F <= 0 || !wide_bias)) return MREC_EINVAL;
+    if ((wide != nullptr) == (wprod != nullptr)) return MREC_EINVAL;
+    if (!h4 || !w5 || !b5 || !logit || !outs) return MREC_EINVAL;
+    if (train ? (!label || !loss || !ws) : ((label != nullptr) != (loss != nullptr))) return MREC_EINVAL;
+    if (K5 % 8 || K5 > 2048 || ((flags & HEAD_POW2) && (!pow2(K5 / 8) || K5 / 8 > 64))) return MREC_EUNSUPPORTED;
+    if ((((uintptr_t)h4 | (uintptr_t)dh4) & 15) != 0) return MREC_EINVAL;
+    *g = head_geom(B, K5);
+    if (train ? ws_bytes < (size_t)g->nblk * (2 * K5 + 2) * sizeof(float) : (label && (!ws || ws_bytes < (size_t)g->nblk * sizeof(float))))
+        return MREC_EWORKSPACE;
+    return MREC_OK;
+}
+
+// f(KIND, NC) with the two as compile-time constants (std::integral_constant): the kernels' template arguments
+template <class Fn> inline void head_dispatch(int kind, int NC, Fn f) {
+    auto chunks = [&](auto k) {
+        if (NC == 1) f(k, std::integral_constant<int, 1>{});
+        else if (NC == 2) f(k, std::integral_constant<int, 2>{});
+        else if (NC == 3) f(k, std::integral_constant<int, 3>{});
+        else f(k, std::integral_constant<int, 4>{});
+    };
+    if (kind == 2) chunks(std::integral_constant<int, 2>{});
+    else if (kind == 1) chunks(std::integral_constant<int, 1>{});
+    else chunks(std::integral_constant<int, 0>{});
+}
+
+// The training head.  fixed: k_head_fwd_bwd and its widths (K5 / 8 a power of two <= 64: G = C, one chunk a lane); else k_head_any.
+int head_train(bool fixed, int kind, const void* h4, const float* w5, const float* b5, const float* wide, const float* wprod, int F,
+               const float* wide_bias, const float* label, int64_t B, int K5, float dscale, float dh_scale, float* logit, float* dlogit,
+               void* dh4, float* dw5, float* db4, float* db5, float* dwide_b, float* loss, void* ws, size_t ws_bytes, void* stream) {
+    HeadGeom g;
+    const int rc = head_check(HEAD_TRAIN | (fixed ? HEAD_POW2 : 0), kind, h4, w5, b5, wide, wprod, F, wide_bias, label, B, K5, dh_scale, logit,
+                              dlogit && dh4 && dw5 && db4 && db5, dh4, loss, ws, ws_bytes, &g);
+    if (rc != MREC_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    head_dispatch(kind, g.NC, [&](auto k, auto n) {
+        constexpr int KIND = decltype(k)::value, NC = decltype(n)::value;
+        if (fixed)
+            k_head_fwd_bwd<KIND><<<g.nb, MB, 0, st>>>((const uint4*)h4, w5, b5, wide, label, B, g.G, g.rows_per_block, dscale, logit, dlogit,
+                                                      (uint4*)dh4, (float*)ws, wprod, F, wide_bias, dh_scale);
+        else
+            k_head_any<KIND, NC><<<g.nb, MB, 0, st>>>((const uint4*)h4, w5, b5, wide, label, B, g.C, g.G, g.rows_per_block, dscale, logit,
+                                                      dlogit, (uint4*)dh4, (float*)ws, wprod, F, wide_bias, dh_scale);
+    });
+    k_head_finish<<<(unsigned)mrec_cdiv(2 * K5 + 2, 32), MB, 0, st>>>((const float*)ws, g.nb, K5, 1.0f / (float)B, dw5, db4, db5, loss, dwide_b);
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
 }
 
 }  // namespace
@@ -439,46 +479,18 @@ MREC_API int mrec_head_workspace_bytes(int64_t B, int32_t K5, size_t* out) {
     return MREC_OK;
 }
 
-static int head_impl(int kind, const void* h4, const float* w5, const float* b5, const float* wide,
-                     const float* label, int64_t B, int32_t K5, float dscale, float dh_scale, float* logit,
-                     float* dlogit, void* dh4, float* dw5, float* db4, float* db5, float* loss,
-                     void* ws, size_t ws_bytes, void* stream, const float* wprod = nullptr, int F = 0,
-                     const float* wide_bias = nullptr, float* dwide_b = nullptr) {
-    if (B <= 0 || K5 <= 0 || !(dh_scale >= 1.0f)) return MREC_EINVAL;
-    if (wprod && (F <= 0 || !wide_bias)) return MREC_EINVAL;
-    if (!h4 || !w5 || !b5 || (!wide && !wprod) || !label || !logit || !dlogit || !dh4 || !dw5 || !db4 || !db5 || !loss || !ws) return MREC_EINVAL;
-    if (K5 % 8 || !pow2(K5 / 8) || K5 / 8 > 64) return MREC_EUNSUPPORTED;
-    if ((((uintptr_t)h4 | (uintptr_t)dh4) & 15) != 0) return MREC_EINVAL;
-    const int CG = K5 / 8, RP = MB / CG;
-    const int nblk = pick_blocks(B, RP);
-    if (ws_bytes < (size_t)nblk * (2 * K5 + 2) * sizeof(float)) return MREC_EWORKSPACE;
-    const int rows_per_block = (int)mrec_cdiv(mrec_cdiv(B, nblk), RP) * RP;
-    const int nb = (int)mrec_cdiv(B, rows_per_block);
-    hipStream_t st = (hipStream_t)stream;
-#define MREC_HEAD_GO(KIND)                                                                                                 \
-    k_head_fwd_bwd<KIND><<<nb, MB, 0, st>>>((const uint4*)h4, w5, b5, wide, label, B, CG, rows_per_block, dscale, logit, dlogit, \
-                                            (uint4*)dh4, (float*)ws, wprod, F, wide_bias, dh_scale)
-    if (kind == 2) MREC_HEAD_GO(2);
-    else if (kind == 1) MREC_HEAD_GO(1);
-    else MREC_HEAD_GO(0);
-#undef MREC_HEAD_GO
-    k_head_finish<<<(unsigned)mrec_cdiv(2 * K5 + 2, 32), MB, 0, st>>>((const float*)ws, nb, K5, 1.0f / (float)B, dw5, db4, db5, loss, dwide_b);
-    MREC_LAUNCH_CHECK();
-    return MREC_OK;
-}
-
 MREC_API int mrec_head_fwd_bwd_bf16(const uint16_t* h4, const float* w5, const float* b5, const float* wide,
                                     const float* label, int64_t B, int32_t K5, float dscale, float dh_scale, float* logit,
                                     float* dlogit, uint16_t* dh4, float* dw5, float* db4, float* db5, float* loss,
                                     void* ws, size_t ws_bytes, void* stream) {
-    return head_impl(0, h4, w5, b5, wide, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, loss, ws, ws_bytes, stream);
+    return head_train(true, 0, h4, w5, b5, wide, nullptr, 0, nullptr, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, nullptr, loss, ws, ws_bytes, stream);
 }
 
 MREC_API int mrec_head_fwd_bwd_f16(const uint16_t* h4, const float* w5, const float* b5, const float* wide,
                                    const float* label, int64_t B, int32_t K5, float dscale, float dh_scale, float* logit,
                                    float* dlogit, uint16_t* dh4, float* dw5, float* db4, float* db5, float* loss,
                                    void* ws, size_t ws_bytes, void* stream) {
-    return head_impl(1, h4, w5, b5, wide, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, loss, ws, ws_bytes, stream);
+    return head_train(true, 1, h4, w5, b5, wide, nullptr, 0, nullptr, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, nullptr, loss, ws, ws_bytes, stream);
 }
 
 /* fp32 activations (the fp32 net: mlp_dtype = fp32 of the Wide&Deep / DeepFM engines): h4, dh4 float32 [B, K5] */
@@ -486,7 +498,7 @@ MREC_API int mrec_head_fwd_bwd_f32(const float* h4, const float* w5, const float
                                    const float* label, int64_t B, int32_t K5, float dscale, float dh_scale, float* logit,
                                    float* dlogit, float* dh4, float* dw5, float* db4, float* db5, float* loss,
                                    void* ws, size_t ws_bytes, void* stream) {
-    return head_impl(2, h4, w5, b5, wide, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, loss, ws, ws_bytes, stream);
+    return head_train(true, 2, h4, w5, b5, wide, nullptr, 0, nullptr, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, nullptr, loss, ws, ws_bytes, stream);
 }
 
 /* The same head with the wide branch given as per-field products [B, F] + the wide bias (see include/mrec.h). */
@@ -494,8 +506,7 @@ MREC_API int mrec_head_fwd_bwd_wide(int32_t f16, const uint16_t* h4, const float
                                     int32_t F, const float* wide_bias, const float* label, int64_t B, int32_t K5, float dscale,
                                     float dh_scale, float* logit, float* dlogit, uint16_t* dh4, float* dw5, float* db4, float* db5, float* dwide_bias,
                                     float* loss, void* ws, size_t ws_bytes, void* stream) {
-    return head_impl(f16 != 0 ? 1 : 0, h4, w5, b5, nullptr, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, loss, ws, ws_bytes,
-                     stream, wide_prod, F, wide_bias, dwide_bias);
+    return head_train(true, f16 != 0 ? 1 : 0, h4, w5, b5, nullptr, wide_prod, F, wide_bias, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, dwide_bias, loss, ws, ws_bytes, stream);
 }
 
 /* The head at any K5 % 8 == 0, 8 <= K5 <= 2048 (k_head_any; see include/mrec.h). */
@@ -503,39 +514,7 @@ MREC_API int mrec_head_fwd_bwd_any(int32_t kind, const void* h4, const float* w5
                                    const float* wide_prod, int32_t F, const float* wide_bias, const float* label, int64_t B, int32_t K5,
                                    float dscale, float dh_scale, float* logit, float* dlogit, void* dh4, float* dw5, float* db4, float* db5,
                                    float* dwide_bias, float* loss, void* ws, size_t ws_bytes, void* stream) {
-    if (B <= 0 || K5 <= 0 || kind < 0 || kind > 2 || !(dh_scale >= 1.0f)) return MREC_EINVAL;
-    if (wide_prod && (F <= 0 || !wide_bias)) return MREC_EINVAL;
-    if ((wide != nullptr) == (wide_prod != nullptr)) return MREC_EINVAL;
-    if (!h4 || !w5 || !b5 || !label || !logit || !dlogit || !dh4 || !dw5 || !db4 || !db5 || !loss || !ws) return MREC_EINVAL;
-    if (K5 % 8 || K5 > 2048) return MREC_EUNSUPPORTED;
-    if ((((uintptr_t)h4 | (uintptr_t)dh4) & 15) != 0) return MREC_EINVAL;
-    const int C = K5 / 8;
-    int G = 1;
-    while (G < C && G < 64) G <<= 1;
-    const int NC = (int)mrec_cdiv(C, G), RP = MB / G;
-    const int nblk = pick_blocks(B, RP);                   // <= 256 of the workspace's 512 partial rows
-    if (ws_bytes < (size_t)nblk * (2 * K5 + 2) * sizeof(float)) return MREC_EWORKSPACE;
-    const int rows_per_block = (int)mrec_cdiv(mrec_cdiv(B, nblk), RP) * RP;
-    const int nb = (int)mrec_cdiv(B, rows_per_block);
-    hipStream_t st = (hipStream_t)stream;
-#define MREC_HEAD_ANY(KIND, NCH)                                                                                                       \
-    k_head_any<KIND, NCH><<<nb, MB, 0, st>>>((const uint4*)h4, w5, b5, wide, label, B, C, G, rows_per_block, dscale, logit, dlogit,    \
-                                             (uint4*)dh4, (float*)ws, wide_prod, F, wide_bias, dh_scale)
-#define MREC_HEAD_ANY_NC(KIND)                                                                                                         \
-    do {                                                                                                                               \
-        if (NC == 1) MREC_HEAD_ANY(KIND, 1);                                                                                           \
-        else if (NC == 2) MREC_HEAD_ANY(KIND, 2);                                                                                      \
-        else if (NC == 3) MREC_HEAD_ANY(KIND, 3);                                                                                      \
-        else MREC_HEAD_ANY(KIND, 4);                                                                                                   \
-    } while (0)
-    if (kind == 2) MREC_HEAD_ANY_NC(2);
-    else if (kind == 1) MREC_HEAD_ANY_NC(1);
-    else MREC_HEAD_ANY_NC(0);
-#undef MREC_HEAD_ANY_NC
-#undef MREC_HEAD_ANY
-    k_head_finish<<<(unsigned)mrec_cdiv(2 * K5 + 2, 32), MB, 0, st>>>((const float*)ws, nb, K5, 1.0f / (float)B, dw5, db4, db5, loss, dwide_bias);
-    MREC_LAUNCH_CHECK();
-    return MREC_OK;
+    return head_train(false, kind, h4, w5, b5, wide, wide_prod, F, wide_bias, label, B, K5, dscale, dh_scale, logit, dlogit, dh4, dw5, db4, db5, dwide_bias, loss, ws, ws_bytes, stream);
 }
 
 /* The evaluation forward of the head at any K5 % 8 == 0, 8 <= K5 <= 2048 (k_head_predict; see include/mrec.h). */
@@ -548,37 +527,16 @@ MREC_API int mrec_head_predict_workspace_bytes(int64_t B, size_t* out) {
 MREC_API int mrec_head_predict(int32_t kind, const void* h4, const float* w5, const float* b5, const float* wide, const float* wide_prod,
                                int32_t F, const float* wide_bias, const float* label, int64_t B, int32_t K5, float* logit, float* prob,
                                float* loss, void* ws, size_t ws_bytes, void* stream) {
-    if (B <= 0 || K5 <= 0 || kind < 0 || kind > 2) return MREC_EINVAL;
-    if (wide_prod && (F <= 0 || !wide_bias)) return MREC_EINVAL;
-    if ((wide != nullptr) == (wide_prod != nullptr)) return MREC_EINVAL;
-    if (!h4 || !w5 || !b5 || !logit || !prob || (label != nullptr) != (loss != nullptr)) return MREC_EINVAL;
-    if (K5 % 8 || K5 > 2048) return MREC_EUNSUPPORTED;
-    if (((uintptr_t)h4 & 15) != 0) return MREC_EINVAL;
-    const int C = K5 / 8;
-    int G = 1;
-    while (G < C && G < 64) G <<= 1;
-    const int NC = (int)mrec_cdiv(C, G), RP = MB / G;
-    const int nblk = pick_blocks(B, RP);                   // <= 256
-    if (label && (!ws || ws_bytes < (size_t)nblk * sizeof(float))) return MREC_EWORKSPACE;
-    const int rows_per_block = (int)mrec_cdiv(mrec_cdiv(B, nblk), RP) * RP;
-    const int nb = (int)mrec_cdiv(B, rows_per_block);
+    HeadGeom g;
+    const int rc = head_check(0, kind, h4, w5, b5, wide, wide_prod, F, wide_bias, label, B, K5, 1.0f, logit, prob != nullptr, nullptr, loss, ws,
+                              ws_bytes, &g);
+    if (rc != MREC_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-#define MREC_HEAD_PRED(KIND, NCH)                                                                                                      \
-    k_head_predict<KIND, NCH><<<nb, MB, 0, st>>>((const uint4*)h4, w5, b5, wide, label, B, C, G, rows_per_block, logit, prob,          \
-                                                 label ? (float*)ws : nullptr, wide_prod, F, wide_bias)
-#define MREC_HEAD_PRED_NC(KIND)                                                                                                        \
-    do {                                                                                                                               \
-        if (NC == 1) MREC_HEAD_PRED(KIND, 1);                                                                                          \
-        else if (NC == 2) MREC_HEAD_PRED(KIND, 2);                                                                                     \
-        else if (NC == 3) MREC_HEAD_PRED(KIND, 3);                                                                                     \
-        else MREC_HEAD_PRED(KIND, 4);                                                                                                  \
-    } while (0)
-    if (kind == 2) MREC_HEAD_PRED_NC(2);
-    else if (kind == 1) MREC_HEAD_PRED_NC(1);
-    else MREC_HEAD_PRED_NC(0);
-#undef MREC_HEAD_PRED_NC
-#undef MREC_HEAD_PRED
-    if (label) k_head_predict_finish<<<1, MB, 0, st>>>((const float*)ws, nb, 1.0f / (float)B, loss);
+    head_dispatch(kind, g.NC, [&](auto k, auto n) {
+        k_head_predict<decltype(k)::value, decltype(n)::value><<<g.nb, MB, 0, st>>>(
+            (const uint4*)h4, w5, b5, wide, label, B, g.C, g.G, g.rows_per_block, logit, prob, label ? (float*)ws : nullptr, wide_prod, F, wide_bias);
+    });
+    if (label) k_head_predict_finish<<<1, MB, 0, st>>>((const float*)ws, g.nb, 1.0f / (float)B, loss);
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }

@@ -307,9 +307,8 @@ __global__ __launch_bounds__(TT, 2) void k_tail(const TailArgs a) {
             }
             const float z = part + bias + wv;
             const float y = hy[pass];
-            const float loss = fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
-            const float sg = 1.0f / (1.0f + expf(-z));
-            const float dl = (sg - y) * a.dscale;
+            const float loss = sigmoid_xent(z, y);
+            const float dl = (sigmoid_of(z) - y) * a.dscale;
             if (cg == 0) {
                 a.logit[r] = z;
                 a.dlogit[r] = dl;

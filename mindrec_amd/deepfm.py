@@ -104,10 +104,6 @@ class _DeepFMNet(DenseNetMixin):
         rows, lin_fm = ops.fm_lookup(V, W, ids_v, wts, ids_w=ids_w, out_dtype=self._amp if self._mfma else torch.float32, **self._clip_kw())
         return self.mlp_predict(rows.view(B, Fd * self.cfg.data_emb_dim), lin_fm, label)
 
-    @staticmethod
-    def _predict_out(out, B):
-        return (out[0].view(B, 1), out[1].view(B, 1)) + ((out[2].view(()),) if len(out) == 3 else ())
-
     def _net_step(self, vx, vx16, linear, label):
         """Forward + backward of everything behind the lookups: FM term, the dense net, the loss.  Returns (loss, g_vx fp32
         [B, F, D], g_linear [B]); dense gradients are left in the slabs / the flat gradient buffer for _dense_adam."""
@@ -211,38 +207,7 @@ class DeepFMEngine(_DeepFMNet):
         ids dtype, label given?): THE RETURNED TENSORS ARE THEN STATIC BUFFERS WHICH THE NEXT CALL OVERWRITES -- copy what must
         outlive it.  Raises ValueError where fused_predict_supported is False."""
         self._check_fused()
-        B = ids.shape[0]
-        if not (self.cfg.graphs != "none" and self._predict_capture):
-            return self._predict_out(self._predict_chain(ids, wts, label), B)
-        key = (tuple(ids.shape), ids.dtype, label is not None)
-        st = self._predict_graphs.setdefault(key, {"calls": 0, "g": None})
-        st["calls"] += 1
-        if st["calls"] <= 2:                             # two eager calls first: every workspace exists by then
-            return self._predict_out(self._predict_chain(ids, wts, label), B)
-        g = st["g"]
-        if g is None:
-            try:
-                g = st["g"] = self._capture_predict(ids, wts, label)
-            except RuntimeError as e:          # capture refused: stay eager
-                import warnings
-                warnings.warn(f"HIP-graph capture of the evaluation forward failed, running it eagerly: {e}")
-                self._predict_capture = False
-                self._predict_graphs = {}
-                return self._predict_out(self._predict_chain(ids, wts, label), B)
-        ins = (ids, wts) if label is None else (ids, wts, label)
-        self.k.copy_many_(list(g["in"]), list(ins))       # one launch
-        g["graph"].replay()
-        return self._predict_out(g["out"], B)
-
-    def _capture_predict(self, ids, wts, label):
-        """The evaluation chain captured on static copies of these inputs: one graph, one stream."""
-        g = {"in": tuple(t.clone().contiguous() for t in ((ids, wts) if label is None else (ids, wts, label)))}
-        torch.cuda.synchronize(self.device)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            g["out"] = self._predict_chain(g["in"][0], g["in"][1], g["in"][2] if label is not None else None)
-        g["graph"] = graph
-        return g
+        return self._predict_run(self._predict_chain, ids, wts, label, capture=self.cfg.graphs != "none")
 
     def release_graphs(self):
         """Drops every captured HIP graph -- the dense net's training step and the evaluation forwards (they are re-captured on demand)."""

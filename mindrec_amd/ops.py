@@ -1456,21 +1456,45 @@ def head_supported(K5):
     return K5 % 8 == 0 and (K5 // 8) & (K5 // 8 - 1) == 0 and K5 // 8 <= 64
 
 
+_HEAD_KIND = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}      # h4's dtype -> the head kernels' kind code (not _KIND's)
+
+
+def _head_kind(h4, f32=True):
+    kind = _HEAD_KIND.get(h4.dtype)
+    if kind is None or (kind == 2 and not f32):
+        raise TypeError("h4 must be bfloat16, float16 or float32" if f32 else "h4 must be bfloat16 or float16")
+    return kind
+
+
+def _head_fields(wide_prod, B):
+    """F of the wide branch's per-field products [B, F, 2]; 0 without them"""
+    if wide_prod is None:
+        return 0
+    if (wide_prod.dtype != torch.float32 or wide_prod.dim() != 3 or wide_prod.shape[0] != B or wide_prod.shape[2] != 2
+            or not wide_prod.is_contiguous()):
+        raise TypeError("wide_prod must be the contiguous float32 [B, F, 2] tensor of gather_rows_wide")
+    return wide_prod.shape[1]
+
+
+def _head_outputs(h4):
+    """(logit [B], dlogit [B], dh4 like h4, loss [1]) and the training head's workspace"""
+    B, K5 = h4.shape
+    dev = h4.device
+    logit = torch.empty(B, dtype=torch.float32, device=dev)
+    dlogit = torch.empty(B, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = workspace("head", _lib.query_bytes("mrec_head_workspace_bytes", B, K5), dev)
+    return logit, dlogit, torch.empty_like(h4), loss, ws
+
+
 def head_fwd_bwd(h4, w5, b5, wide, label, dscale, dw5_out, db4_out, db5_out, dh_scale=1.0):
     """Output layer + wide/deep add + sigmoid cross-entropy, forward and backward, one pass over h4.
     Returns (loss [1], logit [B], dlogit [B], dh4 [B, K5] of h4's dtype: bfloat16, float16 or float32)."""
     _need_cuda(h4, w5, b5, wide, label)
     B, K5 = h4.shape
-    dev = h4.device
-    logit = torch.empty(B, dtype=torch.float32, device=dev)
-    dlogit = torch.empty(B, dtype=torch.float32, device=dev)
-    dh4 = torch.empty_like(h4)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    nb = _lib.query_bytes("mrec_head_workspace_bytes", B, K5)
-    ws = workspace("head", nb, dev)
-    if h4.dtype not in _DT16 and h4.dtype != torch.float32:
-        raise TypeError("h4 must be bfloat16, float16 or float32")
-    _lib.call("mrec_head_fwd_bwd_" + ("f32" if h4.dtype == torch.float32 else _DT16[h4.dtype]), _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide.contiguous()),
+    kind = _head_kind(h4)
+    logit, dlogit, dh4, loss, ws = _head_outputs(h4)
+    _lib.call("mrec_head_fwd_bwd_" + ("bf16", "f16", "f32")[kind], _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide.contiguous()),
               _ptr(label.contiguous()), B, K5, float(dscale), float(dh_scale), _ptr(logit), _ptr(dlogit), _ptr(dh4), _ptr(dw5_out),
               _ptr(db4_out), _ptr(db5_out), _ptr(loss), _ptr(ws), ws.numel(), _stream())
     return loss, logit, dlogit, dh4
@@ -1481,20 +1505,11 @@ def head_fwd_bwd_wide(h4, w5, b5, wide_prod, wide_bias, label, dscale, dw5_out, 
     the ReduceSum over the fields (wide_and_deep.py:305-306) happens inside the head, in field order."""
     _need_cuda(h4, w5, b5, wide_prod, wide_bias, label)
     B, K5 = h4.shape
-    dev = h4.device
-    if (wide_prod.dtype != torch.float32 or wide_prod.dim() != 3 or wide_prod.shape[0] != B or wide_prod.shape[2] != 2
-            or not wide_prod.is_contiguous()):
-        raise TypeError("wide_prod must be the contiguous float32 [B, F, 2] tensor of gather_rows_wide")
-    if h4.dtype not in _DT16:
-        raise TypeError("h4 must be bfloat16 or float16")
-    logit = torch.empty(B, dtype=torch.float32, device=dev)
-    dlogit = torch.empty(B, dtype=torch.float32, device=dev)
-    dh4 = torch.empty_like(h4)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    nb = _lib.query_bytes("mrec_head_workspace_bytes", B, K5)
-    ws = workspace("head", nb, dev)
-    _lib.call("mrec_head_fwd_bwd_wide", int(h4.dtype == torch.float16), _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide_prod),
-              wide_prod.shape[1], _ptr(wide_bias), _ptr(label.contiguous()), B, K5, float(dscale), float(dh_scale), _ptr(logit), _ptr(dlogit),
+    F = _head_fields(wide_prod, B)
+    kind = _head_kind(h4, f32=False)
+    logit, dlogit, dh4, loss, ws = _head_outputs(h4)
+    _lib.call("mrec_head_fwd_bwd_wide", kind, _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide_prod),
+              F, _ptr(wide_bias), _ptr(label.contiguous()), B, K5, float(dscale), float(dh_scale), _ptr(logit), _ptr(dlogit),
               _ptr(dh4), _ptr(dw5_out), _ptr(db4_out), _ptr(db5_out), _ptr(dwide_bias_out), _ptr(loss), _ptr(ws), ws.numel(), _stream())
     return loss, logit, dlogit, dh4
 
@@ -1511,22 +1526,9 @@ def head_fwd_bwd_any(h4, w5, b5, wide, label, dscale, dw5_out, db4_out, db5_out,
     Returns (loss [1], logit [B], dlogit [B], dh4 [B, K5] of h4's dtype)."""
     _need_cuda(h4, w5, b5, wide, wide_prod, wide_bias, label)
     B, K5 = h4.shape
-    dev = h4.device
-    if h4.dtype not in _DT16 and h4.dtype != torch.float32:
-        raise TypeError("h4 must be bfloat16, float16 or float32")
-    F = 0
-    if wide_prod is not None:
-        if (wide_prod.dtype != torch.float32 or wide_prod.dim() != 3 or wide_prod.shape[0] != B or wide_prod.shape[2] != 2
-                or not wide_prod.is_contiguous()):
-            raise TypeError("wide_prod must be the contiguous float32 [B, F, 2] tensor of gather_rows_wide")
-        F = wide_prod.shape[1]
-    logit = torch.empty(B, dtype=torch.float32, device=dev)
-    dlogit = torch.empty(B, dtype=torch.float32, device=dev)
-    dh4 = torch.empty_like(h4)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    nb = _lib.query_bytes("mrec_head_workspace_bytes", B, K5)
-    ws = workspace("head", nb, dev)
-    kind = 2 if h4.dtype == torch.float32 else int(h4.dtype == torch.float16)
+    kind = _head_kind(h4)
+    F = _head_fields(wide_prod, B)
+    logit, dlogit, dh4, loss, ws = _head_outputs(h4)
     _lib.call("mrec_head_fwd_bwd_any", kind, _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide.contiguous() if wide is not None else None),
               _ptr(wide_prod), F, _ptr(wide_bias), _ptr(label.contiguous()), B, K5, float(dscale), float(dh_scale), _ptr(logit), _ptr(dlogit),
               _ptr(dh4), _ptr(dw5_out), _ptr(db4_out), _ptr(db5_out), _ptr(dwide_bias_out), _ptr(loss), _ptr(ws), ws.numel(), _stream())
@@ -1547,14 +1549,8 @@ def head_predict(h4, w5, b5, wide=None, wide_prod=None, wide_bias=None, label=No
     _need_cuda(h4, w5, b5, wide, wide_prod, wide_bias, label)
     B, K5 = h4.shape
     dev = h4.device
-    if h4.dtype not in _DT16 and h4.dtype != torch.float32:
-        raise TypeError("h4 must be bfloat16, float16 or float32")
-    F = 0
-    if wide_prod is not None:
-        if (wide_prod.dtype != torch.float32 or wide_prod.dim() != 3 or wide_prod.shape[0] != B or wide_prod.shape[2] != 2
-                or not wide_prod.is_contiguous()):
-            raise TypeError("wide_prod must be the contiguous float32 [B, F, 2] tensor of gather_rows_wide")
-        F = wide_prod.shape[1]
+    kind = _head_kind(h4)
+    F = _head_fields(wide_prod, B)
     o = out if out is not None else {}
 
     def buf(name, n):
@@ -1571,7 +1567,6 @@ def head_predict(h4, w5, b5, wide=None, wide_prod=None, wide_bias=None, label=No
         loss = buf("loss", 1)
         ws = workspace("head_predict", _lib.query_bytes("mrec_head_predict_workspace_bytes", B), dev)
         ws_bytes = ws.numel()
-    kind = 2 if h4.dtype == torch.float32 else int(h4.dtype == torch.float16)
     _lib.call("mrec_head_predict", kind, _ptr(h4.contiguous()), _ptr(w5), _ptr(b5), _ptr(wide.contiguous() if wide is not None else None),
               _ptr(wide_prod), F, _ptr(wide_bias), _ptr(label.contiguous() if label is not None else None), B, K5, _ptr(logit), _ptr(prob),
               _ptr(loss), _ptr(ws), ws_bytes, _stream())

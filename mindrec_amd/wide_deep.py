@@ -511,45 +511,9 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             mode = ("row shards (world > 1)" if self._sharded else "the host cache (host_cache_rows > 0)" if self.hb is not None
                     else "this device / op set")
             raise ValueError(f"predict_fused is not supported with {mode}: use predict")
-        B = ids.shape[0]
         if self.index is not None:
             ids, _ = self._translate_keys(ids)          # MapTensorGet inserts default rows in eval too, as predict
-            return self._predict_out(self._predict_chain(ids, wts, label), B)
-        if not (self._graph_level >= 1 and self._predict_capture):
-            return self._predict_out(self._predict_chain(ids, wts, label), B)
-        key = (tuple(ids.shape), ids.dtype, label is not None)
-        st = self._predict_graphs.setdefault(key, {"calls": 0, "g": None})
-        st["calls"] += 1
-        if st["calls"] <= 2:                             # two eager calls first: every workspace exists by then
-            return self._predict_out(self._predict_chain(ids, wts, label), B)
-        g = st["g"]
-        if g is None:
-            try:
-                g = st["g"] = self._capture_predict(ids, wts, label)
-            except RuntimeError as e:          # capture refused: stay eager
-                import warnings
-                warnings.warn(f"HIP-graph capture of the evaluation forward failed, running it eagerly: {e}")
-                self._predict_capture = False
-                self._predict_graphs = {}
-                return self._predict_out(self._predict_chain(ids, wts, label), B)
-        ins = (ids, wts) if label is None else (ids, wts, label)
-        self.k.copy_many_(list(g["in"]), list(ins))       # one launch
-        g["graph"].replay()
-        return self._predict_out(g["out"], B)
-
-    def _capture_predict(self, ids, wts, label):
-        """The evaluation chain captured on static copies of these inputs: one graph, one stream."""
-        g = {"in": tuple(t.clone().contiguous() for t in ((ids, wts) if label is None else (ids, wts, label)))}
-        torch.cuda.synchronize(self.device)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            g["out"] = self._predict_chain(g["in"][0], g["in"][1], g["in"][2] if label is not None else None)
-        g["graph"] = graph
-        return g
-
-    @staticmethod
-    def _predict_out(out, B):
-        return (out[0].view(B, 1), out[1].view(B, 1)) + ((out[2].view(()),) if len(out) == 3 else ())
+        return self._predict_run(self._predict_chain, ids, wts, label, capture=self._graph_level >= 1 and self.index is None)
 
     def _map_tables(self):
         """(tensor, sigma, fill, seed) of the six tables that share the key index's row numbering, with the values a row gets

@@ -289,6 +289,68 @@ class DenseNetMixin:
                                        wt=self._dense16_t.get(i)))
         return hs
 
+    # ---- the evaluation forward of an engine (its predict_fused), eager or replayed from one captured graph ----------------------------
+    @staticmethod
+    def _predict_out(out, B):
+        return (out[0].view(B, 1), out[1].view(B, 1)) + ((out[2].view(()),) if len(out) == 3 else ())
+
+    def _predict_run(self, chain, ids, wts, label, capture):
+        """chain(ids, wts, label) -> (logit, prob[, loss]), shaped as predict shapes them.  capture: from the third call at a given
+        (ids shape, ids dtype, label given?) the chain replays as one HIP graph captured on static copies of the inputs (one graph,
+        one stream; two eager calls first: every workspace exists by then) -- the returned tensors are then the graph's static
+        outputs.  State: self._predict_graphs (key -> {"calls", "g"}), self._predict_capture (cleared when a capture is refused)."""
+        B = ids.shape[0]
+        if not (capture and self._predict_capture):
+            return self._predict_out(chain(ids, wts, label), B)
+        st = self._predict_graphs.setdefault((tuple(ids.shape), ids.dtype, label is not None), {"calls": 0, "g": None})
+        st["calls"] += 1
+        if st["calls"] <= 2:
+            return self._predict_out(chain(ids, wts, label), B)
+        ins = (ids, wts) if label is None else (ids, wts, label)
+        g = st["g"]
+        if g is None:
+            try:
+                g = {"in": tuple(t.clone().contiguous() for t in ins)}
+                torch.cuda.synchronize(self.device)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    g["out"] = chain(g["in"][0], g["in"][1], g["in"][2] if label is not None else None)
+                g["graph"] = graph
+                st["g"] = g
+            except RuntimeError as e:          # capture refused: stay eager
+                import warnings
+                warnings.warn(f"HIP-graph capture of the evaluation forward failed, running it eagerly: {e}")
+                self._predict_capture = False
+                self._predict_graphs = {}
+                return self._predict_out(chain(ids, wts, label), B)
+        self.k.copy_many_(list(g["in"]), list(ins))       # one launch
+        g["graph"].replay()
+        return self._predict_out(g["out"], B)
+
+    def _head(self, h, wide, label, dh_scale):
+        """The output head of this net on h = the last hidden layer's activations: output layer + wide/deep add + sigmoid
+        cross-entropy, forward AND backward, one pass over h.  wide: [B], or the _WideProd of the folded lookup.  Returns (loss 0-d,
+        dlogit, dh); the gradients of W5, b5 and the last hidden bias (and of Wide_b, with products) land in dense_grad / wide_b_grad.
+        None where the op set has no head for this width."""
+        n = len(self.dims) - 1
+        K5, B = self.dims[n - 1], h.shape[0]
+        prod = isinstance(wide, _WideProd)
+        args = (h, self.dense[2 * (n - 1)].detach().view(-1), self.dense[2 * (n - 1) + 1].detach())
+        grads = (self.dense_grad[2 * (n - 1)].view(-1), self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1])
+        if self.k is ops and not ops.head_supported(K5) and ops.head_any_supported(K5):
+            # a last hidden width that is no power of two times 8, or wider than 512: the head kernel for any multiple of 8 up to 2048
+            loss, _, dlogit, dh = ops.head_fwd_bwd_any(*args, None if prod else wide, label.view(-1), self._sens / B, *grads, dh_scale=dh_scale,
+                                                       wide_prod=wide.prod if prod else None, wide_bias=self.wide_b if prod else None,
+                                                       dwide_bias_out=self.wide_b_grad if prod else None)
+        elif prod:
+            loss, _, dlogit, dh = self.k.head_fwd_bwd_wide(*args, wide.prod, self.wide_b, label.view(-1), self._sens / B, *grads,
+                                                            dwide_bias_out=self.wide_b_grad, dh_scale=dh_scale)
+        elif self.k.head_supported(K5):
+            loss, _, dlogit, dh = self.k.head_fwd_bwd(*args, wide, label.view(-1), self._sens / B, *grads, dh_scale=dh_scale)
+        else:
+            return None
+        return loss.view(()), dlogit, dh
+
     @torch.no_grad()
     def _mlp_head(self, hs, wide, label):
         """Output layer + wide/deep add + sigmoid cross-entropy, forward AND backward.  Returns the context the
@@ -296,7 +358,6 @@ class DenseNetMixin:
         amp, n = self._amp, len(self.dims) - 1
         B = hs[0].shape[0]
         W5, b5 = self.dense[2 * (n - 1)], self.dense[2 * (n - 1) + 1]
-        K5 = self.dims[n - 1]
         dl = self._drop(n - 1, B)
         dhs = dl.scale if dl is not None else 1.0
         if len(hs) == n - 2:
@@ -309,29 +370,10 @@ class DenseNetMixin:
                 self.dense_grad[2 * (n - 3) + 1], self.dense_grad[2 * (n - 4) + 1], dwide_bias_out=self.wide_b_grad if prod else None,
                 drop_in=self._drop(n - 3, B), out=self._tail_out.setdefault((B, hs[-1].dtype, self._slot), {}))
             return {"hs": hs + [y2], "loss": loss.view(()), "g_wide": dlogit.view(-1), "dh": dz2, "tail": (dz4, dz3)}
-        if self.k is ops and not ops.head_supported(K5) and ops.head_any_supported(K5):
-            # a last hidden width that is no power of two times 8, or wider than 512: the head kernel for any multiple of 8 up to 2048
-            prod = isinstance(wide, _WideProd)
-            loss, _, dlogit, dh = ops.head_fwd_bwd_any(hs[-1], W5.detach().view(-1), b5.detach(), None if prod else wide, label.view(-1),
-                                                       self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
-                                                       self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1], dh_scale=dhs,
-                                                       wide_prod=wide.prod if prod else None, wide_bias=self.wide_b if prod else None,
-                                                       dwide_bias_out=self.wide_b_grad if prod else None)
-            loss = loss.view(())
-        elif isinstance(wide, _WideProd):
-            loss, _, dlogit, dh = self.k.head_fwd_bwd_wide(hs[-1], W5.detach().view(-1), b5.detach(), wide.prod, self.wide_b,
-                                                            label.view(-1), self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
-                                                            self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1],
-                                                            dwide_bias_out=self.wide_b_grad, dh_scale=dhs)
-            loss = loss.view(())
-        elif self.k.head_supported(K5):
-            # output layer + wide/deep add + sigmoid cross-entropy, forward AND backward, one pass over h4
-            loss, _, dlogit, dh = self.k.head_fwd_bwd(hs[-1], W5.detach().view(-1), b5.detach(), wide, label.view(-1),
-                                                       self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
-                                                       self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1], dh_scale=dhs)
-            loss = loss.view(())
-        else:
+        out = self._head(hs[-1], wide, label, dhs)
+        if out is None:
             return self._head_generic(hs, wide, label, dhs)
+        loss, dlogit, dh = out
         return {"hs": hs, "loss": loss, "g_wide": dlogit.view(-1), "dh": dh}
 
     @torch.no_grad()
@@ -402,17 +444,9 @@ class DenseNetMixin:
                 k.dropout_(h, drops[i + 1])
             hs.append(h)
         K5 = self.dims[n - 1]
-        if k.head_supported(K5):
-            loss, _, dlogit, dh = k.head_fwd_bwd(hs[-1], self.dense[2 * (n - 1)].detach().view(-1), self.dense[2 * (n - 1) + 1].detach(),
-                                                 wide, label.view(-1), self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
-                                                 self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1],
-                                                 dh_scale=drops[n - 1].scale if drops[n - 1] is not None else 1.0)
-        elif not k.dcn_head_supported(K5, 2):
-            # wider than the detour below reaches (1024 < K5 <= 2048): the head kernel for any multiple of 8
-            loss, _, dlogit, dh = k.head_fwd_bwd_any(hs[-1], self.dense[2 * (n - 1)].detach().view(-1), self.dense[2 * (n - 1) + 1].detach(),
-                                                     wide, label.view(-1), self._sens / B, self.dense_grad[2 * (n - 1)].view(-1),
-                                                     self.dense_grad[2 * (n - 2) + 1], self.dense_grad[2 * (n - 1) + 1],
-                                                     dh_scale=drops[n - 1].scale if drops[n - 1] is not None else 1.0)
+        if k.head_supported(K5) or not k.dcn_head_supported(K5, 2):
+            # (wider than the detour below reaches, 1024 < K5 <= 2048: the head kernel for any multiple of 8)
+            loss, dlogit, dh = self._head(hs[-1], wide, label, drops[n - 1].scale if drops[n - 1] is not None else 1.0)
         else:
             # a last hidden layer wider than the head kernel's 512 columns (the reference's benchmark net ends 1024 -> 1): the
             # output end of Deep&Cross does the same arithmetic over [h | c] . w3 -- with c = [wide, 0] and w3 = [W5 | 1, 0] that is

@@ -146,6 +146,11 @@ def test_head_any_rows_do_not_depend_on_the_partition(dev, oracle, K5, kind):
 def _geometry(B, K5):
     """the launch's workgroups, restated from mrec_head_fwd_bwd_any: G lanes a row, 256 / G rows a pass, at most 256 workgroups of
     at least 4 passes (fewer rows: fewer workgroups)"""
+    return _launch(B, K5)[0]
+
+
+def _launch(B, K5):
+    """(workgroups, rows a workgroup, rows a pass) of that launch"""
     Cn = K5 // 8
     G = 1
     while G < Cn and G < 64:
@@ -155,7 +160,7 @@ def _geometry(B, K5):
     while nblk > 1 and B // nblk < 4 * RP:
         nblk //= 2
     per = -(-(-(-B // nblk)) // RP) * RP
-    return -(-B // per)
+    return -(-B // per), per, RP
 
 
 def _finish_sum(rows):
@@ -223,6 +228,57 @@ def test_head_any_workspace_window_and_guard_rows(dev, oracle, K5, B, nb, kind):
     r = _call(ops, dev, h4, w5, b5, wide, label, 1024.0 / B, kind, 2.0)
     assert torch.equal(_bits(r[3]), _bits(dh4[:B])) and torch.equal(r[1], logit[:B]) and torch.equal(r[2], dlogit[:B])
     assert torch.equal(r[4], o["dw5"]) and torch.equal(r[5], o["db4"]) and torch.equal(r[6], o["db5"]) and torch.equal(r[0], o["loss"])
+
+
+# (K5, batch of at least two workgroups whose last one ends in a partly filled pass); B = 3 is one partly filled pass at each
+FIXED_K5_B = [(8, 2100), (64, 301), (512, 301)]
+
+
+def _call_fixed(ops, dev, h4, w5, b5, wide, label, dscale, kind, dhs, prod=None, wb=None):
+    """_call through ops.head_fwd_bwd / ops.head_fwd_bwd_wide, the head of the power-of-two widths up to 512"""
+    K5 = h4.shape[1]
+    dw5 = torch.full((K5,), FILL, device=dev); db4 = torch.full((K5,), FILL, device=dev); db5 = torch.full((1,), FILL, device=dev)
+    dwb = torch.full((1,), FILL, device=dev)
+    if prod is None:
+        r = ops.head_fwd_bwd(_head_dev(h4, kind, dev), _t(w5, dev), _t(b5, dev), _t(wide, dev), _t(label, dev), dscale, dw5, db4, db5, dh_scale=dhs)
+    else:
+        r = ops.head_fwd_bwd_wide(_head_dev(h4, kind, dev), _t(w5, dev), _t(b5, dev), _t(prod, dev), _t(np.float32([wb]), dev), _t(label, dev),
+                                  dscale, dw5, db4, db5, dwide_bias_out=dwb, dh_scale=dhs)
+    return [t.clone() for t in r] + [dw5, db4, db5, dwb]
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f16", "f32"])
+@pytest.mark.parametrize("K5,Bbig", FIXED_K5_B)
+def test_fixed_width_heads_equal_head_any_bit_for_bit(dev, oracle, K5, Bbig, kind):
+    """ops.head_fwd_bwd and ops.head_fwd_bwd_wide == ops.head_fwd_bwd_any in every bit of every output (loss, logit, dlogit, dh4, dw5,
+    db4, db5, dwide_bias) at widths both serve: the two training heads share one launch geometry, one row arithmetic and one order
+    of partial sums.  Batches: several workgroups with a ragged last one, and a single partly filled pass."""
+    from mindrec_amd import ops
+    assert ops.head_supported(K5) and ops.head_any_supported(K5)
+    nb, per, RP = _launch(Bbig, K5)
+    assert nb >= 2 and (Bbig - (nb - 1) * per) % RP != 0, "the last workgroup must end in a partly filled pass"
+    assert _launch(3, K5)[0] == 1 and 3 % RP != 0
+    for B in (Bbig, 3):
+        for dhs in (1.0, 2.0):
+            rng = np.random.default_rng([K5, B, int(dhs), 11])
+            h4, w5, b5, wide, label = _head_inputs(rng, B, K5, kind, oracle)
+            dscale = 1.0 / B if kind == "f32" else 1024.0 / B
+            a = _call_fixed(ops, dev, h4, w5, b5, wide, label, dscale, kind, dhs)
+            b = _call(ops, dev, h4, w5, b5, wide, label, dscale, kind, dhs)
+            for n, x, y in zip(NAMES, a, b):
+                assert torch.equal(_bits(x), _bits(y)), (K5, kind, B, dhs, n)
+            if kind == "f32":
+                continue                      # head_fwd_bwd_wide: the two 16-bit kinds
+            for F in (1, 39, 70):
+                prod = np.zeros((B, F, 2), np.float32)
+                prod[:, :, 0] = (rng.standard_normal((B, F)) * 10.0 ** rng.uniform(-4, 0, (B, F))).astype(np.float32)
+                prod[:, :, 1] = np.float32("nan")          # the pad word is not part of the sum
+                wb = np.float32(-0.2)
+                a = _call_fixed(ops, dev, h4, w5, b5, None, label, dscale, kind, dhs, prod=prod, wb=wb)
+                b = _call(ops, dev, h4, w5, b5, None, label, dscale, kind, dhs, prod=prod, wb=wb)
+                for n, x, y in zip(NAMES + ("dwide_bias",), a, b):
+                    assert torch.equal(_bits(x), _bits(y)), (K5, kind, B, dhs, F, n)
+                assert torch.equal(a[7], a[6]), (K5, kind, B, dhs, F, "dwide_bias is db5")
 
 
 def test_head_any_refuses_through_the_python_layer(dev):
