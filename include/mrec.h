@@ -985,6 +985,23 @@ int mrec_dcn_head_fwd_bwd(const float* d2, int64_t ldd, const float* c, int64_t 
                           float* dc, int64_t lddc, float* dw3_out, float* db2_out, float* db3_out, float* loss_out, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* The evaluation forward of Deep&Cross behind the hidden layers in ONE launch: the cross stack on x0 [B, X] (contiguous; cw, cb
+ * [L, X] as mrec_cross_layers_f32 takes them, the same device code for a row's stack, so x_L has that entry's bits), logit =
+ * [d2 | x_L] . w3 + b3 with x_L held in registers (never written), prob = sigmoid(logit).  d2 [B, H] fp32 with row stride ldd.
+ *   label (nullable) [B] and loss (one float): both or neither.  With a label every workgroup leaves one partial loss sum in ws
+ *   and a second one-wave launch adds them in a fixed order and multiplies by 1 / B: no float atomics, the same bits on every
+ *   run.  Without a label: one launch, ws is not used and may be NULL.  ws: mrec_dcn_predict_workspace_bytes(B).
+ * The logit's order of additions is fixed and documented at the kernel (csrc/mrec_cross.hip); it is not mrec_dcn_head_fwd_bwd's
+ * logit_out bit for bit (other lane layouts), the two agree to rounding.
+ * Shapes: every X and L of mrec_cross_layers_f32 (X <= 2048); H % 4 == 0, H <= 1024, ldd % 4 == 0, d2 and w3 16-byte aligned.
+ * Decided before any launch, in this order: MREC_EINVAL (B, L < 0; H, X <= 0; ldd < H), B == 0: MREC_OK with nothing touched,
+ * MREC_EINVAL (a null x0 / d2 / w3 / b3 / logit / prob, null cw / cb with L > 0, label and loss not both null or both set),
+ * MREC_EUNSUPPORTED (the shapes and alignments above), MREC_EWORKSPACE (with a label only). */
+int mrec_dcn_predict_workspace_bytes(int64_t B, size_t* out);
+int mrec_dcn_predict(const float* x0, const float* cw, const float* cb, int32_t L, const float* d2, int64_t ldd, const float* w3,
+                     const float* b3, const float* label, int64_t B, int32_t H, int32_t X, float* logit, float* prob, float* loss,
+                     void* ws, size_t ws_bytes, void* stream);
+
 /* ---- row-shard routing (hybrid-parallel embedding, README.md:140-144) --------
  * owner(id) = id mod n_shards, local row = id div n_shards.  Stable bucketing of ids by owner so
  * one RCCL all-to-all can ship them: send_local[k] = local row of the k-th id in bucket order,

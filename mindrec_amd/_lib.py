@@ -196,6 +196,8 @@ _SIGS = {
     "mrec_dcn_head_workspace_bytes": [_i64, _i32, _i32, _szp],
     "mrec_dcn_head_fwd_bwd": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
                               _vp, _sz, _vp],
+    "mrec_dcn_predict_workspace_bytes": [_i64, _szp],
+    "mrec_dcn_predict": [_vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp],
     "mrec_dense32_fwd": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _int, _vp, _i64, _vp],
     "mrec_dense32_bwd_input": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp],
     "mrec_dense32_bwd_weight": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp],

@@ -177,6 +177,79 @@ __device__ __forceinline__ f4 wload4(const float* __restrict__ g, const float* s
 constexpr int FWD_NT = 1024;   // 16 waves: one block per CU, w / b staged once per CU
 constexpr int BWD_NT = 512;   // 8 waves: one block per CU at two waves per SIMD -> one slab per CU for the reduction kernel
 
+// The row side of the forward, one column per lane (columns lane + 64 j): a wave's pair of rows A, B (row B absent: a resource
+// of 0 bytes, all zeros) from x0 into registers, and the L layers on them -- x_l stays in lA / lB, x0 in xA / xB.  Called by the
+// stack's own kernel (k_cross_fwd, which then stores x_L) and by the evaluation kernel (k_dcn_predict, which takes x_L's dot with
+// W3[H:] instead): the same device code, so the same bits of x_L.
+template <int NPL>
+__device__ __forceinline__ void cross_rows_load(__amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB, int voff, float (&xA)[NPL],
+                                                float (&lA)[NPL], float (&xB)[NPL], float (&lB)[NPL]) {
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+        xA[j] = row_load(rA, voff, 256 * j);
+        xB[j] = row_load(rB, voff, 256 * j);
+        lA[j] = xA[j];
+        lB[j] = xB[j];
+    }
+}
+template <int NPL, bool WLDS>
+__device__ __forceinline__ void cross_rows_stack(const float* __restrict__ w, const float* __restrict__ b, const float* sw,
+                                                 const float* sb, int L, int lane, int D, const float (&xA)[NPL], float (&lA)[NPL],
+                                                 const float (&xB)[NPL], float (&lB)[NPL]) {
+    constexpr int DP = NPL * 64;
+    for (int l = 0; l < L; ++l) {
+        float pA = 0.0f, pB = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const float wv = wload<WLDS>(w, sw, l, lane, j, D, DP);
+            pA += lA[j] * wv;
+            pB += lB[j] * wv;
+        }
+        const float sA = wave_sum(pA), sB = wave_sum(pB);
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const float bv = wload<WLDS>(b, sb, l, lane, j, D, DP);
+            lA[j] = (xA[j] * sA + bv) + lA[j];
+            lB[j] = (xB[j] * sB + bv) + lB[j];
+        }
+    }
+}
+
+// The same, four columns per lane (columns 256 q + 4 lane + {0..3})
+template <int NQ>
+__device__ __forceinline__ void cross_rows_load4(__amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB, int voff, f4 (&xA)[NQ],
+                                                 f4 (&lA)[NQ], f4 (&xB)[NQ], f4 (&lB)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        xA[q] = act_load4(rA, voff, 1024 * q);
+        xB[q] = act_load4(rB, voff, 1024 * q);
+        lA[q] = xA[q];
+        lB[q] = xB[q];
+    }
+}
+template <int NQ, bool WLDS>
+__device__ __forceinline__ void cross_rows_stack4(const float* __restrict__ w, const float* __restrict__ b, const float* sw,
+                                                  const float* sb, int L, int lane, int D, const f4 (&xA)[NQ], f4 (&lA)[NQ],
+                                                  const f4 (&xB)[NQ], f4 (&lB)[NQ]) {
+    constexpr int DP = NQ * 256;
+    for (int l = 0; l < L; ++l) {
+        f4 pA = bc4(0.0f), pB = bc4(0.0f);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const f4 wv = wload4<WLDS>(w, sw, l, lane, q, D, DP);
+            pA += lA[q] * wv;
+            pB += lB[q] * wv;
+        }
+        const f4 sA = bc4(wave_sum_dpp(hsum4(pA))), sB = bc4(wave_sum_dpp(hsum4(pB)));
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const f4 bv = wload4<WLDS>(b, sb, l, lane, q, D, DP);
+            lA[q] = (xA[q] * sA + bv) + lA[q];
+            lB[q] = (xB[q] * sB + bv) + lB[q];
+        }
+    }
+}
+
 template <int NPL, bool WLDS>
 __global__ __launch_bounds__(FWD_NT) void k_cross_fwd(const float* __restrict__ x0, const float* __restrict__ w,
                                                       const float* __restrict__ b, int L, int64_t B, int D,
@@ -197,29 +270,8 @@ __global__ __launch_bounds__(FWD_NT) void k_cross_fwd(const float* __restrict__ 
         float xA[NPL], lA[NPL], xB[NPL], lB[NPL];
         const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
         const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
-#pragma unroll
-        for (int j = 0; j < NPL; ++j) {
-            xA[j] = row_load(rA, voff, 256 * j);
-            xB[j] = row_load(rB, voff, 256 * j);
-            lA[j] = xA[j];
-            lB[j] = xB[j];
-        }
-        for (int l = 0; l < L; ++l) {
-            float pA = 0.0f, pB = 0.0f;
-#pragma unroll
-            for (int j = 0; j < NPL; ++j) {
-                const float wv = wload<WLDS>(w, sw, l, lane, j, D, DP);
-                pA += lA[j] * wv;
-                pB += lB[j] * wv;
-            }
-            const float sA = wave_sum(pA), sB = wave_sum(pB);
-#pragma unroll
-            for (int j = 0; j < NPL; ++j) {
-                const float bv = wload<WLDS>(b, sb, l, lane, j, D, DP);
-                lA[j] = (xA[j] * sA + bv) + lA[j];
-                lB[j] = (xB[j] * sB + bv) + lB[j];
-            }
-        }
+        cross_rows_load<NPL>(rA, rB, voff, xA, lA, xB, lB);
+        cross_rows_stack<NPL, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
         const __amdgpu_buffer_rsrc_t oA = row_rsrc(out + rowA * D, D * 4);
         const __amdgpu_buffer_rsrc_t oB = row_rsrc(out + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
 #pragma unroll
@@ -252,29 +304,8 @@ __global__ __launch_bounds__(FWD_NT) void k_cross_fwd4(const float* __restrict__
         f4 xA[NQ], lA[NQ], xB[NQ], lB[NQ];
         const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
         const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            xA[q] = act_load4(rA, voff, 1024 * q);
-            xB[q] = act_load4(rB, voff, 1024 * q);
-            lA[q] = xA[q];
-            lB[q] = xB[q];
-        }
-        for (int l = 0; l < L; ++l) {
-            f4 pA = bc4(0.0f), pB = bc4(0.0f);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const f4 wv = wload4<WLDS>(w, sw, l, lane, q, D, DP);
-                pA += lA[q] * wv;
-                pB += lB[q] * wv;
-            }
-            const f4 sA = bc4(wave_sum_dpp(hsum4(pA))), sB = bc4(wave_sum_dpp(hsum4(pB)));
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const f4 bv = wload4<WLDS>(b, sb, l, lane, q, D, DP);
-                lA[q] = (xA[q] * sA + bv) + lA[q];
-                lB[q] = (xB[q] * sB + bv) + lB[q];
-            }
-        }
+        cross_rows_load4<NQ>(rA, rB, voff, xA, lA, xB, lB);
+        cross_rows_stack4<NQ, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
         const __amdgpu_buffer_rsrc_t oA = row_rsrc(out + rowA * D, D * 4);
         const __amdgpu_buffer_rsrc_t oB = row_rsrc(out + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
 #pragma unroll
@@ -283,6 +314,222 @@ __global__ __launch_bounds__(FWD_NT) void k_cross_fwd4(const float* __restrict__
             act_store4(oB, voff, 1024 * q, lB[q]);
         }
     }
+}
+
+// ---- evaluation: the cross stack and the output end of Deep&Cross in ONE launch (deep_and_cross.py:300-309 + the loss :326-331) ----
+//     logit = [d2 | x_L] . W3 + b3,  prob = sigmoid(logit),  with a label: the row's SigmoidCrossEntropyWithLogits term
+// The wave that holds x_L of a row in registers (cross_rows_stack / cross_rows_stack4 above: the stack's own device code) takes its
+// dot with W3[H:] at once, so x_L -- the [B, X] tensor mrec_cross_layers_f32 writes and the output layer reads back -- never
+// exists in memory.  d2 [B, H] (H % 4 == 0, H <= 1024) is read as up to four 16-byte slots a lane, before the stack runs.
+//
+// W3 is staged as the file stages w and b: W3[:H] always in LDS, padded with zeros to 1024 columns; W3[H:] in LDS padded to whole
+// 256-column blocks (WLDS) or through a range-checked buffer resource (!WLDS); the rows of d2 through a buffer resource of H * 4
+// bytes.  No loop carries a column guard: a slot past H or X holds +0 in both operands.
+//
+// THE ORDER OF ADDITIONS OF THE LOGIT (fixed; restated in tests/_dcn_predict_cases.py, which the device must match bit for bit;
+// no fused multiply-add anywhere: -ffp-contract=off):
+//   deep half, lane l, slots q = 0 .. 3 of columns 256 q + 4 l + {0, 1, 2, 3} =: (x, y, z, w):
+//       dd = +0;  dd += (d.x W.x + d.y W.y) + (d.z W.z + d.w W.w)                     for q = 0, 1, 2, 3
+//   cross half, one column per lane (X <= 128; lane l owns columns l + 64 j):
+//       pc = +0;  pc += c_j W_j                                                       for j = 0 .. NPL - 1
+//   cross half, four columns per lane (X > 128; lane l owns columns 256 q + 4 l + {0, 1, 2, 3}):
+//       p = (+0, +0, +0, +0);  p += c_q * W_q componentwise                           for q = 0 .. NQ - 1
+//       pc = (p.x + p.y) + (p.z + p.w)
+//   the wave, each half by itself: wave_sum_dpp: lanes pairwise (t_0 + t_1), (t_2 + t_3), ..; those sums pairwise; .. six levels,
+//                    a balanced tree over the lanes in lane order (every step adds two values that differ only in which is named
+//                    first).  The deep half's tree is taken BEFORE the stack runs and waits in a scalar register.
+//   logit = (tree(pc) + tree(dd)) + b3                                                (cross half + deep half, then the bias)
+// The longest path from a product to the logit is the cross half's at four columns a lane: the product, NQ <= 8 additions into p,
+// 2 in pc, 6 in the tree, the deep half, the bias: 19 roundings (deep half: 1 + 2 + 4 + 6 + 2 = 15).
+// NOT k_dcn_head's logit_out bit for bit: that kernel's lanes own float2 slots of the cross half and float4 slots q 64 + l of
+// the deep half and add them in another order (mrec_dcn.hip); the two logits agree to the rounding bounds of their orders.
+//
+// prob: k_dcn_head's branch-stable sigmoid, z >= 0 ? 1 / (1 + e) : e / (1 + e) with e = expf(-|z|); the row's loss term is
+// max(z, 0) - z y + log1pf(e).  The loss: a wave adds its rows' terms in row order (A then B of each pair), the block its 16 waves'
+// sums in wave order through LDS, k_dcn_predict_finish the blocks' partials (lane l: partials l, l + 64, l + 128, l + 192 in that
+// order, then the tree above), times the rounded 1 / B.  No atomics: the same bits on every run.
+constexpr int PRED_HQ = 4;                       // 16-byte slots a lane of the deep half: H <= 64 * 4 * PRED_HQ = 1024
+constexpr int PRED_HP = 64 * 4 * PRED_HQ;        // W3[:H] in LDS, padded
+constexpr int pred_xblocks(int npl) { return (npl * 64 + 255) / 256; }      // 256-column blocks of W3[H:] in LDS
+
+// W3 into LDS: wave q < XB requests block q of W3[H:] (WLDS only), wave 8 + q block q of W3[:H], as one 16-byte buffer load a
+// lane (the range check pads with zeros); requested BEFORE w / b are staged, stored behind them -- one memory round trip for all
+template <int XB, bool WLDS>
+__device__ __forceinline__ f4 pred_w3_request(const float* __restrict__ w3, int H, int X, int lane, int wave) {
+    static_assert(XB <= 8 && 8 + PRED_HQ <= FWD_NT / 64, "one piece a wave");
+    const bool deep = wave >= 8 && wave < 8 + PRED_HQ, cross = WLDS && wave < XB;        // (wave-uniform)
+    const int q = deep ? wave - 8 : (cross ? wave : 0);
+    return row_load4(row_rsrc(w3 + (deep ? 0 : H), deep ? H * 4 : (cross ? X * 4 : 0)), lane * 16, 1024 * q);
+}
+template <int XB, bool WLDS>
+__device__ __forceinline__ void pred_w3_commit(f4 piece, float* s3c, float* s3d, int lane, int wave) {
+    if (wave >= 8 && wave < 8 + PRED_HQ) *(f4*)(s3d + 256 * (wave - 8) + 4 * lane) = piece;
+    else if (WLDS && wave < XB) *(f4*)(s3c + 256 * wave + 4 * lane) = piece;
+    __syncthreads();
+}
+
+// a row's deep slots: requested with the row of x0, consumed (pred_deep_dot) before the stack runs, so that they are live
+// together with x0 but not with x_l
+__device__ __forceinline__ void pred_deep_load(__amdgpu_buffer_rsrc_t r, int lane, f4 (&d)[PRED_HQ]) {
+#pragma unroll
+    for (int q = 0; q < PRED_HQ; ++q) d[q] = act_load4(r, lane * 16, 1024 * q);
+}
+__device__ __forceinline__ float pred_deep_dot(const f4 (&d)[PRED_HQ], const float* s3d, int lane) {
+    float dd = 0.0f;
+#pragma unroll
+    for (int q = 0; q < PRED_HQ; ++q) {
+        const f4 wv = *(const f4*)(s3d + 256 * q + 4 * lane);
+        dd += (d[q].x * wv.x + d[q].y * wv.y) + (d[q].z * wv.z + d[q].w * wv.w);
+    }
+    return dd;
+}
+
+// a value every lane holds alike, moved to a scalar register (the wave's loss sum: no vector register across the stack)
+__device__ __forceinline__ float wave_uniform(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// behind the wave's sum: bias, outputs, the row's loss term (every lane computes it; lane 0 stores)
+__device__ __forceinline__ float pred_row_out(float tree, float bias, const float* __restrict__ label, int64_t row, int lane,
+                                              float* __restrict__ logit, float* __restrict__ prob) {
+    const float z = tree + bias;
+    const float e = expf(-fabsf(z));
+    const float sig = z >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+    if (lane == 0) {
+        logit[row] = z;
+        prob[row] = sig;
+    }
+    if (!label) return 0.0f;                  // (uniform: a kernel argument)
+    const float y = label[row];
+    return fmaxf(z, 0.0f) - z * y + log1pf(e);
+}
+
+// the block's 16 wave sums in wave order -> partial[blockIdx.x]
+__device__ __forceinline__ void pred_block_loss(float lsum, float* __restrict__ partial) {
+    __shared__ float s_loss[FWD_NT / 64];
+    if ((threadIdx.x & 63) == 0) s_loss[threadIdx.x >> 6] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = s_loss[0];
+#pragma unroll
+        for (int i = 1; i < FWD_NT / 64; ++i) s += s_loss[i];
+        partial[blockIdx.x] = s;
+    }
+}
+
+template <int NPL, bool WLDS>
+__global__ __launch_bounds__(FWD_NT) void k_dcn_predict(const float* __restrict__ x0, const float* __restrict__ w,
+                                                        const float* __restrict__ b, int L, int64_t B, int D,
+                                                        const float* __restrict__ d2, int64_t ldd, int H,
+                                                        const float* __restrict__ w3, const float* __restrict__ b3,
+                                                        const float* __restrict__ label, float* __restrict__ logit,
+                                                        float* __restrict__ prob, float* __restrict__ partial) {
+    constexpr int DP = NPL * 64, XB = pred_xblocks(NPL);
+    extern __shared__ float smem[];
+    float* sw = smem;
+    float* sb = smem + (WLDS ? L * DP : 0);
+    float* s3c = smem + (WLDS ? 2 * L * DP : 0);
+    float* s3d = s3c + (WLDS ? XB * 256 : 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const f4 piece = pred_w3_request<XB, WLDS>(w3, H, D, lane, wave);
+    if (WLDS) stage_wb<FWD_NT, DP>(w, b, L, D, sw, sb);
+    pred_w3_commit<XB, WLDS>(piece, s3c, s3d, lane, wave);
+    const float bias = b3[0];
+    const int voff = lane * 4;
+    constexpr int WPB = FWD_NT / 64;
+    const int64_t nw = (int64_t)gridDim.x * WPB;
+    float lsum = 0.0f;
+    for (int64_t rowA = (int64_t)blockIdx.x * WPB + wave; rowA < B; rowA += 2 * nw) {
+        const int64_t rowB = rowA + nw;
+        const bool vB = rowB < B;
+        float xA[NPL], lA[NPL], xB[NPL], lB[NPL];
+        f4 dA[PRED_HQ], dB[PRED_HQ];
+        const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
+        const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
+        cross_rows_load<NPL>(rA, rB, voff, xA, lA, xB, lB);
+        pred_deep_load(row_rsrc(d2 + rowA * ldd, H * 4), lane, dA);
+        pred_deep_load(row_rsrc(d2 + (vB ? rowB : rowA) * ldd, vB ? H * 4 : 0), lane, dB);
+        const float deepA = wave_sum_dpp(pred_deep_dot(dA, s3d, lane)), deepB = wave_sum_dpp(pred_deep_dot(dB, s3d, lane));
+        __builtin_amdgcn_sched_barrier(0);       // the deep slots die here, in front of x_l
+        cross_rows_stack<NPL, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
+        float pA = 0.0f, pB = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const float wv = wload<WLDS>(w3 + H, s3c, 0, lane, j, D, DP);
+            pA += lA[j] * wv;
+            pB += lB[j] * wv;
+        }
+        const float tA = wave_sum_dpp(pA) + deepA, tB = wave_sum_dpp(pB) + deepB;
+        lsum += pred_row_out(tA, bias, label, rowA, lane, logit, prob);
+        if (vB) lsum += pred_row_out(tB, bias, label, rowB, lane, logit, prob);
+        lsum = wave_uniform(lsum);
+    }
+    if (label) pred_block_loss(lsum, partial);
+}
+
+template <int NPL, bool WLDS>
+__global__ __launch_bounds__(FWD_NT) void k_dcn_predict4(const float* __restrict__ x0, const float* __restrict__ w,
+                                                         const float* __restrict__ b, int L, int64_t B, int D,
+                                                         const float* __restrict__ d2, int64_t ldd, int H,
+                                                         const float* __restrict__ w3, const float* __restrict__ b3,
+                                                         const float* __restrict__ label, float* __restrict__ logit,
+                                                         float* __restrict__ prob, float* __restrict__ partial) {
+    static_assert(NPL % 4 == 0, "256-column blocks");
+    constexpr int DP = NPL * 64, NQ = NPL / 4;
+    extern __shared__ float smem[];
+    float* sw = smem;
+    float* sb = smem + (WLDS ? L * DP : 0);
+    float* s3c = smem + (WLDS ? 2 * L * DP : 0);
+    float* s3d = s3c + (WLDS ? DP : 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const f4 piece = pred_w3_request<NQ, WLDS>(w3, H, D, lane, wave);
+    if (WLDS) stage_rows4<FWD_NT, NPL, true>(w, b, L, D, sw, sb);
+    pred_w3_commit<NQ, WLDS>(piece, s3c, s3d, lane, wave);
+    const float bias = b3[0];
+    const int voff = lane * 16;
+    constexpr int WPB = FWD_NT / 64;
+    const int64_t nw = (int64_t)gridDim.x * WPB;
+    float lsum = 0.0f;
+    for (int64_t rowA = (int64_t)blockIdx.x * WPB + wave; rowA < B; rowA += 2 * nw) {
+        const int64_t rowB = rowA + nw;
+        const bool vB = rowB < B;
+        f4 xA[NQ], lA[NQ], xB[NQ], lB[NQ];
+        f4 dA[PRED_HQ], dB[PRED_HQ];
+        const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
+        const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
+        cross_rows_load4<NQ>(rA, rB, voff, xA, lA, xB, lB);
+        pred_deep_load(row_rsrc(d2 + rowA * ldd, H * 4), lane, dA);
+        pred_deep_load(row_rsrc(d2 + (vB ? rowB : rowA) * ldd, vB ? H * 4 : 0), lane, dB);
+        const float deepA = wave_sum_dpp(pred_deep_dot(dA, s3d, lane)), deepB = wave_sum_dpp(pred_deep_dot(dB, s3d, lane));
+        __builtin_amdgcn_sched_barrier(0);       // the deep slots die here, in front of x_l
+        cross_rows_stack4<NQ, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
+        f4 pA = bc4(0.0f), pB = bc4(0.0f);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const f4 wv = wload4<WLDS>(w3 + H, s3c, 0, lane, q, D, DP);
+            pA += lA[q] * wv;
+            pB += lB[q] * wv;
+        }
+        const float tA = wave_sum_dpp(hsum4(pA)) + deepA, tB = wave_sum_dpp(hsum4(pB)) + deepB;
+        lsum += pred_row_out(tA, bias, label, rowA, lane, logit, prob);
+        if (vB) lsum += pred_row_out(tB, bias, label, rowB, lane, logit, prob);
+        lsum = wave_uniform(lsum);
+    }
+    if (label) pred_block_loss(lsum, partial);
+}
+
+// loss = (the blocks' partials: lane l adds partials l, l + 64, l + 128, l + 192 in that order, the lanes the tree) / B: one wave
+__global__ __launch_bounds__(64) void k_dcn_predict_finish(const float* __restrict__ partial, int nblk, float inv_B,
+                                                           float* __restrict__ loss) {
+    const int lane = threadIdx.x;
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = lane + 64 * k;
+        s += i < nblk ? partial[i] : 0.0f;
+    }
+    s = wave_sum_dpp(s);
+    if (lane == 0) *loss = s * inv_B;
 }
 
 // slab layout per block: [LMAX][D] sums of u_l*x0, then [D] colsum(dy), then [LMAX] sums of t_l.
@@ -685,6 +932,57 @@ MREC_API int mrec_cross_layers_f32(const float* x0, const float* w, const float*
     int rc = MREC_OK;
     MREC_NPL_DISPATCH(npl, (rc = launch_fwd<N_>(x0, w, b, L, B, D, out, st)));
     if (rc != MREC_OK) return rc;
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+namespace {
+// mrec_cross_layers_f32's grid and path choice (launch_fwd), with W3 in the LDS budget: W3[H:] beside w and b, W3[:H] always
+template <int NPL>
+int launch_predict(const float* x0, const float* w, const float* b, int L, int64_t B, int D, const float* d2, int64_t ldd, int H,
+                   const float* w3, const float* b3, const float* label, float* logit, float* prob, float* partial, hipStream_t st) {
+    constexpr bool four = NPL % 4 == 0;
+    const size_t deep = (size_t)PRED_HP * sizeof(float);
+    const size_t lds = ((size_t)2 * L * NPL * 64 + (four ? NPL * 64 : pred_xblocks(NPL) * 256)) * sizeof(float) + deep;
+    int64_t blocks = mrec_cdiv(B, 2 * (FWD_NT / 64));            // 16 waves x 2 rows per pass
+    if (blocks > 256) blocks = 256;
+    // (four columns a lane: stage_rows4 holds its pieces in a register array sized for LMAX layers)
+    const bool wlds = lds <= kMaxLds && (!four || L <= LMAX);
+    auto go = [&](auto kern, size_t bytes) {
+        int rc = set_lds(kern, bytes);
+        if (rc != MREC_OK) return rc;
+        kern<<<(unsigned)blocks, FWD_NT, bytes, st>>>(x0, w, b, L, B, D, d2, ldd, H, w3, b3, label, logit, prob, partial);
+        return (int)MREC_OK;
+    };
+    if constexpr (four) return wlds ? go(k_dcn_predict4<NPL, true>, lds) : go(k_dcn_predict4<NPL, false>, deep);
+    else return wlds ? go(k_dcn_predict<NPL, true>, lds) : go(k_dcn_predict<NPL, false>, deep);
+}
+}  // namespace
+
+/* The evaluation forward of Deep&Cross behind the hidden layers in one launch (k_dcn_predict / k_dcn_predict4; see include/mrec.h). */
+MREC_API int mrec_dcn_predict_workspace_bytes(int64_t B, size_t* out) {
+    if (!out || B < 0) return MREC_EINVAL;
+    *out = (size_t)256 * sizeof(float) + 256;          // one loss partial a workgroup, at most 256 of them
+    return MREC_OK;
+}
+
+MREC_API int mrec_dcn_predict(const float* x0, const float* cw, const float* cb, int32_t L, const float* d2, int64_t ldd,
+                              const float* w3, const float* b3, const float* label, int64_t B, int32_t H, int32_t X, float* logit,
+                              float* prob, float* loss, void* ws, size_t ws_bytes, void* stream) {
+    if (B < 0 || H <= 0 || X <= 0 || L < 0 || ldd < H) return MREC_EINVAL;
+    if (B == 0) return MREC_OK;
+    if (!x0 || !d2 || !w3 || !b3 || !logit || !prob || (L > 0 && (!cw || !cb)) || (label == nullptr) != (loss == nullptr)) return MREC_EINVAL;
+    const int npl = npl_bucket(X);
+    if (npl < 0 || H % 4 || H > PRED_HP || ldd % 4 || ((((uintptr_t)d2) | ((uintptr_t)w3)) & 15)) return MREC_EUNSUPPORTED;
+    if (label && (!ws || ws_bytes < (size_t)256 * sizeof(float))) return MREC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = MREC_OK;
+    MREC_NPL_DISPATCH(npl, (rc = launch_predict<N_>(x0, cw, cb, L, B, X, d2, ldd, H, w3, b3, label, logit, prob, (float*)ws, st)));
+    if (rc != MREC_OK) return rc;
+    if (label) {
+        const int nblk = (int)(mrec_cdiv(B, 2 * (FWD_NT / 64)) > 256 ? 256 : mrec_cdiv(B, 2 * (FWD_NT / 64)));
+        k_dcn_predict_finish<<<1, 64, 0, st>>>((const float*)ws, nblk, 1.0f / (float)B, loss);
+    }
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }

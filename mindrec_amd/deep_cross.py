@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .wide_deep_mlp import _flat_views
+from .wide_deep_mlp import PredictGraphs, _flat_views
 
 
 @dataclass
@@ -54,7 +54,7 @@ class DeepCrossConfig:
                                   # emb_dim = 30 cannot clip
 
 
-class DeepCrossEngine:
+class DeepCrossEngine(PredictGraphs):
     _kernels = ops               # the op set (tests/ subclass the engine with the oracle's restatements to check it step for step)
     _allow_cpu = False           # the product has no CPU path
 
@@ -104,6 +104,9 @@ class DeepCrossEngine:
         self._state_step = -1
         self._bufs = {}               # batch size -> the step's persistent intermediates (graph replays write the same buffers)
         self._side = torch.cuda.Stream(self.device) if self._native else None      # the step's Unique + inverted index, under the GEMMs
+        self._predict_graphs = {}     # (ids shape, ids dtype, label given?) -> calls seen + the captured evaluation forward (predict_fused)
+        self._predict_capture = True  # cleared when a capture of the evaluation forward is refused
+        self._eval_bufs = {}          # batch size -> predict_fused's intermediates where no training step has run at that batch size
 
     def forward(self, emb):
         """DeepCrossModel.construct behind the lookup (deep_and_cross.py:299-309), inference: logit [B, 1]."""
@@ -142,6 +145,78 @@ class DeepCrossEngine:
         with torch.no_grad():
             logit = self.forward(emb)
         return logit, torch.sigmoid(logit)
+
+    # ---- the evaluation forward on the step's kernels ------------------------------------------------------------------
+    def _fused_refusal(self):
+        """Why predict_fused cannot run here (None: it can)"""
+        cfg = self.cfg
+        if not self._native:
+            return (f"deep_layer_dim {cfg.deep_layer_dim}, input width {cfg.field_size * cfg.emb_dim}, table {cfg.vocab_size} x {cfg.emb_dim} "
+                    f"on {self.device} (no hand-written Deep&Cross path)")
+        if not ops.dcn_predict_supported(cfg.deep_layer_dim[1], cfg.field_size * cfg.emb_dim, cfg.cross_layer_num):
+            return f"deep_layer_dim {cfg.deep_layer_dim} and input width {cfg.field_size * cfg.emb_dim} (no one-launch output end)"
+        return None
+
+    @property
+    def fused_predict_supported(self):
+        """predict_fused runs here: the hand-written path (a GPU, the product's op set, an output end mrec_dcn serves) and shapes
+        ops.dcn_predict takes."""
+        return self._fused_refusal() is None
+
+    def _predict_chain(self, ids, wts, label):
+        """lookup -> the two hidden layers exactly as _step_native's forward runs them at this batch size -> ops.dcn_predict (cross
+        stack, output layer over [d2 | x_L], sigmoid, loss: one launch; x_L never reaches memory).  No torch arithmetic in between."""
+        cfg, k = self.cfg, self.k
+        B, Fd = ids.shape
+        X = Fd * cfg.emb_dim
+        h1, h2 = cfg.deep_layer_dim
+        W1, b1, W2, b2, W3, b3, cw, cb = [p.detach() for p in self.dense]
+        # the step's own buffers where a step has run at this batch size (both write d1 / d2 and the parts before they read them)
+        bf = self._bufs.get(B)
+        if bf is None:
+            bf = self._eval_bufs.get(B)
+            if bf is None:
+                f32 = dict(dtype=torch.float32, device=self.device)
+                bf = self._eval_bufs[B] = {"d1": torch.empty((B, h1), **f32), "d2": torch.empty((B, h2), **f32)}
+        emb = k.gather_rows(self.table, ids, wts, **self._clip_kw()).view(B, X)
+        if self._x3(B):
+            P = bf.get("x3") or bf.get("x3_eval")
+            if P is None:
+                P = bf["x3_eval"] = {"emb": k.x3_parts(B, X, self.device), "W1": k.x3_parts(X, h1, self.device),
+                                     "W2": k.x3_parts(h1, h2, self.device), "d1": k.x3_parts(B, h1, self.device)}
+            k.x3_split(emb, out=P["emb"])
+            k.x3_split(W1, out=P["W1"])
+            k.x3_split(W2, out=P["W2"])
+            k.x3_fwd(P["emb"], P["W1"], B, X, h1, bf["d1"], bias=b1, relu=True, parts_out=P["d1"])
+            d2 = k.x3_fwd(P["d1"], P["W2"], B, h1, h2, bf["d2"], bias=b2, relu=True)
+        else:
+            d1 = k.dense32_fwd(emb, W1, b1, relu=True, out=bf["d1"])
+            d2 = k.dense32_fwd(d1, W2, b2, relu=True, out=bf["d2"])
+        out = bf.setdefault("predict", {}).setdefault(label is not None, {})
+        return k.dcn_predict(emb, cw, cb, d2, W3.view(-1), b3, None if label is None else label.view(-1), out=out)
+
+    def predict_fused(self, ids, wts, label=None):
+        """predict() on the training step's kernels end to end: the lookup, the two hidden layers on the GEMMs the step runs at this
+        batch size (the three-part bf16 ones with fp32_matmul="x3"), and ONE launch for the cross stack, the output layer over
+        [deep | cross], the sigmoid and the loss (ops.dcn_predict).  Returns (logit [B, 1], prob [B, 1]) as predict does and, with
+        `label`, the batch's mean sigmoid cross-entropy (0-d) as a third value.  Evaluation only: no parameter, optimizer or step
+        state is read for writing, and the captured training step is left alone.
+        With cfg.graphs != "none" the chain replays as one captured graph from the third call at a given (ids shape, ids dtype,
+        label given?): THE RETURNED TENSORS ARE STATIC BUFFERS WHICH THE NEXT CALL OVERWRITES -- copy what must outlive it.
+        Raises ValueError where fused_predict_supported is False."""
+        why = self._fused_refusal()
+        if why is not None:
+            raise ValueError(f"predict_fused is not supported with {why}: use predict")
+        return self._predict_run(self._predict_chain, ids, wts, label, capture=self.cfg.graphs != "none")
+
+    def release_graphs(self):
+        """Drops every captured HIP graph -- the training step and the evaluation forwards (they are re-captured on demand)."""
+        if self._gpu:
+            torch.cuda.synchronize(self.device)
+        self._graph = None
+        self._predict_graphs = {}
+        if self._gpu:
+            torch.cuda.synchronize(self.device)
 
     # ---- the hand-written step ------------------------------------------------------------------------------------------
     def _x3(self, B):
@@ -246,8 +321,9 @@ class DeepCrossEngine:
         return loss.view(())
 
     def close(self):
-        """Drops the captured step (nothing of it outlives the engine; symmetrical with WideDeepEngine.close)."""
-        self._graph = None
+        """Drops the captured step and the evaluation graphs (nothing of them outlives the engine; symmetrical with
+        WideDeepEngine.close)."""
+        self.release_graphs()
 
     def _train_step_native(self, ids, wts, label):
         if self._state is None:

@@ -2152,6 +2152,54 @@ def dcn_head_fwd_bwd(d2, c, w3, b3, label, dscale, dw3_out, db2_out, db3_out, ou
     return loss, logit, dd2, dc
 
 
+def dcn_predict_supported(H, X, L):
+    """Shapes of the one-launch evaluation forward (csrc/mrec_cross.hip: k_dcn_predict / k_dcn_predict4): every cross width and depth
+    cross_layers takes, a last hidden width that is a multiple of 4 up to 1024."""
+    return H > 0 and H % 4 == 0 and H <= 1024 and 0 < X <= 2048 and L >= 0
+
+
+def dcn_predict(x0, cw, cb, d2, w3, b3, label=None, out=None):
+    """The evaluation forward of Deep&Cross behind the hidden layers in one launch: the cross stack on x0 [B, X] (cw, cb [L, X]; the
+    device code of cross_layers, whose output never reaches memory here), the output layer over [d2 | x_L] without the concat (d2
+    [B, H] with a row stride, w3 [H + X], b3 [1]), the sigmoid and, with `label` [B], the mean sigmoid cross-entropy (one more small
+    launch; fixed order, the same bits on every run).  Returns (logit [B], prob [B]), with a label (logit, prob, loss [1]).
+    out: dict of persistent output tensors with those names (filled on first use), so that a captured graph replays into fixed
+    addresses."""
+    _need_cuda(x0, cw, cb, d2, w3, b3, label)
+    B, X, ldx = _mat32(x0, "x0")
+    B2, H, ldd = _mat32(d2, "d2")
+    L = cw.shape[0]
+    if not x0.is_contiguous() or B2 != B:
+        raise TypeError("dcn_predict: x0 contiguous [B, X], d2 [B, H]")
+    for t_ in (cw, cb):
+        if t_.dtype != torch.float32 or tuple(t_.shape) != (L, X) or not t_.is_contiguous():
+            raise TypeError("dcn_predict: cw, cb must be contiguous float32 [L, X] tensors")
+    if w3.dtype != torch.float32 or w3.numel() != H + X or not w3.is_contiguous() or b3.dtype != torch.float32 or b3.numel() != 1:
+        raise TypeError("dcn_predict: w3 contiguous float32 [H + X], b3 float32 [1]")
+    if label is not None and (label.dtype != torch.float32 or label.numel() != B):
+        raise TypeError("dcn_predict: label must be a float32 [B] tensor")
+    dev = x0.device
+    o = out if out is not None else {}
+
+    def buf(name, n):
+        t = o.get(name)
+        if t is None:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+            o[name] = t
+        elif t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device != dev:
+            raise TypeError(f"dcn_predict: out[{name!r}] must be a contiguous float32 [{n}] tensor on x0's device")
+        return t
+    logit, prob = buf("logit", B), buf("prob", B)
+    loss, ws, ws_bytes = None, None, 0
+    if label is not None:
+        loss = buf("loss", 1)
+        ws = workspace("dcn_predict", _lib.query_bytes("mrec_dcn_predict_workspace_bytes", B), dev)
+        ws_bytes = ws.numel()
+    _lib.call("mrec_dcn_predict", _ptr(x0), _ptr(cw), _ptr(cb), L, _ptr(d2), ldd, _ptr(w3), _ptr(b3),
+              _ptr(label.contiguous() if label is not None else None), B, H, X, _ptr(logit), _ptr(prob), _ptr(loss), _ptr(ws), ws_bytes, _stream())
+    return (logit, prob) if label is None else (logit, prob, loss)
+
+
 # ---- DeepFM second-order term ------------------------------------------------------------------
 def _fm_vx(who, vx):
     if vx.dtype != torch.float32 or vx.dim() != 3:

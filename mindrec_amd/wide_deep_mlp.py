@@ -31,7 +31,49 @@ class _WideProd:
         self.prod = prod
 
 
-class DenseNetMixin:
+class PredictGraphs:
+    """The evaluation forward of an engine (its predict_fused), eager or replayed from one captured graph.  Needs from its host class:
+    self.k (op set: copy_many_), self.device, self._predict_graphs = {} and self._predict_capture = True."""
+
+    @staticmethod
+    def _predict_out(out, B):
+        return (out[0].view(B, 1), out[1].view(B, 1)) + ((out[2].view(()),) if len(out) == 3 else ())
+
+    def _predict_run(self, chain, ids, wts, label, capture):
+        """chain(ids, wts, label) -> (logit, prob[, loss]), shaped as predict shapes them.  capture: from the third call at a given
+        (ids shape, ids dtype, label given?) the chain replays as one HIP graph captured on static copies of the inputs (one graph,
+        one stream; two eager calls first: every workspace exists by then) -- the returned tensors are then the graph's static
+        outputs.  State: self._predict_graphs (key -> {"calls", "g"}), self._predict_capture (cleared when a capture is refused)."""
+        B = ids.shape[0]
+        if not (capture and self._predict_capture):
+            return self._predict_out(chain(ids, wts, label), B)
+        st = self._predict_graphs.setdefault((tuple(ids.shape), ids.dtype, label is not None), {"calls": 0, "g": None})
+        st["calls"] += 1
+        if st["calls"] <= 2:
+            return self._predict_out(chain(ids, wts, label), B)
+        ins = (ids, wts) if label is None else (ids, wts, label)
+        g = st["g"]
+        if g is None:
+            try:
+                g = {"in": tuple(t.clone().contiguous() for t in ins)}
+                torch.cuda.synchronize(self.device)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    g["out"] = chain(g["in"][0], g["in"][1], g["in"][2] if label is not None else None)
+                g["graph"] = graph
+                st["g"] = g
+            except RuntimeError as e:          # capture refused: stay eager
+                import warnings
+                warnings.warn(f"HIP-graph capture of the evaluation forward failed, running it eagerly: {e}")
+                self._predict_capture = False
+                self._predict_graphs = {}
+                return self._predict_out(chain(ids, wts, label), B)
+        self.k.copy_many_(list(g["in"]), list(ins))       # one launch
+        g["graph"].replay()
+        return self._predict_out(g["out"], B)
+
+
+class DenseNetMixin(PredictGraphs):
     """Needs from its host class: self.k (op set), self.device, self._gpu, self._amp (torch dtype of the 16-bit net, None: fp32),
     self._mfma, self._graph_level, self.rank, self.step_count, self._step_state, self._dropout / self._training / self._emb_dropped,
     self.cfg.dropout_keep_prob / .seed (Dropout only)."""
@@ -288,44 +330,6 @@ class DenseNetMixin:
             hs.append(self.k.dense_fwd(hs[i], self.dense16[2 * i], self.dense[2 * i + 1].detach(), relu=True, drop_next=self._drop(i + 1, B),
                                        wt=self._dense16_t.get(i)))
         return hs
-
-    # ---- the evaluation forward of an engine (its predict_fused), eager or replayed from one captured graph ----------------------------
-    @staticmethod
-    def _predict_out(out, B):
-        return (out[0].view(B, 1), out[1].view(B, 1)) + ((out[2].view(()),) if len(out) == 3 else ())
-
-    def _predict_run(self, chain, ids, wts, label, capture):
-        """chain(ids, wts, label) -> (logit, prob[, loss]), shaped as predict shapes them.  capture: from the third call at a given
-        (ids shape, ids dtype, label given?) the chain replays as one HIP graph captured on static copies of the inputs (one graph,
-        one stream; two eager calls first: every workspace exists by then) -- the returned tensors are then the graph's static
-        outputs.  State: self._predict_graphs (key -> {"calls", "g"}), self._predict_capture (cleared when a capture is refused)."""
-        B = ids.shape[0]
-        if not (capture and self._predict_capture):
-            return self._predict_out(chain(ids, wts, label), B)
-        st = self._predict_graphs.setdefault((tuple(ids.shape), ids.dtype, label is not None), {"calls": 0, "g": None})
-        st["calls"] += 1
-        if st["calls"] <= 2:
-            return self._predict_out(chain(ids, wts, label), B)
-        ins = (ids, wts) if label is None else (ids, wts, label)
-        g = st["g"]
-        if g is None:
-            try:
-                g = {"in": tuple(t.clone().contiguous() for t in ins)}
-                torch.cuda.synchronize(self.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    g["out"] = chain(g["in"][0], g["in"][1], g["in"][2] if label is not None else None)
-                g["graph"] = graph
-                st["g"] = g
-            except RuntimeError as e:          # capture refused: stay eager
-                import warnings
-                warnings.warn(f"HIP-graph capture of the evaluation forward failed, running it eagerly: {e}")
-                self._predict_capture = False
-                self._predict_graphs = {}
-                return self._predict_out(chain(ids, wts, label), B)
-        self.k.copy_many_(list(g["in"]), list(ins))       # one launch
-        g["graph"].replay()
-        return self._predict_out(g["out"], B)
 
     def _head(self, h, wide, label, dh_scale):
         """The output head of this net on h = the last hidden layer's activations: output layer + wide/deep add + sigmoid
