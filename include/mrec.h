@@ -965,7 +965,11 @@ int mrec_scatter_add_rows_f32(float* table, int64_t ld, int32_t D, const int32_t
  *                            (nullable): [ceil(M / 64), K] column sums of dx per 64 rows = partial sums of the layer
  *                            below's bias gradient, to be added up in tile order (mrec_dense_adam_slabs_f32 does)
  *   mrec_dense32_bwd_weight: dw_slabs[s] = x[rows of slab s]^T . dy[rows of slab s], fp32 [S, K, N]: the batch is cut into S
- *                            slabs of ceil(M / S / 32) * 32 rows (mrec_dense32_bwd_weight_slabs proposes an S that fills the chip) */
+ *                            slabs of ceil(M / S / 32) * 32 rows (mrec_dense32_bwd_weight_slabs proposes an S that fills the chip)
+ *   mrec_dense32_load_widths: read-only: floats per staged load (4, 2 or 1) that form 0 (fwd: a = x, b = w), 1 (bwd_input: dy, w)
+ *                            or 2 (bwd_weight: x, dy) picks for its two operands from their addresses (never dereferenced),
+ *                            row strides and K, N: 4 where address, stride and contiguous extent are multiples of 16 bytes,
+ *                            2 where of 8 */
 int mrec_dense32_fwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, int64_t M, int32_t K, int32_t N,
                      int relu, float* y, int64_t ldy, void* stream);
 int mrec_dense32_bwd_input(const float* dy, int64_t lddy, const float* w, int64_t ldw, const float* h, int64_t ldh, int64_t M, int32_t K,
@@ -973,6 +977,8 @@ int mrec_dense32_bwd_input(const float* dy, int64_t lddy, const float* w, int64_
 int mrec_dense32_bwd_weight(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t M, int32_t K, int32_t N, int32_t S,
                             float* dw_slabs, void* stream);
 int mrec_dense32_bwd_weight_slabs(int64_t M, int32_t K, int32_t N, int32_t* out);
+int mrec_dense32_load_widths(int form, const float* a, int64_t lda, const float* b, int64_t ldb, int32_t K, int32_t N,
+                             int32_t* va_out, int32_t* vb_out);
 
 /* The output end of Deep&Cross in one pass (deep_and_cross.py:306-309,326-331): logit = [d2 | c] . w3 + b3 (the concat is never
  * materialised), loss = mean sigmoid cross-entropy, dlogit = (sigmoid(logit) - label) * dscale, and the bprops that hang off it:

@@ -202,6 +202,7 @@ _SIGS = {
     "mrec_dense32_bwd_input": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp],
     "mrec_dense32_bwd_weight": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp],
     "mrec_dense32_bwd_weight_slabs": [_i64, _i32, _i32, C.POINTER(C.c_int32)],
+    "mrec_dense32_load_widths": [_int, _vp, _i64, _vp, _i64, _i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "mrec_fm_fwd_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp],
     "mrec_fm_bwd_f32": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp],
     "mrec_fm_fwd_add_f32": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp],

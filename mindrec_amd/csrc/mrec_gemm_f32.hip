@@ -314,6 +314,13 @@ inline int vec_of(const float* p, int64_t ld, int ext_c) {
     return 1;
 }
 
+// the (VA, VB) a form stages its operands with.  Contiguous extents: form 0 (fwd) x K, w N; form 1 (dgrad) dy N, w N; form 2
+// (wgrad) x K, dy N.  The launching entries and the query mrec_dense32_load_widths both ask here.
+inline void load_widths(int form, const float* a, int64_t lda, const float* b, int64_t ldb, int K, int N, int* va, int* vb) {
+    *va = vec_of(a, lda, form == 1 ? N : K);
+    *vb = vec_of(b, ldb, N);
+}
+
 template <bool AKC, bool BKC, int EPI, int VA, int VB>
 int launch_one(const Args& a, unsigned grid, hipStream_t st) {
     static bool attr_done = false;      // (per instantiation; racing threads set the same value)
@@ -362,7 +369,9 @@ MREC_API int mrec_dense32_fwd(const float* x, int64_t ldx, const float* w, int64
     a.M = (int)M; a.N = N; a.K = K;
     a.k_per_slab = (int)mrec_align_up((size_t)K, gf32::BK);
     a.bias = bias; a.relu = relu;
-    return gf32::launch<true, false, gf32::EPI_FWD>(a, gf32::vec_of(x, ldx, K), gf32::vec_of(w, ldw, N), 1, (hipStream_t)stream);
+    int va, vb;
+    gf32::load_widths(0, x, ldx, w, ldw, K, N, &va, &vb);
+    return gf32::launch<true, false, gf32::EPI_FWD>(a, va, vb, 1, (hipStream_t)stream);
 }
 
 /* dx = (dy . w^T) * (h > 0): dy [M, N] (lddy), w [K, N] (ldw), h [M, K] (ldh, nullable), dx [M, K] (lddx);
@@ -378,7 +387,9 @@ MREC_API int mrec_dense32_bwd_input(const float* dy, int64_t lddy, const float* 
     a.M = (int)M; a.N = K; a.K = N;                       // outputs [M, K], reduction over N
     a.k_per_slab = (int)mrec_align_up((size_t)N, gf32::BK);
     a.H = h; a.ldh = ldh; a.colsum = colsum_ws;
-    return gf32::launch<true, true, gf32::EPI_DGRAD>(a, gf32::vec_of(dy, lddy, N), gf32::vec_of(w, ldw, N), 1, (hipStream_t)stream);
+    int va, vb;
+    gf32::load_widths(1, dy, lddy, w, ldw, K, N, &va, &vb);
+    return gf32::launch<true, true, gf32::EPI_DGRAD>(a, va, vb, 1, (hipStream_t)stream);
 }
 
 /* dw_slabs[s] = x[slab s]^T . dy[slab s]: x [M, K] (ldx), dy [M, N] (lddy), dw_slabs [S, K, N] contiguous; the batch is cut
@@ -399,7 +410,22 @@ MREC_API int mrec_dense32_bwd_weight(const float* x, int64_t ldx, const float* d
     a.k_per_slab = (int)mrec_align_up((size_t)mrec_cdiv(M, S), gf32::BK);
     a.slab_stride = (int64_t)K * N;
     if ((int64_t)a.k_per_slab * (S - 1) >= M && S > 1) return MREC_EINVAL;      // an empty slab: S too large for this batch
-    return gf32::launch<false, false, gf32::EPI_PLAIN>(a, gf32::vec_of(x, ldx, K), gf32::vec_of(dy, lddy, N), S, (hipStream_t)stream);
+    int va, vb;
+    gf32::load_widths(2, x, ldx, dy, lddy, K, N, &va, &vb);
+    return gf32::launch<false, false, gf32::EPI_PLAIN>(a, va, vb, S, (hipStream_t)stream);
+}
+
+/* Read-only: the floats per staged load (4, 2 or 1) the launch of `form` (0 fwd, 1 bwd_input, 2 bwd_weight) picks for its two
+ * operands a, b as the entry above takes them (x / w, dy / w, x / dy), from their addresses (never dereferenced), row strides
+ * and K, N.  What the tests pin their cases with. */
+MREC_API int mrec_dense32_load_widths(int form, const float* a, int64_t lda, const float* b, int64_t ldb, int32_t K, int32_t N,
+                                      int32_t* va_out, int32_t* vb_out) {
+    if (form < 0 || form > 2 || K <= 0 || N <= 0 || !va_out || !vb_out) return MREC_EINVAL;
+    if (lda < (form == 1 ? N : K) || ldb < N) return MREC_EINVAL;
+    int va, vb;
+    gf32::load_widths(form, a, lda, b, ldb, K, N, &va, &vb);
+    *va_out = va; *vb_out = vb;
+    return MREC_OK;
 }
 
 /* Batch slabs: the output has only ceil(K / 128) * ceil(N / 128) tiles.  The count

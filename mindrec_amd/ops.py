@@ -1983,6 +1983,16 @@ def dense32_bwd_weight_slabs(M, K, N):
     return int(s.value)
 
 
+def dense32_load_widths(form, a, b):
+    """(VA, VB): floats per staged load the launch of form 0 (dense32_fwd: a = x, b = w), 1 (dense32_bwd_input: dy, w) or 2
+    (dense32_bwd_weight: x, dy) picks for these two operands."""
+    ra, ca, lda = _mat32(a, "a")
+    rb, cb, ldb = _mat32(b, "b")
+    va, vb = C.c_int32(0), C.c_int32(0)
+    _lib.call("mrec_dense32_load_widths", int(form), _ptr(a), lda, _ptr(b), ldb, rb if form == 1 else ca, cb, C.byref(va), C.byref(vb))
+    return int(va.value), int(vb.value)
+
+
 def dense32_bwd_weight(x, dy, out_slabs):
     """out_slabs[s] = x[slab s]^T . dy[slab s], fp32 [S, K, N]."""
     _need_cuda(x, dy, out_slabs)
