@@ -758,6 +758,28 @@ int mrec_tail_fwd_bwd(int32_t f16, const uint16_t* x, int64_t ldx, const uint16_
                       float* dwide_bias, float* loss, float* db3, float* db2, void* ws, size_t ws_bytes,
                       const mrec_dropout_t* drop_in, void* stream);
 
+/* The evaluation forward of that tail (PredictWithSigmoid, wide_and_deep.py:495-518): dense_layer_3, dense_layer_4 and the output
+ * head in ONE launch, 64 samples per workgroup, both hidden activations in LDS only -- mrec_dense_fwd_* x2 and mrec_head_predict as
+ * one.  The forward half of mrec_tail_fwd_bwd and nothing of its backward; no Dropout.  logit and prob are bit for bit what that
+ * chain of three launches leaves (same products in the same order, the head's lane geometry at K5 = 128); what a row gets depends
+ * on that row's inputs alone, never on B or on the rows that share its workgroup.
+ *   x, ldx, packed (only its two forward copies are read), b2, b3, w5, b5, the two forms of the wide branch: as mrec_tail_fwd_bwd.
+ *   ANY 1 <= B <= 32768 (a ragged last tile reads row B - 1 in place of the rows past it and stores nothing for them).
+ *   logit, prob: float32 [B].  label (nullable) [B] and loss (one float): both or neither.  With a label every workgroup leaves one
+ *   partial loss sum in ws and a second one-workgroup launch adds them in workgroup order and multiplies by 1 / B: no float atomics,
+ *   the same bits on every run.  Without a label: one launch, ws is not used and may be NULL.  ws: mrec_tail_predict_workspace_bytes(B)
+ *   (one float per workgroup of 64 rows).
+ * Decided before any launch, in this order: MREC_EINVAL (B <= 0, ldx < K2, a null x / packed / b2 / b3 / w5 / b5 / logit / prob, both
+ * or neither wide form, a products form without F or bias, label and loss not both null or both set), MREC_EUNSUPPORTED (a shape
+ * outside mrec_tail_predict_supported: widths other than 512 / 256 / 128 or B > 32768; F > 64; ldx % 8 != 0; x, packed, b2, b3 or w5
+ * not 16-byte aligned), MREC_EWORKSPACE (with a label only). */
+int mrec_tail_predict_supported(int64_t B, int32_t K2, int32_t N2, int32_t N3);
+int mrec_tail_predict_workspace_bytes(int64_t B, size_t* out);
+int mrec_tail_predict(int32_t f16, const uint16_t* x, int64_t ldx, const uint16_t* packed, const float* b2, const float* b3,
+                      const float* w5, const float* b5, const float* wide, const float* wide_prod, int32_t F,
+                      const float* wide_bias, const float* label, int64_t B, int32_t K2, int32_t N2, int32_t N3,
+                      float* logit, float* prob, float* loss, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- MapParameter key index ---------------------------------------------------------------
  * mindspore.experimental.MapParameter as built by HashEmbeddingLookup
  * (mindspore_rec/ops/embedding.py:136-146) and driven by MapTensorGet/Put/Erase

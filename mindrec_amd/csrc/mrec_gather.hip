@@ -645,7 +645,7 @@ MREC_API int mrec_crc32c_host(const void* data, size_t n, uint32_t* out) {
 }
 
 MREC_API int mrec_last_hip_error(void) { return g_mrec_last_hip_error; }
-MREC_API int mrec_version(void) { return 106; }
+MREC_API int mrec_version(void) { return 107; }
 
 MREC_API int mrec_device_ok(void) {
     int n = 0;

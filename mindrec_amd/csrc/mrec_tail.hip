@@ -14,6 +14,7 @@
 // k-steps in lockstep, sweep a contiguous window.  (Read from the row-major matrices -- 16 rows x 64 B per instruction, the same
 // column offset in every wave -- the stream ran at 26 GB/s per CU, a third of what the XCD's L2 delivers: 10 us per 256-KB pass.)
 // Accumulators hold C transposed as in mrec_gemm.h: a lane owns 4 consecutive output columns of one row.
+// k_tail_predict is the forward half alone, for evaluation: any batch size, label optional (further down).
 //
 // (Round 5, built, parity-green and measured, not kept: the tail THREE layers deep -- the 1024 -> 512 layer's forward as a phase in
 // front and its input gradient as a phase behind, its 1-MB weight copies streamed through a two-chunk register ring, its three
@@ -405,6 +406,163 @@ __global__ __launch_bounds__(MB) void k_tail_finish(const float* __restrict__ pa
     else if (c >= P_DB2) db2[c - P_DB2] = sacc;
 }
 
+// ---- the forward half of k_tail: evaluation ----------------------------------------------------------------------------------
+// X tile -> LDS, Y2 = relu(X . W2 + b2) -> LDS, Y3 = relu(Y2 . W3 + b3) -> LDS, the head on Y3: logit, sigmoid(logit) and, with a
+// label, the row's loss term.  The phases are k_tail's own (load_q, mma, epi_fwd on the same fragment-ordered copies w2f | w3f, a
+// zero DropArgs: evaluation never draws a mask), so Y2 and Y3 are the bits mrec_dense_fwd_* leaves in global memory, and the head
+// has k_head_predict's geometry at K5 = 128 (16 lanes a row, one 8-value chunk a lane): a row's logit and prob are the bits of
+// dense_fwd -> dense_fwd -> head_predict.  Nothing of the backward: no w3b / w2b, no gradient tiles, no partial row.
+// ANY 1 <= B <= 32768: the rows of the last tile at or past B are loaded from row B - 1 (clamped addresses, unconditional loads:
+// no loop carries a per-element guard) and computed like every other row -- a row's result depends on that row's inputs alone --
+// and only the stores of logit / prob and the loss term ask r < B.
+struct PredictArgs {
+    const uint16_t* x; int64_t ldx;                    // [B, K2] input of the first tail layer
+    const uint16_t *w2f, *w3f;                         // fragment-ordered forward operands (the head of k_tail's `packed`)
+    const float *b2, *b3, *w5, *b5;
+    const float *wide, *wprod, *wide_bias; int F;      // wide branch: per sample, or per-field products + bias
+    const float* label;                                // nullable: then no loss term, no partial, no LDS reduction
+    int64_t B;
+    float *logit, *prob, *partial;                     // partial [ceil(B / 64)]: the workgroup's loss sum (with a label)
+};
+constexpr int PO3 = OX, PRED = O3;                     // Y3 over X (dead after the first phase's barrier); 8 floats behind Y2
+constexpr int PREDICT_LDS_BYTES = PRED + 8 * 4;
+static_assert(PO3 + R * S3 <= O2 && PREDICT_LDS_BYTES <= 160 * 1024, "LDS layout of k_tail_predict");
+
+template <bool F16>
+__global__ __launch_bounds__(TT, 2) void k_tail_predict(const PredictArgs a) {
+    extern __shared__ __attribute__((aligned(1024))) char smem_raw[];
+    MGEMM_LDS char* const sm = (MGEMM_LDS char*)smem_raw;
+    const int tid = threadIdx.x, l = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t row0 = (int64_t)blockIdx.x * R, rlast = a.B - 1;
+    const DropArgs d{};
+    constexpr int CG = N3 / 8, RP = TT / CG, NPASS = R / RP, WR = 4;      // head: 16 lanes per row, 32 rows per pass; <= 64 wide fields
+    const int cg = tid % CG, rl = tid / CG;
+
+    // ---- requests, in k_tail's order: the X tile, the biases, the weights of both layers, the head's per-sample inputs
+    u32x4_t xv[R / 8];
+#pragma unroll
+    for (int i = 0; i < R / 8; ++i) {
+        const int64_t rr = row0 + w * (R / 8) + i, r = rr < rlast ? rr : rlast;
+        xv[i] = *(const u32x4_t*)(a.x + r * a.ldx + l * 8);
+    }
+    float4 bias2[2], bias3[1];
+    bias2[0] = *(const float4*)(a.b2 + w * 32 + 4 * (l >> 4));
+    bias2[1] = *(const float4*)(a.b2 + w * 32 + 16 + 4 * (l >> 4));
+    bias3[0] = *(const float4*)(a.b3 + w * 16 + 4 * (l >> 4));
+    const float4 w5a = *(const float4*)(a.w5 + cg * 8), w5b = *(const float4*)(a.w5 + cg * 8 + 4);
+    const float bias = *a.b5;
+    const float wbias = a.wprod ? *a.wide_bias : 0.0f;
+    u32x4_t qA[K2 / 32][2], qB[N2 / 32][1];
+    load_q<2, K2 / 32, N2 / 16>(qA, a.w2f, w * 2, l);
+    load_q<1, N2 / 32, N3 / 16>(qB, a.w3f, w, l);
+    // (unconditional loads from clamped addresses, as k_tail's; without a label the lane reads b5 in its place)
+    float hy[NPASS], hw[NPASS][WR];
+    {
+        const float* wsrc = a.wprod ? a.wprod : a.wide;
+        const int64_t wstride = a.wprod ? 2 * (int64_t)a.F : 1;      // floats per sample
+        const int wstep = a.wprod ? 2 : 0;                            // floats per field
+        const int fmax = a.wprod ? a.F - 1 : 0;
+        const float* ysrc = a.label ? a.label : a.b5;
+        const int64_t ystride = a.label ? 1 : 0;
+#pragma unroll
+        for (int pass = 0; pass < NPASS; ++pass) {
+            const int64_t rr = row0 + pass * RP + rl, r = rr < rlast ? rr : rlast;
+            hy[pass] = ysrc[r * ystride];
+#pragma unroll
+            for (int q = 0; q < WR; ++q) {
+                const int f = min(q * CG + cg, fmax);
+                hw[pass][q] = wsrc[r * wstride + f * wstep];
+            }
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < R / 8; ++i) *(MGEMM_LDS u32x4_t*)(sm + OX + (w * (R / 8) + i) * SX + l * 16) = xv[i];
+    lds_barrier();
+
+    // ---- first tail layer: Y2 = relu(X . W2 + b2), this wave's 32 columns
+    {
+        f32x4_t acc[4][2];
+        zero_acc<2>(acc);
+        mma<F16, 2, K2 / 32, SX>(acc, sm + OX, qA, l);
+        epi_fwd<F16, 2, S2>(acc, bias2, w * 32, l, sm + O2, nullptr, N2, row0, d, 0ull);
+    }
+    lds_barrier();              // every wave has read X: Y3 may go over it
+    // ---- second tail layer: Y3 = relu(Y2 . W3 + b3), this wave's 16 columns
+    {
+        f32x4_t acc[4][1];
+        zero_acc<1>(acc);
+        mma<F16, 1, N2 / 32, S2>(acc, sm + O2, qB, l);
+        epi_fwd<F16, 1, S3>(acc, bias3, w * 16, l, sm + PO3, nullptr, N3, row0, d, 0ull);
+    }
+    lds_barrier();
+
+    // ---- output head on Y3: k_head_predict at G = 16, NC = 1, restated on the LDS tile (k_tail's head without its backward)
+    const float wv5[8] = {w5a.x, w5a.y, w5a.z, w5a.w, w5b.x, w5b.y, w5b.z, w5b.w};      // (k_head_predict: w[0][k] = w5[cg * 8 + k])
+    float accl = 0.0f;
+#pragma unroll
+    for (int pass = 0; pass < NPASS; ++pass) {
+        const int p = pass * RP + rl;
+        const int64_t r = row0 + p;
+        float fh[8];
+        const u32x4_t hv = *(const MGEMM_LDS u32x4_t*)(sm + PO3 + p * S3 + cg * 16);
+        unpack8t<F16>(make_uint4(hv[0], hv[1], hv[2], hv[3]), fh);                         // head_widen
+        float part = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) part += fh[k] * wv5[k];                                // head_row_dot: products in element order,
+        for (int dd = CG >> 1; dd >= 1; dd >>= 1) part += __shfl_xor(part, dd, 64);        // then head_group_sum's tree 8, 4, 2, 1
+        float wv;
+        if (a.wprod) {                 // head_wide_term: the fields in FIELD ORDER from 0, then + wide_bias
+            const int lane_row0 = l - cg;
+            float acc_w = 0.0f;
+#pragma unroll
+            for (int q = 0; q < WR; ++q) {
+                const int f0 = q * CG;
+                if (f0 < a.F) {            // (uniform) all 16 lane reads issued together, then the adds in field order
+                    float pv[CG];
+#pragma unroll
+                    for (int c = 0; c < CG; ++c) pv[c] = __shfl(hw[pass][q], lane_row0 + c, 64);
+#pragma unroll
+                    for (int c = 0; c < CG; ++c)
+                        if (f0 + c < a.F) acc_w = acc_w + pv[c];
+                }
+            }
+            wv = acc_w + wbias;
+        } else {
+            wv = hw[pass][0];          // head_wide_term: wide[r]
+        }
+        if (cg == 0 && r < a.B) {      // k_head_predict's `valid && cg == 0` block, line for line
+            const float z = part + bias + wv;
+            const float sg = sigmoid_of(z);
+            a.logit[r] = z;
+            a.prob[r] = sg;
+            if (a.label) accl += sigmoid_xent(z, hy[pass]);
+        }
+    }
+    if (!a.label) return;              // (uniform: a kernel argument)
+    // the workgroup's ONE partial: a wave's 4 lane groups by shuffles, then the 8 waves in wave order -- a fixed order
+    accl += __shfl_xor(accl, 16, 64);
+    accl += __shfl_xor(accl, 32, 64);
+    float* const reds = (float*)(smem_raw + PRED);
+    if (l == 0) reds[w] = accl;
+    lds_barrier();
+    if (tid == 0) {
+        float s = reds[0];
+#pragma unroll
+        for (int q = 1; q < 8; ++q) s += reds[q];
+        a.partial[blockIdx.x] = s;
+    }
+}
+
+// loss = (the workgroups' partials added in workgroup order, finish_column's order as k_head_predict_finish) / B: one workgroup
+__global__ __launch_bounds__(MB) void k_tail_predict_finish(const float* __restrict__ partial, int nblk, float inv_B,
+                                                            float* __restrict__ loss) {
+    __shared__ float sm[8][32];
+    const float s = finish_column(partial, nblk, 1, threadIdx.x & 31, sm);
+    if (threadIdx.x == 0) *loss = s * inv_B;
+}
+
 // Fragment-ordered copies of one weight W [K, N] (row-major, as the reference stores it): one thread per 16-byte chunk.
 //   forward operand  F[ks][nt][l][j] = W[ks*32 + 8*(l>>4) + j][nt*16 + (l&15)]     (output column q = n, reduction over k)
 //   backward operand G[ks][kt][l][j] = W[kt*16 + (l&15)][ks*32 + 8*(l>>4) + j]     (output column q = k, reduction over n)
@@ -581,5 +739,48 @@ MREC_API int mrec_tail_fwd_bwd(int32_t f16, const uint16_t* x, int64_t ldx, cons
 MREC_API int mrec_tail_workspace_bytes(int64_t B, size_t* out) {
     if (!out || B < 0) return MREC_EINVAL;
     *out = (size_t)mrec_cdiv(B > 0 ? B : 1, tail::R) * tail::PW * sizeof(float);
+    return MREC_OK;
+}
+
+/* The evaluation forward of the tail (k_tail_predict; see include/mrec.h). */
+MREC_API int mrec_tail_predict_supported(int64_t B, int32_t K2, int32_t N2, int32_t N3) {
+    return B >= 1 && B <= 512 * tail::R && K2 == tail::K2 && N2 == tail::N2 && N3 == tail::N3;
+}
+MREC_API int mrec_tail_predict_workspace_bytes(int64_t B, size_t* out) {
+    if (!out || B < 0) return MREC_EINVAL;
+    *out = (size_t)mrec_cdiv(B > 0 ? B : 1, tail::R) * sizeof(float);          // one loss partial a workgroup
+    return MREC_OK;
+}
+MREC_API int mrec_tail_predict(int32_t f16, const uint16_t* x, int64_t ldx, const uint16_t* packed, const float* b2, const float* b3,
+                               const float* w5, const float* b5, const float* wide, const float* wide_prod, int32_t F,
+                               const float* wide_bias, const float* label, int64_t B, int32_t K2, int32_t N2, int32_t N3,
+                               float* logit, float* prob, float* loss, void* ws, size_t ws_bytes, void* stream) {
+    if (B <= 0 || ldx < K2) return MREC_EINVAL;
+    if (!x || !packed || !b2 || !b3 || !w5 || !b5 || !logit || !prob) return MREC_EINVAL;
+    if ((wide != nullptr) == (wide_prod != nullptr)) return MREC_EINVAL;
+    if (wide_prod && (F <= 0 || !wide_bias)) return MREC_EINVAL;
+    if ((label != nullptr) != (loss != nullptr)) return MREC_EINVAL;
+    if (!mrec_tail_predict_supported(B, K2, N2, N3)) return MREC_EUNSUPPORTED;
+    if (wide_prod && F > 64) return MREC_EUNSUPPORTED;
+    if (ldx % 8 || (((uintptr_t)x | (uintptr_t)packed | (uintptr_t)b2 | (uintptr_t)b3 | (uintptr_t)w5) & 15)) return MREC_EUNSUPPORTED;
+    const int nb = (int)mrec_cdiv(B, tail::R);
+    if (label && (!ws || ws_bytes < (size_t)nb * sizeof(float))) return MREC_EWORKSPACE;
+    tail::PredictArgs a{};
+    a.x = x; a.ldx = ldx;
+    a.w2f = packed; a.w3f = a.w2f + (int64_t)K2 * N2;
+    a.b2 = b2; a.b3 = b3; a.w5 = w5; a.b5 = b5;
+    a.wide = wide; a.wprod = wide_prod; a.wide_bias = wide_bias; a.F = F; a.label = label;
+    a.B = B; a.logit = logit; a.prob = prob; a.partial = label ? (float*)ws : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    static bool attr_set = false;
+    if (!attr_set) {
+        MREC_HIP_CHECK(hipFuncSetAttribute((const void*)tail::k_tail_predict<false>, hipFuncAttributeMaxDynamicSharedMemorySize, tail::PREDICT_LDS_BYTES));
+        MREC_HIP_CHECK(hipFuncSetAttribute((const void*)tail::k_tail_predict<true>, hipFuncAttributeMaxDynamicSharedMemorySize, tail::PREDICT_LDS_BYTES));
+        attr_set = true;
+    }
+    if (f16) tail::k_tail_predict<true><<<nb, tail::TT, tail::PREDICT_LDS_BYTES, st>>>(a);
+    else tail::k_tail_predict<false><<<nb, tail::TT, tail::PREDICT_LDS_BYTES, st>>>(a);
+    if (label) tail::k_tail_predict_finish<<<1, MB, 0, st>>>((const float*)ws, nb, 1.0f / (float)B, loss);
+    MREC_LAUNCH_CHECK();
     return MREC_OK;
 }

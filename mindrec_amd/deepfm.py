@@ -44,6 +44,8 @@ class DeepFMConfig:
                                   # deepfm.py:135-145); "bf16" runs the same kernels, "fp32" the fp32 kernels (ops.x3_* / ops.dense32_*)
     graphs: str = "mlp"           # "mlp": the dense net's step replays as HIP graphs (16-bit net), "none": kernel by kernel
     fp32_matmul: str = "x3"       # fp32 net: "x3" three-part bf16 operands on the 16-bit matrix instruction, "exact" the fp32-input one
+    fused_tail_eval: bool = True  # predict_fused on a 16-bit net that ends 512 -> 256 -> 128: those two layers and the output head as one
+                                  # launch (ops.tail_predict; the same logit and prob bits); False: the three launches
     max_norm: Optional[float] = None   # nn.EmbeddingLookup(max_norm=c) of the [V, D] table (embedding.py:156-161,202-205): every looked-up
                                   # row is clipped to norm c before the mask multiply, and the table's gradient goes through the clip's
                                   # Jacobian (ops.clip_group_sums_ in front of the dense Adam; the hash engine: the clipped LazyAdam).
@@ -60,7 +62,7 @@ class _DeepFMNet(DenseNetMixin):
         self._graph_level = 1 if (cfg.graphs == "mlp" and self._mfma) else 0
         self.rank, self.step_count, self._step_state = getattr(self, "rank", 0), 0, None
         self._dropout = self._training = self._emb_dropped = False
-        self._init_dense_net(dims, cfg.seed + 2, cfg.init_sigma, cfg.loss_scale)
+        self._init_dense_net(dims, cfg.seed + 2, cfg.init_sigma, cfg.loss_scale, fused_tail_eval=cfg.fused_tail_eval)
         self.beta1, self.beta2 = np.float32(0.9), np.float32(0.999)
         self.beta1_power, self.beta2_power = np.float32(1.0), np.float32(1.0)
 

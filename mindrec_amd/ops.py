@@ -1662,6 +1662,67 @@ def tail_fwd_bwd(x, packed, b2, b3, w5, b5, wide, wide_bias, label, dscale, dw5_
     return loss, dlogit, y2, dz4, dz3, dz2
 
 
+def tail_predict_supported(B, K2, N2, N3):
+    """Shapes of the evaluation tail (csrc/mrec_tail.hip: k_tail_predict): 512 -> 256 -> 128 at any 1 <= B <= 32768."""
+    return bool(_lib.lib().mrec_tail_predict_supported(int(B), int(K2), int(N2), int(N3)))
+
+
+def tail_predict(x, packed, b2, b3, w5, b5, wide, wide_bias=None, label=None, out=None):
+    """The evaluation forward of tail_fwd_bwd -- the last two hidden DenseLayers and head_predict's output end (output layer +
+    wide/deep add + sigmoid and, with `label`, the mean sigmoid cross-entropy) -- in ONE launch over x [B, 512] (16-bit, any row
+    stride that is a multiple of 8), 64 samples per workgroup, the hidden activations in LDS only; no Dropout, nothing of the backward.
+    packed: tail_pack_weights(w2, w3) (only its forward copies are read).  wide: the [B, F, 2] per-field products of gather_rows_wide
+    (then wide_bias is needed, F <= 64) or the per-sample wide sum [B].  Any batch size tail_predict_supported() names.  logit and
+    prob are bit for bit those of dense_fwd(x, w2, b2) -> dense_fwd(., w3, b3) -> head_predict(.).
+    Returns (logit [B], prob [B]), with a label (logit, prob, loss [1]).  out: dict of persistent output tensors with those names
+    (filled on first use; "logit" / "prob" may be longer than B: the first B elements are written and returned), so that a captured
+    graph replays into fixed addresses."""
+    _need_cuda(x, packed, b2, b3, w5, b5, wide, wide_bias, label)
+    B, K2, ldx = _mat16(x, "x")
+    N2, N3 = b2.numel(), b3.numel()
+    dt, dev = x.dtype, x.device
+    if not tail_predict_supported(B, K2, N2, N3):
+        raise ValueError("tail_predict: unsupported shape (see tail_predict_supported)")
+    if packed.dtype != dt or packed.numel() != 2 * (K2 * N2 + N2 * N3) or not packed.is_contiguous():
+        raise TypeError("tail_predict: packed must be tail_pack_weights(w2, w3) in x's dtype")
+    for t in (b2, b3, w5, b5):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("tail_predict: biases and the output layer's weight are contiguous float32")
+    if w5.numel() != N3 or b5.numel() != 1:
+        raise TypeError("tail_predict: w5 [N3], b5 [1]")
+    prod = wide.dim() == 3
+    if prod:
+        if _head_fields(wide, B) > 64:
+            raise ValueError("tail_predict: at most 64 wide fields per sample")
+        if wide_bias is None or wide_bias.dtype != torch.float32:
+            raise TypeError("tail_predict: the products form needs the float32 wide_bias")
+    elif wide.dtype != torch.float32 or wide.numel() != B:
+        raise TypeError("wide must be the contiguous float32 [B, F, 2] tensor of gather_rows_wide (with wide_bias) or a float32 [B] tensor")
+    if label is not None and (label.dtype != torch.float32 or label.numel() != B):
+        raise TypeError("tail_predict: label must be float32 [B]")
+    o = out if out is not None else {}
+
+    def buf(name, n, exact):
+        t = o.get(name)
+        if t is None:
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+            o[name] = t
+        elif t.dtype != torch.float32 or t.dim() != 1 or (t.numel() != n if exact else t.numel() < n) or not t.is_contiguous() or t.device != dev:
+            raise TypeError(f"tail_predict: out[{name!r}] must be a contiguous float32 [{n}] tensor on x's device")
+        return t
+    logit, prob = buf("logit", B, False), buf("prob", B, False)
+    loss, ws, ws_bytes = None, None, 0
+    if label is not None:
+        loss = buf("loss", 1, True)
+        ws = workspace("tail_predict", _lib.query_bytes("mrec_tail_predict_workspace_bytes", B), dev)
+        ws_bytes = ws.numel()
+    _lib.call("mrec_tail_predict", int(dt == torch.float16), _ptr(x), ldx, _ptr(packed), _ptr(b2), _ptr(b3), _ptr(w5), _ptr(b5),
+              None if prod else _ptr(wide.contiguous()), _ptr(wide) if prod else None, wide.shape[1] if prod else 0,
+              _ptr(wide_bias) if prod else None, _ptr(label.contiguous()) if label is not None else None, B, K2, N2, N3,
+              _ptr(logit), _ptr(prob), _ptr(loss), _ptr(ws), ws_bytes, _stream())
+    return (logit[:B], prob[:B]) if label is None else (logit[:B], prob[:B], loss)
+
+
 # ---- Dropout (csrc/mrec_dropout.h) ---------------------------------------------------------------------
 class _DropDesc(C.Structure):      # mrec_dropout_t
     _fields_ = [("step_state", C.c_void_p), ("seed", C.c_uint64), ("step", C.c_int64), ("row0", C.c_int64), ("layer", C.c_int32),

@@ -88,6 +88,8 @@ class WideDeepConfig:
     graphs: str = "step"           # what replays as HIP graphs: "step" the whole step (sinks of steps: train_steps), "front" everything in
                                    # front of the optimizers, "mlp" the dense net only, "none" kernel by kernel
     fused_tail: bool = True        # the last two hidden layers, the output head and their input-gradient bprops as one launch
+    fused_tail_eval: bool = True   # predict_fused on a net with the fused tail: those two layers and the output head as one launch
+                                   # (ops.tail_predict; the same logit and prob bits); False: the three launches
     fp32_matmul: str = "x3"        # the MatMuls of an fp32 net (amp "none"): "x3" three-part bf16 operands on the 16-bit matrix
                                    # instruction (fp32-class accuracy, csrc/mrec_gemm_x3.hip), "exact" the fp32-input matrix instruction
     wide_b_optimizer: str = "ftrl"  # which optimizer owns the wide bias.  "ftrl": what the reference's code does on MindSpore --
@@ -348,7 +350,8 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             # `"wide" in params.name` (wide_and_deep.py:407-411) and the bias is named "Wide_b" (:161-163), so it belongs to the
             # DEEP optimizer (Adam), not to FTRL; in that buffer it is updated by the same dense-Adam launch.
             self._init_dense_net(dims, cfg.seed + 2, cfg.init_sigma, cfg.sens, extra_seed=cfg.seed + 3,
-                                 fused_tail=bool(cfg.fused_tail and cfg.field_size <= 64))      # (<= 64 wide products per sample)
+                                 fused_tail=bool(cfg.fused_tail and cfg.field_size <= 64),      # (<= 64 wide products per sample)
+                                 fused_tail_eval=cfg.fused_tail_eval)
             self.wide_b, self.wide_b_grad = self.extra_p, self.extra_g
             if cfg.wide_b_optimizer not in ("ftrl", "adam"):
                 raise ValueError("wide_b_optimizer must be 'ftrl' or 'adam'")

@@ -78,13 +78,14 @@ class DenseNetMixin(PredictGraphs):
     self._mfma, self._graph_level, self.rank, self.step_count, self._step_state, self._dropout / self._training / self._emb_dropped,
     self.cfg.dropout_keep_prob / .seed (Dropout only)."""
 
-    def _init_dense_net(self, dims, seed, init_sigma, sens, extra_seed=None, fused_tail=True):
+    def _init_dense_net(self, dims, seed, init_sigma, sens, extra_seed=None, fused_tail=True, fused_tail_eval=True):
         """The dense net's state: fp32 master weights in one flat buffer, same for gradients / Adam moments.  Flat order: the
         hidden layers' weight matrices first (the 16-bit GEMM operands), then the biases and the fp32 output layer; `self.dense`
         lists them in layer order W0, b0, W1, b1, ...  One EXTRA scalar parameter rides behind them (self.extra_p / extra_g: the
         Wide&Deep model's "Wide_b"), then padding to a multiple of 4 floats: the dense Adam is one float4 launch (a 1-element
         tail launch cost 5 us + a gap every step; the pad elements are parameters nobody reads, gradient always 0).
-        sens: the loss scale the backward is seeded with (TrainStepWrap(sens=...), wide_and_deep.py:390,479-486)."""
+        sens: the loss scale the backward is seeded with (TrainStepWrap(sens=...), wide_and_deep.py:390,479-486).
+        fused_tail_eval: where the net has the fused tail, mlp_predict runs its forward as one launch too (ops.tail_predict)."""
         dev = self.device
         self.dims, self._sens = list(dims), float(sens)
         nl = len(dims) - 1
@@ -140,6 +141,7 @@ class DenseNetMixin(PredictGraphs):
                                  or ops.head_any_supported(dims[nl - 1])))
         self._tail_packed, self._dense16_t = None, None
         self._tail_ok = bool(self._mfma and fused_tail and nl >= 4 and self.k.tail_supported(64, *self.dims[nl - 3:nl]))
+        self._tail_eval = bool(self._tail_ok and fused_tail_eval)
         self._mlp_graph = None        # dict: captured MLP step + its static input / output tensors
         self._dw = {}                 # hidden layer -> fp32 batch slabs [S, in, out] of its weight gradient (persistent:
                                       # graph replays and eager steps write the same buffers, the dense Adam reads them)
@@ -243,7 +245,9 @@ class DenseNetMixin(PredictGraphs):
         """The evaluation forward on the training step's kernels: the hidden layers as the training forward runs them (16-bit
         nets: both GEMM operands K-contiguous, the transposes _refresh_tail keeps current; no Dropout), then the output layer, the
         wide/deep add, the sigmoid and -- with `label` -- the mean sigmoid cross-entropy as ONE pass over the last activation
-        (ops.head_predict).  emb: the looked-up rows in the net's dtype; wide: a _WideProd (summed inside the head) or a [B] tensor.
+        (ops.head_predict).  A net with the fused tail (... -> 512 -> 256 -> 128 -> 1, fused_tail_eval on): its last two hidden layers
+        and that pass as ONE launch with both activations in LDS (ops.tail_predict) -- the same bits in logit and prob, whatever the
+        batch size.  emb: the looked-up rows in the net's dtype; wide: a _WideProd (summed inside the head) or a [B] tensor.
         Returns (logit [B], prob [B]) or, with a label, (logit, prob, loss [1]).  No cast, add or sigmoid runs outside the kernels."""
         n = len(self.dims) - 1
         K5 = self.dims[n - 1]
@@ -252,16 +256,21 @@ class DenseNetMixin(PredictGraphs):
         if emb.dtype != (self._amp if self._mfma else torch.float32):
             raise TypeError(f"mlp_predict: the looked-up rows arrive in the net's dtype, got {emb.dtype}")
         h = emb
+        prod = isinstance(wide, _WideProd)
+        W5, b5 = self.dense[2 * (n - 1)].detach().view(-1), self.dense[2 * (n - 1) + 1].detach()
+        tail = self._tail_eval and ops.tail_predict_supported(emb.shape[0], *self.dims[n - 3:n])
         if self._mfma:
-            for i in range(n - 1):
+            for i in range(n - 3 if tail else n - 1):
                 h = ops.dense_fwd(h, self.dense16[2 * i], self.dense[2 * i + 1].detach(), relu=True, wt=self._dense16_t.get(i))
         else:
             h = h.contiguous()
             for i in range(n - 1):
                 h = ops.dense32_fwd(h, self.dense[2 * i].detach(), self.dense[2 * i + 1].detach(), relu=True)
-        prod = isinstance(wide, _WideProd)
-        return ops.head_predict(h, self.dense[2 * (n - 1)].detach().view(-1), self.dense[2 * (n - 1) + 1].detach(),
-                                wide=None if prod else wide.view(-1), wide_prod=wide.prod if prod else None,
+        if tail:
+            return ops.tail_predict(h, self._tail_packed, self.dense[2 * (n - 3) + 1].detach(), self.dense[2 * (n - 2) + 1].detach(), W5, b5,
+                                    wide.prod if prod else wide.view(-1), wide_bias=self.wide_b if prod else None,
+                                    label=label.view(-1) if label is not None else None)
+        return ops.head_predict(h, W5, b5, wide=None if prod else wide.view(-1), wide_prod=wide.prod if prod else None,
                                 wide_bias=self.wide_b if prod else None, label=label.view(-1) if label is not None else None)
 
     # ---- hooks: nets without a HIP path.  The product refuses them; tests/_torch_net.py implements them for the oracle side ----
