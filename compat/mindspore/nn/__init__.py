@@ -1,7 +1,7 @@
 """`mindspore.nn`."""
 from . import layer, metrics, optim, wrap  # noqa: F401
 from .cell import Cell, GraphCell  # noqa: F401
-from .layer import ClipByNorm, Dense, Dropout, EmbeddingLookup, MatMul  # noqa: F401
+from .layer import ClipByNorm, Dense, Dropout, EmbeddingLookup, Flatten, MatMul  # noqa: F401
 from .metrics import Loss, Metric  # noqa: F401
 from .optim import FTRL, Adam, LazyAdam, Optimizer  # noqa: F401
 from .wrap import DistributedGradReducer, TrainOneStepCell, VirtualDatasetCellTriple, WithEvalCell, WithLossCell  # noqa: F401

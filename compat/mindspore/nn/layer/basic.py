@@ -79,6 +79,17 @@ class Dense(Cell):
         return self.activation(y) if self.activation is not None else y
 
 
+class Flatten(Cell):
+    """nn.Flatten(): [N, ...] -> [N, prod(...)], the batch axis kept (wide_and_deep_multitable/src/wide_and_deep.py:24,269,292-299)."""
+
+    def __init__(self):
+        super().__init__()
+        self.reshape = P.Reshape()
+
+    def construct(self, x):
+        return self.reshape(x, (x.shape[0], -1))
+
+
 class MatMul(Cell):
     """nn.MatMul(transpose_x1=False, transpose_x2=False): broadcasting batched matmul (CrossLayer, deep_and_cross.py:130,146)."""
 

@@ -244,6 +244,46 @@ int mrec_gather_pool_fields_keyed_clip(const float* table, int64_t V, int64_t ld
                                        uint64_t seed, float sigma, float fill, void* out, int32_t out_kind, int64_t ldo, float max_norm,
                                        void* stream);
 
+/* ---- the multitable Wide&Deep's input stage: the input row of dense_layer_1 and the wide logit term, ONE launch ------------------
+ * models/wide_and_deep_multitable/src/wide_and_deep.py:286-352 (input_embedding = Concat((val_hldr * 1, ind_emb, emb128_id_emb,
+ * emb64_sgl_emb, mult_embedding)): Gather + Flatten x3, Gather -> Mul(mask) -> ReduceMean(axis 1) x6) and :361-424 (wide_out: the
+ * continuous values times wide_continue_w, the [V] wide weights of every id, masked where the field has a mask, summed, BiasAdd).
+ * A SEGMENT is one id tensor over one table: ids[b * ld_ids + s], s = 0 .. L-1, mask in the same layout (NULL: all ones).  Per sample b:
+ *   x[b, 0 : C]                            = cont[b, :]
+ *   pooled == 0 (Gather + Flatten):          x[b, col + s*D : col + (s+1)*D] = table[ids[b,s]] * mask[b,s] -- L rows side by side,
+ *                                            each mrec_gather_rows' row (NULL mask: the row itself)
+ *   pooled == 1 (Gather -> Mul -> ReduceMean): x[b, col : col + D] = mrec_gather_pool_fields' mode 1 exactly -- slot 0's product starts
+ *                                            the sum, every later slot is product then add (no fma) in ascending slot order, ONE IEEE
+ *                                            division by (float)L (not by the number of unmasked slots)
+ *   an id outside [0, V) contributes a +0.0 row; 16-bit outputs (out_kind 0 = fp32, 1 = bf16, 2 = IEEE half, as mrec_gather_pool) are
+ *   rounded once, at the end; columns of [0, K0) that no block covers are written as +0; columns K0 .. ldx-1 are not touched.
+ *   wide_out[b] = sum_c cont[b,c] * wide_cont[c] + sum over segments with wide != NULL, over slots, of wide[ids[b,s]] * mask[b,s]
+ *                 + *wide_bias, in fp32; a NULL mask is 1, an id out of range contributes 0.  The order of the sum is fixed by the
+ *                 layout (no atomics): the same bits on every run.
+ * The caller lays the columns out: the blocks [0, C) and [col, col + width) (width = D pooled, L * D otherwise) must be disjoint and
+ * inside [0, K0), K0 <= ldx (row stride of x in ELEMENTS).  segs is HOST memory, read during the call only and copied into the
+ * kernel's arguments by value: no device-side table, no allocation, no synchronisation -- one launch (k_mt_input), capturable.
+ * Decided before any HIP call, in this order:
+ *   MREC_EINVAL: n_segs outside [0, MREC_MT_MAX_SEGS], null segs; B, C, K0 < 0, out_kind, ldx < K0, ld_cont < C; an L < 1, pooled not
+ *     0 / 1, D < 1, V < 0, ld < D, ld_ids < L, col < 0;
+ *   MREC_EUNSUPPORTED: C, K0 or ldx not a multiple of 8, ld_cont or an ld not a multiple of 4; a D not a multiple of 8 or > 256, a col
+ *     not a multiple of 8; the L of all segments together > MREC_POOL_MAX_BAG; B * n_segs >= 2^31;
+ *   MREC_EINVAL: overlapping column blocks, or a block outside [0, K0);
+ *   B == 0: MREC_OK, nothing launched;
+ *   MREC_EINVAL: a null x, wide_out, wide_bias, table or ids, null cont / wide_cont with C > 0 (C == 0: both may be NULL), V == 0;
+ *   MREC_EUNSUPPORTED: x, cont or a table not 16-byte aligned. */
+typedef struct {
+  const float* table; int64_t V; int64_t ld; int32_t D;   /* deep rows [V, D], row stride ld          */
+  const float* wide;                                      /* [V] wide weights of the same ids, or NULL */
+  const int32_t* ids;  int64_t ld_ids;                    /* ids[b * ld_ids + s], s = 0 .. L-1        */
+  const float* mask;                                      /* same layout as ids, or NULL = all ones   */
+  int32_t L;  int32_t pooled;  int32_t col;               /* see above                                */
+} mrec_mt_seg_t;
+#define MREC_MT_MAX_SEGS 16
+int mrec_mt_input(const float* cont, int64_t ld_cont, int32_t C, const float* wide_cont, const float* wide_bias,
+                  const mrec_mt_seg_t* segs, int32_t n_segs, int64_t B, void* x, int32_t out_kind, int64_t ldx, int32_t K0,
+                  float* wide_out, void* stream);
+
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row
  * stride ldw floats: 1 for a dense column, 4 when it lives in a fused w|accum|linear|pad record). */

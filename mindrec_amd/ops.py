@@ -6,6 +6,7 @@ only: no arithmetic on the hot path is done by torch here.
 """
 import ctypes as C
 import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -374,6 +375,100 @@ def gather_pool_fields_keyed(values, rows, keys, fields, mask=None, mode="mean",
         raise ValueError(f"default must hold a finite sigma (or None) and a finite fill, got {default!r}")
     return _gather_pool("gather_pool_fields_keyed", values, rows, lens, mask, mode, out, out_dtype, keyed=(keys, int(seed), sigma, fill),
                         max_norm=max_norm)
+
+
+MT_MAX_SEGS = 16       # MREC_MT_MAX_SEGS
+
+
+class MtSeg(C.Structure):          # mrec_mt_seg_t
+    _fields_ = [("table", C.c_void_p), ("V", C.c_int64), ("ld", C.c_int64), ("D", C.c_int32), ("wide", C.c_void_p), ("ids", C.c_void_p),
+                ("ld_ids", C.c_int64), ("mask", C.c_void_p), ("L", C.c_int32), ("pooled", C.c_int32), ("col", C.c_int32)]
+
+
+class MtSegment(NamedTuple):
+    """One id tensor over one table, for multitable_input: table [V, D] float32; ids int32 [B, L] (or [B]: L = 1); col: the first
+    column of the segment's block in the input row; pooled: False = Gather + Flatten, L rows side by side (L * D columns), True =
+    Gather -> Mul(mask) -> ReduceMean over the L slots (D columns); mask: float32 of the shape of ids, or None (all ones); wide: the
+    [V] float32 wide weights of the same ids, or None (the segment adds nothing to the wide sum)."""
+    table: torch.Tensor
+    ids: torch.Tensor
+    col: int
+    pooled: bool = False
+    mask: Optional[torch.Tensor] = None
+    wide: Optional[torch.Tensor] = None
+
+    @property
+    def width(self):
+        L = self.ids.shape[1] if self.ids.dim() == 2 else 1
+        return self.table.shape[1] * (1 if self.pooled else L)
+
+
+def multitable_input(cont, wide_cont, wide_bias, segments, K0=None, out=None, wide_out=None, out_dtype=torch.float16):
+    """The input stage of the multitable Wide&Deep in ONE launch (mrec_mt_input; models/wide_and_deep_multitable/src/wide_and_deep.py:
+    286-352, 361-424): the input row of dense_layer_1 -- Concat((val_hldr * 1, ind_emb, emb128_id_emb, emb64_sgl_emb, mult_embedding)) --
+    in the net's type, and the wide logit term beside it; no [B, F, D] lookup result and no concat reaches memory.
+    cont: float32 [B, C] (columns 0 .. C-1 of the row) with wide_cont [C], or None for C = 0; wide_bias: float32 [1].
+    segments: MtSegment records or plain tuples in MtSegment's field order; the caller lays the columns out (every block a multiple of
+    8 wide at a multiple of 8, disjoint, inside [0, K0); K0 defaults to the end of the last block; columns nobody covers are written
+    as zero).  Per block the arithmetic is gather_rows' (pooled False) or gather_pool_fields' mode "mean" (pooled True), bit for bit.
+    out: a [B, K0] float32 / bfloat16 / float16 tensor or column block (unit column stride: columns past K0 of a wider matrix are left
+    alone); wide_out: a contiguous float32 [B] tensor; both for persistent buffers.  Returns (x [B, K0], wide [B] float32)."""
+    segs = [s if isinstance(s, MtSegment) else MtSegment(*s) for s in segments]
+    if len(segs) > MT_MAX_SEGS:
+        raise ValueError(f"multitable_input takes at most {MT_MAX_SEGS} segments, got {len(segs)}")
+    _need_cuda(cont, wide_cont, wide_bias, out, wide_out, *[t for s in segs for t in (s.table, s.ids, s.mask, s.wide)])
+    if cont is not None:
+        if cont.dtype != torch.float32 or cont.dim() != 2 or cont.stride(1) != 1:
+            raise TypeError("cont must be a float32 [B, C] tensor with unit column stride")
+        if wide_cont is None or wide_cont.dtype != torch.float32 or wide_cont.numel() != cont.shape[1] or not wide_cont.is_contiguous():
+            raise TypeError("wide_cont must be a contiguous float32 [C] tensor")
+        B, Cc = cont.shape
+        ld_cont = cont.stride(0) if B > 1 else Cc
+    elif segs:
+        B, Cc, ld_cont = segs[0].ids.shape[0], 0, 0
+    else:
+        raise TypeError("multitable_input needs cont or at least one segment")
+    if wide_bias is None or wide_bias.dtype != torch.float32 or wide_bias.numel() != 1:
+        raise TypeError("wide_bias must be a float32 [1] tensor")
+    dev = cont.device if cont is not None else segs[0].table.device
+    arr = (MtSeg * max(len(segs), 1))()
+    keep = []                        # contiguous copies stay referenced until the launch is issued
+    end = Cc
+    for i, s in enumerate(segs):
+        V, D, ld = _table(s.table)
+        ids, mask = s.ids, s.mask
+        if ids.dtype != torch.int32 or ids.dim() not in (1, 2) or ids.shape[0] != B:
+            raise TypeError(f"segment {i}: ids must be int32 [{B}, L] (or [{B}])")
+        if ids.dim() == 1:
+            ids = ids.unsqueeze(1)
+            mask = mask.unsqueeze(1) if mask is not None and mask.dim() == 1 else mask
+        L = ids.shape[1]
+        if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
+            raise TypeError(f"segment {i}: mask must be float32 of the shape of ids")
+        if ids.stride(1) != 1 or (mask is not None and mask.stride() != ids.stride()):      # one layout for both
+            ids = ids.contiguous()
+            mask = mask.contiguous() if mask is not None else None
+        if s.wide is not None and (s.wide.dtype != torch.float32 or s.wide.numel() != V or not s.wide.is_contiguous()):
+            raise TypeError(f"segment {i}: wide must be a contiguous float32 [{V}] tensor")
+        keep += [ids, mask]
+        arr[i] = MtSeg(s.table.data_ptr(), V, ld, D, s.wide.data_ptr() if s.wide is not None else None, ids.data_ptr(),
+                       ids.stride(0) if B > 1 else L, mask.data_ptr() if mask is not None else None, L, int(bool(s.pooled)), int(s.col))
+        end = max(end, int(s.col) + D * (1 if s.pooled else L))
+    K0 = end if K0 is None else int(K0)
+    if out is None:
+        if out_dtype not in _KIND:
+            raise TypeError("multitable_input out_dtype must be float32, bfloat16 or float16")
+        out = torch.empty((B, K0), dtype=out_dtype, device=dev)
+    elif out.dtype not in _KIND or out.dim() != 2 or tuple(out.shape) != (B, K0) or out.stride(1) != 1:
+        raise TypeError(f"multitable_input out must be a [{B}, {K0}] float32 / bfloat16 / float16 tensor with unit column stride")
+    if wide_out is None:
+        wide_out = torch.empty((B,), dtype=torch.float32, device=dev)
+    elif wide_out.dtype != torch.float32 or tuple(wide_out.shape) != (B,) or not wide_out.is_contiguous():
+        raise TypeError(f"multitable_input wide_out must be a contiguous float32 [{B}] tensor")
+    _lib.call("mrec_mt_input", _ptr(cont), ld_cont, Cc, _ptr(wide_cont), _ptr(wide_bias), C.cast(arr, C.c_void_p), len(segs), B, _ptr(out),
+              _KIND[out.dtype], out.stride(0) if B > 1 else K0, K0, _ptr(wide_out), _stream())
+    del keep
+    return out, wide_out
 
 
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
