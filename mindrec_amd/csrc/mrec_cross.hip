@@ -16,6 +16,8 @@
 //     db_l = colsum(dy) + sum_{l'>l} w_l' * sum_rows t_l'
 // One pass reads x0 and dy, writes dx0, and keeps the [L, D] batch sums sum_rows u_l x0 in
 // registers per wave; per-wave slabs are then added in wave order (bitwise reproducible).
+#include <type_traits>
+
 #include "mrec_common.h"
 
 namespace {
@@ -70,14 +72,8 @@ __device__ __forceinline__ void row_store(__amdgpu_buffer_rsrc_t r, int voff, in
 // weights per 9 KB row), and with the padding the inner loops need no `c < D` guards -- a guard per LDS
 // read compiled to a branch per read and serialised the reads (~1100 branches in the backward kernel).
 // WLDS = false reads w / b from global memory through a per-layer buffer resource (also guard-free) for stacks
-// too large for LDS.
-template <bool WLDS>
-__device__ __forceinline__ float wload(const float* __restrict__ g, const float* s, int l, int lane, int j, int D, int DP) {
-    if (WLDS) return s[l * DP + lane + 64 * j];
-    return row_load(row_rsrc(g + (int64_t)l * D, D * 4), lane * 4, j * 256);
-}
-
-template <int NT, int DP, bool WITH_B = true>
+// too large for LDS (the layouts' wload below).
+template <int NT, int DP>
 __device__ __forceinline__ void stage_wb(const float* __restrict__ w, const float* __restrict__ b, int L, int D,
                                          float* sw, float* sb) {
     const int total = L * DP;
@@ -89,7 +85,7 @@ __device__ __forceinline__ void stage_wb(const float* __restrict__ w, const floa
             const int l = i / DP, cc = i - l * DP;
             const bool ok = i < total && cc < D;
             const int src = ok ? l * D + cc : 0;
-            const float a = w[src], bb = WITH_B ? b[src] : 0.0f;
+            const float a = w[src], bb = b[src];
             tw[u] = ok ? a : 0.0f;
             tb[u] = ok ? bb : 0.0f;
         }
@@ -98,7 +94,7 @@ __device__ __forceinline__ void stage_wb(const float* __restrict__ w, const floa
             const int i = base + u * NT + (int)threadIdx.x;
             if (i < total) {
                 sw[i] = tw[u];
-                if (WITH_B) sb[i] = tb[u];
+                sb[i] = tb[u];
             }
         }
     }
@@ -139,186 +135,166 @@ __device__ __forceinline__ f4 bc4(float u) { return f4{u, u, u, u}; }
 __device__ __forceinline__ float hsum4(f4 v) { return (v.x + v.y) + (v.z + v.w); }
 
 
-// w (and b) of all layers into LDS in ONE memory round trip: the (array, layer, 256-column block) pieces are dealt out to the
+// w and b of all layers into LDS in ONE memory round trip: the (array, layer, 256-column block) pieces are dealt out to the
 // waves, every wave requests its pieces as 16-byte buffer loads (the range check pads the rows with zeros) before it stores
 // the first.  (stage_wb above takes total / (4 NT) dependent rounds: two in the forward -- 4 of its 32 us.)
-template <int NT, int NPL, bool WITH_B>
+template <int NT, int NPL>
 __device__ __forceinline__ void stage_rows4(const float* __restrict__ w, const float* __restrict__ b, int L, int D,
                                             float* sw, float* sb) {
     constexpr int DP = NPL * 64, NQ = NPL / 4, WPB = NT / 64;
-    constexpr int NSTG = ((WITH_B ? 2 : 1) * LMAX * NQ + WPB - 1) / WPB;
+    constexpr int NSTG = (2 * LMAX * NQ + WPB - 1) / WPB;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int per = L * NQ, total = (WITH_B ? 2 : 1) * per;
+    const int per = L * NQ, total = 2 * per;
     f4 stg[NSTG];
 #pragma unroll
     for (int i = 0; i < NSTG; ++i) {
         const int pc = wave + i * WPB;
         const bool ok = pc < total;
         const int a = pc >= per ? 1 : 0, r = pc - a * per, l = r / NQ, q = r - l * NQ;
-        const float* src = (WITH_B && a) ? b : w;
+        const float* src = a ? b : w;
         stg[i] = row_load4(row_rsrc(src + (int64_t)(ok ? l : 0) * D, ok ? D * 4 : 0), lane * 16, 1024 * q);
     }
 #pragma unroll
     for (int i = 0; i < NSTG; ++i) {
         const int pc = wave + i * WPB;
         const int a = pc >= per ? 1 : 0, r = pc - a * per, l = r / NQ, q = r - l * NQ;
-        if (pc < total) *(f4*)(((WITH_B && a) ? sb : sw) + l * DP + 256 * q + 4 * lane) = stg[i];
+        if (pc < total) *(f4*)((a ? sb : sw) + l * DP + 256 * q + 4 * lane) = stg[i];
     }
     __syncthreads();
 }
 
-// forward, 4 columns per lane (NPL a multiple of 4: every D > 128): 16-byte row accesses, ds_read_b128 for w and b, packed
-// fp32 arithmetic; the update keeps the oracle's operation order (x * s + b, then + x_l; no fused multiply-add)
-template <bool WLDS>
-__device__ __forceinline__ f4 wload4(const float* __restrict__ g, const float* s, int l, int lane, int q, int D, int DP) {
-    if (WLDS) return *(const f4*)(s + l * DP + 256 * q + 4 * lane);
-    return row_load4(row_rsrc(g + (int64_t)l * D, D * 4), lane * 16, q * 1024);
-}
 constexpr int FWD_NT = 1024;   // 16 waves: one block per CU, w / b staged once per CU
 constexpr int BWD_NT = 512;   // 8 waves: one block per CU at two waves per SIMD -> one slab per CU for the reduction kernel
 
-// The row side of the forward, one column per lane (columns lane + 64 j): a wave's pair of rows A, B (row B absent: a resource
-// of 0 bytes, all zeros) from x0 into registers, and the L layers on them -- x_l stays in lA / lB, x0 in xA / xB.  Called by the
-// stack's own kernel (k_cross_fwd, which then stores x_L) and by the evaluation kernel (k_dcn_predict, which takes x_L's dot with
-// W3[H:] instead): the same device code, so the same bits of x_L.
+// ---- the two lane layouts of the forward-shaped kernels (k_cross_fwd, k_dcn_predict) ----
+// Lane1<NPL>: one column per lane, slot j = column lane + 64 j (NPL = 1, 2: D <= 128).  4-byte row accesses, plain.
+// Lane4<NPL>: four columns per lane, slot q = columns 256 q + 4 lane + {0..3} (NPL a multiple of 4: every D > 128).  16-byte row
+//             accesses (results nontemporal), ds_read_b128 for w and b, packed fp32 arithmetic.
+// A layout states everything in which the two forms of a kernel differ, and nothing else; the kernels are written once over it.
+// What differs matters for bits or for speed: the slot's register type; the bytes a lane owns per slot and the slot stride; the
+// row accesses and their aux bits; how w / b / W3[H:] are read (LDS, or a range-checked resource when !WLDS); how a lane folds
+// its slot before the wave sum; WHICH wave sum the stack takes (wave_sum's butterfly at one column, wave_sum_dpp's lane-order tree
+// at four: different orders of additions, each pinned bit for bit by tests/_cross_ref.py cross_fwd_bits); the staging routine
+// and the deepest stack it takes (stage_wb loops: any depth; stage_rows4 holds its pieces in a register array sized for LMAX
+// layers: a deeper stack reads w / b from global memory); the 256-column blocks of W3[H:] in the evaluation kernel's LDS.
 template <int NPL>
-__device__ __forceinline__ void cross_rows_load(__amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB, int voff, float (&xA)[NPL],
-                                                float (&lA)[NPL], float (&xB)[NPL], float (&lB)[NPL]) {
+struct Lane1 {
+    typedef float reg;
+    static constexpr int DP = NPL * 64, NS = NPL, LANE_BYTES = 4, SLOT_BYTES = 256, STAGE_LMAX = 1 << 30, XB = (DP + 255) / 256;
+    static __device__ __forceinline__ reg bc(float u) { return u; }
+    static __device__ __forceinline__ float fold(reg p) { return p; }
+    static __device__ __forceinline__ float stack_sum(float p) { return wave_sum(p); }
+    static __device__ __forceinline__ reg load(__amdgpu_buffer_rsrc_t r, int voff, int soff) { return row_load(r, voff, soff); }
+    static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, int voff, int soff, reg v) { row_store(r, voff, soff, v); }
+    template <bool WLDS>
+    static __device__ __forceinline__ reg wload(const float* __restrict__ g, const float* s, int l, int lane, int j, int D) {
+        if (WLDS) return s[l * DP + lane + 64 * j];
+        return row_load(row_rsrc(g + (int64_t)l * D, D * 4), lane * 4, j * 256);
+    }
+    static __device__ __forceinline__ void stage(const float* __restrict__ w, const float* __restrict__ b, int L, int D, float* sw,
+                                                 float* sb) {
+        stage_wb<FWD_NT, DP>(w, b, L, D, sw, sb);
+    }
+};
+template <int NPL>
+struct Lane4 {
+    static_assert(NPL % 4 == 0, "256-column blocks");
+    typedef f4 reg;
+    static constexpr int DP = NPL * 64, NS = NPL / 4, LANE_BYTES = 16, SLOT_BYTES = 1024, STAGE_LMAX = LMAX, XB = NS;
+    static __device__ __forceinline__ reg bc(float u) { return bc4(u); }
+    static __device__ __forceinline__ float fold(reg p) { return hsum4(p); }
+    static __device__ __forceinline__ float stack_sum(float p) { return wave_sum_dpp(p); }
+    static __device__ __forceinline__ reg load(__amdgpu_buffer_rsrc_t r, int voff, int soff) { return act_load4(r, voff, soff); }
+    static __device__ __forceinline__ void store(__amdgpu_buffer_rsrc_t r, int voff, int soff, reg v) { act_store4(r, voff, soff, v); }
+    template <bool WLDS>
+    static __device__ __forceinline__ reg wload(const float* __restrict__ g, const float* s, int l, int lane, int q, int D) {
+        if (WLDS) return *(const f4*)(s + l * DP + 256 * q + 4 * lane);
+        return row_load4(row_rsrc(g + (int64_t)l * D, D * 4), lane * 16, q * 1024);
+    }
+    static __device__ __forceinline__ void stage(const float* __restrict__ w, const float* __restrict__ b, int L, int D, float* sw,
+                                                 float* sb) {
+        stage_rows4<FWD_NT, NPL>(w, b, L, D, sw, sb);
+    }
+};
+
+// The row side of the forward: a wave's pair of rows A, B (row B absent: a resource of 0 bytes, all zeros) from x0 into
+// registers, and the L layers on them -- x_l stays in lA / lB, x0 in xA / xB.  Called by the stack's own kernel (k_cross_fwd, which
+// then stores x_L) and by the evaluation kernel (k_dcn_predict, which takes x_L's dot with W3[H:] instead): the same device code, so
+// the same bits of x_L.  The update keeps the oracle's operation order (x * s + b, then + x_l; no fused multiply-add).
+template <class Ly>
+__device__ __forceinline__ void cross_rows_load(__amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB, int voff,
+                                                typename Ly::reg (&xA)[Ly::NS], typename Ly::reg (&lA)[Ly::NS],
+                                                typename Ly::reg (&xB)[Ly::NS], typename Ly::reg (&lB)[Ly::NS]) {
 #pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-        xA[j] = row_load(rA, voff, 256 * j);
-        xB[j] = row_load(rB, voff, 256 * j);
+    for (int j = 0; j < Ly::NS; ++j) {
+        xA[j] = Ly::load(rA, voff, Ly::SLOT_BYTES * j);
+        xB[j] = Ly::load(rB, voff, Ly::SLOT_BYTES * j);
         lA[j] = xA[j];
         lB[j] = xB[j];
     }
 }
-template <int NPL, bool WLDS>
+template <class Ly, bool WLDS>
 __device__ __forceinline__ void cross_rows_stack(const float* __restrict__ w, const float* __restrict__ b, const float* sw,
-                                                 const float* sb, int L, int lane, int D, const float (&xA)[NPL], float (&lA)[NPL],
-                                                 const float (&xB)[NPL], float (&lB)[NPL]) {
-    constexpr int DP = NPL * 64;
+                                                 const float* sb, int L, int lane, int D, const typename Ly::reg (&xA)[Ly::NS],
+                                                 typename Ly::reg (&lA)[Ly::NS], const typename Ly::reg (&xB)[Ly::NS],
+                                                 typename Ly::reg (&lB)[Ly::NS]) {
+    typedef typename Ly::reg reg;
     for (int l = 0; l < L; ++l) {
-        float pA = 0.0f, pB = 0.0f;
+        reg pA = Ly::bc(0.0f), pB = Ly::bc(0.0f);
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) {
-            const float wv = wload<WLDS>(w, sw, l, lane, j, D, DP);
+        for (int j = 0; j < Ly::NS; ++j) {
+            const reg wv = Ly::template wload<WLDS>(w, sw, l, lane, j, D);
             pA += lA[j] * wv;
             pB += lB[j] * wv;
         }
-        const float sA = wave_sum(pA), sB = wave_sum(pB);
+        const reg sA = Ly::bc(Ly::stack_sum(Ly::fold(pA))), sB = Ly::bc(Ly::stack_sum(Ly::fold(pB)));
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) {
-            const float bv = wload<WLDS>(b, sb, l, lane, j, D, DP);
+        for (int j = 0; j < Ly::NS; ++j) {
+            const reg bv = Ly::template wload<WLDS>(b, sb, l, lane, j, D);
             lA[j] = (xA[j] * sA + bv) + lA[j];
             lB[j] = (xB[j] * sB + bv) + lB[j];
         }
     }
 }
 
-// The same, four columns per lane (columns 256 q + 4 lane + {0..3})
-template <int NQ>
-__device__ __forceinline__ void cross_rows_load4(__amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB, int voff, f4 (&xA)[NQ],
-                                                 f4 (&lA)[NQ], f4 (&xB)[NQ], f4 (&lB)[NQ]) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        xA[q] = act_load4(rA, voff, 1024 * q);
-        xB[q] = act_load4(rB, voff, 1024 * q);
-        lA[q] = xA[q];
-        lB[q] = xB[q];
-    }
-}
-template <int NQ, bool WLDS>
-__device__ __forceinline__ void cross_rows_stack4(const float* __restrict__ w, const float* __restrict__ b, const float* sw,
-                                                  const float* sb, int L, int lane, int D, const f4 (&xA)[NQ], f4 (&lA)[NQ],
-                                                  const f4 (&xB)[NQ], f4 (&lB)[NQ]) {
-    constexpr int DP = NQ * 256;
-    for (int l = 0; l < L; ++l) {
-        f4 pA = bc4(0.0f), pB = bc4(0.0f);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const f4 wv = wload4<WLDS>(w, sw, l, lane, q, D, DP);
-            pA += lA[q] * wv;
-            pB += lB[q] * wv;
-        }
-        const f4 sA = bc4(wave_sum_dpp(hsum4(pA))), sB = bc4(wave_sum_dpp(hsum4(pB)));
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const f4 bv = wload4<WLDS>(b, sb, l, lane, q, D, DP);
-            lA[q] = (xA[q] * sA + bv) + lA[q];
-            lB[q] = (xB[q] * sB + bv) + lB[q];
-        }
-    }
-}
-
-template <int NPL, bool WLDS>
+template <class Ly, bool WLDS>
 __global__ __launch_bounds__(FWD_NT) void k_cross_fwd(const float* __restrict__ x0, const float* __restrict__ w,
                                                       const float* __restrict__ b, int L, int64_t B, int D,
                                                       float* __restrict__ out) {
-    constexpr int DP = NPL * 64;
+    typedef typename Ly::reg reg;
+    constexpr int DP = Ly::DP, NS = Ly::NS;
     extern __shared__ float smem[];
     float* sw = smem;
     float* sb = smem + (WLDS ? L * DP : 0);
-    if (WLDS) stage_wb<FWD_NT, DP>(w, b, L, D, sw, sb);
+    if (WLDS) Ly::stage(w, b, L, D, sw, sb);
     const int lane = threadIdx.x & 63;
-    const int voff = lane * 4;
+    const int voff = lane * Ly::LANE_BYTES;
     constexpr int WPB = FWD_NT / 64;
     const int64_t nw = (int64_t)gridDim.x * WPB;
-    // two rows per wave per iteration: one LDS read of w / b serves both
+    // two rows per wave per iteration: one LDS read of w / b serves both.  (Four columns per lane, requesting a wave's next pair
+    // right behind the stores of the one before, the first pair in front of the staging: 31.1 us against 28.4 at B = 16384 -- not
+    // kept.)
     for (int64_t rowA = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6); rowA < B; rowA += 2 * nw) {
         const int64_t rowB = rowA + nw;
         const bool vB = rowB < B;
-        float xA[NPL], lA[NPL], xB[NPL], lB[NPL];
+        reg xA[NS], lA[NS], xB[NS], lB[NS];
         const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
         const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
-        cross_rows_load<NPL>(rA, rB, voff, xA, lA, xB, lB);
-        cross_rows_stack<NPL, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
+        cross_rows_load<Ly>(rA, rB, voff, xA, lA, xB, lB);
+        cross_rows_stack<Ly, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
         const __amdgpu_buffer_rsrc_t oA = row_rsrc(out + rowA * D, D * 4);
         const __amdgpu_buffer_rsrc_t oB = row_rsrc(out + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) {
-            row_store(oA, voff, 256 * j, lA[j]);
-            row_store(oB, voff, 256 * j, lB[j]);
-        }
-    }
-}
-
-template <int NPL, bool WLDS>
-__global__ __launch_bounds__(FWD_NT) void k_cross_fwd4(const float* __restrict__ x0, const float* __restrict__ w,
-                                                       const float* __restrict__ b, int L, int64_t B, int D,
-                                                       float* __restrict__ out) {
-    static_assert(NPL % 4 == 0, "256-column blocks");
-    constexpr int DP = NPL * 64, NQ = NPL / 4;
-    extern __shared__ float smem[];
-    float* sw = smem;
-    float* sb = smem + (WLDS ? L * DP : 0);
-    if (WLDS) stage_rows4<FWD_NT, NPL, true>(w, b, L, D, sw, sb);
-    const int lane = threadIdx.x & 63;
-    const int voff = lane * 16;
-    constexpr int WPB = FWD_NT / 64;
-    const int64_t nw = (int64_t)gridDim.x * WPB;
-    // two rows per wave per iteration: one LDS read of w / b serves both.  (Requesting a wave's next pair right behind the
-    // stores of the one before, the first pair in front of the staging: 31.1 us against 28.4 at B = 16384 -- not kept.)
-    for (int64_t rowA = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6); rowA < B; rowA += 2 * nw) {
-        const int64_t rowB = rowA + nw;
-        const bool vB = rowB < B;
-        f4 xA[NQ], lA[NQ], xB[NQ], lB[NQ];
-        const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
-        const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
-        cross_rows_load4<NQ>(rA, rB, voff, xA, lA, xB, lB);
-        cross_rows_stack4<NQ, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
-        const __amdgpu_buffer_rsrc_t oA = row_rsrc(out + rowA * D, D * 4);
-        const __amdgpu_buffer_rsrc_t oB = row_rsrc(out + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            act_store4(oA, voff, 1024 * q, lA[q]);
-            act_store4(oB, voff, 1024 * q, lB[q]);
+        for (int j = 0; j < NS; ++j) {
+            Ly::store(oA, voff, Ly::SLOT_BYTES * j, lA[j]);
+            Ly::store(oB, voff, Ly::SLOT_BYTES * j, lB[j]);
         }
     }
 }
 
 // ---- evaluation: the cross stack and the output end of Deep&Cross in ONE launch (deep_and_cross.py:300-309 + the loss :326-331) ----
 //     logit = [d2 | x_L] . W3 + b3,  prob = sigmoid(logit),  with a label: the row's SigmoidCrossEntropyWithLogits term
-// The wave that holds x_L of a row in registers (cross_rows_stack / cross_rows_stack4 above: the stack's own device code) takes its
+// The wave that holds x_L of a row in registers (cross_rows_stack above: the stack's own device code) takes its
 // dot with W3[H:] at once, so x_L -- the [B, X] tensor mrec_cross_layers_f32 writes and the output layer reads back -- never
 // exists in memory.  d2 [B, H] (H % 4 == 0, H <= 1024) is read as up to four 16-byte slots a lane, before the stack runs.
 //
@@ -331,15 +307,15 @@ __global__ __launch_bounds__(FWD_NT) void k_cross_fwd4(const float* __restrict__
 //   deep half, lane l, slots q = 0 .. 3 of columns 256 q + 4 l + {0, 1, 2, 3} =: (x, y, z, w):
 //       dd = +0;  dd += (d.x W.x + d.y W.y) + (d.z W.z + d.w W.w)                     for q = 0, 1, 2, 3
 //   cross half, one column per lane (X <= 128; lane l owns columns l + 64 j):
-//       pc = +0;  pc += c_j W_j                                                       for j = 0 .. NPL - 1
+//       pc = +0;  pc += c_j W_j                                                       for j = 0 .. NS - 1
 //   cross half, four columns per lane (X > 128; lane l owns columns 256 q + 4 l + {0, 1, 2, 3}):
-//       p = (+0, +0, +0, +0);  p += c_q * W_q componentwise                           for q = 0 .. NQ - 1
+//       p = (+0, +0, +0, +0);  p += c_q * W_q componentwise                           for q = 0 .. NS - 1
 //       pc = (p.x + p.y) + (p.z + p.w)
 //   the wave, each half by itself: wave_sum_dpp: lanes pairwise (t_0 + t_1), (t_2 + t_3), ..; those sums pairwise; .. six levels,
 //                    a balanced tree over the lanes in lane order (every step adds two values that differ only in which is named
 //                    first).  The deep half's tree is taken BEFORE the stack runs and waits in a scalar register.
 //   logit = (tree(pc) + tree(dd)) + b3                                                (cross half + deep half, then the bias)
-// The longest path from a product to the logit is the cross half's at four columns a lane: the product, NQ <= 8 additions into p,
+// The longest path from a product to the logit is the cross half's at four columns a lane: the product, NS <= 8 additions into p,
 // 2 in pc, 6 in the tree, the deep half, the bias: 19 roundings (deep half: 1 + 2 + 4 + 6 + 2 = 15).
 // NOT k_dcn_head's logit_out bit for bit: that kernel's lanes own float2 slots of the cross half and float4 slots q 64 + l of
 // the deep half and add them in another order (mrec_dcn.hip); the two logits agree to the rounding bounds of their orders.
@@ -350,10 +326,10 @@ __global__ __launch_bounds__(FWD_NT) void k_cross_fwd4(const float* __restrict__
 // order, then the tree above), times the rounded 1 / B.  No atomics: the same bits on every run.
 constexpr int PRED_HQ = 4;                       // 16-byte slots a lane of the deep half: H <= 64 * 4 * PRED_HQ = 1024
 constexpr int PRED_HP = 64 * 4 * PRED_HQ;        // W3[:H] in LDS, padded
-constexpr int pred_xblocks(int npl) { return (npl * 64 + 255) / 256; }      // 256-column blocks of W3[H:] in LDS
 
-// W3 into LDS: wave q < XB requests block q of W3[H:] (WLDS only), wave 8 + q block q of W3[:H], as one 16-byte buffer load a
-// lane (the range check pads with zeros); requested BEFORE w / b are staged, stored behind them -- one memory round trip for all
+// W3 into LDS: wave q < XB (the layout's count of 256-column blocks) requests block q of W3[H:] (WLDS only), wave 8 + q block q
+// of W3[:H], as one 16-byte buffer load a lane (the range check pads with zeros); requested BEFORE w / b are staged, stored
+// behind them -- one memory round trip for all
 template <int XB, bool WLDS>
 __device__ __forceinline__ f4 pred_w3_request(const float* __restrict__ w3, int H, int X, int lane, int wave) {
     static_assert(XB <= 8 && 8 + PRED_HQ <= FWD_NT / 64, "one piece a wave");
@@ -417,14 +393,15 @@ __device__ __forceinline__ void pred_block_loss(float lsum, float* __restrict__ 
     }
 }
 
-template <int NPL, bool WLDS>
+template <class Ly, bool WLDS>
 __global__ __launch_bounds__(FWD_NT) void k_dcn_predict(const float* __restrict__ x0, const float* __restrict__ w,
                                                         const float* __restrict__ b, int L, int64_t B, int D,
                                                         const float* __restrict__ d2, int64_t ldd, int H,
                                                         const float* __restrict__ w3, const float* __restrict__ b3,
                                                         const float* __restrict__ label, float* __restrict__ logit,
                                                         float* __restrict__ prob, float* __restrict__ partial) {
-    constexpr int DP = NPL * 64, XB = pred_xblocks(NPL);
+    typedef typename Ly::reg reg;
+    constexpr int DP = Ly::DP, NS = Ly::NS, XB = Ly::XB;
     extern __shared__ float smem[];
     float* sw = smem;
     float* sb = smem + (WLDS ? L * DP : 0);
@@ -432,85 +409,35 @@ __global__ __launch_bounds__(FWD_NT) void k_dcn_predict(const float* __restrict_
     float* s3d = s3c + (WLDS ? XB * 256 : 0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const f4 piece = pred_w3_request<XB, WLDS>(w3, H, D, lane, wave);
-    if (WLDS) stage_wb<FWD_NT, DP>(w, b, L, D, sw, sb);
+    if (WLDS) Ly::stage(w, b, L, D, sw, sb);
     pred_w3_commit<XB, WLDS>(piece, s3c, s3d, lane, wave);
     const float bias = b3[0];
-    const int voff = lane * 4;
+    const int voff = lane * Ly::LANE_BYTES;
     constexpr int WPB = FWD_NT / 64;
     const int64_t nw = (int64_t)gridDim.x * WPB;
     float lsum = 0.0f;
     for (int64_t rowA = (int64_t)blockIdx.x * WPB + wave; rowA < B; rowA += 2 * nw) {
         const int64_t rowB = rowA + nw;
         const bool vB = rowB < B;
-        float xA[NPL], lA[NPL], xB[NPL], lB[NPL];
+        reg xA[NS], lA[NS], xB[NS], lB[NS];
         f4 dA[PRED_HQ], dB[PRED_HQ];
         const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
         const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
-        cross_rows_load<NPL>(rA, rB, voff, xA, lA, xB, lB);
+        cross_rows_load<Ly>(rA, rB, voff, xA, lA, xB, lB);
         pred_deep_load(row_rsrc(d2 + rowA * ldd, H * 4), lane, dA);
         pred_deep_load(row_rsrc(d2 + (vB ? rowB : rowA) * ldd, vB ? H * 4 : 0), lane, dB);
         const float deepA = wave_sum_dpp(pred_deep_dot(dA, s3d, lane)), deepB = wave_sum_dpp(pred_deep_dot(dB, s3d, lane));
         __builtin_amdgcn_sched_barrier(0);       // the deep slots die here, in front of x_l
-        cross_rows_stack<NPL, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
-        float pA = 0.0f, pB = 0.0f;
+        cross_rows_stack<Ly, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
+        reg pA = Ly::bc(0.0f), pB = Ly::bc(0.0f);
 #pragma unroll
-        for (int j = 0; j < NPL; ++j) {
-            const float wv = wload<WLDS>(w3 + H, s3c, 0, lane, j, D, DP);
+        for (int j = 0; j < NS; ++j) {
+            const reg wv = Ly::template wload<WLDS>(w3 + H, s3c, 0, lane, j, D);
             pA += lA[j] * wv;
             pB += lB[j] * wv;
         }
-        const float tA = wave_sum_dpp(pA) + deepA, tB = wave_sum_dpp(pB) + deepB;
-        lsum += pred_row_out(tA, bias, label, rowA, lane, logit, prob);
-        if (vB) lsum += pred_row_out(tB, bias, label, rowB, lane, logit, prob);
-        lsum = wave_uniform(lsum);
-    }
-    if (label) pred_block_loss(lsum, partial);
-}
-
-template <int NPL, bool WLDS>
-__global__ __launch_bounds__(FWD_NT) void k_dcn_predict4(const float* __restrict__ x0, const float* __restrict__ w,
-                                                         const float* __restrict__ b, int L, int64_t B, int D,
-                                                         const float* __restrict__ d2, int64_t ldd, int H,
-                                                         const float* __restrict__ w3, const float* __restrict__ b3,
-                                                         const float* __restrict__ label, float* __restrict__ logit,
-                                                         float* __restrict__ prob, float* __restrict__ partial) {
-    static_assert(NPL % 4 == 0, "256-column blocks");
-    constexpr int DP = NPL * 64, NQ = NPL / 4;
-    extern __shared__ float smem[];
-    float* sw = smem;
-    float* sb = smem + (WLDS ? L * DP : 0);
-    float* s3c = smem + (WLDS ? 2 * L * DP : 0);
-    float* s3d = s3c + (WLDS ? DP : 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const f4 piece = pred_w3_request<NQ, WLDS>(w3, H, D, lane, wave);
-    if (WLDS) stage_rows4<FWD_NT, NPL, true>(w, b, L, D, sw, sb);
-    pred_w3_commit<NQ, WLDS>(piece, s3c, s3d, lane, wave);
-    const float bias = b3[0];
-    const int voff = lane * 16;
-    constexpr int WPB = FWD_NT / 64;
-    const int64_t nw = (int64_t)gridDim.x * WPB;
-    float lsum = 0.0f;
-    for (int64_t rowA = (int64_t)blockIdx.x * WPB + wave; rowA < B; rowA += 2 * nw) {
-        const int64_t rowB = rowA + nw;
-        const bool vB = rowB < B;
-        f4 xA[NQ], lA[NQ], xB[NQ], lB[NQ];
-        f4 dA[PRED_HQ], dB[PRED_HQ];
-        const __amdgpu_buffer_rsrc_t rA = row_rsrc(x0 + rowA * D, D * 4);
-        const __amdgpu_buffer_rsrc_t rB = row_rsrc(x0 + (vB ? rowB : rowA) * D, vB ? D * 4 : 0);
-        cross_rows_load4<NQ>(rA, rB, voff, xA, lA, xB, lB);
-        pred_deep_load(row_rsrc(d2 + rowA * ldd, H * 4), lane, dA);
-        pred_deep_load(row_rsrc(d2 + (vB ? rowB : rowA) * ldd, vB ? H * 4 : 0), lane, dB);
-        const float deepA = wave_sum_dpp(pred_deep_dot(dA, s3d, lane)), deepB = wave_sum_dpp(pred_deep_dot(dB, s3d, lane));
-        __builtin_amdgcn_sched_barrier(0);       // the deep slots die here, in front of x_l
-        cross_rows_stack4<NQ, WLDS>(w, b, sw, sb, L, lane, D, xA, lA, xB, lB);
-        f4 pA = bc4(0.0f), pB = bc4(0.0f);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const f4 wv = wload4<WLDS>(w3 + H, s3c, 0, lane, q, D, DP);
-            pA += lA[q] * wv;
-            pB += lB[q] * wv;
-        }
-        const float tA = wave_sum_dpp(hsum4(pA)) + deepA, tB = wave_sum_dpp(hsum4(pB)) + deepB;
+        // (the lane-order tree at either layout, whichever wave sum the stack took)
+        const float tA = wave_sum_dpp(Ly::fold(pA)) + deepA, tB = wave_sum_dpp(Ly::fold(pB)) + deepB;
         lsum += pred_row_out(tA, bias, label, rowA, lane, logit, prob);
         if (vB) lsum += pred_row_out(tB, bias, label, rowB, lane, logit, prob);
         lsum = wave_uniform(lsum);
@@ -562,12 +489,12 @@ constexpr int bwd_regions(int npl, int lt) {
 //    six-step shuffle chain);
 //  * epilogue: the eight waves' sums are added pairwise through LDS -- (w0+w4), (w1+w5), .. then (.. + ..) -- three
 //    exchanges instead of eight turns on one LDS slab; wave 0 stores the block's slab straight from its registers.
-template <int NPL, int LT, bool WLDS>
+template <int NPL, int LT>
 __global__ __launch_bounds__(BWD_NT) __attribute__((amdgpu_waves_per_eu(bwd_occ(NPL, LT), bwd_occ(NPL, LT)))) void k_cross_bwd(const float* __restrict__ x0, const float* __restrict__ w,
                                                       const float* __restrict__ b, int L, int64_t B, int D,
                                                       const float* __restrict__ dy, float* __restrict__ dx0,
                                                       float* __restrict__ slabs, int accumulate) {
-    static_assert(NPL % 4 == 0 && WLDS, "the backward is instantiated for 256-column blocks with w staged in LDS");
+    static_assert(NPL % 4 == 0, "the backward is instantiated for 256-column blocks (w always staged in LDS)");
     constexpr int DP = NPL * 64;
     constexpr int NQ = NPL / 4;             // 256-column blocks
     extern __shared__ float smem[];
@@ -870,30 +797,50 @@ int set_lds(Kern kern, size_t bytes) {
     return MREC_OK;
 }
 
+// ---- the host side of the forward-shaped launches (k_cross_fwd, k_dcn_predict) ----
+// the lane layout of a width bucket
+template <int NPL>
+using Lane = std::conditional_t<NPL % 4 == 0, Lane4<NPL>, Lane1<NPL>>;
+
+// the grid: 16 waves x 2 rows a pass, one workgroup per CU at the most (B > 0).  k_dcn_predict writes one loss partial a
+// workgroup, so k_dcn_predict_finish's count is this number too
+inline unsigned fwd_blocks(int64_t B) {
+    const int64_t blocks = mrec_cdiv(B, 2 * (FWD_NT / 64));
+    return (unsigned)(blocks > 256 ? 256 : blocks);
+}
+
+// w / b (with whatever else the kernel keeps beside them: `bytes` in all) in LDS?  They fit, and the layout's staging routine
+// takes the depth; no layers and nothing else to stage: nothing to keep there
+template <class Ly>
+bool wb_in_lds(size_t bytes, int L) { return bytes > 0 && bytes <= kMaxLds && L <= Ly::STAGE_LMAX; }
+
+template <class Kern, class... Args>
+int launch_rows(Kern kern, unsigned blocks, size_t lds, hipStream_t st, Args... args) {
+    int rc = set_lds(kern, lds);
+    if (rc != MREC_OK) return rc;
+    kern<<<blocks, FWD_NT, lds, st>>>(args...);
+    return MREC_OK;
+}
+
 template <int NPL>
 int launch_fwd(const float* x0, const float* w, const float* b, int L, int64_t B, int D, float* out, hipStream_t st) {
-    const size_t lds = (size_t)2 * L * NPL * 64 * sizeof(float);
-    int64_t blocks = mrec_cdiv(B, 2 * (FWD_NT / 64));            // 16 waves x 2 rows per pass
-    if (blocks > 256) blocks = 256;
-    if constexpr (NPL % 4 == 0) {
-        // stage_rows4 holds its pieces in a register array sized for LMAX layers: a deeper stack reads w / b from global memory
-        if (lds > 0 && lds <= kMaxLds && L <= LMAX) {
-            int rc = set_lds(k_cross_fwd4<NPL, true>, lds);
-            if (rc != MREC_OK) return rc;
-            k_cross_fwd4<NPL, true><<<(unsigned)blocks, FWD_NT, lds, st>>>(x0, w, b, L, B, D, out);
-        } else {
-            k_cross_fwd4<NPL, false><<<(unsigned)blocks, FWD_NT, 0, st>>>(x0, w, b, L, B, D, out);
-        }
-        return MREC_OK;
-    }
-    if (lds > 0 && lds <= kMaxLds) {
-        int rc = set_lds(k_cross_fwd<NPL, true>, lds);
-        if (rc != MREC_OK) return rc;
-        k_cross_fwd<NPL, true><<<(unsigned)blocks, FWD_NT, lds, st>>>(x0, w, b, L, B, D, out);
-    } else {
-        k_cross_fwd<NPL, false><<<(unsigned)blocks, FWD_NT, 0, st>>>(x0, w, b, L, B, D, out);
-    }
-    return MREC_OK;
+    using Ly = Lane<NPL>;
+    const size_t lds = (size_t)2 * L * Ly::DP * sizeof(float);
+    if (wb_in_lds<Ly>(lds, L)) return launch_rows(k_cross_fwd<Ly, true>, fwd_blocks(B), lds, st, x0, w, b, L, B, D, out);
+    return launch_rows(k_cross_fwd<Ly, false>, fwd_blocks(B), 0, st, x0, w, b, L, B, D, out);
+}
+
+// the same path choice with W3 in the LDS budget: W3[H:] beside w and b, W3[:H] always
+template <int NPL>
+int launch_predict(const float* x0, const float* w, const float* b, int L, int64_t B, int D, const float* d2, int64_t ldd, int H,
+                   const float* w3, const float* b3, const float* label, float* logit, float* prob, float* partial, unsigned blocks,
+                   hipStream_t st) {
+    using Ly = Lane<NPL>;
+    const size_t deep = (size_t)PRED_HP * sizeof(float);
+    const size_t lds = ((size_t)2 * L * Ly::DP + Ly::XB * 256) * sizeof(float) + deep;
+    if (wb_in_lds<Ly>(lds, L))
+        return launch_rows(k_dcn_predict<Ly, true>, blocks, lds, st, x0, w, b, L, B, D, d2, ldd, H, w3, b3, label, logit, prob, partial);
+    return launch_rows(k_dcn_predict<Ly, false>, blocks, deep, st, x0, w, b, L, B, D, d2, ldd, H, w3, b3, label, logit, prob, partial);
 }
 
 template <int NPL, int LT>
@@ -905,9 +852,9 @@ int launch_bwd_lt(const float* x0, const float* w, const float* b, int L, int64_
     const size_t wlds = (size_t)L * DP * sizeof(float);
     const size_t lds = wlds > xlds ? wlds : xlds;
     static_assert((size_t)bwd_regions(NPL, LT) * bwd_region_floats(NPL, LT) * sizeof(float) <= 160 * 1024, "LDS");
-    int rc = set_lds(k_cross_bwd<NPL, LT, true>, lds);
+    int rc = set_lds(k_cross_bwd<NPL, LT>, lds);
     if (rc != MREC_OK) return rc;
-    k_cross_bwd<NPL, LT, true><<<blocks, BWD_NT, lds, st>>>(x0, w, b, L, B, D, dy, dx0, slabs, acc);
+    k_cross_bwd<NPL, LT><<<blocks, BWD_NT, lds, st>>>(x0, w, b, L, B, D, dy, dx0, slabs, acc);
     return MREC_OK;
 }
 
@@ -936,30 +883,7 @@ MREC_API int mrec_cross_layers_f32(const float* x0, const float* w, const float*
     return MREC_OK;
 }
 
-namespace {
-// mrec_cross_layers_f32's grid and path choice (launch_fwd), with W3 in the LDS budget: W3[H:] beside w and b, W3[:H] always
-template <int NPL>
-int launch_predict(const float* x0, const float* w, const float* b, int L, int64_t B, int D, const float* d2, int64_t ldd, int H,
-                   const float* w3, const float* b3, const float* label, float* logit, float* prob, float* partial, hipStream_t st) {
-    constexpr bool four = NPL % 4 == 0;
-    const size_t deep = (size_t)PRED_HP * sizeof(float);
-    const size_t lds = ((size_t)2 * L * NPL * 64 + (four ? NPL * 64 : pred_xblocks(NPL) * 256)) * sizeof(float) + deep;
-    int64_t blocks = mrec_cdiv(B, 2 * (FWD_NT / 64));            // 16 waves x 2 rows per pass
-    if (blocks > 256) blocks = 256;
-    // (four columns a lane: stage_rows4 holds its pieces in a register array sized for LMAX layers)
-    const bool wlds = lds <= kMaxLds && (!four || L <= LMAX);
-    auto go = [&](auto kern, size_t bytes) {
-        int rc = set_lds(kern, bytes);
-        if (rc != MREC_OK) return rc;
-        kern<<<(unsigned)blocks, FWD_NT, bytes, st>>>(x0, w, b, L, B, D, d2, ldd, H, w3, b3, label, logit, prob, partial);
-        return (int)MREC_OK;
-    };
-    if constexpr (four) return wlds ? go(k_dcn_predict4<NPL, true>, lds) : go(k_dcn_predict4<NPL, false>, deep);
-    else return wlds ? go(k_dcn_predict<NPL, true>, lds) : go(k_dcn_predict<NPL, false>, deep);
-}
-}  // namespace
-
-/* The evaluation forward of Deep&Cross behind the hidden layers in one launch (k_dcn_predict / k_dcn_predict4; see include/mrec.h). */
+/* The evaluation forward of Deep&Cross behind the hidden layers in one launch (k_dcn_predict; see include/mrec.h). */
 MREC_API int mrec_dcn_predict_workspace_bytes(int64_t B, size_t* out) {
     if (!out || B < 0) return MREC_EINVAL;
     *out = (size_t)256 * sizeof(float) + 256;          // one loss partial a workgroup, at most 256 of them
@@ -976,13 +900,11 @@ MREC_API int mrec_dcn_predict(const float* x0, const float* cw, const float* cb,
     if (npl < 0 || H % 4 || H > PRED_HP || ldd % 4 || ((((uintptr_t)d2) | ((uintptr_t)w3)) & 15)) return MREC_EUNSUPPORTED;
     if (label && (!ws || ws_bytes < (size_t)256 * sizeof(float))) return MREC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
+    const unsigned nblk = fwd_blocks(B);                // the launch's grid and the count of its loss partials
     int rc = MREC_OK;
-    MREC_NPL_DISPATCH(npl, (rc = launch_predict<N_>(x0, cw, cb, L, B, X, d2, ldd, H, w3, b3, label, logit, prob, (float*)ws, st)));
+    MREC_NPL_DISPATCH(npl, (rc = launch_predict<N_>(x0, cw, cb, L, B, X, d2, ldd, H, w3, b3, label, logit, prob, (float*)ws, nblk, st)));
     if (rc != MREC_OK) return rc;
-    if (label) {
-        const int nblk = (int)(mrec_cdiv(B, 2 * (FWD_NT / 64)) > 256 ? 256 : mrec_cdiv(B, 2 * (FWD_NT / 64)));
-        k_dcn_predict_finish<<<1, 64, 0, st>>>((const float*)ws, nblk, 1.0f / (float)B, loss);
-    }
+    if (label) k_dcn_predict_finish<<<1, 64, 0, st>>>((const float*)ws, (int)nblk, 1.0f / (float)B, loss);
     MREC_LAUNCH_CHECK();
     return MREC_OK;
 }

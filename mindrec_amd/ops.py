@@ -2319,7 +2319,7 @@ def dcn_head_fwd_bwd(d2, c, w3, b3, label, dscale, dw3_out, db2_out, db3_out, ou
 
 
 def dcn_predict_supported(H, X, L):
-    """Shapes of the one-launch evaluation forward (csrc/mrec_cross.hip: k_dcn_predict / k_dcn_predict4): every cross width and depth
+    """Shapes of the one-launch evaluation forward (csrc/mrec_cross.hip: k_dcn_predict at either lane layout): every cross width and depth
     cross_layers takes, a last hidden width that is a multiple of 4 up to 1024."""
     return H > 0 and H % 4 == 0 and H <= 1024 and 0 < X <= 2048 and L >= 0
 

@@ -1,5 +1,5 @@
-"""Case tables, input builders and references of the one-launch Deep&Cross evaluation forward (csrc/mrec_cross.hip: k_dcn_predict /
-k_dcn_predict4 behind ops.dcn_predict; test_dcn_predict_ref.py checks them without a device, test_dcn_predict_gpu.py runs them).
+"""Case tables, input builders and references of the one-launch Deep&Cross evaluation forward (csrc/mrec_cross.hip: k_dcn_predict at
+either lane layout, behind ops.dcn_predict; test_dcn_predict_ref.py checks them without a device, test_dcn_predict_gpu.py runs them).
 
 The kernel computes logit = [d2 | c] . w3 + b3 with c = x_L, the cross stack's output, held in registers.  The references take c as
 GIVEN (on the device: ops.cross_layers' own output, whose per-row device code the kernel shares) and restate what happens behind it.
@@ -31,6 +31,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from _cross_ref import lane_tree       # the balanced tree over the 64 lane sums in lane order, shared with the stack's restatement
 from _dcn_head_cases import VALUE_LABELS, VALUE_LOGITS, loss64  # noqa: F401  (the values and the loss model of the head's tests)
 
 U = 2.0 ** -24
@@ -110,13 +111,6 @@ def logit64(d2, c, w3, b3):
     return d2.astype(np.float64) @ w3[:H].astype(np.float64) + c.astype(np.float64) @ w3[H:].astype(np.float64) + float(b3[0])
 
 
-def _tree(t):
-    """[B, 64] -> [B]: the lanes pairwise in lane order, six levels"""
-    while t.shape[1] > 1:
-        t = t[:, 0::2] + t[:, 1::2]
-    return t[:, 0]
-
-
 def logit32(d2, c, w3, b3, drop=None):
     """The kernel's logit, bit for bit.  drop: a wrong variant -- "deep" / "cross": the last owned slot of that half is left out."""
     d2, c, w3 = d2.astype(F32), c.astype(F32), w3.astype(F32)
@@ -151,7 +145,7 @@ def logit32(d2, c, w3, b3, drop=None):
         pc = np.zeros((B, 64), F32)
         for j in range(npl):
             pc = pc + pr[:, j]
-    z = (_tree(pc) + _tree(dd)) + b3.astype(F32)[0]
+    z = (lane_tree(pc) + lane_tree(dd)) + b3.astype(F32)[0]
     assert z.dtype == F32
     return z
 

@@ -50,6 +50,40 @@ def test_float64_gradient_is_the_gradient():
         assert np.abs(num - grad).max() <= 1e-7 * max(1.0, np.abs(grad).max()), k
 
 
+FWD_BAR = 1e-5      # the forward's bar (include/mrec.h; tests/test_cross_sweep_gpu.py), row_rel; the device's largest observed: 2.0e-6
+
+
+def test_forward_restatement_is_a_forward_and_sees_its_wave_sum():
+    """cross_fwd_bits, which the device is held to bit for bit, is itself within the forward's bar of the float64 stack at every
+    pinned shape; and with the two wave sums exchanged it gives other bits at some shape of EACH layout -- the difference the
+    pin exists to see is one it can see."""
+    differs = {False: 0, True: 0}
+    for B in R.BITS_B:
+        for D, L in R.BITS_DL:
+            x0, w, b, _ = R.inputs(B, D, L)
+            y = R.cross_f64(x0, w, b)[0]
+            got = R.cross_fwd_bits(x0, w, b)
+            assert got.dtype == np.float32 and got.shape == (B, D)
+            err = R.row_rel(got, y)
+            print((B, D, L), f"err {err:.2e}")
+            assert err <= FWD_BAR, (B, D, L, err)
+            swapped = R.cross_fwd_bits(x0, w, b, swap_sums=True)
+            assert R.row_rel(swapped, y) <= FWD_BAR
+            differs[D > 128] += not np.array_equal(got.view(np.int32), swapped.view(np.int32))
+    print("shapes at which the swapped wave sums change bits:", differs)
+    assert differs[False] >= 1 and differs[True] >= 1
+
+
+def test_wave_sums():
+    """Both wave sums are sums (exact on small integers), and they are different orders: 2^24 in lane 0, 1 in lanes 1 and 33.
+    The tree adds lanes 0 and 1 first and lane 33's 1 to 2^24 at the last level: both are lost to rounding.  The butterfly
+    adds lanes 1 and 33 first (d = 32), and their 2 reaches 2^24 whole at d = 1."""
+    t = np.arange(128, dtype=np.float32).reshape(2, 64)
+    assert list(R.lane_tree(t)) == [2016.0, 6112.0] and list(R.lane_butterfly(t)) == [2016.0, 6112.0]
+    t = np.zeros((1, 64), np.float32); t[0, 0] = 2.0 ** 24; t[0, 1] = 1; t[0, 33] = 1
+    assert R.lane_tree(t)[0] == 2.0 ** 24 and R.lane_butterfly(t)[0] == 2.0 ** 24 + 2
+
+
 def test_metrics():
     r = np.array([[3.0, 4.0], [0.0, 1.0]])
     a = np.array([[3.0, 4.5], [0.0, 1.0]])

@@ -9,9 +9,11 @@ the order of their additions only, which 4x covers; the floor is a few units in 
 restatement happens to land exactly.
 
 Reach of the parameter lists, counted from the dispatch in mrec_cross.hip:
-  forward   k_cross_fwd<1|2, LDS>; k_cross_fwd4<4|8|12|16|20|24|32, LDS> (L <= 8) and <4|8|12|16|20|24|32, global> (L > 8;
-            D = 2048 at L = 11 is also past the LDS-size condition): 16 of the 18 instantiations.  k_cross_fwd<1|2, global>
-            needs 2 L DP 4 > 160 KB at DP <= 128, i.e. L > 160: not reachable at a test's size, not run.
+  forward   k_cross_fwd<Lane1<1|2>, LDS> (one column per lane); k_cross_fwd<Lane4<4|8|12|16|20|24|32>, LDS> (four columns per lane,
+            L <= 8) and <Lane4<4|8|12|16|20|24|32>, global> (L > 8; D = 2048 at L = 11 is also past the LDS-size condition): 16
+            of the 18 instantiations.  k_cross_fwd<Lane1<1|2>, global> needs 2 L DP 4 > 160 KB at DP <= 128, i.e. L > 160: not
+            reachable at a test's size, not run.  test_forward_bit_for_bit holds both layouts, and the global form of Lane4, to
+            _cross_ref.cross_fwd_bits bit for bit.
   backward  k_cross_bwd<4|8|16|20|32, LT = 2|4|6|8>: all 20, each at L = LT and at L = LT - 1.
 
 Largest err_gpu / err_closed32 observed on an MI355X over the 90 backward cases of this module (the bar allows 4):
@@ -160,7 +162,7 @@ def offset_input(a, dev):
     return v
 
 
-# D = 3, 67: k_cross_fwd (4-byte accesses); 1170, 2047: k_cross_fwd4 (16-byte accesses); lead = 1: bases 4- but not 16-byte aligned
+# D = 3, 67: one column per lane (4-byte accesses); 1170, 2047: four columns per lane (16-byte accesses); lead = 1: bases 4- but not 16-byte aligned
 @pytest.mark.parametrize("D,L,lead", [(3, 3, 0), (67, 5, 1), (1170, 6, 0), (2047, 8, 1), (1170, 7, 3)])
 def test_written_exactly_once_nowhere_else(dev, D, L, lead):
     from mindrec_amd import ops
@@ -198,6 +200,30 @@ def test_written_exactly_once_nowhere_else(dev, D, L, lead):
     assert torch.equal(dw3, dw) and torch.equal(db3, db)
 
 
+@functools.lru_cache(maxsize=None)
+def bits_case(B, D, L):
+    x0, w, b, _ = R.inputs(B, D, L)
+    want = R.cross_fwd_bits(x0, w, b)
+    for v in (x0, w, b, want):
+        v.setflags(write=False)
+    return x0, w, b, want
+
+
+@pytest.mark.parametrize("D,L", R.BITS_DL)
+@pytest.mark.parametrize("B", R.BITS_B)
+def test_forward_bit_for_bit(dev, B, D, L):
+    """The forward's bits: ops.cross_layers against _cross_ref.cross_fwd_bits, the kernel's order of operations restated in
+    float32 -- lane ownership, slot order and, per layout, its own wave sum (the butterfly at one column per lane, the lane-order
+    tree at four).  The evaluation kernel's logit is held bit for bit to a dot with THIS output (test_dcn_predict_gpu.py)."""
+    from mindrec_amd import ops
+    x0, w, b, want = bits_case(B, D, L)
+    got = ops.cross_layers(T(x0, dev), T(w, dev), T(b, dev)).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == want.shape
+    differ = got.view(np.int32) != want.view(np.int32)
+    print(f"CROSSBITS B={B} D={D} L={L} elements that differ: {int(differ.sum())} of {differ.size}")
+    assert np.array_equal(got.view(np.int32), want.view(np.int32)), (B, D, L, int(differ.sum()))
+
+
 def test_out_argument_is_checked(dev):
     from mindrec_amd import ops
     x0 = torch.zeros((4, 6), device=dev); w = torch.zeros((2, 6), device=dev)
@@ -207,8 +233,9 @@ def test_out_argument_is_checked(dev):
             ops.cross_layers(x0, w, w, out=bad)
 
 
-# The forward takes any depth.  Past 8 layers k_cross_fwd4 (D > 128) reads w / b from global memory, layer by layer; D = 30, 100
-# stay on k_cross_fwd's LDS form, whose staging loop has no depth bound (its global form would need L > 160: not run).  The
+# The forward takes any depth.  Past 8 layers the four-column layout (D > 128) reads w / b from global memory, layer by layer;
+# D = 30, 100 stay on the one-column layout's LDS form, whose staging loop has no depth bound (its global form would need L > 160:
+# not run).  The
 # bias is non-zero: a stack that loses or garbles b_7, b_8 .. is far outside the bar.
 @pytest.mark.parametrize("L", [9, 12, 16])
 @pytest.mark.parametrize("D", [30, 100, 1170, 1537])
@@ -218,7 +245,7 @@ def test_forward_past_eight_layers(dev, D, L):
 
 @pytest.mark.parametrize("D", [129, 257, 513, 769, 1281])
 def test_forward_global_form_in_the_other_buckets(dev, D):
-    """k_cross_fwd4<4|8|12|16|24, global> (1170 and 1537 above are buckets 20 and 32), each at its narrowest width."""
+    """k_cross_fwd<Lane4<4|8|12|16|24>, global> (1170 and 1537 above are buckets 20 and 32), each at its narrowest width."""
     _deep_forward(dev, 40, D, 9)
 
 

@@ -1,4 +1,4 @@
-"""ops.dcn_predict (csrc/mrec_cross.hip: k_dcn_predict / k_dcn_predict4) on the device against the references of
+"""ops.dcn_predict (csrc/mrec_cross.hip: k_dcn_predict, both lane layouts) on the device against the references of
 _dcn_predict_cases.py.  c of the references is the device's own ops.cross_layers(x0, cw, cb) -- the kernel runs the same device code
 on a row and never writes it.  Per case: the logit equals the fp32 restatement bit for bit and lies within the derived bound of
 float64; prob within 0.25 bound + 2^-23 of the float64 sigmoid of the float64 logit; the loss within (B + 8) u T / B of float64 BCE of

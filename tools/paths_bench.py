@@ -39,6 +39,15 @@ b = torch.randn(L, D, device=dev) * 0.1
 dy = torch.randn(B, D, device=dev)
 show("cross_layers fwd (6 layers, one pass)", timeit(lambda: ops.cross_layers(x0, w, b)), 2 * B * D * 4)
 show("cross_layers bwd (dx0, dw, db)", timeit(lambda: ops.cross_layers_bwd(x0, w, b, dy)), 3 * B * D * 4)
+# ---- Deep&Cross evaluation forward behind the hidden layers: the same stack + the output layer over [d2 | x_L], H = 1024 (deep_layer_dim[1])
+H = 1024
+d2 = torch.relu(torch.randn(B, H, device=dev))
+w3 = torch.randn(H + D, device=dev) * (1.5 / (H + D) ** 0.5)
+b3 = torch.full((1,), 0.1, device=dev)
+label = (torch.rand(B, device=dev) < 0.3).float()
+for name, lab in (("dcn_predict (stack + head, no label)", None), ("dcn_predict (stack + head + loss)", label)):
+    out = {}
+    show(name, timeit(lambda: ops.dcn_predict(x0, w, b, d2, w3, b3, label=lab, out=out)), B * (D + H + 2) * 4)
 # ---- DeepFM FM term: vx [B, 39, 80]
 vx = torch.randn(B, 39, 80, device=dev) * 0.1
 fm, cs = ops.fm_forward(vx)

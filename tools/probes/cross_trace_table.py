@@ -17,4 +17,4 @@ for i, B in enumerate(sizes):
     f = [dur(r) for r in fin[55 * i + 10:55 * (i + 1)]]
     fw = [dur(r) for r in fwd[55 * i + 10:55 * (i + 1)]] or [float("nan")]
     print(f"{sys.argv[3] if len(sys.argv) > 3 else ''} B = {B:6d}: k_cross_bwd {sum(m) / len(m):7.1f} us   k_cross_bwd_finish {sum(f) / len(f):6.1f} us   "
-          f"k_cross_fwd4 {sum(fw) / len(fw):6.1f} us")
+          f"k_cross_fwd {sum(fw) / len(fw):6.1f} us")
