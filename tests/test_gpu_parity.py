@@ -105,16 +105,16 @@ def test_unique_and_group(dev, oracle, dtype, kind, n):
     if dtype == np.int64 and kind == "uniform":
         x = x - 2**39  # negative keys too
     u_ref, inv_ref = oracle.unique(x)
-    plan = ops.sparse_plan(T(x, dev)) if n % 2 else ops.group_by_inverse(ops.unique(T(x, dev)))   # fused and two-call forms
-    assert plan.U == u_ref.size
-    assert np.array_equal(plan.uniq.cpu().numpy(), u_ref)          # first-occurrence order, bit-exact
-    assert np.array_equal(plan.inv.cpu().numpy(), inv_ref)
     # inverted index: stable sort of positions by group
     order = np.argsort(inv_ref, kind="stable").astype(np.int32)
-    assert np.array_equal(plan.sorted_pos[:n].cpu().numpy(), order)
-    assert np.array_equal(plan.sorted_seg[:n].cpu().numpy(), inv_ref[order])
     offs = np.concatenate([[0], np.cumsum(np.bincount(inv_ref, minlength=u_ref.size))]).astype(np.int32)
-    assert np.array_equal(plan.seg_offsets[: u_ref.size + 1].cpu().numpy(), offs)
+    for plan in (ops.sparse_plan(T(x, dev)), ops.group_by_inverse(ops.unique(T(x, dev)))):           # fused and two-call forms
+        assert plan.U == u_ref.size
+        assert np.array_equal(plan.uniq.cpu().numpy(), u_ref)          # first-occurrence order, bit-exact
+        assert np.array_equal(plan.inv.cpu().numpy(), inv_ref)
+        assert np.array_equal(plan.sorted_pos[:n].cpu().numpy(), order)
+        assert np.array_equal(plan.sorted_seg[:n].cpu().numpy(), inv_ref[order])
+        assert np.array_equal(plan.seg_offsets[: u_ref.size + 1].cpu().numpy(), offs)
 
 
 def test_unique_empty(dev):
@@ -141,6 +141,9 @@ def test_unique_large_bitexact(dev, oracle):
     assert np.array_equal(plan.inv.cpu().numpy(), inv_ref)
     order = np.argsort(inv_ref, kind="stable").astype(np.int32)
     assert np.array_equal(plan.sorted_pos.cpu().numpy(), order)
+    assert np.array_equal(plan.sorted_seg.cpu().numpy(), inv_ref[order])
+    offs = np.concatenate([[0], np.cumsum(np.bincount(inv_ref, minlength=u_ref.size))]).astype(np.int32)
+    assert np.array_equal(plan.seg_offsets[: u_ref.size + 1].cpu().numpy(), offs)
 
 
 def test_fill_normal_bitexact(dev, oracle):

@@ -1,8 +1,8 @@
 """The key index and the step's plan through the pieces their host and device layers share: the tile scan of mrec_common.h past one
 look-back round (65 x 2048 + 1 items: 66 tiles, one more than the 64 a round reads, the last one ragged) in each kernel that runs it --
 the plan's rank kernel, the lookup chain's place kernel, evict -- and the entries that go through FindWs / rank_flags / launch_rebuild /
-by_key.  References: numpy for the plan (first-occurrence Unique, stable argsort), tests/_map_model.py for the index; everything is an
-integer and compared exactly.  Already held elsewhere and not repeated: the place kernel past the look-back window for BOTH key widths
+by_key.  References: numpy for the plan (first-occurrence Unique, stable argsort: plan_ref of tests/_plan_cases.py),
+tests/_map_model.py for the index; everything is an integer and compared exactly.  Already held elsewhere and not repeated: the place kernel past the look-back window for BOTH key widths
 at 69 tiles (tests/test_map_edges_gpu.py::test_many_tiles_past_the_lookback_window -- the int64 case below is the issue's size, with the
 counters and the export on top); evict, reuse and rebuild at small capacities (::test_evict_then_reuse_and_rebuild); the refusals
 (tests/test_map_plan_abi.py)."""
@@ -11,52 +11,11 @@ import pytest
 import torch
 
 from _map_model import MapModel
+from _plan_cases import T, check_plan
 
 pytestmark = pytest.mark.gpu
 
 N66 = 65 * 2048 + 1
-
-
-def T(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def plan_ref(ids, skip_negative=False):
-    """(uniq, inv, sorted_pos, sorted_seg, seg_offsets, n_valid) as mrec.h defines them"""
-    n = ids.size
-    valid = ids >= 0 if skip_negative else np.ones(n, bool)
-    vpos = np.flatnonzero(valid)
-    u, first, inv_s = np.unique(ids[vpos], return_index=True, return_inverse=True)
-    order = np.argsort(first, kind="stable")                     # groups in the order of first appearance
-    rank = np.empty(u.size, np.int64)
-    rank[order] = np.arange(u.size)
-    inv = np.full(n, -1, np.int64)
-    inv[vpos] = rank[inv_s]
-    U = u.size
-    pos_v = vpos[np.argsort(inv[vpos], kind="stable")]
-    pad = np.flatnonzero(~valid)
-    sorted_pos = np.concatenate([pos_v, pad])
-    sorted_seg = np.concatenate([inv[pos_v], np.full(pad.size, U, np.int64)])
-    offs = np.concatenate([[0], np.cumsum(np.bincount(inv[vpos], minlength=U))])
-    if pad.size:
-        offs = np.concatenate([offs, [n]])
-    return u[order], inv, sorted_pos, sorted_seg, offs, vpos.size
-
-
-def check_plan(ops, dev, ids, skip_negative=False):
-    p = ops.sparse_plan(T(ids, dev), skip_negative=skip_negative)
-    torch.cuda.synchronize()
-    uniq, inv, spos, sseg, offs, n_valid = plan_ref(ids, skip_negative)
-    U = uniq.size
-    assert p.U == U
-    assert np.array_equal(p.uniq_buf[:U].cpu().numpy(), uniq) and np.array_equal(p.inv.cpu().numpy(), inv)
-    assert np.array_equal(p.sorted_pos[:ids.size].cpu().numpy(), spos) and np.array_equal(p.sorted_seg[:ids.size].cpu().numpy(), sseg)
-    assert np.array_equal(p.seg_offsets[:offs.size].cpu().numpy(), offs)
-    if skip_negative:
-        assert int(p.n_valid_dev.item()) == n_valid
-        if n_valid < ids.size:
-            assert int(p.uniq_buf[U].item()) == -1
-    return p
 
 
 def ids_with_firsts_in_every_tile(rng, n, dtype):
