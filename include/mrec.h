@@ -284,6 +284,65 @@ int mrec_mt_input(const float* cont, int64_t ld_cont, int32_t C, const float* wi
                   const mrec_mt_seg_t* segs, int32_t n_segs, int64_t B, void* x, int32_t out_kind, int64_t ldx, int32_t K0,
                   float* wide_out, void* stream);
 
+/* ---- the backward of mrec_mt_input: the tables' row-gradient sums and the wide weights' gradient sums, at most TWO launches ---------
+ * The reference's tables are dense Parameters under P.Gather (wide_and_deep.py:286-349, 361-424): a table's gradient is the sum, per
+ * row, of what every occurrence of the row received.  g_x [B, K0] (row stride ldg ELEMENTS; g_kind 0 = fp32, 1 = bf16, 2 = IEEE half, as
+ * mrec_mt_input's out_kind) is the gradient of the input row, read IN PLACE -- a table's gradient is a column block of it -- and g_wide
+ * [B] (fp32) the gradient of the wide term.
+ * A GROUP is the set of segments that share a table.  Its ids are the segments' ids side by side per sample, [B, Ls], Ls = sum L, in
+ * segment order, and the caller passes the index mrec_sparse_plan_ex_i32 built over exactly those n = B * Ls ids (no flags beyond
+ * MREC_PLAN_WS_PRIMED): sorted_pos, sorted_seg, seg_offsets and the device count n_uniq_dev.  Position i = b * Ls + s lies in the
+ * segment f whose slots hold s (s_local = s - first slot of f) and contributes, with m = mask[b * ld_ids + s_local] (NULL mask: 1),
+ *   deep:  widen(g_x[b, c0 : c0 + D]) * scale   c0 = col + s_local * D, scale = m                       (pooled == 0)
+ *                                              c0 = col,               scale = fp32(m * fp32(1 / L))   (pooled == 1)
+ *   wide:  g_wide[b] * m                        (a sum, not a mean: no division by L)
+ * Of a segment only D, L, pooled, col, mask and ld_ids are read (the layout of mask is that of the ids); table, V, ld, wide and ids are
+ * ignored: the kernels index NO table by id -- they read g_x, g_wide, mask and cont by position and write by group index, so an id
+ * outside [0, V) cannot make them touch memory they do not own (positions and offsets read from the index are clamped to [0, n]).
+ * Results, all fp32, each multiplied ONCE, last, by grad_scale (1 / sens):
+ *   sums[u, 0:D]  of every group, u < *n_uniq_dev: the deep contributions of group u's positions;   sums: [>= n, D] contiguous
+ *   wsums[u]      where wsums != NULL: their wide contributions;                                     wsums: [>= n]
+ *   d_wide_cont[c] = sum_b g_wide[b] * cont[b, c], d_wide_bias[0] = sum_b g_wide[b]                  (C > 0 only)
+ *   rows u >= *n_uniq_dev are not written.
+ * The order of every sum is fixed by the layout -- no atomics, the same bits on every run -- and no workgroup waits for another:
+ *   a RUN of sorted entries [e0, e1) is summed by one wave of R = 64 / lpr row slots (lpr = the power of two >= D / 8 lanes hold a row,
+ *     8 columns each): slot r adds the products of entries e0 + r, e0 + r + R, .. in ascending order onto +0, then the slots are added by
+ *     a butterfly at lane distances lpr, 2 lpr, .. 32;
+ *   a group of at most MREC_MT_BWD_CHUNK positions is one run;
+ *   a longer group is cut where the windows [c * CHUNK, (c + 1) * CHUNK) of the SORTED index cut it: each piece is a run whose partial
+ *     sum goes to the workspace (first launch), and the second launch adds the pieces in ascending window order, the first one
+ *     starting the sum (16 table rows under B * n ids -- emb64_indicator -- are long groups every step: the normal case);
+ *   d_wide_cont / d_wide_bias: slabs of 256 samples; inside a slab each of four waves adds its 64 samples in ascending order onto +0,
+ *     the waves are added in wave order; slabs are added in ascending order (more than one slab: by the second launch).
+ * The second launch exists only where some group has n > MREC_MT_BWD_CHUNK or C > 0 with B > 256.  groups is HOST memory, read during
+ * the call only and copied into the kernels' arguments by value: no device-side table, no host read of a device count (the grids are
+ * sized by n, an upper bound of the group count), no allocation, no synchronisation: capturable.
+ * Decided before any HIP call, in this order:
+ *   MREC_EINVAL: n_groups outside [0, MREC_MT_BWD_MAX_GROUPS], null groups; B, C, K0 < 0, g_kind, ldg < K0, ld_cont < C, a grad_scale
+ *     that is not finite; a group's n_segs < 1 or null segs, more than MREC_MT_MAX_SEGS segments in all, n < 0; an L < 1, pooled not
+ *     0 / 1, D < 1, ld_ids < L, col < 0; a group whose segments differ in D; a group whose Ls does not divide n, or n / Ls != B;
+ *   MREC_EUNSUPPORTED: K0 or ldg not a multiple of 8; a D not a multiple of 8 or > 256, a col not a multiple of 8; n >= 2^31;
+ *   MREC_EINVAL: a column block outside [0, K0);
+ *   B == 0: MREC_OK, nothing launched;
+ *   MREC_EINVAL: a null g_x, sorted_pos, sorted_seg, seg_offsets, n_uniq_dev or sums; a null g_wide with a wsums or C > 0; C > 0 with
+ *     a null cont, d_wide_cont or d_wide_bias; MREC_EWORKSPACE: ws null or smaller than mrec_mt_input_bwd_workspace_bytes says
+ *     (where that is not 0);
+ *   MREC_EUNSUPPORTED: g_x, a sums or ws not 16-byte aligned. */
+typedef struct {
+  const mrec_mt_seg_t* segs; int32_t n_segs;              /* the group's segments, in the order of its ids' columns (HOST) */
+  const int32_t* sorted_pos; const int32_t* sorted_seg;   /* the plan over the group's [B, Ls] ids                          */
+  const int32_t* seg_offsets; const int64_t* n_uniq_dev;
+  int64_t n;                                              /* B * Ls                                                          */
+  float* sums;                                            /* [>= n, D]                                                       */
+  float* wsums;                                           /* [>= n], or NULL: the group has no wide weights                  */
+} mrec_mt_grp_t;
+#define MREC_MT_BWD_MAX_GROUPS 8
+#define MREC_MT_BWD_CHUNK 256
+int mrec_mt_input_bwd_workspace_bytes(const mrec_mt_grp_t* groups, int32_t n_groups, int64_t B, int32_t C, size_t* out);
+int mrec_mt_input_bwd(const void* g_x, int32_t g_kind, int64_t ldg, int32_t K0, const float* g_wide, const float* cont, int64_t ld_cont,
+                      int32_t C, const mrec_mt_grp_t* groups, int32_t n_groups, int64_t B, float grad_scale, float* d_wide_cont,
+                      float* d_wide_bias, void* ws, size_t ws_bytes, void* stream);
+
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row
  * stride ldw floats: 1 for a dense column, 4 when it lives in a fused w|accum|linear|pad record). */

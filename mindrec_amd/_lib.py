@@ -79,6 +79,8 @@ _SIGS = {
     "mrec_gather_pool_fields_keyed_clip": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _u64, _f32, _f32, _vp, _i32,
                                            _i64, _f32, _vp],
     "mrec_mt_input": [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _i32, _i64, _i32, _vp, _vp],
+    "mrec_mt_input_bwd_workspace_bytes": [_vp, _i32, _i64, _i32, _szp],
+    "mrec_mt_input_bwd": [_vp, _i32, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _f32, _vp, _vp, _vp, _sz, _vp],
     "mrec_gather_rows_clip_f32_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
     "mrec_gather_rows_clip_f32_i64": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
     "mrec_gather_rows_clip_bf16_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],

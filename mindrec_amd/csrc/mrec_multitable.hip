@@ -300,3 +300,390 @@ MREC_API int mrec_mt_input(const float* cont, int64_t ld_cont, int32_t C, const 
     hipStream_t st = (hipStream_t)stream;
     return by_out(x, out_kind, [&](auto* op) { return mt_launch(op, a, (unsigned)nblocks, st); });
 }
+
+// ---- the backward: mrec_mt_input_bwd (the contract and the order of every sum: include/mrec.h) ------------------------------------
+// g_x's column blocks -> per-table row-gradient sums, g_wide -> the wide weights' gradient sums, both per GROUP of a sparse plan over
+// the table's ids, and the continuous weights' / the bias' gradients.  Shape: a wave per run of the sorted index; lpr lanes hold a
+// gradient row, eight columns each (one 16-byte load of a 16-bit gradient, two of an fp32 one), so a wave-instruction requests
+// R = 64 / lpr rows, kBwUn of them in flight per lane; fp32 accumulation, a butterfly over the row slots last.  The first launch has
+// three kinds of work, each in workgroups of its own (a workgroup's kind, group and geometry are uniform: scalar branches):
+//   group waves   stride over the group indices u < U: a group of at most CHUNK positions is one run, its sums are stored at once;
+//   window waves  stride over the windows of CHUNK sorted entries of a group's index that has more than CHUNK entries: a window meets
+//                 at most two LONG groups (one that holds its first entry, one that holds its last: a third would have to fit inside),
+//                 and their pieces go to slots 0 / 1 of the window's workspace record [2][D + 4] (column D: the wide sum);
+//   slabs         256 samples of g_wide x cont.
+// The second launch (only where a group can be long or there is more than one slab) folds: a wave per window adds the pieces of the
+// long group that BEGINS in that window, in window order -- nobody waits for anybody: the launch boundary is the only hand-off.
+namespace {
+
+constexpr int kBwUn = 4;                          // rows in flight per lane
+constexpr int kBwMaxWaves = 8192;                 // waves of one kind of work of one group: 256 CUs x 32
+constexpr int kBwSlab = 256;                      // samples of a slab
+constexpr int kBwPad = 4;                         // floats behind the D columns of a workspace record: [0] the wide sum
+
+struct BwSeg { const float* mask; int64_t ld_mask; int s0, L, col, pooled; float inv_l; };
+struct BwGrp {
+    const int32_t* sorted_pos; const int32_t* sorted_seg; const int32_t* seg_offsets; const int64_t* n_uniq;
+    float* sums; float* wsums; float* part;
+    int64_t n;
+    int D, Ls, seg0, nseg, lpr;
+    unsigned blk_g, nblk_g, blk_w, nblk_w, blk_f, nblk_f;      // first workgroup and workgroups of: group waves, window waves, the fold
+};
+struct BwArgs {
+    int64_t ldg, ld_cont, B;
+    const float* g_wide; const float* cont;
+    float* d_cont; float* d_bias; float* part_cont;
+    float grad_scale;
+    int C, n_groups, fold;
+    unsigned blk_cont, blk_cont_f;                // the slabs' first workgroup; the fold launch's workgroup for them
+    BwGrp grp[MREC_MT_BWD_MAX_GROUPS];
+    BwSeg seg[MREC_MT_MAX_SEGS];
+};
+
+struct g_bf16_t { uint16_t v; };
+struct g_f16_t { uint16_t v; };
+__device__ __forceinline__ void bw_load8(const float* p, float v[8]) {
+    const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__device__ __forceinline__ void bw_load8(const g_bf16_t* p, float v[8]) {
+    const uint4 u = *(const uint4*)p;
+    const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u); }
+}
+__device__ __forceinline__ void bw_load8(const g_f16_t* p, float v[8]) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const uint4 u = *(const uint4*)p;
+    const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const h2 h = __builtin_bit_cast(h2, w[i]); v[2 * i] = (float)h.x; v[2 * i + 1] = (float)h.y; }
+}
+
+// one run [e0, e1) of a group's sorted index: acc[8] (this lane's columns) and wacc, the same bits in every lane of a column / in every lane
+template <class GT>
+__device__ __forceinline__ void bw_run(const BwArgs& a, const BwGrp& gr, const GT* __restrict__ g, int64_t e0, int64_t e1, int lane,
+                                       float acc[8], float& wacc) {
+    const int lpr = gr.lpr, R = 64 / lpr;
+    const int r = lane / lpr, c0 = (lane - r * lpr) * 8;
+    const bool colok = c0 < gr.D, wide = gr.wsums != nullptr;
+    const unsigned Ls = (unsigned)gr.Ls, nmax = (unsigned)(gr.n - 1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.0f;
+    wacc = 0.0f;
+    for (int64_t eb = e0; eb < e1; eb += (int64_t)kBwUn * R) {
+        unsigned pos[kBwUn];
+        bool has[kBwUn];
+        float x[kBwUn][8], m[kBwUn], sc[kBwUn], gw[kBwUn];
+#pragma unroll
+        for (int k = 0; k < kBwUn; ++k) {
+            const int64_t e = eb + (int64_t)k * R + r;
+            has[k] = e < e1;
+            pos[k] = 0;
+            if (has[k]) {                          // (a slot past the end of the run requests nothing: short runs are the common case)
+                const unsigned p = (unsigned)gr.sorted_pos[e];
+                pos[k] = p < nmax ? p : nmax;      // a position is a position: inside [0, n)
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kBwUn; ++k) {
+            m[k] = sc[k] = gw[k] = 0.0f;
+            if (!has[k]) continue;
+            const unsigned b = pos[k] / Ls, s = pos[k] - b * Ls;
+            int j = gr.seg0;
+            for (int i = 1; i < gr.nseg; ++i) j += (int)s >= a.seg[gr.seg0 + i].s0 ? 1 : 0;
+            const BwSeg& sg = a.seg[j];
+            const int sl = (int)s - sg.s0;
+            m[k] = sg.mask ? sg.mask[(int64_t)b * sg.ld_mask + sl] : 1.0f;
+            sc[k] = sg.pooled ? m[k] * sg.inv_l : m[k];
+            gw[k] = wide ? a.g_wide[b] : 0.0f;
+            const int col = sg.col + (sg.pooled ? 0 : sl * gr.D);
+            if (colok) bw_load8(g + (int64_t)b * a.ldg + col + c0, x[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < kBwUn; ++k) {
+            if (has[k]) {
+                if (colok) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) acc[i] = acc[i] + x[k][i] * sc[k];
+                }
+                wacc = wacc + gw[k] * m[k];
+            }
+        }
+    }
+    for (int d = lpr; d < 64; d <<= 1) {          // the row slots
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = acc[i] + __shfl_xor(acc[i], d, 64);
+        wacc = wacc + __shfl_xor(wacc, d, 64);
+    }
+}
+
+__device__ __forceinline__ void bw_store(float* __restrict__ dst, float* __restrict__ wdst, int D, int lpr, int lane, const float acc[8],
+                                         float wacc, float gs) {
+    const int c0 = lane * 8;
+    if (lane < lpr && c0 < D) {
+        *(float4*)(dst + c0) = make_float4(acc[0] * gs, acc[1] * gs, acc[2] * gs, acc[3] * gs);
+        *(float4*)(dst + c0 + 4) = make_float4(acc[4] * gs, acc[5] * gs, acc[6] * gs, acc[7] * gs);
+    }
+    if (wdst && lane == 0) *wdst = wacc * gs;
+}
+
+// a group's bounds in the sorted index, inside [0, n] whatever the index holds
+__device__ __forceinline__ void bw_bounds(const BwGrp& gr, int64_t u, int64_t& o0, int64_t& o1) {
+    o0 = gr.seg_offsets[u];
+    o1 = gr.seg_offsets[u + 1];
+    o0 = o0 < 0 ? 0 : (o0 > gr.n ? gr.n : o0);
+    o1 = o1 < o0 ? o0 : (o1 > gr.n ? gr.n : o1);
+}
+__device__ __forceinline__ int64_t bw_count(const BwGrp& gr) {
+    const int64_t U = *gr.n_uniq;
+    return U < 0 ? 0 : (U > gr.n ? gr.n : U);
+}
+
+template <class GT>
+__global__ __launch_bounds__(256) void k_mt_input_bwd(const GT* __restrict__ g, const BwArgs a) {
+    __shared__ float red[4][64];
+    const unsigned blk = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blk >= a.blk_cont) {                      // a slab of samples: column c of cont (column C: ones, the bias) times g_wide
+        const int64_t b0 = (int64_t)(blk - a.blk_cont) * kBwSlab + wave * 64;
+        for (int cb = 0; cb <= a.C; cb += 64) {
+            const int c = cb + lane;
+            float acc = 0.0f;
+            if (c <= a.C) {
+                for (int i = 0; i < 64; ++i) {
+                    const int64_t b = b0 + i;
+                    if (b < a.B) acc = acc + a.g_wide[b] * (c < a.C ? a.cont[b * a.ld_cont + c] : 1.0f);
+                }
+            }
+            red[wave][lane] = acc;
+            __syncthreads();
+            if (wave == 0 && c <= a.C) {
+                const float t = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+                if (a.fold) a.part_cont[(int64_t)(blk - a.blk_cont) * (a.C + 1) + c] = t;
+                else if (c < a.C) a.d_cont[c] = t * a.grad_scale;
+                else a.d_bias[0] = t * a.grad_scale;
+            }
+            __syncthreads();
+        }
+        return;
+    }
+    int gi = 0, win = 0;                          // (uniform: the workgroup's group and kind)
+    for (int i = 0; i < a.n_groups; ++i) {
+        if (blk >= a.grp[i].blk_g) { gi = i; win = 0; }
+        if (a.grp[i].nblk_w > 0 && blk >= a.grp[i].blk_w) { gi = i; win = 1; }
+    }
+    const BwGrp& gr = a.grp[gi];
+    const int64_t U = bw_count(gr);
+    float acc[8], wacc;
+    if (!win) {
+        const int64_t nw = (int64_t)gr.nblk_g * 4;
+        for (int64_t u = (int64_t)(blk - gr.blk_g) * 4 + wave; u < U; u += nw) {
+            int64_t o0, o1;
+            bw_bounds(gr, u, o0, o1);
+            if (o1 - o0 > MREC_MT_BWD_CHUNK) continue;            // a long group: the window waves and the fold
+            bw_run(a, gr, g, o0, o1, lane, acc, wacc);
+            bw_store(gr.sums + u * gr.D, gr.wsums ? gr.wsums + u : nullptr, gr.D, gr.lpr, lane, acc, wacc, a.grad_scale);
+        }
+        return;
+    }
+    const int64_t nw = (int64_t)gr.nblk_w * 4, nwin = (gr.n + MREC_MT_BWD_CHUNK - 1) / MREC_MT_BWD_CHUNK;
+    for (int64_t c = (int64_t)(blk - gr.blk_w) * 4 + wave; c < nwin; c += nw) {
+        const int64_t e0 = c * MREC_MT_BWD_CHUNK, e1 = e0 + MREC_MT_BWD_CHUNK < gr.n ? e0 + MREC_MT_BWD_CHUNK : gr.n;
+        const int64_t ua = gr.sorted_seg[e0], ub = gr.sorted_seg[e1 - 1];
+        for (int slot = 0; slot < 2; ++slot) {
+            const int64_t u = slot ? ub : ua;
+            if ((slot && ub == ua) || u < 0 || u >= U) continue;
+            int64_t o0, o1;
+            bw_bounds(gr, u, o0, o1);
+            if (o1 - o0 <= MREC_MT_BWD_CHUNK) continue;
+            const int64_t lo = o0 > e0 ? o0 : e0, hi = o1 < e1 ? o1 : e1;
+            if (hi <= lo) continue;
+            bw_run(a, gr, g, lo, hi, lane, acc, wacc);
+            float* rec = gr.part + (c * 2 + slot) * (gr.D + kBwPad);
+            bw_store(rec, rec + gr.D, gr.D, gr.lpr, lane, acc, wacc, 1.0f);
+        }
+    }
+}
+
+// the pieces of the long groups, added in window order; the slabs, in slab order
+__global__ __launch_bounds__(256) void k_mt_input_bwd_fold(const BwArgs a) {
+    const unsigned blk = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blk == a.blk_cont_f) {
+        if (wave != 0) return;
+        const int64_t ns = (a.B + kBwSlab - 1) / kBwSlab;
+        for (int c = lane; c <= a.C; c += 64) {
+            float t = a.part_cont[c];
+            for (int64_t s = 1; s < ns; ++s) t = t + a.part_cont[s * (a.C + 1) + c];
+            if (c < a.C) a.d_cont[c] = t * a.grad_scale;
+            else a.d_bias[0] = t * a.grad_scale;
+        }
+        return;
+    }
+    int gi = 0;
+    for (int i = 1; i < a.n_groups; ++i) gi = (a.grp[i].nblk_f > 0 && blk >= a.grp[i].blk_f) ? i : gi;
+    const BwGrp& gr = a.grp[gi];
+    const int64_t U = bw_count(gr);
+    const int64_t nw = (int64_t)gr.nblk_f * 4, nwin = (gr.n + MREC_MT_BWD_CHUNK - 1) / MREC_MT_BWD_CHUNK;
+    const int D = gr.D, stride = D + kBwPad, c4 = lane * 4;
+    for (int64_t c = (int64_t)(blk - gr.blk_f) * 4 + wave; c < nwin; c += nw) {
+        const int64_t e0 = c * MREC_MT_BWD_CHUNK, e1 = e0 + MREC_MT_BWD_CHUNK < gr.n ? e0 + MREC_MT_BWD_CHUNK : gr.n;
+        const int64_t ua = gr.sorted_seg[e0], ub = gr.sorted_seg[e1 - 1];
+        for (int slot = 0; slot < 2; ++slot) {
+            const int64_t u = slot ? ub : ua;
+            if ((slot && ub == ua) || u < 0 || u >= U) continue;
+            int64_t o0, o1;
+            bw_bounds(gr, u, o0, o1);
+            // the group that BEGINS here: at the window's first entry (slot 0) or inside it (slot 1)
+            if (o1 - o0 <= MREC_MT_BWD_CHUNK || o0 < e0 || o0 >= e1 || (slot == 0) != (o0 == e0)) continue;
+            const int64_t c1 = (o1 - 1) / MREC_MT_BWD_CHUNK;
+            const float* __restrict__ rec = gr.part + (c * 2 + slot) * stride;
+            float4 s = c4 < D ? *(const float4*)(rec + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            float w = rec[D];
+#pragma unroll 4
+            for (int64_t cc = c + 1; cc <= c1; ++cc) {            // every later window holds the group at its first entry: slot 0
+                rec = gr.part + cc * 2 * stride;
+                if (c4 < D) s = vadd(s, *(const float4*)(rec + c4));
+                w = w + rec[D];
+            }
+            if (c4 < D) *(float4*)(gr.sums + u * D + c4) = vscale(s, a.grad_scale);
+            if (gr.wsums && lane == 0) gr.wsums[u] = w * a.grad_scale;
+        }
+    }
+}
+
+// the layout of a call: the segments flattened, the workgroups of every kind of work, the workspace carved.  MREC_OK or the refusal.
+int bw_plan(const mrec_mt_grp_t* groups, int32_t n_groups, int64_t B, int32_t C, int32_t K0, int64_t ldg, MrecArena& ar, BwArgs& a,
+            unsigned* blocks, unsigned* blocks_f) {
+    // 1. the record
+    if (n_groups < 0 || n_groups > MREC_MT_BWD_MAX_GROUPS || (n_groups > 0 && !groups) || B < 0 || C < 0 || K0 < 0) return MREC_EINVAL;
+    int total = 0;
+    for (int gq = 0; gq < n_groups; ++gq) {
+        const mrec_mt_grp_t& q = groups[gq];
+        if (q.n_segs < 1 || !q.segs || q.n < 0) return MREC_EINVAL;
+        total += q.n_segs;
+        if (total > MREC_MT_MAX_SEGS) return MREC_EINVAL;
+        int64_t Ls = 0;
+        for (int i = 0; i < q.n_segs; ++i) {
+            const mrec_mt_seg_t& s = q.segs[i];
+            if (s.L < 1 || (s.pooled != 0 && s.pooled != 1) || s.D < 1 || s.ld_ids < s.L || s.col < 0) return MREC_EINVAL;
+            Ls += s.L;
+        }
+        for (int i = 1; i < q.n_segs; ++i) {
+            if (q.segs[i].D != q.segs[0].D) return MREC_EINVAL;
+        }
+        if (q.n % Ls || q.n / Ls != B) return MREC_EINVAL;
+    }
+    // 2. shapes outside what the kernels cover
+    if (K0 % 8 || ldg % 8) return MREC_EUNSUPPORTED;
+    for (int gq = 0; gq < n_groups; ++gq) {
+        for (int i = 0; i < groups[gq].n_segs; ++i) {
+            const mrec_mt_seg_t& s = groups[gq].segs[i];
+            if (s.D % 8 || s.D > 256 || s.col % 8) return MREC_EUNSUPPORTED;
+        }
+        if (groups[gq].n > (int64_t(1) << 31) - 1) return MREC_EUNSUPPORTED;
+    }
+    // 3. the column blocks
+    for (int gq = 0; gq < n_groups; ++gq) {
+        for (int i = 0; i < groups[gq].n_segs; ++i) {
+            const mrec_mt_seg_t& s = groups[gq].segs[i];
+            if ((int64_t)s.col + (int64_t)s.D * (s.pooled ? 1 : s.L) > K0) return MREC_EINVAL;
+        }
+    }
+    a.B = B; a.C = C; a.n_groups = n_groups;
+    a.fold = (C > 0 && B > kBwSlab) ? 1 : 0;
+    for (int gq = 0; gq < n_groups; ++gq) a.fold |= groups[gq].n > MREC_MT_BWD_CHUNK ? 1 : 0;
+    uint64_t nb = 0, nbf = 0;
+    int seg = 0;
+    for (int gq = 0; gq < n_groups; ++gq) {
+        const mrec_mt_grp_t& q = groups[gq];
+        BwGrp& gr = a.grp[gq];
+        gr.sorted_pos = q.sorted_pos; gr.sorted_seg = q.sorted_seg; gr.seg_offsets = q.seg_offsets; gr.n_uniq = q.n_uniq_dev;
+        gr.sums = q.sums; gr.wsums = q.wsums; gr.n = q.n;
+        gr.D = q.segs[0].D; gr.seg0 = seg; gr.nseg = q.n_segs; gr.lpr = pow2_lanes(gr.D / 8);
+        int s0 = 0;
+        for (int i = 0; i < q.n_segs; ++i) {
+            const mrec_mt_seg_t& s = q.segs[i];
+            a.seg[seg++] = {s.mask, s.ld_ids, s0, s.L, s.col, s.pooled, 1.0f / (float)s.L};
+            s0 += s.L;
+        }
+        gr.Ls = s0;
+        const int64_t nwin = q.n > MREC_MT_BWD_CHUNK ? mrec_cdiv(q.n, MREC_MT_BWD_CHUNK) : 0;
+        gr.part = nwin ? ar.take<float>((size_t)nwin * 2 * (gr.D + kBwPad)) : nullptr;
+        const auto blocks_of = [](int64_t waves) { return (unsigned)mrec_cdiv(waves < kBwMaxWaves ? waves : kBwMaxWaves, 4); };
+        gr.blk_g = (unsigned)nb; gr.nblk_g = blocks_of(q.n); nb += gr.nblk_g;
+        gr.blk_w = (unsigned)nb; gr.nblk_w = blocks_of(nwin); nb += gr.nblk_w;
+        gr.blk_f = (unsigned)nbf; gr.nblk_f = gr.nblk_w; nbf += gr.nblk_f;
+    }
+    a.blk_cont = (unsigned)nb;
+    a.blk_cont_f = 0xFFFFFFFFu;
+    a.part_cont = nullptr;
+    if (C > 0) {
+        const int64_t ns = mrec_cdiv(B, kBwSlab);
+        if (nb + (uint64_t)ns > 0x7FFFFFFFull) return MREC_EUNSUPPORTED;
+        nb += (uint64_t)ns;
+        if (a.fold) {
+            a.part_cont = ar.take<float>((size_t)ns * (C + 1));
+            a.blk_cont_f = (unsigned)nbf++;
+        }
+    }
+    *blocks = (unsigned)nb;
+    *blocks_f = a.fold ? (unsigned)nbf : 0;
+    return MREC_OK;
+}
+
+}  // namespace
+
+MREC_API int mrec_mt_input_bwd_workspace_bytes(const mrec_mt_grp_t* groups, int32_t n_groups, int64_t B, int32_t C, size_t* out) {
+    if (!out) return MREC_EINVAL;
+    MrecArena ar;
+    BwArgs a{};
+    unsigned nb, nbf;
+    const int rc = bw_plan(groups, n_groups, B, C, 0x7FFFFFF8, 0, ar, a, &nb, &nbf);
+    if (rc != MREC_OK) return rc;
+    *out = ar.off;
+    return MREC_OK;
+}
+
+MREC_API int mrec_mt_input_bwd(const void* g_x, int32_t g_kind, int64_t ldg, int32_t K0, const float* g_wide, const float* cont,
+                               int64_t ld_cont, int32_t C, const mrec_mt_grp_t* groups, int32_t n_groups, int64_t B, float grad_scale,
+                               float* d_wide_cont, float* d_wide_bias, void* ws, size_t ws_bytes, void* stream) {
+    if (g_kind < 0 || g_kind > 2 || (K0 >= 0 && ldg < K0) || (C > 0 && ld_cont < C) || !(grad_scale - grad_scale == 0.0f)) return MREC_EINVAL;
+    MrecArena count;
+    BwArgs a{};
+    unsigned nb = 0, nbf = 0;
+    int rc = bw_plan(groups, n_groups, B, C, K0, ldg, count, a, &nb, &nbf);
+    if (rc != MREC_OK) return rc;
+    if (B == 0) return MREC_OK;
+    // 5. pointers, the workspace, alignment
+    bool wide = C > 0;
+    for (int gq = 0; gq < n_groups; ++gq) {
+        const mrec_mt_grp_t& q = groups[gq];
+        if (!q.sorted_pos || !q.sorted_seg || !q.seg_offsets || !q.n_uniq_dev || !q.sums) return MREC_EINVAL;
+        wide = wide || q.wsums;
+    }
+    if (!g_x || (wide && !g_wide) || (C > 0 && (!cont || !d_wide_cont || !d_wide_bias))) return MREC_EINVAL;
+    if (count.off > 0 && (!ws || ws_bytes < count.off)) return MREC_EWORKSPACE;
+    if (!al16(g_x) || (count.off > 0 && !al16(ws))) return MREC_EUNSUPPORTED;
+    for (int gq = 0; gq < n_groups; ++gq) {
+        if (!al16(groups[gq].sums)) return MREC_EUNSUPPORTED;
+    }
+    MrecArena ar(ws, count.off > 0 ? ws_bytes : 0);
+    a = BwArgs{};
+    rc = bw_plan(groups, n_groups, B, C, K0, ldg, ar, a, &nb, &nbf);
+    if (rc != MREC_OK || !ar.ok) return rc != MREC_OK ? rc : MREC_EWORKSPACE;
+    a.ldg = ldg; a.ld_cont = ld_cont; a.g_wide = g_wide; a.cont = cont; a.d_cont = d_wide_cont; a.d_bias = d_wide_bias;
+    a.grad_scale = grad_scale;
+    if (nb == 0) return MREC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (g_kind == 0) k_mt_input_bwd<float><<<nb, 256, 0, st>>>((const float*)g_x, a);
+    else if (g_kind == 1) k_mt_input_bwd<g_bf16_t><<<nb, 256, 0, st>>>((const g_bf16_t*)g_x, a);
+    else k_mt_input_bwd<g_f16_t><<<nb, 256, 0, st>>>((const g_f16_t*)g_x, a);
+    MREC_LAUNCH_CHECK();
+    if (nbf > 0) {
+        k_mt_input_bwd_fold<<<nbf, 256, 0, st>>>(a);
+        MREC_LAUNCH_CHECK();
+    }
+    return MREC_OK;
+}

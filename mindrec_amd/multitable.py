@@ -17,8 +17,27 @@ predict_fused is three kinds of launch and nothing else:
   2. ops.dense_fwd x5 on the K-contiguous weight copies (mlp_dtype "fp32": ops.dense32_fwd x5, exact fp32);
   3. ops.head_predict -- deep_predict, the wide/deep add, the sigmoid and, with a label, the mean sigmoid cross-entropy.
 No torch arithmetic runs on that path and nothing synchronises with the host.  (Off it, when the parameters are initialised or loaded,
-the 16-bit copies of the hidden weights are made by a torch cast, as the engines make theirs, and transposed by ops.operand_copies.)  Eager only: a HIP-graph replay of the chain, the
-backward and the optimizers of this model are not here.  Evaluation has no Dropout (and the reference's keep_prob is 1.0)."""
+the 16-bit copies of the hidden weights are made by a torch cast, as the engines make theirs, and transposed by ops.operand_copies.)
+Evaluation has no Dropout (and the reference's keep_prob is 1.0).
+
+train_step(batch, label) is TrainStepWrap.construct (wide_and_deep.py:510-612) on one GPU: FTRL over every parameter whose name holds
+"wide" (lr ftrl_lr, l1 = l2 = 5e-4, initial accum 0.1), Adam over the rest (lr adam_lr, eps 1e-6), both with loss_scale sens = 1000;
+the loss is the mean sigmoid cross-entropy, no L2 term.  The tables are dense Parameters under P.Gather, so both optimizers are DENSE:
+Adam moves untouched rows on their momentum, FTRL recomputes every weight from linear and accum.  Its launches, in order:
+  1. ops.multitable_input                          the input row and the wide term (one launch)
+  2. the dense net's forward, head and backward    DenseNetMixin's chain (wide_deep_mlp.py: ops.dense_fwd, the output head with
+                                                   dscale = sens / B, ops.dense_bwd; the fp32 net: ops.dense32_* / ops.x3_*): the loss, the
+                                                   16-bit (fp32 net: fp32) gradient g_x of the input row, g_wide [B]
+  3. ops.sparse_plan x4                            one per table; the multi-hot table's ids are the six id tensors torch.cat'ed
+  4. ops.multitable_input_bwd                      g_x, g_wide -> the four tables' row-gradient sums, the wide vectors' gradient sums,
+                                                   d wide_continue_w, d wide_bias, times 1 / sens (two launches; its sum order: include/mrec.h)
+  5. ops.dense_adam_rows_l2_ x4                    Adam over each whole table from its groups' sums (l2_scaled = 0)
+  6. per wide vector: ops.scatter_unique_rows_ into a [V] gradient kept zero between steps, ops.dense_ftrl_, the touched entries
+     cleared again; ops.dense_ftrl_ on wide_continue_w and wide_bias
+  7. the dense net's Adam (ops.dense_adam_slabs_, which also writes the 16-bit weights; the fp32 net: ops.dense_adam_)
+  8. ops.operand_copies: the K-contiguous weight copies predict_fused reads
+Eager only: no HIP-graph replay of either chain, one GPU, no Dropout.  Ids must lie in [0, V) when training -- the contract of
+ops.dense_adam_rows_l2_ and of the scatter; it is not checked on the device."""
 from dataclasses import dataclass
 from typing import Tuple
 
@@ -27,7 +46,7 @@ import torch
 
 from . import ops
 from .metrics import DeviceAUCMAPMetric
-from .wide_deep_mlp import UnsupportedNet
+from .wide_deep_mlp import DenseNetMixin, UnsupportedNet
 
 # the six multi-hot fields in the order of the reference's Concat (wide_and_deep.py:301-349): mult_emb_1 .. mult_emb_6
 MULTI_KEYS = ("multi_doc_ad_category_id", "multi_doc_event_entity_id", "multi_doc_ad_entity_id", "multi_doc_event_topic_id",
@@ -59,12 +78,40 @@ class MultiTableConfig:
     emb_sigma: float = 0.01
     dense_sigma: float = 0.01
     device: str = "cuda:0"
+    # training (TrainStepWrap, wide_and_deep.py:510-535; src/config.py:31-32)
+    adam_lr: float = 0.003
+    adam_eps: float = 1e-6
+    ftrl_lr: float = 0.1
+    ftrl_l1: float = 5e-4
+    ftrl_l2: float = 5e-4
+    ftrl_initial_accum: float = 0.1
+    sens: float = 1000.0
 
     @property
     def input_emb_dim(self):
         """src/datasets.py:310-314"""
         return (self.n_continue + self.n_indicator * self.indicator_dim + self.n_emb128 * self.emb128_dim
                 + self.n_emb64_single * self.emb64_single_dim + len(self.multi_bags) * self.emb64_multi_dim)
+
+
+class _TrainNet(DenseNetMixin):
+    """The dense net's training state and step of MultiTableWideDeep: DenseNetMixin as the DeepFM engines host it -- fp32 master weights,
+    gradients and Adam moments in flat buffers, the 16-bit operand shadow and its transposes, eager (no graphs), no Dropout, every
+    hidden layer a launch of its own (no fused tail: the transposes then cover every layer and are the copies predict_fused reads)."""
+    k = ops
+
+    def __init__(self, cfg, dims, dtype, device, seed):
+        self.cfg, self.device, self._gpu, self._amp = cfg, device, True, (None if dtype == torch.float32 else dtype)
+        self._mfma = self._amp is not None
+        self._graph_level, self.rank, self.step_count, self._step_state = 0, 0, 0, None
+        self._dropout = self._training = self._emb_dropped = False
+        self._init_dense_net(dims, seed, 0.01, cfg.sens, fused_tail=False)
+
+
+# the four tables with their wide vectors and the keys of their id tensors, in the order of the input launch's segments
+_TABLES = (("emb64_indicator", "wide_indicator_w"), ("emb128_embedding", "wide_emb128_w"), ("emb64_single", "wide_emb64_single_w"),
+           ("emb64_multi", "wide_emb64_multi_w"))
+_WIDE = tuple(w for _, w in _TABLES) + ("wide_continue_w", "wide_bias")
 
 
 class MultiTableWideDeep:
@@ -109,10 +156,16 @@ class MultiTableWideDeep:
         # 16-bit nets: the MFMA DenseLayer's widths (multiples of 8); the fp32 net's dense32_fwd takes any width
         hidden = self._dt == f32 or all(ops.dense_supported(1, self.dims[i], self.dims[i + 1]) for i in range(nl - 1))
         self._net_ok = bool(hidden and ops.head_predict_supported(self.dims[nl - 1]))
+        self._net = self._opt = None      # training state: made by the first train_step
         self._refresh()
 
     def _refresh(self):
         """the 16-bit copies of the hidden weights and their transposes, from the fp32 parameters"""
+        if self._net is not None:          # they are the training net's shadow and its transposes
+            if self._net._mfma:
+                self._net.dense16_flat.copy_(self._net.dense_flat.detach())
+                self._net._refresh_tail()
+            return
         if self._w16 is None or not self._net_ok:
             return
         for i, w16 in enumerate(self._w16):
@@ -209,3 +262,129 @@ class MultiTableWideDeep:
             logit, prob = self.predict_fused(batch)
             metric.update(logit, prob, batch["label"], batch["display_id"])
         return metric.eval()
+
+    # ---- training ---------------------------------------------------------------------------------------------------------------
+    def _train_refusal(self):
+        """None where train_step runs, else what DenseNetMixin has no hand-written step for"""
+        d, nl = self.dims, len(self.dims) - 1
+        K5 = d[nl - 1]
+        if nl < 2:
+            return "a net without a hidden layer"
+        if self.cfg.n_continue == 0:       # wide_bias's gradient comes out of the backward launch's continuous block (C > 0)
+            return "a model without continuous values (n_continue = 0): the backward launch gives wide_bias its gradient with them"
+        if self._dt == torch.float32:
+            ok = ops.head_supported(K5) or ops.dcn_head_supported(K5, 2) or ops.head_any_supported(K5)
+        else:
+            ok = (DenseNetMixin.mfma_net_ok(d) and all(ops.dense_supported(1, d[i], d[i + 1]) for i in range(nl - 1))
+                  and (ops.head_supported(K5) or ops.head_any_supported(K5)))
+        return None if ok and self._net_ok else f"the {self.cfg.mlp_dtype} dense net {d}"
+
+    def _train_state(self):
+        """The training state, made on first use: the dense net as a DenseNetMixin host (_TrainNet) holding the CURRENT dense parameters
+        -- self.params' dense entries become views of its flat buffer, the 16-bit copies predict_fused reads its shadow and transposes --
+        Adam m, v per table, FTRL accum (ftrl_initial_accum), linear (0) and a zero [V] gradient buffer per wide vector."""
+        if self._net is not None:
+            return self._net
+        why = self._train_refusal()
+        if why is not None:
+            raise UnsupportedNet(f"MREC_EUNSUPPORTED: training step: no hand-written HIP path for {why}")
+        cfg, p, nl = self.cfg, self.params, len(self.dims) - 1
+        names = [f"dense_layer_{i + 1}" for i in range(nl - 1)] + ["deep_predict"]
+        with torch.enable_grad():          # (the mixin ties each parameter view to its gradient view)
+            net = _TrainNet(cfg, self.dims, self._dt, self.device, int(cfg.seed) + 64)
+        net.load_dense_parameters([p[n + ".weight"] for n in names], [p[n + ".bias"] for n in names])
+        for i, n in enumerate(names):
+            p[n + ".weight"], p[n + ".bias"] = net.dense[2 * i].detach(), net.dense[2 * i + 1].detach()
+        if net._mfma:
+            self._w16 = [net.dense16[2 * i] for i in range(nl - 1)]
+            self._wt16 = [net._dense16_t[i] for i in range(nl - 1)]
+        opt = {"adam": {t: (torch.zeros_like(p[t]), torch.zeros_like(p[t])) for t, _ in _TABLES}, "ftrl": {}, "gbuf": {}, "zeros": {},
+               "b1": np.float32(0.9), "b2": np.float32(0.999), "b1p": np.float32(1.0), "b2p": np.float32(1.0)}
+        for w in _WIDE:
+            opt["ftrl"][w] = (torch.full_like(p[w], float(cfg.ftrl_initial_accum)), torch.zeros_like(p[w]))
+        for _, w in _TABLES:
+            opt["gbuf"][w] = torch.zeros_like(p[w])
+        self._net, self._opt = net, opt
+        return net
+
+    def _groups(self, batch, segs):
+        """the four tables' MtGroups over a batch: a plan per table; the multi-hot table's ids are its six id tensors side by side"""
+        cfg = self.cfg
+        ids = [batch["indicator_id"], batch["emb_128_id"], batch["emb_64_single_id"], torch.cat([batch[k] for k in MULTI_KEYS], dim=1)]
+        parts = [segs[0:1], segs[1:2], segs[2:3], segs[3:3 + len(cfg.multi_bags)]]
+        return [ops.MtGroup(tuple(sg), ops.sparse_plan(i), True) for sg, i in zip(parts, ids)]
+
+    @torch.no_grad()
+    def _backward(self, batch, label):
+        """Steps 1 - 4 of train_step: the gradient of the batch's mean sigmoid cross-entropy with respect to every parameter, nothing
+        updated.  Returns {"loss": 0-d, "g_x": [B, input_emb_dim] and "g_wide": [B] TIMES sens (what the net's backward leaves),
+        "groups": [(table name, wide name, plan, sums [n, D], wsums [n])] -- row u < plan.U is the gradient of table row plan.uniq[u] --
+        "d_wide_cont": [C] or None, "d_wide_bias": [1] or None}, all but g_x / g_wide unscaled (1 / sens applied); the dense net's
+        gradients stay, times sens, in the net's slabs / flat buffer (dense_gradients() reads them)."""
+        net, cfg = self._train_state(), self.cfg
+        if not isinstance(label, torch.Tensor) or label.dtype != torch.float32:
+            raise TypeError("label must be a float32 [B] or [B, 1] tensor")
+        segs = self._segments(batch)
+        x, wide = self.input_row(batch)
+        if net._mfma:
+            loss, g_x, g_wide = net._mlp_step_eager(x, wide, label)
+        else:
+            loss, g_x, g_wide = net._mlp_step_f32(x, wide, label)
+        groups = self._groups(batch, segs)
+        outs, (d_cont, d_bias) = ops.multitable_input_bwd(g_x, g_wide, groups, cont=batch["continue_val"],
+                                                          grad_scale=1.0 / cfg.sens)
+        return {"loss": loss, "g_x": g_x, "g_wide": g_wide, "d_wide_cont": d_cont, "d_wide_bias": d_bias,
+                "groups": [(t, w, q.plan, s, ws) for (t, w), q, (s, ws) in zip(_TABLES, groups, outs)]}
+
+    @torch.no_grad()
+    def dense_gradients(self):
+        """{parameter name: gradient} of the dense net after _backward, unscaled (a copy; the 16-bit net's slabs are summed first)"""
+        net, nl = self._train_state(), len(self.dims) - 1
+        if net._mfma:
+            net._sum_dw_slabs()
+        names = [f"dense_layer_{i + 1}" for i in range(nl - 1)] + ["deep_predict"]
+        out = {}
+        for i, n in enumerate(names):
+            out[n + ".weight"] = net.dense_grad[2 * i] / self.cfg.sens
+            out[n + ".bias"] = net.dense_grad[2 * i + 1] / self.cfg.sens
+        return out
+
+    @torch.no_grad()
+    def train_step(self, batch, label):
+        """One step of TrainStepWrap (module docstring: the launch list) on `batch` (predict_fused's mapping) and `label` (float32 [B] or
+        [B, 1]).  The dense net runs on DenseNetMixin (its forward, head, backward and dense Adam, as the DeepFM engines use it) -- not on
+        a copy of that chain.  Returns the step's loss (before the update) as a 0-d device tensor; nothing synchronises with the host.
+        Ids must lie in [0, V): not checked.  UnsupportedNet, before any state exists or changes, where the net has no hand-written step
+        -- and for n_continue = 0, which is refused and not trained without its wide_bias (the reference always trains it).
+        predict_fused after it sees the new parameters."""
+        net = self._train_state()
+        cfg, p, o = self.cfg, self.params, self._opt
+        g = self._backward(batch, label)
+        o["b1p"], o["b2p"] = np.float32(o["b1p"] * o["b1"]), np.float32(o["b2p"] * o["b2"])
+        net.step_count += 1
+        adam = dict(lr=cfg.adam_lr, beta1=float(o["b1"]), beta2=float(o["b2"]), eps=cfg.adam_eps, beta1_power=float(o["b1p"]),
+                    beta2_power=float(o["b2p"]))
+        ftrl = dict(lr=cfg.ftrl_lr, l1=cfg.ftrl_l1, l2=cfg.ftrl_l2, lr_power=-0.5, grad_scale=1.0)
+        for table, w, plan, sums, wsums in g["groups"]:
+            m, v = o["adam"][table]
+            ops.dense_adam_rows_l2_(p[table], m, v, plan, sums, 0.0, grad_scale=1.0, **adam)
+            gb, zeros = o["gbuf"][w], o["zeros"].get(plan.n)
+            if zeros is None:
+                zeros = o["zeros"][plan.n] = torch.zeros((max(plan.n, 1), 1), dtype=torch.float32, device=self.device)
+            ops.scatter_unique_rows_(gb.view(-1, 1), plan, wsums.view(-1, 1))
+            ops.dense_ftrl_(p[w], *o["ftrl"][w], gb, **ftrl)
+            ops.scatter_unique_rows_(gb.view(-1, 1), plan, zeros)
+        ops.dense_ftrl_(p["wide_continue_w"], *o["ftrl"]["wide_continue_w"], g["d_wide_cont"], **ftrl)
+        ops.dense_ftrl_(p["wide_bias"], *o["ftrl"]["wide_bias"], g["d_wide_bias"], **ftrl)
+        if net._mfma:
+            ops.dense_adam_slabs_(net.dense_flat.detach(), net.dense_m, net.dense_v, net.dense_grad_flat, net._slab_segments(),
+                                  shadow16=net.dense16_flat, grad_scale=1.0 / cfg.sens, **adam)
+            net._refresh_tail()
+        else:
+            ops.dense_adam_(net.dense_flat.detach(), net.dense_m, net.dense_v, net.dense_grad_flat, grad_scale=1.0 / cfg.sens, **adam)
+        return g["loss"]
+
+    def train(self, batches):
+        """train.py's loop: train_step over `batches` (mappings as predict_fused's that also hold label); returns the steps' losses (0-d
+        device tensors: reading one synchronises)"""
+        return [self.train_step(batch, batch["label"]) for batch in batches]

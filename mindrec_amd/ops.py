@@ -471,6 +471,101 @@ def multitable_input(cont, wide_cont, wide_bias, segments, K0=None, out=None, wi
     return out, wide_out
 
 
+MT_BWD_MAX_GROUPS = 8      # MREC_MT_BWD_MAX_GROUPS
+MT_BWD_CHUNK = 256         # MREC_MT_BWD_CHUNK
+
+
+class MtGrp(C.Structure):          # mrec_mt_grp_t
+    _fields_ = [("segs", C.c_void_p), ("n_segs", C.c_int32), ("sorted_pos", C.c_void_p), ("sorted_seg", C.c_void_p),
+                ("seg_offsets", C.c_void_p), ("n_uniq_dev", C.c_void_p), ("n", C.c_int64), ("sums", C.c_void_p), ("wsums", C.c_void_p)]
+
+
+class MtGroup(NamedTuple):
+    """The segments of multitable_input that share ONE table, for multitable_input_bwd: segments: MtSegment records (or tuples) in
+    the order in which their ids stand side by side per sample; plan: ops.sparse_plan over exactly those ids -- [B, sum L] int32, a
+    single segment's ids as they are, several torch.cat'ed along dimension 1; wide: the table has wide weights (their gradient sums are
+    wanted)."""
+    segments: tuple
+    plan: SparsePlan
+    wide: bool = True
+
+
+def multitable_input_bwd(g_x, g_wide, groups, cont=None, grad_scale=1.0):
+    """The backward of multitable_input in at most two launches (mrec_mt_input_bwd; the bprop of the reference's dense Gathers,
+    wide_and_deep.py:286-349, 361-424): g_x [B, K0] -- the gradient of the input row, float32 / bfloat16 / float16, unit column stride,
+    read in place through its row stride: every table's gradient is a column block of it -- and g_wide float32 [B] become, per MtGroup,
+    (sums [n, D], wsums [n] or None): row u < plan.U holds the sum over the group's positions of g_x's block (times mask, times 1 / L
+    for a pooled segment) and of g_wide (times mask); rows >= U are unspecified, as segment_sum's.  cont: float32 [B, C] gives
+    (d_wide_cont [C], d_wide_bias [1]) = (g_wide @ cont, sum g_wide), else (None, None).  Every result is multiplied by grad_scale,
+    once, last.  No float atomics: the order of every sum is fixed by the layout (include/mrec.h), the same bits on every run.
+    Of a segment the table's width, ids' shape, col, pooled and mask are used; no table is read or indexed.
+    Returns ([(sums, wsums), ..] in group order, (d_wide_cont, d_wide_bias))."""
+    grps = [q if isinstance(q, MtGroup) else MtGroup(*q) for q in groups]
+    if len(grps) > MT_BWD_MAX_GROUPS:
+        raise ValueError(f"multitable_input_bwd takes at most {MT_BWD_MAX_GROUPS} groups, got {len(grps)}")
+    _need_cuda(g_x, g_wide, cont)
+    if not isinstance(g_x, torch.Tensor) or g_x.dtype not in _KIND or g_x.dim() != 2 or g_x.stride(1) != 1:
+        raise TypeError("multitable_input_bwd: g_x must be a [B, K0] float32 / bfloat16 / float16 tensor with unit column stride")
+    B, K0 = g_x.shape
+    if not isinstance(g_wide, torch.Tensor) or g_wide.dtype != torch.float32 or g_wide.numel() != B or not g_wide.is_contiguous():
+        raise TypeError(f"multitable_input_bwd: g_wide must be a contiguous float32 [{B}] tensor")
+    Cc, ld_cont = 0, 0
+    if cont is not None:
+        if cont.dtype != torch.float32 or cont.dim() != 2 or cont.shape[0] != B or cont.stride(1) != 1:
+            raise TypeError(f"multitable_input_bwd: cont must be a float32 [{B}, C] tensor with unit column stride")
+        Cc = cont.shape[1]
+        ld_cont = cont.stride(0) if B > 1 else Cc
+    dev = g_x.device
+    nseg = sum(len(q.segments) for q in grps)
+    if nseg > MT_MAX_SEGS:
+        raise ValueError(f"multitable_input_bwd takes at most {MT_MAX_SEGS} segments in all, got {nseg}")
+    garr = (MtGrp * max(len(grps), 1))()
+    sarrs, keep, outs = [], [], []
+    for gi, q in enumerate(grps):
+        segs = [s if isinstance(s, MtSegment) else MtSegment(*s) for s in q.segments]
+        if not segs:
+            raise ValueError(f"group {gi}: no segments")
+        if not isinstance(q.plan, SparsePlan) or q.plan.sorted_pos.dtype != torch.int32:
+            raise TypeError(f"group {gi}: plan must be an ops.sparse_plan result")
+        _need_cuda(q.plan.sorted_pos, *[s.mask for s in segs])
+        sarr = (MtSeg * len(segs))()
+        D, Ls = segs[0].table.shape[1], 0
+        for i, s in enumerate(segs):
+            if s.table.dim() != 2 or s.table.shape[1] != D:
+                raise ValueError(f"group {gi}: its segments share one table, so one width; segment {i} has another")
+            if s.ids.dim() not in (1, 2) or s.ids.shape[0] != B:
+                raise TypeError(f"group {gi} segment {i}: ids must be [{B}, L] (or [{B}])")
+            L = s.ids.shape[1] if s.ids.dim() == 2 else 1
+            mask = s.mask
+            if mask is not None:
+                if mask.dtype != torch.float32 or mask.numel() != B * L or mask.shape[0] != B:
+                    raise TypeError(f"group {gi} segment {i}: mask must be float32 of the shape of ids")
+                mask = mask.reshape(B, L)
+                mask = mask if mask.stride(1) == 1 else mask.contiguous()
+                keep.append(mask)
+            sarr[i] = MtSeg(None, s.table.shape[0], D, D, None, None, (mask.stride(0) if B > 1 else L) if mask is not None else L,
+                            mask.data_ptr() if mask is not None else None, L, int(bool(s.pooled)), int(s.col))
+            Ls += L
+        if q.plan.n != B * Ls:
+            raise ValueError(f"group {gi}: the plan holds {q.plan.n} positions, the group's ids are [{B}, {Ls}]")
+        n = max(q.plan.n, 1)
+        sums = torch.empty((n, D), dtype=torch.float32, device=dev)
+        wsums = torch.empty((n,), dtype=torch.float32, device=dev) if q.wide else None
+        garr[gi] = MtGrp(C.cast(sarr, C.c_void_p), len(segs), q.plan.sorted_pos.data_ptr(), q.plan.sorted_seg.data_ptr(),
+                         q.plan.seg_offsets.data_ptr(), q.plan.n_uniq_dev.data_ptr(), q.plan.n, sums.data_ptr(),
+                         wsums.data_ptr() if wsums is not None else None)
+        sarrs.append(sarr)
+        outs.append((sums, wsums))
+    d_cont = torch.empty((Cc,), dtype=torch.float32, device=dev) if Cc else None
+    d_bias = torch.empty((1,), dtype=torch.float32, device=dev) if Cc else None
+    gp = C.cast(garr, C.c_void_p)
+    ws = workspace("mt_bwd", max(_lib.query_bytes("mrec_mt_input_bwd_workspace_bytes", gp, len(grps), B, Cc), 16), dev)
+    _lib.call("mrec_mt_input_bwd", _ptr(g_x), _KIND[g_x.dtype], g_x.stride(0) if B > 1 else K0, K0, _ptr(g_wide), _ptr(cont), ld_cont, Cc,
+              gp, len(grps), B, float(grad_scale), _ptr(d_cont), _ptr(d_bias), _ptr(ws), ws.numel(), _stream())
+    del keep, sarrs
+    return outs, (d_cont, d_bias)
+
+
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
                      max_norm=None):
     """Both lookups of WideDeepModel.construct (wide_and_deep.py:300-302) in one pass over fused rows: returns
