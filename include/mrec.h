@@ -343,6 +343,51 @@ int mrec_mt_input_bwd(const void* g_x, int32_t g_kind, int64_t ldg, int32_t K0, 
                       int32_t C, const mrec_mt_grp_t* groups, int32_t n_groups, int64_t B, float grad_scale, float* d_wide_cont,
                       float* d_wide_bias, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the table optimizers of the multitable Wide&Deep's step: at most THREE graph nodes for all tables together --------------------
+ * TrainStepWrap (wide_and_deep.py:510-535) on dense tables: nn.Adam over every table, nn.FTRL over every wide vector and over the
+ * plain wide parameters.  One call does, for up to MREC_MT_BWD_MAX_GROUPS table records and up to MREC_MT_OPT_MAX_VECS plain vectors,
+ * what mrec_dense_adam_rows_l2_f32 per table, a scatter of wsums into a zero [V] gradient + mrec_dense_ftrl_f32 + a clearing scatter
+ * per wide vector and mrec_dense_ftrl_f32 per plain vector do -- bit for bit: the same element formulas on the same expressions in
+ * the same order -- as: one memset (-1) of a concatenated row -> group map of sum(V) ints, one kernel that enters uniq[g] -> g for
+ * every table's groups, one update kernel in which a workgroup belongs to ONE item (a table, a wide vector or a plain vector).
+ * Per table record, with rg[r] = the g < min(U, *n_uniq_dev) with uniq[g] == r, else none (a uniq entry outside [0, V) or at an
+ * index >= *n_uniq_dev enters nothing; the uniq entries of a call are distinct):
+ *   Adam on every element (r, c) of p, m, v [V, D] contiguous:  g = rg[r] exists ? sums[rg[r], c] : 0;  g = g + l2_scaled * p
+ *     (product rounded, then added);  adam(p, m, v, g * adam->grad_scale)                           -- mrec_dense_adam_rows_l2_f32
+ *   FTRL on every entry r of w, accum, linear [V] (all three NULL: the table has no wide vector):
+ *     g = rg[r] exists ? wsums[rg[r]] : 0;  ftrl(w, accum, linear, g * ftrl->grad_scale)           -- mrec_dense_ftrl_f32
+ * Per plain vector: ftrl(w, accum, linear, g[i] * ftrl->grad_scale), i < n.
+ * sums [>= U, D] and wsums [>= U] are read at rows < min(U, *n_uniq_dev) only; U is the host's bound of the group count (the plan's
+ * n), n_uniq_dev (nullable: all U) the device count.  D % 4 == 0: float4 lanes (p, m, v, sums 16-byte aligned), else scalar ones.
+ * step_state (nullable): an mrec_step_state_t; the Adam step size comes from it instead of b1_pow / b2_pow.  tabs / vecs / adam /
+ * ftrl are HOST memory, read during the call only and copied into the kernels' arguments by value: no device-side record, no host
+ * read of a device count, no allocation, no atomics, no synchronisation: capturable, every argument constant from step to step.
+ * Decided before any HIP call, in this order:
+ *   MREC_EINVAL: n_tabs outside [0, MREC_MT_BWD_MAX_GROUPS], n_vecs outside [0, MREC_MT_OPT_MAX_VECS], null tabs / vecs with a
+ *     count > 0; a V < 0, D <= 0, U < 0, n < 0;
+ *   MREC_EUNSUPPORTED: a V or U >= 2^31, V * D >= 2^40;
+ *   MREC_EINVAL: null adam / ftrl; w, accum, linear neither all set nor all NULL; V > 0 with a null p, m or v; U > 0 with a null
+ *     uniq, sums or (with a wide vector) wsums; n > 0 with a null w, accum, linear or g;
+ *   MREC_EUNSUPPORTED: D % 4 == 0 with p, m, v or sums not 16-byte aligned;
+ *   MREC_EWORKSPACE: sum(V) > 0 with ws null or smaller than mrec_mt_optim_workspace_bytes says. */
+typedef struct {
+  float* p; float* m; float* v;                           /* [V, D] contiguous: the table and its Adam moments               */
+  int64_t V; int32_t D;
+  float* w; float* accum; float* linear;                  /* [V]: the wide vector and its FTRL state, or all NULL            */
+  const int32_t* uniq; int64_t U;                         /* the plan's group rows [>= U]; U: the host's bound               */
+  const int64_t* n_uniq_dev;                              /* the device count of groups, or NULL (U)                         */
+  const float* sums;                                      /* [>= U, D]                                                       */
+  const float* wsums;                                     /* [>= U]; read only with a wide vector                            */
+} mrec_mt_opt_tab_t;
+typedef struct { float* w; float* accum; float* linear; const float* g; int64_t n; } mrec_mt_opt_vec_t;
+typedef struct { float lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, l2_scaled; int32_t nesterov; } mrec_mt_opt_adam_t;
+typedef struct { float lr, l1, l2, lr_power, grad_scale; } mrec_mt_opt_ftrl_t;
+#define MREC_MT_OPT_MAX_VECS 4
+int mrec_mt_optim_workspace_bytes(const mrec_mt_opt_tab_t* tabs, int32_t n_tabs, size_t* out);
+int mrec_mt_optim(const mrec_mt_opt_tab_t* tabs, int32_t n_tabs, const mrec_mt_opt_vec_t* vecs, int32_t n_vecs,
+                  const mrec_mt_opt_adam_t* adam, const mrec_mt_opt_ftrl_t* ftrl, const void* step_state, void* ws, size_t ws_bytes,
+                  void* stream);
+
 /* Wide branch of WideDeepModel.construct (wide_and_deep.py:300,303-306) in one pass:
  * out[b] = sum_f w[ids[b,f] * ldw] * wts[b,f] + *bias_dev   (w is the [V,1] wide table, row
  * stride ldw floats: 1 for a dense column, 4 when it lives in a fused w|accum|linear|pad record). */
@@ -550,6 +595,11 @@ int mrec_dense_adam_f32(float* p, float* m, float* v, const float* g, int64_t n,
 int mrec_dense_adam_ex_f32(float* p, float* m, float* v, const void* g, int g_is_bf16, uint16_t* shadow_bf16,
                            int64_t n, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,
                            float grad_scale, int nesterov, void* stream);
+/* mrec_dense_adam_ex_f32 with step_state (nullable): an mrec_step_state_t in device memory; when given, the Adam step size comes
+ * from it instead of b1_pow / b2_pow, as in the other dense Adam entries -- the fp32 net's optimizer in a captured step. */
+int mrec_dense_adam_step_f32(float* p, float* m, float* v, const void* g, int g_is_bf16, uint16_t* shadow_bf16,
+                             int64_t n, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,
+                             float grad_scale, int nesterov, const void* step_state, void* stream);
 /* Dense Adam over a flat buffer whose gradient is, for up to 16 segments, the sum of S fp32 slabs
  * slabs[q][s*lens[q] + e], s < splits[q] (what mrec_dense_bwd_weight_* leaves behind), added in slab order; every other
  * element reads g.  shadow_kind: 0 none, 1 bf16, 2 fp16 -- the 16-bit operand copy of the updated parameters

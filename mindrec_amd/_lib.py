@@ -81,6 +81,8 @@ _SIGS = {
     "mrec_mt_input": [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _i32, _i64, _i32, _vp, _vp],
     "mrec_mt_input_bwd_workspace_bytes": [_vp, _i32, _i64, _i32, _szp],
     "mrec_mt_input_bwd": [_vp, _i32, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _f32, _vp, _vp, _vp, _sz, _vp],
+    "mrec_mt_optim_workspace_bytes": [_vp, _i32, _szp],
+    "mrec_mt_optim": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp],
     "mrec_gather_rows_clip_f32_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
     "mrec_gather_rows_clip_f32_i64": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
     "mrec_gather_rows_clip_bf16_i32": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _f32, _vp],
@@ -110,6 +112,7 @@ _SIGS = {
                                  _f32, _f32, _f32, _f32, _f32, _vp, _sz, _vp, _vp],
     "mrec_dense_adam_f32": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp],
     "mrec_dense_adam_ex_f32": [_vp, _vp, _vp, _vp, _int, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp],
+    "mrec_dense_adam_step_f32": [_vp, _vp, _vp, _vp, _int, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _vp],
     "mrec_sparse_lazy_adam_wide_defer": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _i64, _vp,
                                          _f32, _f32, _f32, _f32, _f32, _f32, _f32, _int, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _sz,
                                          _vp, _vp, _vp, _vp, _vp],

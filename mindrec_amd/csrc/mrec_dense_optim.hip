@@ -23,7 +23,9 @@ __device__ __forceinline__ float g_widen(uint16_t x) { return __uint_as_float(((
 template <class GT, bool SH>
 __global__ __launch_bounds__(256) void k_dense_adam(float* __restrict__ p, float* __restrict__ m,
                                                     float* __restrict__ v, const GT* __restrict__ g, int64_t n,
-                                                    AdamH h, uint16_t* __restrict__ shadow, Ftrl1 f1) {
+                                                    AdamH h, uint16_t* __restrict__ shadow, Ftrl1 f1,
+                                                    const StepState* __restrict__ ss) {
+    if (ss) h.lr_t = ss->lr_t;             // this step's bias-corrected step size from device memory (mrec_step_advance)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float pp = p[i], mm = m[i], vv = v[i];
         adam_or_ftrl(pp, mm, vv, g_widen(g[i]) * h.gscale, h, i == f1.idx, f1.h);
@@ -35,7 +37,9 @@ __global__ __launch_bounds__(256) void k_dense_adam(float* __restrict__ p, float
 template <bool SH>
 __global__ __launch_bounds__(256) void k_dense_adam4(float4* __restrict__ p, float4* __restrict__ m,
                                                      float4* __restrict__ v, const float4* __restrict__ g,
-                                                     int64_t n4, AdamH h, uint2* __restrict__ shadow, Ftrl1 f1) {
+                                                     int64_t n4, AdamH h, uint2* __restrict__ shadow, Ftrl1 f1,
+                                                     const StepState* __restrict__ ss) {
+    if (ss) h.lr_t = ss->lr_t;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         float4 pp = p[i], mm = m[i], vv = v[i];
         const float4 gg = g[i];
@@ -200,7 +204,9 @@ __global__ __launch_bounds__(256) void k_clip_group_sums(const float* __restrict
 template <bool SH>
 __global__ __launch_bounds__(256) void k_dense_adam4_g16(float4* __restrict__ p, float4* __restrict__ m,
                                                          float4* __restrict__ v, const uint2* __restrict__ g,
-                                                         int64_t n4, AdamH h, uint2* __restrict__ shadow) {
+                                                         int64_t n4, AdamH h, uint2* __restrict__ shadow,
+                                                         const StepState* __restrict__ ss) {
+    if (ss) h.lr_t = ss->lr_t;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         float4 pp = p[i], mm = m[i], vv = v[i];
         const uint2 u = g[i];
@@ -259,7 +265,7 @@ void by_shadow(const void* shadow, F&& f) {
 
 static int dense_adam_launch(float* p, float* m, float* v, const void* g, int g_bf16, uint16_t* shadow, int64_t n,
                              float lr, float b1, float b2, float eps, float b1_pow, float b2_pow, float grad_scale,
-                             int nesterov, void* stream, const mrec_ftrl1_t* one = nullptr) {
+                             int nesterov, void* stream, const mrec_ftrl1_t* one = nullptr, const void* step_state = nullptr) {
     if (n < 0) return MREC_EINVAL;
     Ftrl1 f1;
     if (int rc = ftrl1_from(one, n, grad_scale, &f1)) return rc;
@@ -267,6 +273,7 @@ static int dense_adam_launch(float* p, float* m, float* v, const void* g, int g_
     if (n == 0) return MREC_OK;
     if (!p || !m || !v || !g) return MREC_EINVAL;
     const AdamH h = adam_hyper(lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov);
+    const StepState* ss = (const StepState*)step_state;
     hipStream_t st = (hipStream_t)stream;
     const bool al = al16(p) && al16(m) && al16(v) && ((((uintptr_t)g) & (g_bf16 ? 7 : 15)) == 0) &&
                     (!shadow || ((((uintptr_t)shadow) & 7) == 0));
@@ -275,8 +282,8 @@ static int dense_adam_launch(float* p, float* m, float* v, const void* g, int g_
         const unsigned gr = stream_grid(n4);
         by_shadow(shadow, [&](auto with) {
             constexpr bool SH = decltype(with)::value;
-            if (g_bf16) k_dense_adam4_g16<SH><<<gr, 256, 0, st>>>((float4*)p, (float4*)m, (float4*)v, (const uint2*)g, n4, h, (uint2*)shadow);
-            else k_dense_adam4<SH><<<gr, 256, 0, st>>>((float4*)p, (float4*)m, (float4*)v, (const float4*)g, n4, h, (uint2*)shadow, f1);
+            if (g_bf16) k_dense_adam4_g16<SH><<<gr, 256, 0, st>>>((float4*)p, (float4*)m, (float4*)v, (const uint2*)g, n4, h, (uint2*)shadow, ss);
+            else k_dense_adam4<SH><<<gr, 256, 0, st>>>((float4*)p, (float4*)m, (float4*)v, (const float4*)g, n4, h, (uint2*)shadow, f1, ss);
         });
     }
     const int64_t done = n4 * 4, rem = n - done;
@@ -287,8 +294,8 @@ static int dense_adam_launch(float* p, float* m, float* v, const void* g, int g_
         fr.idx = f1.idx >= done ? f1.idx - done : -1;
         by_shadow(sh, [&](auto with) {
             constexpr bool SH = decltype(with)::value;
-            if (g_bf16) k_dense_adam<uint16_t, SH><<<gr, 256, 0, st>>>(p + done, m + done, v + done, (const uint16_t*)g + done, rem, h, sh, fr);
-            else k_dense_adam<float, SH><<<gr, 256, 0, st>>>(p + done, m + done, v + done, (const float*)g + done, rem, h, sh, fr);
+            if (g_bf16) k_dense_adam<uint16_t, SH><<<gr, 256, 0, st>>>(p + done, m + done, v + done, (const uint16_t*)g + done, rem, h, sh, fr, ss);
+            else k_dense_adam<float, SH><<<gr, 256, 0, st>>>(p + done, m + done, v + done, (const float*)g + done, rem, h, sh, fr, ss);
         });
     }
     MREC_LAUNCH_CHECK();
@@ -306,6 +313,13 @@ MREC_API int mrec_dense_adam_ex_f32(float* p, float* m, float* v, const void* g,
                                     float grad_scale, int nesterov, void* stream) {
     return dense_adam_launch(p, m, v, g, g_is_bf16, shadow_bf16, n, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov,
                              stream);
+}
+
+MREC_API int mrec_dense_adam_step_f32(float* p, float* m, float* v, const void* g, int g_is_bf16, uint16_t* shadow_bf16,
+                                      int64_t n, float lr, float b1, float b2, float eps, float b1_pow, float b2_pow,
+                                      float grad_scale, int nesterov, const void* step_state, void* stream) {
+    return dense_adam_launch(p, m, v, g, g_is_bf16, shadow_bf16, n, lr, b1, b2, eps, b1_pow, b2_pow, grad_scale, nesterov,
+                             stream, nullptr, step_state);
 }
 
 MREC_API int mrec_dense_adam_l2_workspace_bytes(int64_t n, size_t* out) {

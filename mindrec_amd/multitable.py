@@ -36,8 +36,15 @@ Adam moves untouched rows on their momentum, FTRL recomputes every weight from l
      cleared again; ops.dense_ftrl_ on wide_continue_w and wide_bias
   7. the dense net's Adam (ops.dense_adam_slabs_, which also writes the 16-bit weights; the fp32 net: ops.dense_adam_)
   8. ops.operand_copies: the K-contiguous weight copies predict_fused reads
-Eager only: no HIP-graph replay of either chain, one GPU, no Dropout.  Ids must lie in [0, V) when training -- the contract of
-ops.dense_adam_rows_l2_ and of the scatter; it is not checked on the device."""
+That list is cfg.graphs == "none" (the default).  With cfg.graphs == "step" the step is one linear chain with constant arguments -- no
+side stream, no parallel branch -- that replays as ONE captured HIP graph from the third step at a batch shape (the first two run it
+eagerly; a new shape captures again; release_graphs() / close() / `with` drop the graph):
+  ops.StepState.advance (the Adam powers live in device memory), 1 - 4 as above, then
+  5 + 6. ops.multitable_optim_ -- Adam over the four tables, FTRL over the four wide vectors, wide_continue_w and wide_bias: one memset
+     of a shared row -> group map, one kernel that fills it, ONE update kernel (three graph nodes where the list above has some 26 launches),
+  7, 8 with the step size read from the step state.
+Both forms give the same bits.  One GPU, no Dropout; predict_fused is not captured.  Ids must lie in [0, V) when training with
+graphs="none" -- the contract of the scatter; it is not checked on the device (ops.multitable_optim_ gives a row outside [0, V) no entry)."""
 from dataclasses import dataclass
 from typing import Tuple
 
@@ -86,6 +93,9 @@ class MultiTableConfig:
     ftrl_l2: float = 5e-4
     ftrl_initial_accum: float = 0.1
     sens: float = 1000.0
+    # "none": train_step issues its launches one by one; "step": from the third step at a batch shape the whole step -- optimizers
+    # included -- replays as ONE captured HIP graph (the reference trains with dataset_sink_mode=True, train_and_eval.py:101)
+    graphs: str = "none"
 
     @property
     def input_emb_dim(self):
@@ -96,7 +106,8 @@ class MultiTableConfig:
 
 class _TrainNet(DenseNetMixin):
     """The dense net's training state and step of MultiTableWideDeep: DenseNetMixin as the DeepFM engines host it -- fp32 master weights,
-    gradients and Adam moments in flat buffers, the 16-bit operand shadow and its transposes, eager (no graphs), no Dropout, every
+    gradients and Adam moments in flat buffers, the 16-bit operand shadow and its transposes, no graphs of its own (the model captures
+    the whole step: MultiTableWideDeep._train_step_graph), no Dropout, every
     hidden layer a launch of its own (no fused tail: the transposes then cover every layer and are the copies predict_fused reads)."""
     k = ops
 
@@ -123,6 +134,9 @@ class MultiTableWideDeep:
             raise ValueError(f"mlp_dtype must be one of {tuple(_DTYPES)}, got {cfg.mlp_dtype!r}")
         if len(cfg.deep_dims) < 1 or min(cfg.n_indicator, cfg.n_emb128, cfg.n_emb64_single) < 1 or cfg.n_continue < 0:
             raise ValueError("deep_dims needs a layer, every field count must be >= 1 and n_continue >= 0")
+        if cfg.graphs not in ("none", "step"):
+            raise ValueError(f"graphs must be 'none' or 'step', got {cfg.graphs!r}")
+        self._graph, self._graph_key, self._graph_eager = None, None, 0      # the captured step, its batch shape, eager steps at that shape
         self.cfg, self.device = cfg, torch.device(cfg.device)
         if self.device.type != "cuda":
             raise RuntimeError("mindrec_amd ops run on the GPU only (no CPU fallback)")
@@ -356,7 +370,11 @@ class MultiTableWideDeep:
         a copy of that chain.  Returns the step's loss (before the update) as a 0-d device tensor; nothing synchronises with the host.
         Ids must lie in [0, V): not checked.  UnsupportedNet, before any state exists or changes, where the net has no hand-written step
         -- and for n_continue = 0, which is refused and not trained without its wide_bias (the reference always trains it).
-        predict_fused after it sees the new parameters."""
+        predict_fused after it sees the new parameters.
+        With cfg.graphs == "step" the step is the fused chain (module docstring) and, from the third step at a batch shape, ONE replayed
+        HIP graph: THE RETURNED LOSS IS THEN A STATIC BUFFER WHICH THE NEXT CALL OVERWRITES -- clone what must outlive it."""
+        if self.cfg.graphs == "step":
+            return self._train_step_graph(batch, label)
         net = self._train_state()
         cfg, p, o = self.cfg, self.params, self._opt
         g = self._backward(batch, label)
@@ -383,6 +401,94 @@ class MultiTableWideDeep:
         else:
             ops.dense_adam_(net.dense_flat.detach(), net.dense_m, net.dense_v, net.dense_grad_flat, grad_scale=1.0 / cfg.sens, **adam)
         return g["loss"]
+
+    # ---- the step as one linear chain with constant arguments, and its captured form (cfg.graphs == "step") ----------------------------
+    def _step_chain(self, batch, label):
+        """One training step, launch by launch, every argument constant from step to step (capturable): the step state's advance, steps
+        1 - 4 of the module docstring's list, ops.multitable_optim_ for steps 5 and 6, the dense net's Adam and the weight copies -- the
+        Adam step size comes from the device-side step state.  No side stream, no parallel branch."""
+        net, cfg, p, o = self._net, self.cfg, self.params, self._opt
+        st = o["state"]
+        st.advance(cfg.adam_lr, float(o["b1"]), float(o["b2"]))
+        g = self._backward(batch, label)
+        adam = dict(lr=cfg.adam_lr, beta1=float(o["b1"]), beta2=float(o["b2"]), eps=cfg.adam_eps, beta1_power=0.0, beta2_power=0.0)
+        ftrl = dict(lr=cfg.ftrl_lr, l1=cfg.ftrl_l1, l2=cfg.ftrl_l2, lr_power=-0.5, grad_scale=1.0)
+        tabs = [ops.MtOptTable(p[t], *o["adam"][t], plan, sums, p[w], *o["ftrl"][w], wsums) for t, w, plan, sums, wsums in g["groups"]]
+        vecs = [ops.MtOptVector(p["wide_continue_w"], *o["ftrl"]["wide_continue_w"], g["d_wide_cont"]),
+                ops.MtOptVector(p["wide_bias"], *o["ftrl"]["wide_bias"], g["d_wide_bias"])]
+        ops.multitable_optim_(tabs, vecs, adam=dict(adam, grad_scale=1.0, l2_scaled=0.0), ftrl=ftrl, step_state=st)
+        if net._mfma:
+            ops.dense_adam_slabs_(net.dense_flat.detach(), net.dense_m, net.dense_v, net.dense_grad_flat, net._slab_segments(),
+                                  shadow16=net.dense16_flat, grad_scale=1.0 / cfg.sens, step_state=st, **adam)
+            net._refresh_tail()
+        else:
+            ops.dense_adam_(net.dense_flat.detach(), net.dense_m, net.dense_v, net.dense_grad_flat, grad_scale=1.0 / cfg.sens,
+                            step_state=st, **adam)
+        return g["loss"]
+
+    def _batch_tensors(self, batch, label):
+        """the 17 tensors a step reads -- continue_val, the ten id tensors, the six masks, the label -- by name, in a fixed order"""
+        names = ("continue_val", "indicator_id", "emb_128_id", "emb_64_single_id") + MULTI_KEYS + tuple(k + "_mask" for k in MULTI_KEYS)
+        ts = [batch[k] for k in names] + [label]
+        for k, t in zip(names + ("label",), ts):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{k} must be a device tensor")
+        return names, ts
+
+    @torch.no_grad()
+    def _train_step_graph(self, batch, label):
+        """train_step with cfg.graphs == "step": the first two steps at a batch shape run _step_chain eagerly (workspaces and the net's
+        buffers come into being), the third captures it over static copies of the batch's tensors, later ones copy (ops.copy_many_: one
+        launch) and replay.  A batch of another shape drops the graph and starts over.  The host's powers are advanced beside the
+        device's, so a StepState.reset after steps that ran elsewhere stays consistent (DeepCrossEngine._train_step_native)."""
+        net, o = self._train_state(), self._opt
+        names, ts = self._batch_tensors(batch, label)
+        key = tuple((tuple(t.shape), t.dtype) for t in ts)
+        if key != self._graph_key:          # a batch of a new shape: checked as the chain checks it, before any state moves
+            self._segments(batch)
+            if label.dtype != torch.float32 or ts[0].dtype != torch.float32 or ts[0].dim() != 2 or ts[0].shape[1] != self.cfg.n_continue:
+                raise TypeError(f"label must be float32 [B] or [B, 1] and continue_val float32 [B, {self.cfg.n_continue}]")
+            self.release_graphs()
+            self._graph_key, self._graph_eager = key, 0
+        if o.get("state") is None:
+            o["state"], o["state_step"] = ops.StepState(self.device), -1
+        if o["state_step"] != net.step_count:
+            o["state"].reset(float(o["b1p"]), float(o["b2p"]), net.step_count)
+        net.step_count += 1
+        o["b1p"], o["b2p"] = np.float32(o["b1p"] * o["b1"]), np.float32(o["b2p"] * o["b2"])
+        o["state_step"] = net.step_count
+        g = self._graph
+        if g is None:
+            if self._graph_eager < 2:
+                self._graph_eager += 1
+                return self._step_chain(batch, label)
+            static = [t.clone() for t in ts]
+            torch.cuda.synchronize(self.device)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                loss = self._step_chain(dict(zip(names, static[:-1])), static[-1])
+            g = self._graph = {"graph": graph, "static": static, "loss": loss}
+        ops.copy_many_(g["static"], ts)
+        g["graph"].replay()
+        return g["loss"]
+
+    def release_graphs(self):
+        """Drops the captured training step (it is re-captured on demand, at once where two steps at the batch shape have run)."""
+        if self._graph is not None:
+            torch.cuda.synchronize(self.device)
+            self._graph = None
+            torch.cuda.synchronize(self.device)
+
+    def close(self):
+        """Drops the captured step (nothing of it outlives the model; symmetrical with the engines' close).  train_step works after it."""
+        self.release_graphs()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
     def train(self, batches):
         """train.py's loop: train_step over `batches` (mappings as predict_fused's that also hold label); returns the steps' losses (0-d

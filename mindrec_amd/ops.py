@@ -566,6 +566,116 @@ def multitable_input_bwd(g_x, g_wide, groups, cont=None, grad_scale=1.0):
     return outs, (d_cont, d_bias)
 
 
+MT_OPT_MAX_VECS = 4        # MREC_MT_OPT_MAX_VECS
+
+
+class MtOptTab(C.Structure):       # mrec_mt_opt_tab_t
+    _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("V", C.c_int64), ("D", C.c_int32), ("w", C.c_void_p),
+                ("accum", C.c_void_p), ("linear", C.c_void_p), ("uniq", C.c_void_p), ("U", C.c_int64), ("n_uniq_dev", C.c_void_p),
+                ("sums", C.c_void_p), ("wsums", C.c_void_p)]
+
+
+class MtOptVec(C.Structure):       # mrec_mt_opt_vec_t
+    _fields_ = [("w", C.c_void_p), ("accum", C.c_void_p), ("linear", C.c_void_p), ("g", C.c_void_p), ("n", C.c_int64)]
+
+
+class MtOptAdam(C.Structure):      # mrec_mt_opt_adam_t
+    _fields_ = [(n, C.c_float) for n in ("lr", "b1", "b2", "eps", "b1_pow", "b2_pow", "grad_scale", "l2_scaled")] + [("nesterov", C.c_int32)]
+
+
+class MtOptFtrl(C.Structure):      # mrec_mt_opt_ftrl_t
+    _fields_ = [(n, C.c_float) for n in ("lr", "l1", "l2", "lr_power", "grad_scale")]
+
+
+class MtOptTable(NamedTuple):
+    """One table of multitable_optim_: p, m, v float32 [V, D] contiguous (the table and its Adam moments); plan: the ops.sparse_plan
+    over the step's ids of that table (its uniq_buf and n_uniq_dev are read); sums float32 [>= plan.n, D]: the groups' row-gradient sums
+    (multitable_input_bwd); w, accum, linear float32 [V]: the table's wide vector and its FTRL state, with wsums float32 [>= plan.n] --
+    or all four None: the table has no wide vector."""
+    p: torch.Tensor
+    m: torch.Tensor
+    v: torch.Tensor
+    plan: Dedup
+    sums: torch.Tensor
+    w: Optional[torch.Tensor] = None
+    accum: Optional[torch.Tensor] = None
+    linear: Optional[torch.Tensor] = None
+    wsums: Optional[torch.Tensor] = None
+
+
+class MtOptVector(NamedTuple):
+    """A plain vector under FTRL for multitable_optim_: w, accum, linear and the gradient g, contiguous float32 of one size."""
+    w: torch.Tensor
+    accum: torch.Tensor
+    linear: torch.Tensor
+    g: torch.Tensor
+
+
+def multitable_optim_(tables, dense_ftrl=(), *, adam, ftrl, step_state=None):
+    """The table optimizers of the multitable Wide&Deep's step in one launch chain (mrec_mt_optim; TrainStepWrap, wide_and_deep.py:
+    510-535): for every MtOptTable what dense_adam_rows_l2_(p, m, v, plan, sums, l2_scaled, ..) does and, where it has a wide vector,
+    what scatter_unique_rows_ of wsums into a zero [V] gradient, dense_ftrl_ and a clearing scatter do; for every MtOptVector of
+    `dense_ftrl` what dense_ftrl_ does -- bit for bit -- as one memset of a shared row -> group map, one kernel that fills it and one
+    update kernel, whatever the number of tables.  At most MT_BWD_MAX_GROUPS tables and MT_OPT_MAX_VECS vectors (records or plain tuples).
+    adam: dense_adam_rows_l2_'s keywords (lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, l2_scaled, use_nesterov);
+    ftrl: dense_ftrl_'s (lr, l1, l2, lr_power, grad_scale).  step_state: the Adam step size from device memory (a captured step).
+    Everything is checked before anything is launched; no host read of a device count, no allocation beyond the cached workspace."""
+    tabs = [t if isinstance(t, MtOptTable) else MtOptTable(*t) for t in tables]
+    vecs = [q if isinstance(q, MtOptVector) else MtOptVector(*q) for q in dense_ftrl]
+    if len(tabs) > MT_BWD_MAX_GROUPS:
+        raise ValueError(f"multitable_optim_ takes at most {MT_BWD_MAX_GROUPS} tables, got {len(tabs)}")
+    if len(vecs) > MT_OPT_MAX_VECS:
+        raise ValueError(f"multitable_optim_ takes at most {MT_OPT_MAX_VECS} plain vectors, got {len(vecs)}")
+    unknown = (set(adam) - {"lr", "beta1", "beta2", "eps", "beta1_power", "beta2_power", "grad_scale", "l2_scaled", "use_nesterov"},
+               set(ftrl) - {"lr", "l1", "l2", "lr_power", "grad_scale"})
+    if unknown[0] or unknown[1]:
+        raise TypeError(f"multitable_optim_: unknown optimizer scalars {sorted(unknown[0] | unknown[1])}")
+    ah = MtOptAdam(adam.get("lr", 3.5e-4), adam.get("beta1", 0.9), adam.get("beta2", 0.999), adam.get("eps", 1e-8), adam.get("beta1_power", 0.9),
+                   adam.get("beta2_power", 0.999), adam.get("grad_scale", 1.0), adam.get("l2_scaled", 0.0), int(bool(adam.get("use_nesterov", False))))
+    fh = MtOptFtrl(ftrl.get("lr", 5e-2), ftrl.get("l1", 1e-8), ftrl.get("l2", 1e-8), ftrl.get("lr_power", -0.5), ftrl.get("grad_scale", 1.0))
+    tarr, varr, keep, dev = (MtOptTab * max(len(tabs), 1))(), (MtOptVec * max(len(vecs), 1))(), [], None
+    for i, t in enumerate(tabs):
+        wide = (t.w, t.accum, t.linear, t.wsums)
+        if any(x is None for x in wide) and not all(x is None for x in wide):
+            raise TypeError(f"table {i}: w, accum, linear and wsums come together, or not at all")
+        if not all(isinstance(x, torch.Tensor) for x in (t.p, t.m, t.v, t.sums)) or not hasattr(t.plan, "uniq_buf"):
+            raise TypeError(f"table {i}: p, m, v and sums must be tensors and plan an ops.sparse_plan result")
+        _need_cuda(t.p, t.m, t.v, t.sums, t.plan.uniq_buf, t.plan.n_uniq_dev, *wide)
+        V, D, ld = _table(t.p)
+        for x in (t.p, t.m, t.v):
+            if x.dtype != torch.float32 or x.dim() != 2 or tuple(x.shape) != (V, D) or not x.is_contiguous():
+                raise TypeError(f"table {i}: p, m, v must be contiguous float32 [V, D] tables of one shape")
+        uniq, U = _group_sums(f"multitable_optim_ table {i}", t.plan, t.sums, D)
+        if t.plan.n_uniq_dev.dtype != torch.int64 or t.plan.n_uniq_dev.numel() < 1:
+            raise TypeError(f"table {i}: the plan's n_uniq_dev must be an int64 device word")
+        if t.w is not None:
+            for x in (t.w, t.accum, t.linear):
+                if x.dtype != torch.float32 or x.numel() != V or x.dim() != 1 or not x.is_contiguous():
+                    raise TypeError(f"table {i}: w, accum and linear must be contiguous float32 [{V}] vectors")
+            if t.wsums.dtype != torch.float32 or t.wsums.dim() != 1 or t.wsums.numel() < U or not t.wsums.is_contiguous():
+                raise TypeError(f"table {i}: wsums must be contiguous float32 [>= {U}]")
+        keep.append(uniq)
+        dev = t.p.device
+        tarr[i] = MtOptTab(t.p.data_ptr(), t.m.data_ptr(), t.v.data_ptr(), V, D, *[x.data_ptr() if x is not None else None for x in wide[:3]],
+                           uniq.data_ptr(), U, t.plan.n_uniq_dev.data_ptr(), t.sums.data_ptr(), t.wsums.data_ptr() if t.wsums is not None else None)
+    for i, q in enumerate(vecs):
+        if not all(isinstance(x, torch.Tensor) for x in q):
+            raise TypeError(f"plain vector {i}: w, accum, linear and g must be tensors")
+        _need_cuda(*q)
+        n = _flat_same(*q)
+        dev = q.w.device
+        varr[i] = MtOptVec(q.w.data_ptr(), q.accum.data_ptr(), q.linear.data_ptr(), q.g.data_ptr(), n)
+    if dev is None:
+        return
+    if step_state is not None and not isinstance(step_state, StepState):
+        raise TypeError("multitable_optim_: step_state must be an ops.StepState")
+    tp = C.cast(tarr, C.c_void_p)
+    ws = workspace("mt_optim", max(_lib.query_bytes("mrec_mt_optim_workspace_bytes", tp, len(tabs)), 16), dev)
+    _lib.call("mrec_mt_optim", tp, len(tabs), C.cast(varr, C.c_void_p), len(vecs), C.cast(C.pointer(ah), C.c_void_p),
+              C.cast(C.pointer(fh), C.c_void_p), _ptr(step_state.buf) if step_state is not None else None, _ptr(ws), ws.numel(), _stream())
+    del keep
+
+
 def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.bfloat16, packed_words=0, drop=None, step_state=None,
                      max_norm=None):
     """Both lookups of WideDeepModel.construct (wide_and_deep.py:300-302) in one pass over fused rows: returns
@@ -955,15 +1065,16 @@ def _ftrl1(one):
 
 
 def dense_adam_(p, m, v, g, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_power=0.9, beta2_power=0.999,
-                grad_scale=1.0, use_nesterov=False, shadow_bf16=None, ftrl1=None):
+                grad_scale=1.0, use_nesterov=False, shadow_bf16=None, ftrl1=None, step_state=None):
     """nn.Adam over a whole tensor (wide_and_deep.py:435-437; deep_and_cross.py:342-344).  g may be
     bfloat16 (widened on load); shadow_bf16 (optional bf16 tensor of the same size) receives the updated
-    parameters rounded to bf16, ready to be the next forward's GEMM operand.  ftrl1: see _ftrl1."""
+    parameters rounded to bf16, ready to be the next forward's GEMM operand.  ftrl1: see _ftrl1.  step_state: the step size
+    from device memory (a captured step); not with ftrl1."""
     _need_cuda(p, m, v, g, shadow_bf16)
     n = _flat_same(p, m, v)
     if ftrl1 is not None:
-        if shadow_bf16 is not None or g.dtype != torch.float32 or g.numel() != n or not g.is_contiguous():
-            raise TypeError("dense_adam_(ftrl1=...): contiguous float32 gradient, no shadow")
+        if shadow_bf16 is not None or g.dtype != torch.float32 or g.numel() != n or not g.is_contiguous() or step_state is not None:
+            raise TypeError("dense_adam_(ftrl1=...): contiguous float32 gradient, no shadow, no step_state")
         f = _ftrl1(ftrl1)
         _lib.call("mrec_dense_adam_one_ftrl_f32", _ptr(p), _ptr(m), _ptr(v), _ptr(g), n, lr, beta1, beta2, eps, beta1_power,
                   beta2_power, grad_scale, int(use_nesterov), C.cast(C.pointer(f), C.c_void_p), _stream())
@@ -973,6 +1084,11 @@ def dense_adam_(p, m, v, g, lr=3.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, beta1_p
     if shadow_bf16 is not None and (shadow_bf16.dtype != torch.bfloat16 or shadow_bf16.numel() != n
                                     or not shadow_bf16.is_contiguous()):
         raise TypeError("shadow_bf16 must be a contiguous bfloat16 tensor of the parameter's size")
+    if step_state is not None:
+        _lib.call("mrec_dense_adam_step_f32", _ptr(p), _ptr(m), _ptr(v), _ptr(g), int(g.dtype == torch.bfloat16),
+                  _ptr(shadow_bf16), n, lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov),
+                  _ptr(step_state.buf), _stream())
+        return
     _lib.call("mrec_dense_adam_ex_f32", _ptr(p), _ptr(m), _ptr(v), _ptr(g), int(g.dtype == torch.bfloat16),
               _ptr(shadow_bf16), n, lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale, int(use_nesterov),
               _stream())
