@@ -1336,6 +1336,42 @@ int mrec_group_rank_ws_bytes(int64_t n, size_t* out);
 int mrec_group_rank_hist(const float* pred, const float* label, const int32_t* inv, const int64_t* n_groups_dev, int64_t n,
                          int32_t topk, int32_t pad_to, int64_t* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- row-wise 8-bit serving records (mrec_q8.hip) ---------------------------------------------------------------------------
+ * A trained fp32 table frozen for evaluation: one record per table row, per-row offset and scale (the FBGEMM / TorchRec row-wise
+ * convention), the row's wide weight in the header so that one read serves the deep and the wide branch.  A record is row_bytes
+ * long and 16-byte aligned, row_bytes % 16 == 0 and row_bytes >= 16 + 16 ceil(D / 16) (the compact size, mrec_q8_row_bytes):
+ *
+ *   bytes 0..3          float lo      the row's minimum, exact
+ *   bytes 4..7          float scale   (hi - lo) / 255 in fp32 (hi: the row's maximum); 0 where hi == lo
+ *   bytes 8..11         float wide    the row's wide weight, copied unchanged; 0 where no wide source is given
+ *   bytes 12..15        zero
+ *   bytes 16..16+D-1    uint8 code[d] = min(255, rint((x[d] - lo) / scale)) -- an fp32 subtraction and an fp32 division, each rounded,
+ *                       rint to nearest even --; 0 where scale == 0
+ *   the rest            zero
+ *
+ * Dequantisation: x'[d] = lo + (float)code[d] * scale, one fp32 multiply and one fp32 add, each rounded (no fused multiply-add).
+ * Shapes: D % 4 == 0 and 4 <= D <= 256; anything else is MREC_EUNSUPPORTED, a row_bytes that is too small or no multiple of 16 is
+ * MREC_EINVAL (the shape is judged first), both before any launch.  Table rows are assumed finite; this is not checked.
+ *
+ * mrec_q8_row_bytes: the compact record size 16 + 16 ceil(D / 16) (D = 80: 96), or the negative code above.
+ *
+ * mrec_q8_quantize_rows: one pass over the fp32 [V, D] view `table` of row stride ld (floats; a fused training row is such a view)
+ *   writes all V records -- header, codes and every padding byte: no memset in front.  wide (nullable): a [V, 1] view of stride ldw
+ *   (for fused rows: column D of the same rows).  ld % 4 == 0, table and records 16-byte aligned (else MREC_EUNSUPPORTED).  V up to
+ *   2^31 and beyond (rows are counted in 64 bits).  One launch, no workspace, capturable.
+ *
+ * mrec_q8_gather_rows: out[i * ldo + d] = round(x'[ids[i]][d] * row_scale[i]) for d < D (row_scale nullable: 1), out_kind 0 / 1 / 2 =
+ *   float / bf16 / f16 rows, rounded once to nearest even; ldo in elements of out, ldo % 4 == 0, out 8-byte aligned (fp32 rows:
+ *   16-byte), else MREC_EUNSUPPORTED.  wide_prod (nullable): wide_prod[i * ldw] = wide * row_scale[i] and wide_prod[i * ldw + 1] = 0,
+ *   stored as one 8-byte pair (ldw even, wide_prod 8-byte aligned) -- the pairs of mrec_gather_rows_wide, which mrec_head_predict and
+ *   mrec_tail_predict sum per sample.  An id outside [0, V) gives a zero row and a zero product.  id_bytes 4 / 8; V >= 1.  One
+ *   launch, no workspace, capturable. */
+int mrec_q8_row_bytes(int32_t D);
+int mrec_q8_quantize_rows(const float* table, int64_t V, int64_t ld, int32_t D, const float* wide, int64_t ldw, void* records,
+                          int64_t row_bytes, void* stream);
+int mrec_q8_gather_rows(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t n,
+                        const float* row_scale, void* out, int32_t out_kind, int64_t ldo, float* wide_prod, int64_t ldw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,9 @@ _SIGS = {
     "mrec_auc_counts": [_vp, _vp, _i64, _vp, _vp, _sz, _vp],
     "mrec_group_rank_ws_bytes": [_i64, _szp],
     "mrec_group_rank_hist": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp],
+    "mrec_q8_row_bytes": [_i32],
+    "mrec_q8_quantize_rows": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
+    "mrec_q8_gather_rows": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i64, _vp],
 }
 _RESTYPES = {"mrec_strerror": C.c_char_p, "mrec_map_counters_dev": _vp, "mrec_map_row_keys_dev": _vp}
 

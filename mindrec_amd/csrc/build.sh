@@ -19,7 +19,9 @@ for src in mrec_*.hip; do
         [ "$stale" = 0 ] && [ "$dep" -nt "$obj" ] && stale=1
     done
     if [ "$stale" = 1 ]; then
-        $HIPCC $FLAGS -c "$src" -o "$obj" &
+        # a source may name flags of its own in a line "// build-flags: ..." (mrec_q8.hip: no packed fp32 instructions -- a device
+        # feature, which the host pass of the same compile answers with a note "not a recognized feature ... (ignoring feature)")
+        $HIPCC $FLAGS $(sed -n 's|^// build-flags: ||p' "$src") -c "$src" -o "$obj" &
         pids+=($!)
     fi
 done

@@ -1,0 +1,221 @@
+// mrec_q8.hip -- row-wise int8 serving tables for gfx950: the quantize pass over a trained fp32 table and the dequantizing lookup
+// (record format and the entries' contract: include/mrec.h, "row-wise 8-bit serving records").
+// build-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
+//
+// A record is [lo scale wide 0 | D codes | zero padding]: a 16-byte header chunk and C = ceil(D / 16) chunks of 16 codes, row_bytes
+// in all (compact: 16 (C + 1); D = 80 -> 96 B against the 336 B the fp32 folded lookup takes out of a 1-KB training row).
+//
+// k_q8_quantize  lane-group = D / 4 lanes per row, one 16-byte load each (a fused training row is read in place through ld); min and
+//                max travel a butterfly inside the group (ds_bpermute; both are idempotent, so a lane whose partner lies past the row
+//                reads the row's last lane instead and still ends with the row's exact extremes); four codes per lane leave as one
+//                dword, lane 0 stores the header as one 16-byte word, the lanes share the padding's dwords.  Workgroups are persistent
+//                over V, rows are counted in 64 bits.  Roofline bytes per row: 4 D + 4 (wide) read, row_bytes written.
+// k_q8_gather    lane-group = C + 1 lanes per looked-up position: lane 0 loads the header chunk, lane c the c-th chunk of 16 codes --
+//                ONE 16-byte load instruction per position, GB = 4 positions in flight per group before the first store.  lo and
+//                scale reach the code lanes by two ds_bpermute reads of lane 0; bytes unpack on v_cvt_f32_ubyte0..3; x' = lo + code
+//                * scale (a multiply and an add, each rounded), then * row_scale.  16-bit rows round once, to nearest even, on
+//                gfx950's packed conversions (v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32) and a code lane leaves with two 16-byte stores
+//                (fp32 rows: four); the header lane stores the wide product pair (wide * row_scale, 0) as 8 bytes.
+//                Lanes per row: D = 80 -> 6 lanes, 10 positions per wave, 60 / 64 lanes busy; D = 256 -> 17 lanes, 3 per wave, 51 / 64
+//                (a group of 16 code lanes with the header fetched a second time by every lane would fill the wave at D = 256 but
+//                doubles the load instructions at every D; the header lane is also where the wide product comes from).
+//                Roofline bytes per position: row_bytes read (+ id, + row_scale), 2 D (16-bit) or 4 D written, + 8 (wide pair).
+#include "mrec_common.h"
+
+namespace {
+
+constexpr int kQ8Hdr = 16;       // bytes of the header chunk
+constexpr int kQ8GB = 4;         // positions in flight per lane-group of the lookup
+
+__device__ __forceinline__ float bperm_f(int src_lane, float v) {
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
+}
+
+__device__ __forceinline__ float q8_code(float x, float lo, float scale) {
+    const float q = fminf(rintf((x - lo) / scale), 255.0f);
+    return scale > 0.0f ? q : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_q8_quantize(const float* __restrict__ table, int64_t V, int64_t ld, int D,
+                                                     const float* __restrict__ wide, int64_t ldw, uint8_t* __restrict__ rec,
+                                                     int64_t row_bytes, RowGeom gm) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, ds = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int nd = gm.lpr, lane0 = lane - ds;
+    const int pad_dw = (int)((row_bytes - kQ8Hdr - D) >> 2);          // zero dwords behind the codes
+    const int64_t stride = (int64_t)gridDim.x * 4 * gm.G;
+    for (int64_t r = ((int64_t)blockIdx.x * 4 + wave) * gm.G + grp; r < V; r += stride) {
+        const float4 x = *(const float4*)(table + r * ld + 4 * ds);
+        float w = 0.0f;
+        if (ds == 0 && wide) w = wide[r * ldw];
+        float lo = fminf(fminf(x.x, x.y), fminf(x.z, x.w));
+        float hi = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
+        for (int m = 1; m < nd; m <<= 1) {
+            const int p = ds ^ m;
+            const int src = lane0 + (p < nd ? p : nd - 1);
+            lo = fminf(lo, bperm_f(src, lo));
+            hi = fmaxf(hi, bperm_f(src, hi));
+        }
+        const float scale = (hi - lo) / 255.0f;
+        const unsigned codes = (unsigned)q8_code(x.x, lo, scale) | ((unsigned)q8_code(x.y, lo, scale) << 8) |
+                               ((unsigned)q8_code(x.z, lo, scale) << 16) | ((unsigned)q8_code(x.w, lo, scale) << 24);
+        uint8_t* const o = rec + r * row_bytes;
+        if (ds == 0) *(uint4*)o = make_uint4(__float_as_uint(lo), __float_as_uint(scale), __float_as_uint(w), 0u);
+        *(uint32_t*)(o + kQ8Hdr + 4 * ds) = codes;
+        for (int j = ds; j < pad_dw; j += nd) *(uint32_t*)(o + kQ8Hdr + D + 4 * j) = 0u;
+    }
+}
+
+// four dequantized, scaled values -> 8 bytes of 16-bit output, rounded once to nearest even
+__device__ __forceinline__ uint2 q8_pack16(const f16o_t*, float a, float b, float c, float d) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 u = {(_Float16)a, (_Float16)b}, v = {(_Float16)c, (_Float16)d};
+    return make_uint2(__builtin_bit_cast(unsigned, u), __builtin_bit_cast(unsigned, v));
+}
+__device__ __forceinline__ uint2 q8_pack16(const bf16o_t*, float a, float b, float c, float d) {
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    const b2 u = {(__bf16)a, (__bf16)b}, v = {(__bf16)c, (__bf16)d};
+    return make_uint2(__builtin_bit_cast(unsigned, u), __builtin_bit_cast(unsigned, v));
+}
+
+// the four codes of one dword -> x' * sc
+__device__ __forceinline__ float4 q8_dequant4(unsigned w, float lo, float scale, float sc) {
+    float4 y;
+    y.x = (lo + (float)(w & 0xFFu) * scale) * sc;
+    y.y = (lo + (float)((w >> 8) & 0xFFu) * scale) * sc;
+    y.z = (lo + (float)((w >> 16) & 0xFFu) * scale) * sc;
+    y.w = (lo + (float)(w >> 24) * scale) * sc;
+    return y;
+}
+
+// st16: the output rows are 16-byte aligned, so a code lane's 16 values leave as 16-byte stores; otherwise (16-bit rows of D % 8 == 4
+// columns) as 8-byte ones.  The last chunk of a row holds 4, 8, 12 or 16 columns: `valid`.
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q8_gather(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                   const K* __restrict__ ids, int64_t n, const float* __restrict__ row_scale,
+                                                   OT* __restrict__ out, int64_t ldo, float* __restrict__ wprod, int64_t ldw,
+                                                   RowGeom gm, bool st16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 16;                                    // (the header lane: -16, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 16 ? D - col0 : 16);
+    const int64_t wave_row0 = ((int64_t)blockIdx.x * 4 + wave) * (gm.G * kQ8GB);
+    const int64_t nlast = n - 1;
+    int64_t row[kQ8GB];
+    float sc[kQ8GB];
+    uint4 x[kQ8GB];
+    // as k_gather_rows: every load is requested unconditionally (a position past the end reads the last id, an id out of range
+    // record 0; both are dropped) so that the GB records are in flight together
+#pragma unroll
+    for (int k = 0; k < kQ8GB; ++k) {
+        const int64_t i = wave_row0 + (int64_t)k * gm.G + grp;
+        const int64_t ic = i < n ? i : nlast;
+        row[k] = (int64_t)ids[ic];
+        sc[k] = row_scale ? row_scale[ic] : 1.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < kQ8GB; ++k) {
+        const bool ok = row[k] >= 0 && row[k] < V;
+        x[k] = *(const uint4*)(rec + (ok ? row[k] : 0) * row_bytes + 16 * sub);
+        if (!ok) row[k] = -1;
+    }
+#pragma unroll
+    for (int k = 0; k < kQ8GB; ++k) {
+        asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+        if (row[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);              // header and codes zero: a zero row, a zero product
+    }
+#pragma unroll
+    for (int k = 0; k < kQ8GB; ++k) {
+        const int64_t i = wave_row0 + (int64_t)k * gm.G + grp;
+        const float lo = bperm_f(lane0, __uint_as_float(x[k].x));
+        const float scale = bperm_f(lane0, __uint_as_float(x[k].y));
+        if (i >= n) continue;
+        if (sub == 0) {
+            if (wprod) *(uint2*)(wprod + ldw * i) = make_uint2(__float_as_uint(__uint_as_float(x[k].z) * sc[k]), 0u);
+            continue;
+        }
+        const float4 y0 = q8_dequant4(x[k].x, lo, scale, sc[k]), y1 = q8_dequant4(x[k].y, lo, scale, sc[k]);
+        const float4 y2 = q8_dequant4(x[k].z, lo, scale, sc[k]), y3 = q8_dequant4(x[k].w, lo, scale, sc[k]);
+        OT* const o = out + i * ldo + col0;
+        if constexpr (sizeof(OT) == 4) {
+            *(float4*)o = y0;
+            if (valid > 4) *(float4*)(o + 4) = y1;
+            if (valid > 8) *(float4*)(o + 8) = y2;
+            if (valid > 12) *(float4*)(o + 12) = y3;
+        } else {
+            const uint2 h0 = q8_pack16((const OT*)nullptr, y0.x, y0.y, y0.z, y0.w), h1 = q8_pack16((const OT*)nullptr, y1.x, y1.y, y1.z, y1.w);
+            const uint2 h2 = q8_pack16((const OT*)nullptr, y2.x, y2.y, y2.z, y2.w), h3 = q8_pack16((const OT*)nullptr, y3.x, y3.y, y3.z, y3.w);
+            if (st16) {
+                if (valid > 4) *(uint4*)o = make_uint4(h0.x, h0.y, h1.x, h1.y);
+                else *(uint2*)o = h0;
+                if (valid > 12) *(uint4*)(o + 8) = make_uint4(h2.x, h2.y, h3.x, h3.y);
+                else if (valid > 8) *(uint2*)(o + 8) = h2;
+            } else {
+                *(uint2*)o = h0;
+                if (valid > 4) *(uint2*)(o + 4) = h1;
+                if (valid > 8) *(uint2*)(o + 8) = h2;
+                if (valid > 12) *(uint2*)(o + 12) = h3;
+            }
+        }
+    }
+}
+
+/* D and row_bytes as include/mrec.h states them: the shape first (MREC_EUNSUPPORTED), then the record size (MREC_EINVAL) */
+int q8_check(int32_t D, int64_t row_bytes) {
+    if (D <= 0) return MREC_EINVAL;
+    if (D % 4 || D > 256) return MREC_EUNSUPPORTED;
+    if (row_bytes % 16 || row_bytes < kQ8Hdr + 16 * ((D + 15) / 16)) return MREC_EINVAL;
+    return MREC_OK;
+}
+
+}  // namespace
+
+MREC_API int mrec_q8_row_bytes(int32_t D) {
+    if (D <= 0) return MREC_EINVAL;
+    if (D % 4 || D > 256) return MREC_EUNSUPPORTED;
+    return kQ8Hdr + 16 * ((D + 15) / 16);
+}
+
+MREC_API int mrec_q8_quantize_rows(const float* table, int64_t V, int64_t ld, int32_t D, const float* wide, int64_t ldw, void* records,
+                                   int64_t row_bytes, void* stream) {
+    if (const int rc = q8_check(D, row_bytes)) return rc;
+    if (V < 0 || ld < D || (wide && ldw < 1)) return MREC_EINVAL;
+    if (V == 0) return MREC_OK;
+    if (!table || !records) return MREC_EINVAL;
+    if (ld % 4 || !al16(table) || !al16(records)) return MREC_EUNSUPPORTED;
+    const RowGeom gm{D / 4, 64 / (D / 4)};
+    int64_t blocks = mrec_cdiv(V, 4 * gm.G);
+    if (blocks > 2048) blocks = 2048;                                   // 256 CUs x 8 workgroups, each walking V
+    k_q8_quantize<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(table, V, ld, D, wide, ldw, (uint8_t*)records, row_bytes, gm);
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+MREC_API int mrec_q8_gather_rows(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t n,
+                                 const float* row_scale, void* out, int32_t out_kind, int64_t ldo, float* wide_prod, int64_t ldw,
+                                 void* stream) {
+    if (const int rc = q8_check(D, row_bytes)) return rc;
+    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || n < 0 || V < 1 || ldo < D) return MREC_EINVAL;
+    if (wide_prod && (ldw < 2 || ldw % 2 || (((uintptr_t)wide_prod) & 7))) return MREC_EINVAL;
+    if (n == 0) return MREC_OK;
+    if (!records || !ids || !out) return MREC_EINVAL;
+    const int esz = out_kind == 0 ? 4 : 2;
+    if (ldo % 4 || !al16(records) || (((uintptr_t)out) & 7)) return MREC_EUNSUPPORTED;
+    const bool st16 = al16(out) && (ldo * esz) % 16 == 0;
+    if (esz == 4 && !st16) return MREC_EUNSUPPORTED;
+    const int lpr = (D + 15) / 16 + 1;
+    const RowGeom gm{lpr, 64 / lpr};
+    const int64_t blocks = mrec_cdiv(n, (int64_t)4 * gm.G * kQ8GB);
+    if (blocks >= (1ll << 31)) return MREC_EUNSUPPORTED;
+    return by_key(ids, id_bytes, [&](auto* kp) {
+        return by_out(out, out_kind, [&](auto* op) {
+            k_q8_gather<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, n, row_scale, op, ldo,
+                                                                            wide_prod, ldw, gm, st16);
+            MREC_LAUNCH_CHECK();
+            return (int)MREC_OK;
+        });
+    });
+}

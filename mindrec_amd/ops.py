@@ -715,6 +715,68 @@ def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.
     return out.view(tuple(ids.shape) + (D,)), wprod.view(tuple(ids.shape) + (2,))
 
 
+# ---- row-wise 8-bit serving records (csrc/mrec_q8.hip; the record format: include/mrec.h) --------------------------------
+class Q8Table(NamedTuple):
+    """A table frozen for evaluation: records uint8 [V, row_bytes], one per row -- [lo scale wide 0 | D codes | zero padding]."""
+    records: torch.Tensor
+    V: int
+    D: int
+    row_bytes: int
+
+
+def q8_row_bytes(D):
+    """The compact record size of a D-column row: 16 + 16 ceil(D / 16) bytes (D % 4 == 0, 4 <= D <= 256)."""
+    rb = _lib.lib().mrec_q8_row_bytes(int(D))
+    _lib.check("mrec_q8_row_bytes", rb if rb < 0 else 0)
+    return rb
+
+
+def _q8_records(q8):
+    r = q8.records
+    if r.dtype != torch.uint8 or tuple(r.shape) != (q8.V, q8.row_bytes) or not r.is_contiguous():
+        raise TypeError("Q8Table.records must be a contiguous uint8 [V, row_bytes] tensor")
+    return r
+
+
+def quantize_rows_q8(table, wide=None, row_bytes=None, out=None):
+    """Freezes the fp32 [V, D] view `table` (any row stride: a fused training row is read in place) into row-wise 8-bit records, one
+    pass, every byte of every record written.  wide: the rows' wide weights, a float32 [V, 1] (or [V]) view of any row stride, copied
+    into the record headers (None: 0).  row_bytes: the record size, a multiple of 16 (default: compact, q8_row_bytes(D); 128-byte
+    multiples keep a record inside one cache line pair at a third more memory).  out: a uint8 [V, row_bytes] tensor to write into."""
+    _need_cuda(table, wide, out)
+    V, D, ld = _table(table)
+    rb = q8_row_bytes(D) if row_bytes is None else int(row_bytes)
+    ldw = 0
+    if wide is not None:
+        if wide.dtype != torch.float32 or wide.shape[0] != V or wide.numel() != V:
+            raise TypeError("wide must be a float32 [V, 1] tensor")
+        ldw = wide.stride(0) if V > 1 else 1
+    if out is None:
+        out = torch.empty((V, max(rb, 0)), dtype=torch.uint8, device=table.device)
+    q8 = Q8Table(out, V, D, rb)
+    _lib.call("mrec_q8_quantize_rows", _ptr(table), V, ld, D, _ptr(wide), ldw, _ptr(_q8_records(q8)), rb, _stream())
+    return q8
+
+
+def gather_rows_q8(q8, ids, row_scale=None, out=None, out_dtype=torch.float16, wide=True):
+    """gather_rows_wide over a Q8Table: (rows [.., D] = the dequantized rows lo + code * scale of `ids`, times row_scale, rounded once
+    to out_dtype (float32, bfloat16 or float16), wide_prod [.., 2] with [.., 0] = the record's wide weight * row_scale and [.., 1] = 0;
+    None with wide=False).  An id outside [0, V) gives a zero row and a zero product."""
+    _need_cuda(q8.records, ids, row_scale, out)
+    flat, n, row_scale = _flat_ids(ids, row_scale)
+    _suffix(ids)
+    if out is None:
+        if out_dtype not in _KIND:
+            raise TypeError("gather_rows_q8 out_dtype must be float32, bfloat16 or float16")
+        out = torch.empty((n, q8.D), dtype=out_dtype, device=q8.records.device)
+    elif out.dtype not in _KIND or out.numel() != n * q8.D or not out.is_contiguous():
+        raise TypeError("gather_rows_q8: out must be a contiguous float32, bfloat16 or float16 tensor of n * D elements")
+    wprod = torch.empty((max(n, 1), 2), dtype=torch.float32, device=out.device)[:n] if wide else None
+    _lib.call("mrec_q8_gather_rows", _ptr(_q8_records(q8)), q8.V, q8.row_bytes, q8.D, _ptr(flat), flat.element_size(), n, _ptr(row_scale),
+              _ptr(out), _KIND[out.dtype], q8.D, _ptr(wprod), 2, _stream())
+    return out.view(tuple(ids.shape) + (q8.D,)), (wprod.view(tuple(ids.shape) + (2,)) if wide else None)
+
+
 def gather_rows_skip_(table, rows, out):
     """out[i, :] = table[rows[i], :] where rows[i] is a row of the table; rows of ids outside it (-1) are LEFT ALONE (the lookup in
     front has written them: KeyIndex.lookup(out=...))."""

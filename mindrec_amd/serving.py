@@ -1,0 +1,54 @@
+"""Serving a trained Wide&Deep model from row-wise 8-bit records (csrc/mrec_q8.hip): the evaluation forward of
+WideDeepEngine.predict_fused with the dequantizing lookup in front, holding neither the fp32 table nor any optimizer slot of it.
+Made by WideDeepEngine.q8_predictor()."""
+import torch
+
+from . import ops
+from .wide_deep_mlp import DenseNetMixin, _WideProd
+
+
+class _ServeNet(DenseNetMixin):
+    """The dense net of a predictor: DenseNetMixin as multitable._TrainNet hosts it -- its own fp32 parameters, the 16-bit operand shadow,
+    the transposes and the tail launch's fragment order --, evaluation only (no Dropout, no step, no graphs of its own)."""
+    k = ops
+
+    def __init__(self, dims, amp, mfma, device, fused_tail, fused_tail_eval):
+        self.cfg, self.device, self._gpu, self._amp, self._mfma = None, device, True, amp, mfma
+        self._graph_level, self.rank, self.step_count, self._step_state = 0, 0, 0, None
+        self._dropout = self._training = self._emb_dropped = False
+        self._init_dense_net(dims, 0, 0.01, 1.0, fused_tail=fused_tail, fused_tail_eval=fused_tail_eval)
+        self.wide_b = self.extra_p                  # what mlp_predict adds to the summed wide products
+        self.dense_m = self.dense_v = None          # a predictor has no optimizer
+
+
+class WideDeepQ8Predictor:
+    """A Q8Table (the deep rows as 8-bit codes, the wide weight in each record's header) + a copy of the dense parameters and the wide
+    bias.  predict_fused is WideDeepEngine.predict_fused's contract over the dequantized table; the launches are issued eagerly."""
+
+    def __init__(self, q8, dims, weights, biases, wide_b, mlp_dtype=None, mfma=None, fused_tail=True, fused_tail_eval=True):
+        """q8: ops.Q8Table on the GPU; dims: [F * D, hidden .., 1]; weights[i] [in_i, out_i], biases[i] [out_i] and wide_b as
+        load_dense_parameters takes them; mlp_dtype: torch.float16 / torch.bfloat16, None for an fp32 net."""
+        self.q8 = q8
+        self.device = q8.records.device
+        if self.device.type != "cuda":
+            raise RuntimeError("WideDeepQ8Predictor runs on an MI355X (no CPU fallback)")
+        if dims[0] % q8.D:
+            raise ValueError(f"the net's input width {dims[0]} is no multiple of the table's emb_dim {q8.D}")
+        mfma = (mlp_dtype is not None and DenseNetMixin.mfma_net_ok(dims)) if mfma is None else bool(mfma)
+        with torch.cuda.device(self.device):
+            self.net = _ServeNet(list(dims), mlp_dtype, mfma, self.device, fused_tail, fused_tail_eval)
+            self.net.load_dense_parameters(weights, biases, extra=wide_b)
+        self._row_dtype = mlp_dtype if mfma else torch.float32
+
+    def _chain(self, ids, wts, label):
+        B, F = ids.shape
+        rows, wprod = ops.gather_rows_q8(self.q8, ids, wts, out_dtype=self._row_dtype)
+        return self.net.mlp_predict(rows.view(B, F * self.q8.D), _WideProd(wprod), label)
+
+    def predict_fused(self, ids, wts, label=None):
+        """ids, wts [B, F] -> (logit [B, 1], prob [B, 1]) and, with `label`, the batch's mean sigmoid cross-entropy (0-d) as a third value:
+        the dequantizing lookup, then the hidden-layer, tail and head launches of the engine's evaluation forward."""
+        if ids.dim() != 2 or ids.shape[1] * self.q8.D != self.net.dims[0]:
+            raise ValueError(f"ids must be [B, {self.net.dims[0] // self.q8.D}], got {tuple(ids.shape)}")
+        with torch.cuda.device(self.device):
+            return self.net._predict_run(self._chain, ids, wts, label, capture=False)

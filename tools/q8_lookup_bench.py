@@ -1,0 +1,78 @@
+"""The dequantizing lookup over row-wise 8-bit records (ops.gather_rows_q8, compact and 128-byte records) against the fp32 folded
+lookup (ops.gather_rows_wide over fused training rows) on the same ids, and the quantize pass over the same table.
+
+    python tools/q8_lookup_bench.py [vocab] [blocks] [calls]
+
+Benchmark shape: 16384 x 39 positions, D = 80, vocabulary 2e7 (fused rows: 20 GB), fp16 rows, uniform ids and the benchmark's Zipf
+stream.  Each arm is warmed, then timed as `blocks` blocks of `calls` calls between two device events, the arms alternating in
+rotation; one JSON line per id distribution with the median (min, max) microseconds per call and the GB/s that implies against the
+arm's algorithmic bytes per position: the record or the 336 bytes of the fp32 row, the fp16 output row, the 8-byte wide pair, id and
+weight.  The quantize pass is timed the same way (read 4 D + 4, write row_bytes per row)."""
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _time(arms, blocks, calls):
+    for f in arms.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    us = {k: [] for k in arms}
+    for _ in range(blocks):
+        for k, f in arms.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                f()
+            b.record()
+            b.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3 / calls)
+    return {k: sorted(v) for k, v in us.items()}
+
+
+def _line(us, nbytes):
+    med = us[len(us) // 2]
+    return {"us": round(med, 2), "min": round(us[0], 2), "max": round(us[-1], 2), "GB/s": round(nbytes / med / 1e3, 1)}
+
+
+def main():
+    from mindrec_amd import ops
+    from mindrec_amd.wide_deep import WideDeepConfig, synthetic_batch
+    V = int(float(sys.argv[1])) if len(sys.argv) > 1 else 20_000_000
+    blocks = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+    calls = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+    dev = torch.device("cuda:0")
+    D, B, F = 80, 16384, 39
+    ld = -(-(3 * D + 4) // 32) * 32
+    state = torch.zeros((V, ld), dtype=torch.float32, device=dev)
+    deep, wide = state[:, :D], state[:, D:D + 1]
+    ops.fill_normal_(deep, 1000)
+    ops.fill_normal_(wide, 1001)
+    compact = ops.q8_row_bytes(D)
+    q8 = {rb: ops.quantize_rows_q8(deep, wide, row_bytes=rb) for rb in (compact, 128)}
+    n = B * F
+    for rb, t in q8.items():
+        us = _time({"q": lambda t=t, rb=rb: ops.quantize_rows_q8(deep, wide, row_bytes=rb, out=t.records)}, max(blocks // 3, 3), 2)["q"]
+        print(json.dumps({"what": "quantize", "V": V, "row_bytes": rb, **_line(us, V * (4 * D + 4 + rb))}), flush=True)
+    cfg = WideDeepConfig(vocab_size=V, emb_dim=D, field_size=F, batch_size=B)
+    for dist in ("uniform", "zipf"):
+        ids, wts, _ = synthetic_batch(cfg, dev, dist, seed=1000)
+        out = torch.empty((n, D), dtype=torch.float16, device=dev)
+        arms = {"fp32_folded": lambda: ops.gather_rows_wide(deep, ids, wts, D, out=out, out_dtype=torch.float16)}
+        for rb, t in q8.items():
+            arms[f"q8_{rb}"] = lambda t=t: ops.gather_rows_q8(t, ids, wts, out=out)
+        us = _time(arms, blocks, calls)
+        common = 2 * D + 8 + 4 + 4
+        res = {"fp32_folded": _line(us["fp32_folded"], n * (4 * D + 16 + common))}
+        for rb in q8:
+            res[f"q8_{rb}"] = _line(us[f"q8_{rb}"], n * (rb + common))
+        print(json.dumps({"what": "lookup", "ids": dist, "positions": n, "V": V, **res}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
