@@ -1365,12 +1365,31 @@ int mrec_group_rank_hist(const float* pred, const float* label, const int32_t* i
  *   16-byte), else MREC_EUNSUPPORTED.  wide_prod (nullable): wide_prod[i * ldw] = wide * row_scale[i] and wide_prod[i * ldw + 1] = 0,
  *   stored as one 8-byte pair (ldw even, wide_prod 8-byte aligned) -- the pairs of mrec_gather_rows_wide, which mrec_head_predict and
  *   mrec_tail_predict sum per sample.  An id outside [0, V) gives a zero row and a zero product.  id_bytes 4 / 8; V >= 1.  One
- *   launch, no workspace, capturable. */
+ *   launch, no workspace, capturable.
+ *
+ * mrec_q8_fm_lookup: mrec_fm_lookup (DeepFM's evaluation lookup, no clip) over records, one launch.  ids, wts [B, F]; for sample b and
+ *   field f let r = ids[b, f], t = wts[b, f] and y[b, f, d] = fl(x'[r][d] * t) in fp32.
+ *     rows[b, f, :] = y rounded once to rows_kind (0 fp32, 1 bf16, 2 f16; nearest even), rows [B, F, D] contiguous: bit for bit what
+ *       mrec_q8_gather_rows writes for the same position with row_scale = wts;
+ *     lin_fm[b]     = lin + 0.5f * sum_d (s_d^2 - q_d), lin = sum_f fl(wide_r * t) from +0 in ascending field order (the record's third
+ *       header float is the FM's first-order weight: mrec_wide_sum's sum), s_d = sum_f y, q_d = sum_f y^2 over the fp32 y -- before
+ *       any 16-bit rounding --, both from +0 in ascending field order.  The sum over d: columns in chunks of 16 (a record's code
+ *       chunks); inside a chunk each group of four columns as ((p0 + p1) + (p2 + p3)), p = s^2 - q, the chunk's valid groups added in
+ *       ascending order; the chunks c = 1 .. C = ceil(D / 16), with +0 in slot 0, by a tree at distances 16, 8, 4, 2, 1: slot i takes
+ *       slot i + dist where i + dist <= C, slot 0 is the sum.  No atomics: lin_fm is the same run to run and whatever rows_kind and
+ *       id_bytes are.
+ *   An id outside [0, V) reads as a zero record: a zero row (+0 * t) and a zero linear weight.  No max_norm.
+ *   The shape and record-size codes above come first; then MREC_EINVAL: id_bytes not 4 or 8, rows_kind outside 0..2, B < 0, F < 1,
+ *   V < 1; B == 0: MREC_OK; then MREC_EINVAL for a NULL pointer other than stream, MREC_EUNSUPPORTED for records not 16-byte aligned or
+ *   rows not 8-byte (fp32 rows: 16-byte) aligned.  Every refusal comes before the launch and leaves rows and lin_fm untouched.  No
+ *   workspace, capturable. */
 int mrec_q8_row_bytes(int32_t D);
 int mrec_q8_quantize_rows(const float* table, int64_t V, int64_t ld, int32_t D, const float* wide, int64_t ldw, void* records,
                           int64_t row_bytes, void* stream);
 int mrec_q8_gather_rows(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t n,
                         const float* row_scale, void* out, int32_t out_kind, int64_t ldo, float* wide_prod, int64_t ldw, void* stream);
+int mrec_q8_fm_lookup(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, const float* wts,
+                      int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm, void* stream);
 
 #ifdef __cplusplus
 }

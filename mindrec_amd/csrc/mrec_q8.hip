@@ -20,12 +20,26 @@
 //                (a group of 16 code lanes with the header fetched a second time by every lane would fill the wave at D = 256 but
 //                doubles the load instructions at every D; the header lane is also where the wide product comes from).
 //                Roofline bytes per position: row_bytes read (+ id, + row_scale), 2 D (16-bit) or 4 D written, + 8 (wide pair).
+// k_q8_fm_lookup DeepFM's evaluation lookup (k_fm_lookup, mrec_fm.hip) over records: k_q8_gather's lane-group turned from a position
+//                onto a SAMPLE -- lane 0 owns the header chunk of every record of its sample, lane c the c-th 16 codes -- walking the
+//                sample's F fields four at a time: the four ids and weights, then the four records (one 16-byte load per lane per
+//                field, all requested unconditionally: a field past F re-reads the batch's last field and is dropped, an id out of
+//                range reads record 0 and is zeroed), consumed in straight-line code.  A code lane writes its 16 masked values per
+//                field under k_q8_gather's store rule and adds them, in fp32 and before any 16-bit rounding, into s[16] and q[16]
+//                (32 VGPRs), field order; the header lane stores nothing per field and only adds wide * wt into the linear sum (no
+//                8-byte wide pair exists here).  Column-sum order of lin_fm: inside a code lane, each group of four columns as
+//                ((p0 + p1) + (p2 + p3)), p = s^2 - q, the lane's one to four valid groups added in ascending order; then the
+//                group's lanes by a shuffle-down tree at distances 16, 8, 4, 2, 1 (lane sub adds lane sub + off where that is a
+//                lane of the group; the header lane enters with +0 and ends with the sum); lane 0 writes lin + 0.5f * part.  No
+//                LDS arrays, no barriers, no atomics.  Four waves per workgroup, a grid stride over samples, at most 2048 workgroups.
+//                Roofline bytes per sample: F (row_bytes + id + weight) read, F D 2 (16-bit rows) or F D 4, + 4 written.
 #include "mrec_common.h"
 
 namespace {
 
 constexpr int kQ8Hdr = 16;       // bytes of the header chunk
 constexpr int kQ8GB = 4;         // positions in flight per lane-group of the lookup
+constexpr int kQ8FmNB = 4;       // fields in flight per lane-group of the FM lookup (8: no faster)
 
 __device__ __forceinline__ float bperm_f(int src_lane, float v) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
@@ -163,6 +177,116 @@ __global__ __launch_bounds__(256) void k_q8_gather(const uint8_t* __restrict__ r
     }
 }
 
+// A code lane's 16 masked values of one field: written once in the output kind (k_q8_gather's store rule: st16, valid) and added into
+// the lane's column sums.  s and q take the fp32 values, whatever the output kind rounds them to.
+template <class OT>
+__device__ __forceinline__ void q8_fm_put(OT* __restrict__ o, const float4 (&y)[4], int valid, bool st16, bool store, float4 (&s)[4],
+                                          float4 (&q)[4]) {
+    if (store) {
+        if constexpr (sizeof(OT) == 4) {
+            *(float4*)o = y[0];
+            if (valid > 4) *(float4*)(o + 4) = y[1];
+            if (valid > 8) *(float4*)(o + 8) = y[2];
+            if (valid > 12) *(float4*)(o + 12) = y[3];
+        } else {
+            uint2 h[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = q8_pack16((const OT*)nullptr, y[j].x, y[j].y, y[j].z, y[j].w);
+            if (st16) {
+                if (valid > 4) *(uint4*)o = make_uint4(h[0].x, h[0].y, h[1].x, h[1].y);
+                else *(uint2*)o = h[0];
+                if (valid > 12) *(uint4*)(o + 8) = make_uint4(h[2].x, h[2].y, h[3].x, h[3].y);
+                else if (valid > 8) *(uint2*)(o + 8) = h[2];
+            } else {
+                *(uint2*)o = h[0];
+                if (valid > 4) *(uint2*)(o + 4) = h[1];
+                if (valid > 8) *(uint2*)(o + 8) = h[2];
+                if (valid > 12) *(uint2*)(o + 12) = h[3];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s[j].x = s[j].x + y[j].x; s[j].y = s[j].y + y[j].y; s[j].z = s[j].z + y[j].z; s[j].w = s[j].w + y[j].w;
+        q[j].x = q[j].x + y[j].x * y[j].x; q[j].y = q[j].y + y[j].y * y[j].y; q[j].z = q[j].z + y[j].z * y[j].z;
+        q[j].w = q[j].w + y[j].w * y[j].w;
+    }
+}
+
+// rows [B, F, D] contiguous.  A lane-group whose sample lies past B (the last wave's) reads sample 0's entries and stores nothing: every
+// lane of a live group-slot stays in the loop, so the ds_bpermute reads below always find their source lane active.
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q8_fm_lookup(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                      const K* __restrict__ ids, const float* __restrict__ wts, int64_t B, int F,
+                                                      OT* __restrict__ rows, float* __restrict__ lin_fm, RowGeom gm, bool st16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 16;                                    // (the header lane: -16, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 16 ? D - col0 : 16);
+    const int64_t ng = (int64_t)gridDim.x * 4 * gm.G;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wave) * gm.G; b0 < B; b0 += ng) {
+        const int64_t b = b0 + grp;
+        const bool live = b < B;
+        const int64_t e0 = (live ? b : 0) * (int64_t)F;
+        float4 s[4] = {zero4, zero4, zero4, zero4}, q[4] = {zero4, zero4, zero4, zero4};
+        float lin = 0.0f;
+        // kQ8FmNB fields, nf of them real: a spare slot reads the batch's last field again and is dropped, so s, q and the linear sum see
+        // the F fields alone, in field order (k_fm_lookup::fields4's rule)
+        const auto fields = [&](const int f, const int nf) {
+            int64_t r[kQ8FmNB];
+            float t[kQ8FmNB];
+            uint4 x[kQ8FmNB];
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) {
+                const int64_t e = e0 + f + (k < nf ? k : nf - 1);
+                r[k] = (int64_t)ids[e];
+                t[k] = wts[e];
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) {
+                const bool ok = r[k] >= 0 && r[k] < V;
+                x[k] = *(const uint4*)(rec + (ok ? r[k] : 0) * row_bytes + 16 * sub);
+                if (!ok) r[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) {
+                asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+                if (r[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);        // header and codes zero: a zero row, a zero linear weight
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) {
+                const float lo = bperm_f(lane0, __uint_as_float(x[k].x));
+                const float scale = bperm_f(lane0, __uint_as_float(x[k].y));
+                if (k >= nf) continue;
+                if (sub == 0) {
+                    lin = lin + __uint_as_float(x[k].z) * t[k];
+                    continue;
+                }
+                const float4 y[4] = {q8_dequant4(x[k].x, lo, scale, t[k]), q8_dequant4(x[k].y, lo, scale, t[k]),
+                                     q8_dequant4(x[k].z, lo, scale, t[k]), q8_dequant4(x[k].w, lo, scale, t[k])};
+                q8_fm_put(rows + ((b * F + f + k) * (int64_t)D + col0), y, valid, st16, live, s, q);
+            }
+        };
+        int f = 0;
+        for (; f + kQ8FmNB <= F; f += kQ8FmNB) fields(f, kQ8FmNB);
+        if (f < F) fields(f, F - f);
+        float part = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (valid > 4 * j)
+                part += ((s[j].x * s[j].x - q[j].x) + (s[j].y * s[j].y - q[j].y)) + ((s[j].z * s[j].z - q[j].z) + (s[j].w * s[j].w - q[j].w));
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) {
+            const float o = __shfl_down(part, off, 64);
+            if (sub + off < gm.lpr) part += o;
+        }
+        if (live && sub == 0) lin_fm[b] = lin + 0.5f * part;
+    }
+}
+
 /* D and row_bytes as include/mrec.h states them: the shape first (MREC_EUNSUPPORTED), then the record size (MREC_EINVAL) */
 int q8_check(int32_t D, int64_t row_bytes) {
     if (D <= 0) return MREC_EINVAL;
@@ -214,6 +338,29 @@ MREC_API int mrec_q8_gather_rows(const void* records, int64_t V, int64_t row_byt
         return by_out(out, out_kind, [&](auto* op) {
             k_q8_gather<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, n, row_scale, op, ldo,
                                                                             wide_prod, ldw, gm, st16);
+            MREC_LAUNCH_CHECK();
+            return (int)MREC_OK;
+        });
+    });
+}
+
+MREC_API int mrec_q8_fm_lookup(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes,
+                               const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm, void* stream) {
+    if (const int rc = q8_check(D, row_bytes)) return rc;
+    if ((id_bytes != 4 && id_bytes != 8) || rows_kind < 0 || rows_kind > 2 || B < 0 || F < 1 || V < 1) return MREC_EINVAL;
+    if (B == 0) return MREC_OK;
+    if (!records || !ids || !wts || !rows || !lin_fm) return MREC_EINVAL;
+    const int esz = rows_kind == 0 ? 4 : 2;
+    if (!al16(records) || (((uintptr_t)rows) & (esz == 4 ? 15 : 7))) return MREC_EUNSUPPORTED;
+    const bool st16 = al16(rows) && (D * esz) % 16 == 0;
+    const int lpr = (D + 15) / 16 + 1;
+    const RowGeom gm{lpr, 64 / lpr};
+    int64_t blocks = mrec_cdiv(B, (int64_t)4 * gm.G);
+    if (blocks > 2048) blocks = 2048;                                   // 256 CUs x 8 workgroups, each walking B
+    return by_key(ids, id_bytes, [&](auto* kp) {
+        return by_out(rows, rows_kind, [&](auto* op) {
+            k_q8_fm_lookup<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, wts, B, F, op,
+                                                                               lin_fm, gm, st16);
             MREC_LAUNCH_CHECK();
             return (int)MREC_OK;
         });

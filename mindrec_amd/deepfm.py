@@ -211,6 +211,27 @@ class DeepFMEngine(_DeepFMNet):
         self._check_fused()
         return self._predict_run(self._predict_chain, ids, wts, label, capture=self.cfg.graphs != "none")
 
+    def q8_predictor(self, row_bytes=None):
+        """Freezes the model as it stands for serving: the [V, D] table quantized to row-wise 8-bit records with the [V, 1] first-order
+        weight in each record's header, one pass (ops.quantize_rows_q8), the dense parameters copied.  Returns a
+        serving.DeepFMQ8Predictor, whose predict_fused has this engine's predict_fused contract (launched eagerly) and which no longer
+        depends on the engine: training on leaves it unchanged.  row_bytes: the record size (default: compact).  max_norm (the clip
+        is not folded into the records), a data_emb_dim outside the records' range and every case where fused_predict_supported is
+        False raise ValueError."""
+        D = self.cfg.data_emb_dim
+        why = ("max_norm" if self._max_norm is not None
+               else f"data_emb_dim={D} (data_emb_dim % 4 == 0 and 4 <= data_emb_dim <= 256)" if D % 4 or not 4 <= D <= 256
+               else self._fused_refusal())
+        if why is not None:
+            raise ValueError(f"q8_predictor is not supported with {why}")
+        from .serving import DeepFMQ8Predictor
+        n = len(self.dims) - 1
+        with torch.cuda.device(self.device):
+            q8 = ops.quantize_rows_q8(self.V_l2, self.W_l2, row_bytes=row_bytes)
+        return DeepFMQ8Predictor(q8, self.dims, [self.dense[2 * i].detach() for i in range(n)],
+                                 [self.dense[2 * i + 1].detach() for i in range(n)], mlp_dtype=self._amp, mfma=self._mfma,
+                                 fused_tail_eval=self._tail_eval)
+
     def release_graphs(self):
         """Drops every captured HIP graph -- the dense net's training step and the evaluation forwards (they are re-captured on demand)."""
         if self._gpu:

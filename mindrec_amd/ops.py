@@ -777,6 +777,37 @@ def gather_rows_q8(q8, ids, row_scale=None, out=None, out_dtype=torch.float16, w
     return out.view(tuple(ids.shape) + (q8.D,)), (wprod.view(tuple(ids.shape) + (2,)) if wide else None)
 
 
+def fm_lookup_q8(q8, ids, wts, out_dtype=torch.float16, out=None):
+    """fm_lookup over a Q8Table whose records carry the FM's first-order weight in the header (quantize_rows_q8(V, W)), one launch
+    (csrc/mrec_q8.hip: k_q8_fm_lookup): ids [B, F] int32 / int64, wts float32 [B, F] -> (rows [B, F, D] in out_dtype -- float32,
+    bfloat16 or float16 --, gather_rows_q8(q8, ids, wts)'s bit for bit, lin_fm [B] = sum_f wide * wt + the FM term over those rows
+    before rounding).  No fp32 [B, F, D] tensor in between; an id outside [0, V) gives a zero row and a zero weight.  out: dict of
+    persistent output tensors "rows" and "lin_fm" (filled on first use)."""
+    _need_cuda(q8.records, ids, wts)
+    _suffix(ids)
+    if ids.dim() != 2:
+        raise ValueError("ids must be [B, F]")
+    B, F = ids.shape
+    if wts.dtype != torch.float32 or tuple(wts.shape) != (B, F):
+        raise TypeError("wts must be float32 with one value per id")
+    if out_dtype not in _KIND:
+        raise TypeError("fm_lookup_q8 out_dtype must be float32, bfloat16 or float16")
+    dev = q8.records.device
+    o = out if out is not None else {}
+    res = []
+    for name, shape, dtype in (("rows", (B, F, q8.D), out_dtype), ("lin_fm", (B,), torch.float32)):
+        t = o.get(name)
+        if t is None:
+            t = o[name] = torch.empty(shape, dtype=dtype, device=dev)
+        elif t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise TypeError(f"fm_lookup_q8: out[{name!r}] must be a contiguous {dtype} {list(shape)} tensor on the records' device")
+        res.append(t)
+    rows, lin_fm = res
+    _lib.call("mrec_q8_fm_lookup", _ptr(_q8_records(q8)), q8.V, q8.row_bytes, q8.D, _ptr(ids.contiguous()), ids.element_size(),
+              _ptr(wts.contiguous()), B, F, _ptr(rows), _KIND[out_dtype], _ptr(lin_fm), _stream())
+    return rows, lin_fm
+
+
 def gather_rows_skip_(table, rows, out):
     """out[i, :] = table[rows[i], :] where rows[i] is a row of the table; rows of ids outside it (-1) are LEFT ALONE (the lookup in
     front has written them: KeyIndex.lookup(out=...))."""

@@ -1,6 +1,7 @@
 """Serving a trained Wide&Deep model from row-wise 8-bit records (csrc/mrec_q8.hip): the evaluation forward of
 WideDeepEngine.predict_fused with the dequantizing lookup in front, holding neither the fp32 table nor any optimizer slot of it.
-Made by WideDeepEngine.q8_predictor()."""
+Made by WideDeepEngine.q8_predictor().  DeepFMQ8Predictor: the same for DeepFMEngine.predict_fused, with the FM lookup over records
+(ops.fm_lookup_q8) in front."""
 import torch
 
 from . import ops
@@ -48,6 +49,41 @@ class WideDeepQ8Predictor:
     def predict_fused(self, ids, wts, label=None):
         """ids, wts [B, F] -> (logit [B, 1], prob [B, 1]) and, with `label`, the batch's mean sigmoid cross-entropy (0-d) as a third value:
         the dequantizing lookup, then the hidden-layer, tail and head launches of the engine's evaluation forward."""
+        if ids.dim() != 2 or ids.shape[1] * self.q8.D != self.net.dims[0]:
+            raise ValueError(f"ids must be [B, {self.net.dims[0] // self.q8.D}], got {tuple(ids.shape)}")
+        with torch.cuda.device(self.device):
+            return self.net._predict_run(self._chain, ids, wts, label, capture=False)
+
+
+class DeepFMQ8Predictor:
+    """DeepFM served from a Q8Table (the [V, D] rows as 8-bit codes, the [V, 1] first-order weight in each record's header) + a copy of
+    the dense parameters.  predict_fused is DeepFMEngine.predict_fused's contract over the dequantized tables; the launches are issued
+    eagerly.  Made by DeepFMEngine.q8_predictor()."""
+
+    def __init__(self, q8, dims, weights, biases, mlp_dtype=None, mfma=None, fused_tail_eval=True):
+        """q8: ops.Q8Table on the GPU; dims: [F * D, hidden .., 1]; weights[i] [in_i, out_i] and biases[i] [out_i] as
+        load_dense_parameters takes them; mlp_dtype: torch.float16 / torch.bfloat16, None for an fp32 net."""
+        self.q8 = q8
+        self.device = q8.records.device
+        if self.device.type != "cuda":
+            raise RuntimeError("DeepFMQ8Predictor runs on an MI355X (no CPU fallback)")
+        if dims[0] % q8.D:
+            raise ValueError(f"the net's input width {dims[0]} is no multiple of the table's emb_dim {q8.D}")
+        mfma = (mlp_dtype is not None and DenseNetMixin.mfma_net_ok(dims)) if mfma is None else bool(mfma)
+        with torch.cuda.device(self.device):
+            self.net = _ServeNet(list(dims), mlp_dtype, mfma, self.device, True, fused_tail_eval)
+            self.net.load_dense_parameters(weights, biases)
+        self._row_dtype = mlp_dtype if mfma else torch.float32
+
+    def _chain(self, ids, wts, label):
+        B, F = ids.shape
+        rows, lin_fm = ops.fm_lookup_q8(self.q8, ids, wts, out_dtype=self._row_dtype)
+        return self.net.mlp_predict(rows.view(B, F * self.q8.D), lin_fm, label)
+
+    def predict_fused(self, ids, wts, label=None):
+        """ids, wts [B, F] -> (logit [B, 1], prob [B, 1]) and, with `label`, the batch's mean sigmoid cross-entropy (0-d) as a third value:
+        one lookup launch for the rows, the linear and the FM term, then the hidden-layer, tail and head launches of the engine's
+        evaluation forward."""
         if ids.dim() != 2 or ids.shape[1] * self.q8.D != self.net.dims[0]:
             raise ValueError(f"ids must be [B, {self.net.dims[0] // self.q8.D}], got {tuple(ids.shape)}")
         with torch.cuda.device(self.device):
