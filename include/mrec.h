@@ -1382,7 +1382,29 @@ int mrec_group_rank_hist(const float* pred, const float* label, const int32_t* i
  *   The shape and record-size codes above come first; then MREC_EINVAL: id_bytes not 4 or 8, rows_kind outside 0..2, B < 0, F < 1,
  *   V < 1; B == 0: MREC_OK; then MREC_EINVAL for a NULL pointer other than stream, MREC_EUNSUPPORTED for records not 16-byte aligned or
  *   rows not 8-byte (fp32 rows: 16-byte) aligned.  Every refusal comes before the launch and leaves rows and lin_fm untouched.  No
- *   workspace, capturable. */
+ *   workspace, capturable.
+ *
+ * mrec_q8_gather_pool_fields: mrec_gather_pool_fields (the multi-hot lookup: F bags of lengths field_len[0 .. F-1] per sample, back to
+ *   back in a row of Ls = sum L_f ids) over records, and the wide side of the same slots, one launch.  ids, mask [B, Ls] contiguous,
+ *   mask nullable; field_len a HOST int32[F], read during the call.  For slot s of sample b let r = ids[b, s], m_s = mask[b, s] and
+ *   (lo_s, scale_s, wide_s, code_s[]) the fields of record r.  All arithmetic is fp32, fl() one rounding:
+ *     t_s = fl(m_s * scale_s), u_s = fl(m_s * lo_s), g_s = fl(m_s * wide_s); with a NULL mask m_s = 1 and the products are the operands;
+ *     for field f, over its slots s = off_f .. off_f + L_f - 1 in ascending order:
+ *       acc_d = fma((float)code_s[d], t_s, acc_d)  from +0  (a fused multiply-add: ONE rounding a slot),
+ *       base  = fl(base + u_s)                     from +0,
+ *       wsum_f = fl(wsum_f + g_s)                  from +0;
+ *     y_d = fl(acc_d + base); mode 1 (mean): y_d = fl(y_d / (float)L_f), an IEEE division by the FIELD's own length (mode 0: the sum);
+ *     out[b * ldo + f * D + d] = y_d rounded once to out_kind (0 fp32, 1 bf16, 2 f16; nearest even);
+ *     wide_out[b * ldw] = ((0 + wsum_0) + wsum_1) + .. + wsum_{F-1}, ascending field order (wide_out nullable: not computed).
+ *   That is sum_s m_s (lo_s + code_s[d] scale_s) with the dequantization factored out of the sum -- NOT the sum of the rows
+ *   mrec_q8_gather_rows writes: the two differ by rounding.  An id outside [0, V) reads as a zero record: it adds +0 to every sum.  No
+ *   atomics: out and wide_out hold the same bits run to run, and wide_out and fp32 rows whatever out_kind and id_bytes are.
+ *   ldo in elements of out: 0 means F * D, else ldo >= F * D.  The shape and record-size codes above come first; then MREC_EINVAL:
+ *   id_bytes not 4 or 8, out_kind outside 0..2, mode not 0 or 1, B < 0, V < 1, F < 1, field_len NULL or an L_f < 1, ldo < F * D, wide_out
+ *   with ldw < 1; then MREC_EUNSUPPORTED: F > MREC_POOL_MAX_FIELDS, Ls > MREC_POOL_MAX_BAG, B * F >= 2^31; B == 0: MREC_OK; then
+ *   MREC_EINVAL for NULL records, ids or out, MREC_EUNSUPPORTED for ldo % 4 != 0, records not 16-byte aligned or out not 8-byte (fp32
+ *   rows: 16-byte) aligned.  Every refusal comes before the launch and leaves out and wide_out untouched.  No workspace, no
+ *   synchronisation, capturable. */
 int mrec_q8_row_bytes(int32_t D);
 int mrec_q8_quantize_rows(const float* table, int64_t V, int64_t ld, int32_t D, const float* wide, int64_t ldw, void* records,
                           int64_t row_bytes, void* stream);
@@ -1390,6 +1412,9 @@ int mrec_q8_gather_rows(const void* records, int64_t V, int64_t row_bytes, int32
                         const float* row_scale, void* out, int32_t out_kind, int64_t ldo, float* wide_prod, int64_t ldw, void* stream);
 int mrec_q8_fm_lookup(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, const float* wts,
                       int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm, void* stream);
+int mrec_q8_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
+                               int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
+                               int64_t ldo, float* wide_out, int64_t ldw, void* stream);
 
 #ifdef __cplusplus
 }

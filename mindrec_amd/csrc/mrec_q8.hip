@@ -33,6 +33,22 @@
 //                lane of the group; the header lane enters with +0 and ends with the sum); lane 0 writes lin + 0.5f * part.  No
 //                LDS arrays, no barriers, no atomics.  Four waves per workgroup, a grid stride over samples, at most 2048 workgroups.
 //                Roofline bytes per sample: F (row_bytes + id + weight) read, F D 2 (16-bit rows) or F D 4, + 4 written.
+// k_q8_gather_pool_fields  the multi-hot lookup (k_gather_pool_fields, mrec_pool.hip: Gather -> Mul(mask) -> ReduceMean / ReduceSum per
+//                field) over records, with the wide side (the sum of every slot's masked wide weight) out of the same header loads.
+//                k_q8_fm_lookup's sample lane-group, walking the sample's Ls = sum L_f slots four at a time: four ids and mask values,
+//                then four records (one 16-byte load per lane per slot, all requested unconditionally: a slot past Ls re-reads the
+//                sample's last slot and is dropped, an id out of range reads record 0 and is zeroed).  The dequantization is factored
+//                out of the bag's sum, sum_s m (lo + c scale) = sum_s m lo + sum_s (m scale) c: every lane forms t = m * scale,
+//                u = m * lo and g = m * wide from ITS chunk's first three words (only the header lane's are the header; no branch),
+//                ONE ds_bpermute brings the header lane's t, and a code byte costs v_cvt_f32_ubyteN + v_fma_f32 into acc[16]; the
+//                header lane's own adds carry base = sum u and wsum = sum g (a code lane's copies of them, and the header lane's acc,
+//                are never read).  The slot -> field mapping is the same for every sample, so slot numbers, field ends and the
+//                closing of a field live in scalar registers and uniform branches: at a field's last slot one more permute brings
+//                base, y = acc + base, one IEEE division by (float)L_f for the mean, one rounding to the output kind, k_q8_gather's
+//                store rule to columns f * D + col0.., and acc, base and wsum start again at +0.  Field (offset, length) words travel
+//                by value in the kernel arguments (read by a uniform index: scalar loads).  No LDS arrays, no barriers, no atomics;
+//                four waves per workgroup, a grid stride over samples, at most 2048 workgroups.
+//                Roofline bytes per sample: Ls (row_bytes + id + mask) read, F D 2 (16-bit rows) or F D 4, + 4 (wide sum) written.
 #include "mrec_common.h"
 
 namespace {
@@ -287,6 +303,130 @@ __global__ __launch_bounds__(256) void k_q8_fm_lookup(const uint8_t* __restrict_
     }
 }
 
+// ===== the pooled (multi-hot) lookup over records ======================================================================================
+constexpr int kQ8PoolNB = 4;     // slots in flight per lane-group of the pooled lookup
+
+struct Q8PoolFields { unsigned w[MREC_POOL_MAX_FIELDS]; };      // w[f] = off_f | L_f << 16 (off_f < 4096, off_f + L_f <= 4096)
+
+// a code lane's 16 pooled values of one field, rounded once to the output kind: k_q8_gather's store rule (st16, valid)
+template <class OT>
+__device__ __forceinline__ void q8_pool_put(OT* __restrict__ o, const float4 (&y)[4], int valid, bool st16) {
+    if constexpr (sizeof(OT) == 4) {
+        *(float4*)o = y[0];
+        if (valid > 4) *(float4*)(o + 4) = y[1];
+        if (valid > 8) *(float4*)(o + 8) = y[2];
+        if (valid > 12) *(float4*)(o + 12) = y[3];
+    } else {
+        uint2 h[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h[j] = q8_pack16((const OT*)nullptr, y[j].x, y[j].y, y[j].z, y[j].w);
+        if (st16) {
+            if (valid > 4) *(uint4*)o = make_uint4(h[0].x, h[0].y, h[1].x, h[1].y);
+            else *(uint2*)o = h[0];
+            if (valid > 12) *(uint4*)(o + 8) = make_uint4(h[2].x, h[2].y, h[3].x, h[3].y);
+            else if (valid > 8) *(uint2*)(o + 8) = h[2];
+        } else {
+            *(uint2*)o = h[0];
+            if (valid > 4) *(uint2*)(o + 4) = h[1];
+            if (valid > 8) *(uint2*)(o + 8) = h[2];
+            if (valid > 12) *(uint2*)(o + 12) = h[3];
+        }
+    }
+}
+
+// the four codes of one dword into four column sums: acc = fma((float)code, t, acc), one byte conversion and one fma a code
+__device__ __forceinline__ void q8_pool_fma4(unsigned w, float t, float4& a) {
+    a.x = __builtin_fmaf((float)(w & 0xFFu), t, a.x);
+    a.y = __builtin_fmaf((float)((w >> 8) & 0xFFu), t, a.y);
+    a.z = __builtin_fmaf((float)((w >> 16) & 0xFFu), t, a.z);
+    a.w = __builtin_fmaf((float)(w >> 24), t, a.w);
+}
+
+// ids, mask [B, Ls] contiguous.  Everything that names a slot or a field (s, f, fend, the branches on them) is the same for every lane of
+// the wave: scalar registers and uniform branches, inside which every lane of a live group-slot runs, so the ds_bpermute reads always
+// find their source lane active.  A lane-group whose sample lies past B (the last wave's) reads sample 0's entries and stores nothing.
+// Every lane forms t, u and g from the first three words of its own chunk and adds u and g into its own base and wsum: only the header
+// lane's are the header's, and only the header lane's base and wsum are ever read (as are only the code lanes' acc).
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q8_gather_pool_fields(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                               const K* __restrict__ ids, const float* __restrict__ mask, int64_t B, int F,
+                                                               int Ls, int mode, OT* __restrict__ out, int64_t ldo,
+                                                               float* __restrict__ wide_out, int64_t ldw, RowGeom gm, bool st16,
+                                                               const Q8PoolFields pf) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 16;                                    // (the header lane: -16, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 16 ? D - col0 : 16);
+    const int64_t ng = (int64_t)gridDim.x * 4 * gm.G;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int slast = Ls - 1;
+    for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wave) * gm.G; b0 < B; b0 += ng) {
+        const int64_t b = b0 + grp;
+        const bool live = b < B;
+        const int64_t e0 = (live ? b : 0) * (int64_t)Ls;
+        float4 acc[4] = {zero4, zero4, zero4, zero4};
+        float base = 0.0f, wsum = 0.0f, wtot = 0.0f;
+        int f = 0;
+        unsigned fw = pf.w[0];
+        int fend = (int)(fw >> 16);                                     // one past the open field's last slot (field 0 starts at slot 0)
+        for (int s0 = 0; s0 < Ls; s0 += kQ8PoolNB) {
+            int64_t r[kQ8PoolNB];
+            float m[kQ8PoolNB];
+            uint4 x[kQ8PoolNB];
+#pragma unroll
+            for (int k = 0; k < kQ8PoolNB; ++k) {
+                const int64_t e = e0 + (s0 + k < slast ? s0 + k : slast);
+                r[k] = (int64_t)ids[e];
+                m[k] = mask ? mask[e] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8PoolNB; ++k) {
+                const bool ok = r[k] >= 0 && r[k] < V;
+                x[k] = *(const uint4*)(rec + (ok ? r[k] : 0) * row_bytes + 16 * sub);
+                if (!ok) r[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8PoolNB; ++k) {
+                asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+                if (r[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);        // header and codes zero: a +0 row, a +0 wide product
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8PoolNB; ++k) {
+                const int s = s0 + k;
+                if (s > slast) continue;                                // a spare slot of the sample's last batch: dropped
+                const float t = bperm_f(lane0, m[k] * __uint_as_float(x[k].y));
+                base = base + m[k] * __uint_as_float(x[k].x);
+                wsum = wsum + m[k] * __uint_as_float(x[k].z);
+                q8_pool_fma4(x[k].x, t, acc[0]);
+                q8_pool_fma4(x[k].y, t, acc[1]);
+                q8_pool_fma4(x[k].z, t, acc[2]);
+                q8_pool_fma4(x[k].w, t, acc[3]);
+                if (s + 1 != fend) continue;
+                // the field's last slot: y = acc + base, the mean's division by the field's own length, one rounding, one store
+                const float bs = bperm_f(lane0, base);
+                float4 y[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[j] = make_float4(acc[j].x + bs, acc[j].y + bs, acc[j].z + bs, acc[j].w + bs);
+                if (mode == 1) {
+                    const float fl = (float)(fw >> 16);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) y[j] = make_float4(y[j].x / fl, y[j].y / fl, y[j].z / fl, y[j].w / fl);
+                }
+                if (live && sub != 0) q8_pool_put(out + (b * ldo + (int64_t)f * D + col0), y, valid, st16);
+                wtot = wtot + wsum;
+                acc[0] = acc[1] = acc[2] = acc[3] = zero4;
+                base = wsum = 0.0f;
+                f = f + 1 < F ? f + 1 : f;                              // (behind the last field: its own word again, never closed twice)
+                fw = pf.w[f];
+                fend = (int)(fw & 0xFFFFu) + (int)(fw >> 16);
+            }
+        }
+        if (live && sub == 0 && wide_out) wide_out[b * ldw] = wtot;
+    }
+}
+
 /* D and row_bytes as include/mrec.h states them: the shape first (MREC_EUNSUPPORTED), then the record size (MREC_EINVAL) */
 int q8_check(int32_t D, int64_t row_bytes) {
     if (D <= 0) return MREC_EINVAL;
@@ -361,6 +501,44 @@ MREC_API int mrec_q8_fm_lookup(const void* records, int64_t V, int64_t row_bytes
         return by_out(rows, rows_kind, [&](auto* op) {
             k_q8_fm_lookup<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, wts, B, F, op,
                                                                                lin_fm, gm, st16);
+            MREC_LAUNCH_CHECK();
+            return (int)MREC_OK;
+        });
+    });
+}
+
+MREC_API int mrec_q8_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes,
+                                        int64_t B, int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out,
+                                        int32_t out_kind, int64_t ldo, float* wide_out, int64_t ldw, void* stream) {
+    if (const int rc = q8_check(D, row_bytes)) return rc;
+    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || (mode != 0 && mode != 1) || B < 0 || V < 1 || F < 1 || !field_len)
+        return MREC_EINVAL;
+    for (int f = 0; f < F; ++f)
+        if (field_len[f] < 1) return MREC_EINVAL;
+    if (ldo == 0) ldo = (int64_t)F * D;
+    if (ldo < (int64_t)F * D || (wide_out && ldw < 1)) return MREC_EINVAL;
+    if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
+    Q8PoolFields pf{};
+    int64_t Ls = 0;
+    for (int f = 0; f < F; ++f) {
+        if (Ls + field_len[f] > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
+        pf.w[f] = (unsigned)Ls | ((unsigned)field_len[f] << 16);
+        Ls += field_len[f];
+    }
+    if (B * F >= (int64_t(1) << 31)) return MREC_EUNSUPPORTED;
+    if (B == 0) return MREC_OK;
+    if (!records || !ids || !out) return MREC_EINVAL;
+    const int esz = out_kind == 0 ? 4 : 2;
+    if (ldo % 4 || !al16(records) || (((uintptr_t)out) & (esz == 4 ? 15 : 7))) return MREC_EUNSUPPORTED;
+    const bool st16 = al16(out) && (ldo * esz) % 16 == 0 && (D * esz) % 16 == 0;      // (every field's column block, every row)
+    const int lpr = (D + 15) / 16 + 1;
+    const RowGeom gm{lpr, 64 / lpr};
+    int64_t blocks = mrec_cdiv(B, (int64_t)4 * gm.G);
+    if (blocks > 2048) blocks = 2048;                                   // 256 CUs x 8 workgroups, each walking B
+    return by_key(ids, id_bytes, [&](auto* kp) {
+        return by_out(out, out_kind, [&](auto* op) {
+            k_q8_gather_pool_fields<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, mask, B, F,
+                                                                                        (int)Ls, mode, op, ldo, wide_out, ldw, gm, st16, pf);
             MREC_LAUNCH_CHECK();
             return (int)MREC_OK;
         });

@@ -51,6 +51,9 @@ one pooled launch (ops.gather_pool_fields(max_norm=c)), train=False included -- 
 in the same pooled apply (ops.sparse_lazy_adam_(pool_max_norm=c)).  "lazy_adam" only, dim % 4 == 0, dim <= 256: anything else is
 refused at construction.
 
+Serving: MultiHotEmbedding.freeze_q8() and MultiHotWideDeep.freeze_q8() freeze the table (and the wide weights, into the record headers)
+into row-wise 8-bit records behind a serving.MultiHotQ8, whose lookup is one pooled launch over records for both sides.
+
 Neither method synchronises with the host, so lookup + apply_ capture into one HIP graph on one stream.  The Adam bias-correction
 powers advance on the host with every apply_: a captured graph holds the powers of the steps it captured (replaying K captured
 steps repeats those K steps; it does not continue the count).  No torch arithmetic on the step."""
@@ -73,6 +76,18 @@ def _clip_arg(max_norm, optimizer, dim):
     if dim % 4 != 0 or dim > 256:
         raise ValueError(f"max_norm: dim must be a multiple of 4 and at most 256, got {dim}")
     return c
+
+
+def _freeze_q8(emb, wide, row_bytes):
+    """freeze_q8 of both classes: emb's table as records (wide: the [V, 1] header weights or None) behind a serving.MultiHotQ8"""
+    from .serving import MultiHotQ8
+    if emb.max_norm is not None:
+        raise ValueError("freeze_q8: max_norm is not folded into 8-bit records")
+    if emb.dim % 4 != 0 or not 4 <= emb.dim <= 256:
+        raise ValueError(f"freeze_q8: 8-bit records hold rows of dim % 4 == 0, 4 <= dim <= 256, got {emb.dim}")
+    with torch.cuda.device(emb.device):
+        q8 = ops.quantize_rows_q8(emb.table, wide, row_bytes=row_bytes)
+    return MultiHotQ8(q8, emb.fields, mode=emb.mode, out_dtype=emb.out_dtype, wide=wide is not None)
 
 
 class MultiHotEmbedding:
@@ -181,6 +196,12 @@ class MultiHotEmbedding:
             ops.dense_adam_rows_l2_(self.table, self.m, self.v, plan, sums, 0.0, grad_scale=1.0, **akw)
         return plan
 
+    def freeze_q8(self, row_bytes=None):
+        """The table frozen into row-wise 8-bit records (ops.quantize_rows_q8; row_bytes: the record size, default compact) behind a
+        serving.MultiHotQ8 of the same bag, mode and out_dtype: lookup only, no fp32 table, no optimizer state.  ValueError where
+        max_norm is set (the clip is not folded into records) or dim is outside the record format (dim % 4 == 0, 4 <= dim <= 256)."""
+        return _freeze_q8(self, None, row_bytes)
+
 
 class MultiHotWideDeep:
     """The deep and the wide side of multi-hot fields, looked up by the same ids and the same mask (every id field of the reference's
@@ -230,6 +251,12 @@ class MultiHotWideDeep:
         wide.lookup(ids, mask, out=wide_out.unsqueeze(1))      # ([B, 1] with wide_out's stride: the lookup's column block)
         wide._ids, wide._mask = deep._ids, deep._mask          # one copy of the ids: apply_ checks that both halves hold it
         return x, wide_out
+
+    def freeze_q8(self, row_bytes=None):
+        """Both halves frozen into ONE set of row-wise 8-bit records -- deep.table as codes, wide.table as each record's header weight --
+        behind a serving.MultiHotQ8(wide=True): its lookup(ids, mask) returns (x, w) from one launch.  ValueError as
+        MultiHotEmbedding.freeze_q8."""
+        return _freeze_q8(self.deep, self.wide.table, row_bytes)
 
     def apply_(self, dy, dwide, grad_scale=1.0):
         """The optimizer steps of both halves for dy [B, F * dim], the gradient of x, and dwide [B] (contiguous float32), the gradient

@@ -808,6 +808,44 @@ def fm_lookup_q8(q8, ids, wts, out_dtype=torch.float16, out=None):
     return rows, lin_fm
 
 
+def gather_pool_fields_q8(q8, ids, fields, mask=None, mode="mean", out=None, out_dtype=torch.float32, wide=False, wide_out=None):
+    """gather_pool_fields over a Q8Table, one launch (csrc/mrec_q8.hip: k_q8_gather_pool_fields): ids [B, Ls] int32 / int64, Ls =
+    sum(fields), field f in slots off_f .. off_f + L_f - 1 -> out [B, F * D], field f's masked sum (mode="mean": divided by L_f) of the
+    dequantized rows lo + code * scale in columns f * D .. (f + 1) * D - 1, fp32 sums rounded once to out_dtype (float32, bfloat16 or
+    float16).  The dequantization is factored out of the bag's sum (include/mrec.h has the arithmetic), so the result is within
+    rounding of, not bit for bit, the pooled rows of gather_rows_q8.  mask: float32 [B, Ls] or None (all ones).  wide=True: also
+    w [B] float32 = the sum over all Ls slots of mask * the record's wide weight (MultiHotWideDeep's wide side, out of the same header
+    loads) -- returns (out, w).  An id outside [0, V) adds nothing to either.  out: a [B, F * D] tensor or column block (unit column
+    stride); wide_out: a float32 [B] tensor of any positive stride (a column of a wider matrix)."""
+    _need_cuda(q8.records, ids, mask, out, wide_out)
+    lens = _fields(fields)
+    _suffix(ids)
+    if ids.dim() != 2 or ids.shape[1] != sum(lens):
+        raise TypeError(f"ids must be [B, {sum(lens)}]: the bags of lengths {lens} back to back")
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
+        raise TypeError("mask must be float32 of the shape of ids")
+    if mode not in ("sum", "mean"):
+        raise ValueError(f"gather_pool_fields_q8 mode must be 'sum' or 'mean', got {mode!r}")
+    B, F, D, dev = ids.shape[0], len(lens), q8.D, q8.records.device
+    if out is None:
+        if out_dtype not in _KIND:
+            raise TypeError("gather_pool_fields_q8 out_dtype must be float32, bfloat16 or float16")
+        out = torch.empty((B, F * D), dtype=out_dtype, device=dev)
+    elif out.dtype not in _KIND or out.dim() != 2 or tuple(out.shape) != (B, F * D) or out.stride(1) != 1:
+        raise TypeError(f"gather_pool_fields_q8 out must be a [{B}, {F * D}] float32 / bfloat16 / float16 tensor with unit column stride")
+    if not wide:
+        if wide_out is not None:
+            raise TypeError("gather_pool_fields_q8: wide_out goes with wide=True")
+    elif wide_out is None:
+        wide_out = torch.empty((B,), dtype=torch.float32, device=dev)
+    elif wide_out.dtype != torch.float32 or wide_out.dim() != 1 or wide_out.shape[0] != B or (B > 1 and wide_out.stride(0) < 1):
+        raise TypeError(f"gather_pool_fields_q8 wide_out must be a float32 [{B}] tensor (any positive stride: a column of a wider matrix)")
+    _lib.call("mrec_q8_gather_pool_fields", _ptr(_q8_records(q8)), q8.V, q8.row_bytes, D, _ptr(ids.contiguous()), ids.element_size(), B, F,
+              (C.c_int32 * F)(*lens), _ptr(mask.contiguous() if mask is not None else None), 1 if mode == "mean" else 0, _ptr(out),
+              _KIND[out.dtype], out.stride(0) if B > 1 else F * D, _ptr(wide_out), wide_out.stride(0) if wide and B > 1 else 1, _stream())
+    return (out, wide_out) if wide else out
+
+
 def gather_rows_skip_(table, rows, out):
     """out[i, :] = table[rows[i], :] where rows[i] is a row of the table; rows of ids outside it (-1) are LEFT ALONE (the lookup in
     front has written them: KeyIndex.lookup(out=...))."""

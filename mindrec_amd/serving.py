@@ -1,7 +1,8 @@
 """Serving a trained Wide&Deep model from row-wise 8-bit records (csrc/mrec_q8.hip): the evaluation forward of
 WideDeepEngine.predict_fused with the dequantizing lookup in front, holding neither the fp32 table nor any optimizer slot of it.
 Made by WideDeepEngine.q8_predictor().  DeepFMQ8Predictor: the same for DeepFMEngine.predict_fused, with the FM lookup over records
-(ops.fm_lookup_q8) in front."""
+(ops.fm_lookup_q8) in front.  MultiHotQ8: the multi-hot lookups of multi_hot.py (MultiHotEmbedding, MultiHotWideDeep) over records, one
+pooled launch (ops.gather_pool_fields_q8)."""
 import torch
 
 from . import ops
@@ -53,6 +54,44 @@ class WideDeepQ8Predictor:
             raise ValueError(f"ids must be [B, {self.net.dims[0] // self.q8.D}], got {tuple(ids.shape)}")
         with torch.cuda.device(self.device):
             return self.net._predict_run(self._chain, ids, wts, label, capture=False)
+
+
+class MultiHotQ8:
+    """Multi-hot fields served from a Q8Table: MultiHotEmbedding.lookup -- and, with wide=True, MultiHotWideDeep.lookup, whose wide
+    weights sit in the record headers -- as ONE pooled launch over records (ops.gather_pool_fields_q8).  It holds the records only: no
+    fp32 table, no optimizer state, no apply_.  Made by MultiHotEmbedding.freeze_q8() / MultiHotWideDeep.freeze_q8()."""
+
+    def __init__(self, q8, bag, mode="mean", out_dtype=torch.float32, wide=False):
+        """q8: ops.Q8Table on the GPU; bag: an int (one field) or a tuple of bag lengths, as MultiHotEmbedding takes it."""
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
+        if q8.records.device.type != "cuda":
+            raise RuntimeError("MultiHotQ8 runs on an MI355X (no CPU fallback)")
+        self.q8, self.device = q8, q8.records.device
+        self.fields = ops._fields(bag if isinstance(bag, (tuple, list)) else (bag,))
+        self.bag, self.dim, self.vocab = sum(self.fields), q8.D, q8.V
+        self.mode, self.out_dtype, self.wide = mode, out_dtype, bool(wide)
+
+    def lookup(self, ids, mask=None, out=None, wide_out=None):
+        """ids, mask [B, Ls] -> x [B, F * dim], or (x, w [B] float32) with wide=True; one field also takes ids [B, G, L] -> [B, G * dim]
+        (G bags of its length per sample; not with wide=True).  mask, out, wide_out: as MultiHotEmbedding.lookup and
+        MultiHotWideDeep.lookup take them."""
+        if ids.dim() not in ((2, 3) if len(self.fields) == 1 and not self.wide else (2,)) or ids.shape[-1] != self.bag:
+            raise TypeError(f"ids must be [B, {self.bag}] (the bags of lengths {self.fields} back to back), or [B, G, {self.bag}] for one "
+                            "length without the wide side")
+        if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
+            raise TypeError("mask must be float32 of the shape of ids")
+        B, G = ids.shape[0], (ids.shape[1] if ids.dim() == 3 else 1)
+        W = len(self.fields) * self.dim
+        if out is None:
+            out = torch.empty((B, G * W), dtype=self.out_dtype, device=self.device)
+        elif tuple(out.shape) != (B, G * W) or (G > 1 and not out.is_contiguous()):
+            raise TypeError("out must be [B, F * dim] (contiguous when ids hold more than one bag per sample)")
+        with torch.cuda.device(self.device):
+            res = ops.gather_pool_fields_q8(self.q8, ids.reshape(B * G, self.bag), self.fields,
+                                            mask.reshape(B * G, self.bag) if mask is not None else None, mode=self.mode,
+                                            out=out if G == 1 else out.view(B * G, W), wide=self.wide, wide_out=wide_out)
+        return (out, res[1]) if self.wide else out
 
 
 class DeepFMQ8Predictor:
