@@ -1416,6 +1416,48 @@ int mrec_q8_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes
                                int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
                                int64_t ldo, float* wide_out, int64_t ldw, void* stream);
 
+/* ---- row-wise 4-bit serving records (mrec_q8.hip) ---------------------------------------------------------------------------
+ * The other row-wise format of the same convention: the 8-bit record with two codes a byte.  A record is row_bytes long and 16-byte
+ * aligned, row_bytes % 16 == 0 and row_bytes >= 16 + 16 ceil(D / 32) (the compact size, mrec_q4_row_bytes: D = 4 -> 32, 20 -> 32,
+ * 36 -> 48, 80 -> 64, 256 -> 144).  The header chunk is the 8-bit format's:
+ *
+ *   bytes 0..3          float lo      the row's minimum, exact
+ *   bytes 4..7          float scale   (hi - lo) / 15 in fp32 (hi: the row's maximum); 0 where hi == lo
+ *   bytes 8..11         float wide    the row's wide weight, copied unchanged; 0 where no wide source is given
+ *   bytes 12..15        zero
+ *   bytes 16..16+D/2-1  byte 16 + j holds code[2 j] in its low nibble and code[2 j + 1] in its high nibble,
+ *                       code[d] = min(15, rint((x[d] - lo) / scale)) -- an fp32 subtraction and an fp32 division, each rounded, rint to
+ *                       nearest even --; 0 where scale == 0
+ *   the rest            zero
+ *
+ * Dequantisation: x'[d] = lo + (float)code[d] * scale, one fp32 multiply and one fp32 add, each rounded (no fused multiply-add): the
+ * 8-bit rule.  Shapes: D % 4 == 0 and 4 <= D <= 256 (every width the 8-bit format serves); anything else is MREC_EUNSUPPORTED, a
+ * row_bytes that is too small or no multiple of 16 is MREC_EINVAL (the shape is judged first), both before any launch.  Table rows
+ * are assumed finite; this is not checked.
+ *
+ * The three entries take the arguments of mrec_q8_row_bytes, mrec_q8_quantize_rows and mrec_q8_gather_rows and keep their contracts:
+ *
+ * mrec_q4_row_bytes: the compact record size 16 + 16 ceil(D / 32), or the negative code above.
+ *
+ * mrec_q4_quantize_rows: one pass over the fp32 [V, D] view `table` of row stride ld (floats; a fused training row is read in place)
+ *   writes all V records -- header, codes and every padding byte: no memset in front.  wide (nullable): a [V, 1] view of stride ldw.
+ *   After the shape and record-size codes: MREC_EINVAL for V < 0, ld < D or a wide with ldw < 1; V == 0: MREC_OK; MREC_EINVAL for a
+ *   NULL table or records; MREC_EUNSUPPORTED for ld % 4 != 0 or a table or records not 16-byte aligned.  Rows are counted in 64 bits.
+ *
+ * mrec_q4_gather_rows: out[i * ldo + d] = round(x'[ids[i]][d] * row_scale[i]) for d < D (row_scale nullable: 1), out_kind 0 / 1 / 2 =
+ *   float / bf16 / f16 rows, rounded once to nearest even; ldo in elements of out, ldo % 4 == 0, out 8-byte aligned (fp32 rows:
+ *   16-byte), else MREC_EUNSUPPORTED.  wide_prod (nullable): the 8-byte pairs (wide * row_scale[i], 0) at wide_prod + i * ldw (ldw
+ *   even, wide_prod 8-byte aligned), which mrec_head_predict and mrec_tail_predict sum per sample.  An id outside [0, V) gives a zero
+ *   row and a zero product.  id_bytes 4 / 8; V >= 1; n == 0: MREC_OK.
+ *
+ * Each is one launch, takes no workspace and is capturable; every refusal comes before the launch and leaves records and out
+ * untouched.  There is no 4-bit form of mrec_q8_fm_lookup or mrec_q8_gather_pool_fields. */
+int mrec_q4_row_bytes(int32_t D);
+int mrec_q4_quantize_rows(const float* table, int64_t V, int64_t ld, int32_t D, const float* wide, int64_t ldw, void* records,
+                          int64_t row_bytes, void* stream);
+int mrec_q4_gather_rows(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t n,
+                        const float* row_scale, void* out, int32_t out_kind, int64_t ldo, float* wide_prod, int64_t ldw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

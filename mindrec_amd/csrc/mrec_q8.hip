@@ -49,6 +49,29 @@
 //                by value in the kernel arguments (read by a uniform index: scalar loads).  No LDS arrays, no barriers, no atomics;
 //                four waves per workgroup, a grid stride over samples, at most 2048 workgroups.
 //                Roofline bytes per sample: Ls (row_bytes + id + mask) read, F D 2 (16-bit rows) or F D 4, + 4 (wide sum) written.
+//
+// Row-wise 4-bit records (include/mrec.h, "row-wise 4-bit serving records"): the same header chunk, then C4 = ceil(D / 32) chunks of 32
+// codes, two a byte, column d in bits 4 d of its dword (compact: 16 (C4 + 1); D = 80 -> 64 B, which never straddles a 128-byte line).
+// k_q4_quantize  lane-group = ceil(D / 8) lanes per row, TWO 16-byte loads each, so that a lane's eight codes are exactly one dword of
+//                the record: one 4-byte store a lane and no nibble ever crosses a lane (D / 4 lanes with one load each, k_q8_quantize's
+//                split, would leave 2-byte stores everywhere, twice the store instructions, and half the rows per wave).  Where
+//                D % 8 == 4 the row's last lane holds four columns: it reads its first 16 bytes twice instead of reading past the row,
+//                and still leaves a whole dword, whose upper half is the first two padding bytes -- no 2-byte store at all.  Min and
+//                max travel k_q8_quantize's idempotent butterfly, lane 0 stores the header as one 16-byte word, the lanes share the
+//                padding's dwords, every byte of the record is written.  D = 80 -> 10 lanes, 6 rows a wave; D = 256 -> 32 lanes, 2.
+//                Persistent workgroups over V, 64-bit row numbers.  Roofline bytes per row: 4 D + 4 read, row_bytes written.
+// k_q4_gather    lane-group = C4 + 1 lanes per position: lane 0 loads the header chunk, lane c the c-th 32 codes -- one 16-byte load
+//                instruction per position, GB = 4 positions in flight, every load unconditional (k_q8_gather's rule).  lo and scale
+//                come by two ds_bpermute reads of lane 0.  A code dword w is taken once as w & 0x0F0F0F0F (its bytes: columns 0, 2, 4,
+//                6 of the dword's eight) and once as (w >> 4) & 0x0F0F0F0F (columns 1, 3, 5, 7): two integer instructions per eight
+//                codes, then v_cvt_f32_ubyte0..3 on either word; byte k of the two words is the adjacent column pair (2 k, 2 k + 1),
+//                which is what v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 take, so no permute follows.  x' = lo + code * scale (a multiply
+//                and an add, each rounded), then * row_scale, rounded once.  A code lane's 32 values leave as four 16-byte stores
+//                (fp32 rows: eight), one per code dword; the row's last chunk holds valid = 4, 8, .., 32 columns, 16-bit rows of
+//                D % 8 == 4 columns take 8-byte stores (the st16 / valid rule); the header lane stores the wide pair.
+//                Lanes per row: D = 80 -> 4 lanes, 16 positions a wave, 64 / 64 lanes busy; D = 64 -> 3 lanes, 21 positions, 63 / 64;
+//                D = 256 -> 9 lanes, 7 positions, 63 / 64.
+//                Roofline bytes per position: row_bytes read (+ id, + row_scale), 2 D (16-bit) or 4 D written, + 8 (wide pair).
 #include "mrec_common.h"
 
 namespace {
@@ -427,6 +450,150 @@ __global__ __launch_bounds__(256) void k_q8_gather_pool_fields(const uint8_t* __
     }
 }
 
+// ===== row-wise 4-bit records: [lo scale wide 0 | D / 2 code bytes | zero padding] =====================================================
+constexpr int kQ4GB = 4;         // positions in flight per lane-group of the 4-bit lookup
+
+__device__ __forceinline__ float q4_code(float x, float lo, float scale) {
+    const float q = fminf(rintf((x - lo) / scale), 15.0f);
+    return scale > 0.0f ? q : 0.0f;
+}
+
+// four codes -> the 16 bits that hold them, column d in bits 4 d
+__device__ __forceinline__ unsigned q4_codes4(const float4& x, float lo, float scale) {
+    return (unsigned)q4_code(x.x, lo, scale) | ((unsigned)q4_code(x.y, lo, scale) << 4) | ((unsigned)q4_code(x.z, lo, scale) << 8) |
+           ((unsigned)q4_code(x.w, lo, scale) << 12);
+}
+
+// gm.lpr = ceil(D / 8) lanes a row.  The row's last lane holds four columns where D % 8 == 4: it reads its first 16 bytes twice (never
+// past the row: a contiguous table's last row ends there), which min and max do not notice, and the upper half of its dword is zero.
+__global__ __launch_bounds__(256) void k_q4_quantize(const float* __restrict__ table, int64_t V, int64_t ld, int D,
+                                                     const float* __restrict__ wide, int64_t ldw, uint8_t* __restrict__ rec,
+                                                     int64_t row_bytes, RowGeom gm) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, ds = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int nd = gm.lpr, lane0 = lane - ds;
+    const bool two = 8 * ds + 4 < D;
+    const int pad_dw = (int)((row_bytes - kQ8Hdr) >> 2) - nd;           // zero dwords behind the code dwords
+    const int64_t stride = (int64_t)gridDim.x * 4 * gm.G;
+    for (int64_t r = ((int64_t)blockIdx.x * 4 + wave) * gm.G + grp; r < V; r += stride) {
+        const float* const src = table + r * ld + 8 * ds;
+        const float4 a = *(const float4*)src;
+        const float4 b = *(const float4*)(src + (two ? 4 : 0));
+        float w = 0.0f;
+        if (ds == 0 && wide) w = wide[r * ldw];
+        float lo = fminf(fminf(fminf(a.x, a.y), fminf(a.z, a.w)), fminf(fminf(b.x, b.y), fminf(b.z, b.w)));
+        float hi = fmaxf(fmaxf(fmaxf(a.x, a.y), fmaxf(a.z, a.w)), fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
+        for (int m = 1; m < nd; m <<= 1) {
+            const int p = ds ^ m;
+            const int src_lane = lane0 + (p < nd ? p : nd - 1);
+            lo = fminf(lo, bperm_f(src_lane, lo));
+            hi = fmaxf(hi, bperm_f(src_lane, hi));
+        }
+        const float scale = (hi - lo) / 15.0f;
+        const unsigned upper = q4_codes4(b, lo, scale) << 16;
+        const unsigned codes = q4_codes4(a, lo, scale) | (two ? upper : 0u);
+        uint8_t* const o = rec + r * row_bytes;
+        if (ds == 0) *(uint4*)o = make_uint4(__float_as_uint(lo), __float_as_uint(scale), __float_as_uint(w), 0u);
+        *(uint32_t*)(o + kQ8Hdr + 4 * ds) = codes;
+        for (int j = ds; j < pad_dw; j += nd) *(uint32_t*)(o + kQ8Hdr + 4 * (nd + j)) = 0u;
+    }
+}
+
+// the eight codes of one dword -> x' * sc, in column order.  The even columns are the bytes of w & 0x0F0F0F0F, the odd ones the bytes
+// of (w >> 4) & 0x0F0F0F0F: two integer instructions a dword, then v_cvt_f32_ubyte0..3 on either word.
+__device__ __forceinline__ void q4_dequant8(unsigned w, float lo, float scale, float sc, float4& y0, float4& y1) {
+    unsigned e = w & 0x0F0F0F0Fu, o = (w >> 4) & 0x0F0F0F0Fu;
+    asm volatile("" : "+v"(e), "+v"(o));            // (keeps the two words: the compiler otherwise extracts a bit field per code)
+    y0.x = (lo + (float)(e & 0xFFu) * scale) * sc;
+    y0.y = (lo + (float)(o & 0xFFu) * scale) * sc;
+    y0.z = (lo + (float)((e >> 8) & 0xFFu) * scale) * sc;
+    y0.w = (lo + (float)((o >> 8) & 0xFFu) * scale) * sc;
+    y1.x = (lo + (float)((e >> 16) & 0xFFu) * scale) * sc;
+    y1.y = (lo + (float)((o >> 16) & 0xFFu) * scale) * sc;
+    y1.z = (lo + (float)(e >> 24) * scale) * sc;
+    y1.w = (lo + (float)(o >> 24) * scale) * sc;
+}
+
+// gm.lpr = ceil(D / 32) + 1 lanes a position: lane 0 the header chunk, lane c the c-th 32 codes (columns 32 (c - 1) ..).  The store rule
+// is k_q8_gather's -- st16: 16-byte stores, else (16-bit rows of D % 8 == 4 columns) 8-byte ones -- over a last chunk of `valid` = 4, 8,
+// .., 32 columns: code dword j of the chunk is columns 8 j .. 8 j + 7, one 16-byte store of 16-bit values or two of fp32 ones.
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q4_gather(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                   const K* __restrict__ ids, int64_t n, const float* __restrict__ row_scale,
+                                                   OT* __restrict__ out, int64_t ldo, float* __restrict__ wprod, int64_t ldw,
+                                                   RowGeom gm, bool st16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 32;                                    // (the header lane: -32, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 32 ? D - col0 : 32);
+    const int64_t wave_row0 = ((int64_t)blockIdx.x * 4 + wave) * (gm.G * kQ4GB);
+    const int64_t nlast = n - 1;
+    int64_t row[kQ4GB];
+    float sc[kQ4GB];
+    uint4 x[kQ4GB];
+    // k_q8_gather's rule: every load is requested unconditionally (a position past the end reads the last id, an id out of range
+    // record 0; both are dropped) so that the GB records are in flight together
+#pragma unroll
+    for (int k = 0; k < kQ4GB; ++k) {
+        const int64_t i = wave_row0 + (int64_t)k * gm.G + grp;
+        const int64_t ic = i < n ? i : nlast;
+        row[k] = (int64_t)ids[ic];
+        sc[k] = row_scale ? row_scale[ic] : 1.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < kQ4GB; ++k) {
+        const bool ok = row[k] >= 0 && row[k] < V;
+        x[k] = *(const uint4*)(rec + (ok ? row[k] : 0) * row_bytes + 16 * sub);
+        if (!ok) row[k] = -1;
+    }
+#pragma unroll
+    for (int k = 0; k < kQ4GB; ++k) {
+        asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+        if (row[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);              // header and codes zero: a zero row, a zero product
+    }
+#pragma unroll
+    for (int k = 0; k < kQ4GB; ++k) {
+        const int64_t i = wave_row0 + (int64_t)k * gm.G + grp;
+        const float lo = bperm_f(lane0, __uint_as_float(x[k].x));
+        const float scale = bperm_f(lane0, __uint_as_float(x[k].y));
+        if (i >= n) continue;
+        if (sub == 0) {
+            if (wprod) *(uint2*)(wprod + ldw * i) = make_uint2(__float_as_uint(__uint_as_float(x[k].z) * sc[k]), 0u);
+            continue;
+        }
+        const unsigned w[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
+        OT* const o = out + i * ldo + col0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float4 y0, y1;
+            q4_dequant8(w[j], lo, scale, sc[k], y0, y1);
+            if constexpr (sizeof(OT) == 4) {
+                if (valid > 8 * j) *(float4*)(o + 8 * j) = y0;
+                if (valid > 8 * j + 4) *(float4*)(o + 8 * j + 4) = y1;
+            } else {
+                const uint2 h0 = q8_pack16((const OT*)nullptr, y0.x, y0.y, y0.z, y0.w);
+                const uint2 h1 = q8_pack16((const OT*)nullptr, y1.x, y1.y, y1.z, y1.w);
+                if (st16 && valid > 8 * j + 4) {
+                    *(uint4*)(o + 8 * j) = make_uint4(h0.x, h0.y, h1.x, h1.y);
+                } else {
+                    if (valid > 8 * j) *(uint2*)(o + 8 * j) = h0;
+                    if (valid > 8 * j + 4) *(uint2*)(o + 8 * j + 4) = h1;
+                }
+            }
+        }
+    }
+}
+
+int q4_check(int32_t D, int64_t row_bytes) {
+    if (D <= 0) return MREC_EINVAL;
+    if (D % 4 || D > 256) return MREC_EUNSUPPORTED;
+    if (row_bytes % 16 || row_bytes < kQ8Hdr + 16 * ((D + 31) / 32)) return MREC_EINVAL;
+    return MREC_OK;
+}
+
 /* D and row_bytes as include/mrec.h states them: the shape first (MREC_EUNSUPPORTED), then the record size (MREC_EINVAL) */
 int q8_check(int32_t D, int64_t row_bytes) {
     if (D <= 0) return MREC_EINVAL;
@@ -539,6 +706,54 @@ MREC_API int mrec_q8_gather_pool_fields(const void* records, int64_t V, int64_t 
         return by_out(out, out_kind, [&](auto* op) {
             k_q8_gather_pool_fields<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, mask, B, F,
                                                                                         (int)Ls, mode, op, ldo, wide_out, ldw, gm, st16, pf);
+            MREC_LAUNCH_CHECK();
+            return (int)MREC_OK;
+        });
+    });
+}
+
+MREC_API int mrec_q4_row_bytes(int32_t D) {
+    if (D <= 0) return MREC_EINVAL;
+    if (D % 4 || D > 256) return MREC_EUNSUPPORTED;
+    return kQ8Hdr + 16 * ((D + 31) / 32);
+}
+
+MREC_API int mrec_q4_quantize_rows(const float* table, int64_t V, int64_t ld, int32_t D, const float* wide, int64_t ldw, void* records,
+                                   int64_t row_bytes, void* stream) {
+    if (const int rc = q4_check(D, row_bytes)) return rc;
+    if (V < 0 || ld < D || (wide && ldw < 1)) return MREC_EINVAL;
+    if (V == 0) return MREC_OK;
+    if (!table || !records) return MREC_EINVAL;
+    if (ld % 4 || !al16(table) || !al16(records)) return MREC_EUNSUPPORTED;
+    const int nd = (D + 7) / 8;
+    const RowGeom gm{nd, 64 / nd};
+    int64_t blocks = mrec_cdiv(V, 4 * gm.G);
+    if (blocks > 2048) blocks = 2048;                                   // 256 CUs x 8 workgroups, each walking V
+    k_q4_quantize<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(table, V, ld, D, wide, ldw, (uint8_t*)records, row_bytes, gm);
+    MREC_LAUNCH_CHECK();
+    return MREC_OK;
+}
+
+MREC_API int mrec_q4_gather_rows(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t n,
+                                 const float* row_scale, void* out, int32_t out_kind, int64_t ldo, float* wide_prod, int64_t ldw,
+                                 void* stream) {
+    if (const int rc = q4_check(D, row_bytes)) return rc;
+    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || n < 0 || V < 1 || ldo < D) return MREC_EINVAL;
+    if (wide_prod && (ldw < 2 || ldw % 2 || (((uintptr_t)wide_prod) & 7))) return MREC_EINVAL;
+    if (n == 0) return MREC_OK;
+    if (!records || !ids || !out) return MREC_EINVAL;
+    const int esz = out_kind == 0 ? 4 : 2;
+    if (ldo % 4 || !al16(records) || (((uintptr_t)out) & 7)) return MREC_EUNSUPPORTED;
+    const bool st16 = al16(out) && (ldo * esz) % 16 == 0;
+    if (esz == 4 && !st16) return MREC_EUNSUPPORTED;
+    const int lpr = (D + 31) / 32 + 1;
+    const RowGeom gm{lpr, 64 / lpr};
+    const int64_t blocks = mrec_cdiv(n, (int64_t)4 * gm.G * kQ4GB);
+    if (blocks >= (1ll << 31)) return MREC_EUNSUPPORTED;
+    return by_key(ids, id_bytes, [&](auto* kp) {
+        return by_out(out, out_kind, [&](auto* op) {
+            k_q4_gather<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, n, row_scale, op, ldo,
+                                                                            wide_prod, ldw, gm, st16);
             MREC_LAUNCH_CHECK();
             return (int)MREC_OK;
         });

@@ -717,11 +717,13 @@ def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.
 
 # ---- row-wise 8-bit serving records (csrc/mrec_q8.hip; the record format: include/mrec.h) --------------------------------
 class Q8Table(NamedTuple):
-    """A table frozen for evaluation: records uint8 [V, row_bytes], one per row -- [lo scale wide 0 | D codes | zero padding]."""
+    """A table frozen for evaluation: records uint8 [V, row_bytes], one per row -- [lo scale wide 0 | D codes | zero padding].  bits:
+    the width of a code, 8 (a byte a column) or 4 (two columns a byte: quantize_rows_q4, gather_rows_q4)."""
     records: torch.Tensor
     V: int
     D: int
     row_bytes: int
+    bits: int = 8
 
 
 def q8_row_bytes(D):
@@ -731,7 +733,9 @@ def q8_row_bytes(D):
     return rb
 
 
-def _q8_records(q8):
+def _q8_records(q8, bits=8):
+    if q8.bits != bits:
+        raise TypeError(f"this lookup reads {bits}-bit records, the table holds {q8.bits}-bit ones")
     r = q8.records
     if r.dtype != torch.uint8 or tuple(r.shape) != (q8.V, q8.row_bytes) or not r.is_contiguous():
         raise TypeError("Q8Table.records must be a contiguous uint8 [V, row_bytes] tensor")
@@ -775,6 +779,49 @@ def gather_rows_q8(q8, ids, row_scale=None, out=None, out_dtype=torch.float16, w
     _lib.call("mrec_q8_gather_rows", _ptr(_q8_records(q8)), q8.V, q8.row_bytes, q8.D, _ptr(flat), flat.element_size(), n, _ptr(row_scale),
               _ptr(out), _KIND[out.dtype], q8.D, _ptr(wprod), 2, _stream())
     return out.view(tuple(ids.shape) + (q8.D,)), (wprod.view(tuple(ids.shape) + (2,)) if wide else None)
+
+
+def q4_row_bytes(D):
+    """The compact 4-bit record size of a D-column row: 16 + 16 ceil(D / 32) bytes (D % 4 == 0, 4 <= D <= 256)."""
+    rb = _lib.lib().mrec_q4_row_bytes(int(D))
+    _lib.check("mrec_q4_row_bytes", rb if rb < 0 else 0)
+    return rb
+
+
+def quantize_rows_q4(table, wide=None, row_bytes=None, out=None):
+    """quantize_rows_q8 into row-wise 4-bit records (scale = (hi - lo) / 15, two codes a byte; csrc/mrec_q8.hip: k_q4_quantize): the
+    same arguments, one pass, every byte of every record written.  row_bytes: default compact, q4_row_bytes(D) -- 64 bytes at D = 80.
+    Returns a Q8Table with bits=4, which gather_rows_q4 reads and every 8-bit lookup refuses."""
+    _need_cuda(table, wide, out)
+    V, D, ld = _table(table)
+    rb = q4_row_bytes(D) if row_bytes is None else int(row_bytes)
+    ldw = 0
+    if wide is not None:
+        if wide.dtype != torch.float32 or wide.shape[0] != V or wide.numel() != V:
+            raise TypeError("wide must be a float32 [V, 1] tensor")
+        ldw = wide.stride(0) if V > 1 else 1
+    if out is None:
+        out = torch.empty((V, max(rb, 0)), dtype=torch.uint8, device=table.device)
+    q4 = Q8Table(out, V, D, rb, 4)
+    _lib.call("mrec_q4_quantize_rows", _ptr(table), V, ld, D, _ptr(wide), ldw, _ptr(_q8_records(q4, 4)), rb, _stream())
+    return q4
+
+
+def gather_rows_q4(q4, ids, row_scale=None, out=None, out_dtype=torch.float16, wide=True):
+    """gather_rows_q8 over a Q8Table of 4-bit records (bits=4; csrc/mrec_q8.hip: k_q4_gather): the same arguments and results."""
+    _need_cuda(q4.records, ids, row_scale, out)
+    flat, n, row_scale = _flat_ids(ids, row_scale)
+    _suffix(ids)
+    if out is None:
+        if out_dtype not in _KIND:
+            raise TypeError("gather_rows_q4 out_dtype must be float32, bfloat16 or float16")
+        out = torch.empty((n, q4.D), dtype=out_dtype, device=q4.records.device)
+    elif out.dtype not in _KIND or out.numel() != n * q4.D or not out.is_contiguous():
+        raise TypeError("gather_rows_q4: out must be a contiguous float32, bfloat16 or float16 tensor of n * D elements")
+    wprod = torch.empty((max(n, 1), 2), dtype=torch.float32, device=out.device)[:n] if wide else None
+    _lib.call("mrec_q4_gather_rows", _ptr(_q8_records(q4, 4)), q4.V, q4.row_bytes, q4.D, _ptr(flat), flat.element_size(), n,
+              _ptr(row_scale), _ptr(out), _KIND[out.dtype], q4.D, _ptr(wprod), 2, _stream())
+    return out.view(tuple(ids.shape) + (q4.D,)), (wprod.view(tuple(ids.shape) + (2,)) if wide else None)
 
 
 def fm_lookup_q8(q8, ids, wts, out_dtype=torch.float16, out=None):

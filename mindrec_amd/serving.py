@@ -24,8 +24,9 @@ class _ServeNet(DenseNetMixin):
 
 
 class WideDeepQ8Predictor:
-    """A Q8Table (the deep rows as 8-bit codes, the wide weight in each record's header) + a copy of the dense parameters and the wide
-    bias.  predict_fused is WideDeepEngine.predict_fused's contract over the dequantized table; the launches are issued eagerly."""
+    """A Q8Table (the deep rows as 8-bit or 4-bit codes, the wide weight in each record's header) + a copy of the dense parameters and
+    the wide bias.  predict_fused is WideDeepEngine.predict_fused's contract over the dequantized table; the launches are issued eagerly.
+    The table's `bits` picks the lookup (ops.gather_rows_q8 / ops.gather_rows_q4); everything behind it is the same."""
 
     def __init__(self, q8, dims, weights, biases, wide_b, mlp_dtype=None, mfma=None, fused_tail=True, fused_tail_eval=True):
         """q8: ops.Q8Table on the GPU; dims: [F * D, hidden .., 1]; weights[i] [in_i, out_i], biases[i] [out_i] and wide_b as
@@ -34,6 +35,8 @@ class WideDeepQ8Predictor:
         self.device = q8.records.device
         if self.device.type != "cuda":
             raise RuntimeError("WideDeepQ8Predictor runs on an MI355X (no CPU fallback)")
+        if q8.bits not in (4, 8):
+            raise TypeError(f"WideDeepQ8Predictor reads 8-bit or 4-bit records, got bits={q8.bits}")
         if dims[0] % q8.D:
             raise ValueError(f"the net's input width {dims[0]} is no multiple of the table's emb_dim {q8.D}")
         mfma = (mlp_dtype is not None and DenseNetMixin.mfma_net_ok(dims)) if mfma is None else bool(mfma)
@@ -44,7 +47,8 @@ class WideDeepQ8Predictor:
 
     def _chain(self, ids, wts, label):
         B, F = ids.shape
-        rows, wprod = ops.gather_rows_q8(self.q8, ids, wts, out_dtype=self._row_dtype)
+        lookup = ops.gather_rows_q4 if self.q8.bits == 4 else ops.gather_rows_q8
+        rows, wprod = lookup(self.q8, ids, wts, out_dtype=self._row_dtype)
         return self.net.mlp_predict(rows.view(B, F * self.q8.D), _WideProd(wprod), label)
 
     def predict_fused(self, ids, wts, label=None):
@@ -67,6 +71,8 @@ class MultiHotQ8:
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         if q8.records.device.type != "cuda":
             raise RuntimeError("MultiHotQ8 runs on an MI355X (no CPU fallback)")
+        if q8.bits != 8:
+            raise TypeError(f"MultiHotQ8 reads 8-bit records (the pooled lookup has no 4-bit form), got bits={q8.bits}")
         self.q8, self.device = q8, q8.records.device
         self.fields = ops._fields(bag if isinstance(bag, (tuple, list)) else (bag,))
         self.bag, self.dim, self.vocab = sum(self.fields), q8.D, q8.V
@@ -106,6 +112,8 @@ class DeepFMQ8Predictor:
         self.device = q8.records.device
         if self.device.type != "cuda":
             raise RuntimeError("DeepFMQ8Predictor runs on an MI355X (no CPU fallback)")
+        if q8.bits != 8:
+            raise TypeError(f"DeepFMQ8Predictor reads 8-bit records (the FM lookup has no 4-bit form), got bits={q8.bits}")
         if dims[0] % q8.D:
             raise ValueError(f"the net's input width {dims[0]} is no multiple of the table's emb_dim {q8.D}")
         mfma = (mlp_dtype is not None and DenseNetMixin.mfma_net_ok(dims)) if mfma is None else bool(mfma)

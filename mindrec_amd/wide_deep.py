@@ -518,13 +518,16 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             ids, _ = self._translate_keys(ids)          # MapTensorGet inserts default rows in eval too, as predict
         return self._predict_run(self._predict_chain, ids, wts, label, capture=self._graph_level >= 1 and self.index is None)
 
-    def q8_predictor(self, row_bytes=None):
+    def q8_predictor(self, row_bytes=None, bits=8):
         """Freezes the model as it stands for serving: the deep table and the wide weights quantized to row-wise 8-bit records in one
         pass (ops.quantize_rows_q8; fused rows are read in place), the dense parameters and the wide bias copied.  Returns a
         serving.WideDeepQ8Predictor, whose predict_fused has this engine's predict_fused contract and which no longer depends on the
-        engine: training on leaves it unchanged.  row_bytes: the record size (default: compact).  Dense resident tables on one
-        GPU only: row shards, the host cache, dynamic_embedding (a key without a record has nowhere to go), max_norm (the clip is not
-        folded into the records) and an emb_dim outside the records' range raise ValueError."""
+        engine: training on leaves it unchanged.  row_bytes: the record size (default: compact).  bits=4: 4-bit records
+        (ops.quantize_rows_q4: 64 bytes an id at emb_dim 80 against 96); any other value raises ValueError.  Dense resident tables on
+        one GPU only: row shards, the host cache, dynamic_embedding (a key without a record has nowhere to go), max_norm (the clip is
+        not folded into the records) and an emb_dim outside the records' range raise ValueError."""
+        if bits not in (4, 8):
+            raise ValueError(f"q8_predictor: bits must be 8 or 4, got {bits!r}")
         D = self.cfg.emb_dim
         mode = ("row shards (world > 1)" if self._sharded else "the host cache (host_cache_rows > 0)" if self.hb is not None
                 else "dynamic_embedding" if self.index is not None else "max_norm" if self._max_norm is not None
@@ -535,7 +538,7 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
         from .serving import WideDeepQ8Predictor
         n = len(self.dims) - 1
         with torch.cuda.device(self.device):
-            q8 = ops.quantize_rows_q8(self.deep, self.wide, row_bytes=row_bytes)
+            q8 = (ops.quantize_rows_q4 if bits == 4 else ops.quantize_rows_q8)(self.deep, self.wide, row_bytes=row_bytes)
         return WideDeepQ8Predictor(q8, self.dims, [self.dense[2 * i].detach() for i in range(n)],
                                    [self.dense[2 * i + 1].detach() for i in range(n)], self.wide_b.detach(), mlp_dtype=self._amp,
                                    mfma=self._mfma, fused_tail=self._tail_ok, fused_tail_eval=self._tail_eval)

@@ -1,5 +1,6 @@
-"""The dequantizing lookup over row-wise 8-bit records (ops.gather_rows_q8, compact and 128-byte records) against the fp32 folded
-lookup (ops.gather_rows_wide over fused training rows) on the same ids, and the quantize pass over the same table.
+"""The dequantizing lookup over row-wise 8-bit records (ops.gather_rows_q8, compact and 128-byte records) and over row-wise 4-bit
+records (ops.gather_rows_q4, compact 64-byte and 128-byte records) against the fp32 folded lookup (ops.gather_rows_wide over fused
+training rows) on the same ids, all arms in one rotation, and the two quantize passes over the same table.
 
     python tools/q8_lookup_bench.py [vocab] [blocks] [calls]
 
@@ -57,10 +58,12 @@ def main():
     ops.fill_normal_(wide, 1001)
     compact = ops.q8_row_bytes(D)
     q8 = {rb: ops.quantize_rows_q8(deep, wide, row_bytes=rb) for rb in (compact, 128)}
+    q4 = {rb: ops.quantize_rows_q4(deep, wide, row_bytes=rb) for rb in (ops.q4_row_bytes(D), 128)}
     n = B * F
-    for rb, t in q8.items():
-        us = _time({"q": lambda t=t, rb=rb: ops.quantize_rows_q8(deep, wide, row_bytes=rb, out=t.records)}, max(blocks // 3, 3), 2)["q"]
-        print(json.dumps({"what": "quantize", "V": V, "row_bytes": rb, **_line(us, V * (4 * D + 4 + rb))}), flush=True)
+    for bits, quantize, tables in ((8, ops.quantize_rows_q8, q8), (4, ops.quantize_rows_q4, q4)):
+        for rb, t in tables.items():
+            us = _time({"q": lambda t=t, rb=rb: quantize(deep, wide, row_bytes=rb, out=t.records)}, max(blocks // 3, 3), 2)["q"]
+            print(json.dumps({"what": "quantize", "bits": bits, "V": V, "row_bytes": rb, **_line(us, V * (4 * D + 4 + rb))}), flush=True)
     cfg = WideDeepConfig(vocab_size=V, emb_dim=D, field_size=F, batch_size=B)
     for dist in ("uniform", "zipf"):
         ids, wts, _ = synthetic_batch(cfg, dev, dist, seed=1000)
@@ -68,11 +71,15 @@ def main():
         arms = {"fp32_folded": lambda: ops.gather_rows_wide(deep, ids, wts, D, out=out, out_dtype=torch.float16)}
         for rb, t in q8.items():
             arms[f"q8_{rb}"] = lambda t=t: ops.gather_rows_q8(t, ids, wts, out=out)
+        for rb, t in q4.items():
+            arms[f"q4_{rb}"] = lambda t=t: ops.gather_rows_q4(t, ids, wts, out=out)
         us = _time(arms, blocks, calls)
         common = 2 * D + 8 + 4 + 4
         res = {"fp32_folded": _line(us["fp32_folded"], n * (4 * D + 16 + common))}
         for rb in q8:
             res[f"q8_{rb}"] = _line(us[f"q8_{rb}"], n * (rb + common))
+        for rb in q4:
+            res[f"q4_{rb}"] = _line(us[f"q4_{rb}"], n * (rb + common))
         print(json.dumps({"what": "lookup", "ids": dist, "positions": n, "V": V, **res}), flush=True)
     # DeepFM's evaluation lookup: (i) the one launch over records, (ii) the composition it replaces -- q8 gather to fp32 rows (no wide
     # pair), then the FM kernel with the 16-bit copy; its linear sum is missing, which favours it --, (iii) ops.fm_lookup over DeepFM's own
