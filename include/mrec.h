@@ -1435,7 +1435,8 @@ int mrec_q8_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes
  * row_bytes that is too small or no multiple of 16 is MREC_EINVAL (the shape is judged first), both before any launch.  Table rows
  * are assumed finite; this is not checked.
  *
- * The three entries take the arguments of mrec_q8_row_bytes, mrec_q8_quantize_rows and mrec_q8_gather_rows and keep their contracts:
+ * The first three entries take the arguments of mrec_q8_row_bytes, mrec_q8_quantize_rows and mrec_q8_gather_rows and keep their
+ * contracts:
  *
  * mrec_q4_row_bytes: the compact record size 16 + 16 ceil(D / 32), or the negative code above.
  *
@@ -1451,12 +1452,48 @@ int mrec_q8_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes
  *   row and a zero product.  id_bytes 4 / 8; V >= 1; n == 0: MREC_OK.
  *
  * Each is one launch, takes no workspace and is capturable; every refusal comes before the launch and leaves records and out
- * untouched.  There is no 4-bit form of mrec_q8_fm_lookup or mrec_q8_gather_pool_fields. */
+ * untouched.
+ *
+ * mrec_q4_fm_lookup: mrec_q8_fm_lookup over 4-bit records -- its arguments, its order of refusals (the 4-bit shape and record-size
+ *   codes first) and its contract, with x' the 4-bit dequantisation.  ids, wts [B, F]; r = ids[b, f], t = wts[b, f],
+ *   y[b, f, d] = fl(x'[r][d] * t) in fp32.
+ *     rows[b, f, :] = y rounded once to rows_kind, rows [B, F, D] contiguous: bit for bit what mrec_q4_gather_rows writes for the same
+ *       position with row_scale = wts;
+ *     lin_fm[b]     = lin + 0.5f * sum_d (s_d^2 - q_d), lin = sum_f fl(wide_r * t), s_d = sum_f y, q_d = sum_f y^2 over the fp32 y --
+ *       before any 16-bit rounding --, all three from +0 in ascending field order.  The sum over d: columns in chunks of 32 (a record's
+ *       code chunks); inside a chunk each group of four columns as ((p0 + p1) + (p2 + p3)), p = s^2 - q, the chunk's valid groups (one
+ *       to eight) added in ascending order from +0; the chunks c = 1 .. C4 = ceil(D / 32) <= 8, with +0 in slot 0, by a tree at
+ *       distances 8, 4, 2, 1: slot i takes slot i + dist where i + dist <= C4, slot 0 is the sum.  No atomics: lin_fm is the same
+ *       run to run and whatever rows_kind and id_bytes are.
+ *   An id outside [0, V) reads as a zero record: a zero row (+0 * t) and a zero linear weight.  No max_norm.
+ *   Refusals, in this order: the 4-bit shape code (MREC_EUNSUPPORTED for D % 4 != 0 or D > 256), the record-size code (MREC_EINVAL for
+ *   row_bytes % 16 != 0 or row_bytes < 16 + 16 ceil(D / 32)); MREC_EINVAL: id_bytes not 4 or 8, rows_kind outside 0..2, B < 0, F < 1,
+ *   V < 1; B == 0: MREC_OK; MREC_EINVAL for a NULL pointer other than stream; MREC_EUNSUPPORTED for records not 16-byte aligned or rows
+ *   not 8-byte (fp32 rows: 16-byte) aligned.  Every refusal comes before the launch and leaves rows and lin_fm untouched.  One launch,
+ *   persistent workgroups (at most 2048), no workspace, capturable.
+ *
+ * mrec_q4_gather_pool_fields: mrec_q8_gather_pool_fields over 4-bit records -- its arguments, its order of refusals (the 4-bit shape
+ *   and record-size codes first; MREC_POOL_MAX_FIELDS and MREC_POOL_MAX_BAG as there) and its arithmetic to the letter, code_s[d] in
+ *   0 .. 15: t_s = fl(m_s * scale_s), u_s = fl(m_s * lo_s), g_s = fl(m_s * wide_s); acc_d = fma((float)code_s[d], t_s, acc_d),
+ *   base = fl(base + u_s) and wsum_f = fl(wsum_f + g_s) from +0 over the field's slots in ascending order; y_d = fl(acc_d + base),
+ *   mode 1: y_d = fl(y_d / (float)L_f); one rounding to out_kind; wide_out[b * ldw] = the ascending sum of the wsum_f from +0.  An id
+ *   outside [0, V) reads as a zero record.  No atomics: the same bits run to run, and wide_out and fp32 rows whatever out_kind and
+ *   id_bytes are.  ldo in elements of out: 0 means F * D, else ldo >= F * D.
+ *   Refusals, in this order: the 4-bit shape and record-size codes as above; MREC_EINVAL: id_bytes not 4 or 8, out_kind outside 0..2,
+ *   mode not 0 or 1, B < 0, V < 1, F < 1, field_len NULL or an L_f < 1, ldo < F * D, wide_out with ldw < 1; MREC_EUNSUPPORTED:
+ *   F > MREC_POOL_MAX_FIELDS, Ls > MREC_POOL_MAX_BAG, B * F >= 2^31; B == 0: MREC_OK; MREC_EINVAL for NULL records, ids or out;
+ *   MREC_EUNSUPPORTED for ldo % 4 != 0, records not 16-byte aligned or out not 8-byte (fp32 rows: 16-byte) aligned.  Every refusal
+ *   comes before the launch and leaves out and wide_out untouched.  One launch, no workspace, no synchronisation, capturable. */
 int mrec_q4_row_bytes(int32_t D);
 int mrec_q4_quantize_rows(const float* table, int64_t V, int64_t ld, int32_t D, const float* wide, int64_t ldw, void* records,
                           int64_t row_bytes, void* stream);
 int mrec_q4_gather_rows(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t n,
                         const float* row_scale, void* out, int32_t out_kind, int64_t ldo, float* wide_prod, int64_t ldw, void* stream);
+int mrec_q4_fm_lookup(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, const float* wts,
+                      int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm, void* stream);
+int mrec_q4_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes, int64_t B,
+                               int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
+                               int64_t ldo, float* wide_out, int64_t ldw, void* stream);
 
 #ifdef __cplusplus
 }

@@ -252,6 +252,8 @@ _SIGS = {
     "mrec_q4_row_bytes": [_i32],
     "mrec_q4_quantize_rows": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
     "mrec_q4_gather_rows": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i64, _vp],
+    "mrec_q4_fm_lookup": [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
+    "mrec_q4_gather_pool_fields": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _i64, _vp, _i64, _vp],
 }
 _RESTYPES = {"mrec_strerror": C.c_char_p, "mrec_map_counters_dev": _vp, "mrec_map_row_keys_dev": _vp}
 

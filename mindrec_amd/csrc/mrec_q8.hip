@@ -72,6 +72,32 @@
 //                Lanes per row: D = 80 -> 4 lanes, 16 positions a wave, 64 / 64 lanes busy; D = 64 -> 3 lanes, 21 positions, 63 / 64;
 //                D = 256 -> 9 lanes, 7 positions, 63 / 64.
 //                Roofline bytes per position: row_bytes read (+ id, + row_scale), 2 D (16-bit) or 4 D written, + 8 (wide pair).
+// k_q4_fm_lookup k_q8_fm_lookup's contract over 4-bit records, designed for the 32-code chunk: lane-group = C4 + 1 lanes a SAMPLE, lane 0 the
+//                header chunk of each of the sample's records, lane c the c-th 32 codes, one 16-byte load a lane a field.  D = 80 -> 4
+//                lanes, 16 samples a wave, 64 / 64 lanes busy (8-bit: 6 lanes, 10 samples, 60 / 64); D = 64 -> 3 lanes, 21 samples;
+//                D = 256 -> 9 lanes, 7 samples.  A code lane carries s[32] and q[32]: 64 VGPRs of sums against the 8-bit kernel's 32.
+//                What keeps that affordable: (1) a field is consumed one code dword at a time -- q4_dequant8's eight values are added
+//                into their sums, the sums are pinned by an empty asm, then the eight values are stored -- so no more than eight y are
+//                alive beside the sums (left alone the compiler sinks every add behind the batch's last store branch and keeps 32 y a
+//                field in flight alive: 242 VGPRs, occupancy 2); (2) no branch on the lane's role: the header lane runs the code lanes'
+//                arithmetic over its header words into sums nobody reads (valid == 0: it stores nothing and is left out of the
+//                column sum) and a code lane adds its third word into a `lin` nobody reads -- a divergent branch around 64 live sums
+//                cost two more registers a sum.  Four fields in flight (kQ4FmNB): 135-140 VGPRs, occupancy 3, no scratch -- the
+//                8-bit kernel's occupancy (152-154 VGPRs) with 16 samples a wave for its 10, so 3 x 4 x 16 = 192 records in flight a
+//                SIMD against 120.  Two fields in flight: 111-112 VGPRs, occupancy 4, 4 x 2 x 16 = 128 records in flight and twice
+//                the dependent round trips a sample (20 at F = 39 for 10); three: 128-131, occupancy 3 for most instantiations;
+//                four held to 128 VGPRs: 44-52 bytes of scratch.  A 16-column lane with an 8-byte load halves the sums but is the
+//                8-bit geometry again (6 lanes at D = 80, 10 samples a wave) with the header lane's load of another width: not taken.
+//                Column-sum order of lin_fm: inside a code lane each group of four columns as ((p0 + p1) + (p2 + p3)), p = s^2 - q, the
+//                lane's one to eight valid groups in ascending order; then the lanes by a shuffle-down tree at distances 8, 4, 2, 1
+//                (lane sub adds lane sub + off where that is a lane of the group; the header lane enters with +0 and ends with the
+//                sum).  No LDS arrays, no barriers, no atomics; four waves a workgroup, a grid stride over samples, at most 2048
+//                workgroups.  Roofline bytes per sample: F (row_bytes + id + weight) read, F D 2 or F D 4, + 4 written.
+// k_q4_gather_pool_fields  k_q8_gather_pool_fields over 4-bit records: the same sample lane-group of C4 + 1 lanes, the same scalar slot and
+//                field bookkeeping, four slots in flight; a code lane holds acc[32], a code costs the nibble split's share (two integer
+//                instructions a dword), v_cvt_f32_ubyteN and v_fma_f32; a field leaves under k_q4_gather's store rule, one 16-byte
+//                store of 16-bit values a code dword.  78-79 VGPRs, occupancy 6, no scratch (8-bit: 61-65, occupancy 7-8).
+//                Roofline bytes per sample: Ls (row_bytes + id + mask) read, F D 2 (16-bit rows) or F D 4, + 4 (wide sum) written.
 #include "mrec_common.h"
 
 namespace {
@@ -587,6 +613,246 @@ __global__ __launch_bounds__(256) void k_q4_gather(const uint8_t* __restrict__ r
     }
 }
 
+// ===== the FM lookup over 4-bit records ================================================================================================
+constexpr int kQ4FmNB = 4;       // fields in flight per lane-group of the 4-bit FM lookup (the header comment has the register count)
+
+// The eight masked values of one code dword of one field: written once in the output kind (k_q4_gather's store rule: st16, `left` = the
+// chunk's valid columns from this dword on) and added into the lane's column sums.  s and q take the fp32 values, whatever the output
+// kind rounds them to; columns past the row's end add into sums that the column sum never reads.
+template <class OT>
+__device__ __forceinline__ void q4_fm_put8(OT* __restrict__ o, const float4& y0, const float4& y1, int left, bool st16, bool store,
+                                           float4& s0, float4& s1, float4& q0, float4& q1) {
+    s0.x = s0.x + y0.x; s0.y = s0.y + y0.y; s0.z = s0.z + y0.z; s0.w = s0.w + y0.w;
+    s1.x = s1.x + y1.x; s1.y = s1.y + y1.y; s1.z = s1.z + y1.z; s1.w = s1.w + y1.w;
+    q0.x = q0.x + y0.x * y0.x; q0.y = q0.y + y0.y * y0.y; q0.z = q0.z + y0.z * y0.z; q0.w = q0.w + y0.w * y0.w;
+    q1.x = q1.x + y1.x * y1.x; q1.y = q1.y + y1.y * y1.y; q1.z = q1.z + y1.z * y1.z; q1.w = q1.w + y1.w * y1.w;
+    // (the sums are taken HERE: the compiler otherwise sinks all 64 adds of a field behind the last store branch of the batch and keeps
+    // every field's 32 values alive until then -- 242 VGPRs instead of 137)
+    asm volatile("" : "+v"(s0.x), "+v"(s0.y), "+v"(s0.z), "+v"(s0.w), "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(s1.w), "+v"(q0.x), "+v"(q0.y),
+                 "+v"(q0.z), "+v"(q0.w), "+v"(q1.x), "+v"(q1.y), "+v"(q1.z), "+v"(q1.w));
+    if (!store) return;
+    if constexpr (sizeof(OT) == 4) {
+        if (left > 0) *(float4*)o = y0;
+        if (left > 4) *(float4*)(o + 4) = y1;
+    } else {
+        const uint2 h0 = q8_pack16((const OT*)nullptr, y0.x, y0.y, y0.z, y0.w);
+        const uint2 h1 = q8_pack16((const OT*)nullptr, y1.x, y1.y, y1.z, y1.w);
+        if (st16 && left > 4) {
+            *(uint4*)o = make_uint4(h0.x, h0.y, h1.x, h1.y);
+        } else {
+            if (left > 0) *(uint2*)o = h0;
+            if (left > 4) *(uint2*)(o + 4) = h1;
+        }
+    }
+}
+
+// rows [B, F, D] contiguous.  gm.lpr = ceil(D / 32) + 1 lanes a SAMPLE: lane 0 the header chunk of each of the sample's records, lane c
+// the c-th 32 codes.  A lane-group whose sample lies past B (the last wave's) reads sample 0's entries and stores nothing: every lane of a
+// live group-slot stays in the loop, so the ds_bpermute reads below always find their source lane active.
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q4_fm_lookup(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                      const K* __restrict__ ids, const float* __restrict__ wts, int64_t B, int F,
+                                                      OT* __restrict__ rows, float* __restrict__ lin_fm, RowGeom gm, bool st16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 32;                                    // (the header lane: -32, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 32 ? D - col0 : 32);
+    const int64_t ng = (int64_t)gridDim.x * 4 * gm.G;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wave) * gm.G; b0 < B; b0 += ng) {
+        const int64_t b = b0 + grp;
+        const bool live = b < B;
+        const int64_t e0 = (live ? b : 0) * (int64_t)F;
+        float4 s[8] = {zero4, zero4, zero4, zero4, zero4, zero4, zero4, zero4};
+        float4 q[8] = {zero4, zero4, zero4, zero4, zero4, zero4, zero4, zero4};
+        float lin = 0.0f;
+        // kQ4FmNB fields, nf of them real: a spare slot reads the batch's last field again and is dropped, so s, q and the linear sum see
+        // the F fields alone, in field order (k_q8_fm_lookup's rule)
+        const auto fields = [&](const int f, const int nf) {
+            int64_t r[kQ4FmNB];
+            float t[kQ4FmNB];
+            uint4 x[kQ4FmNB];
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) {
+                const int64_t e = e0 + f + (k < nf ? k : nf - 1);
+                r[k] = (int64_t)ids[e];
+                t[k] = wts[e];
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) {
+                const bool ok = r[k] >= 0 && r[k] < V;
+                x[k] = *(const uint4*)(rec + (ok ? r[k] : 0) * row_bytes + 16 * sub);
+                if (!ok) r[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) {
+                asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+                if (r[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);        // header and codes zero: a zero row, a zero linear weight
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) {
+                const float lo = bperm_f(lane0, __uint_as_float(x[k].x));
+                const float scale = bperm_f(lane0, __uint_as_float(x[k].y));
+                if (k >= nf) continue;
+                // no branch on the lane's role: every lane adds its chunk's third word into lin and its 32 "codes" into s and q -- only
+                // the header lane's lin and the code lanes' sums are ever read (valid == 0 keeps the header lane from storing)
+                lin = lin + __uint_as_float(x[k].z) * t[k];
+                const unsigned w[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
+                OT* const o = rows + ((b * F + f + k) * (int64_t)D + col0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float4 y0, y1;
+                    q4_dequant8(w[j], lo, scale, t[k], y0, y1);
+                    q4_fm_put8(o + 8 * j, y0, y1, valid - 8 * j, st16, live, s[2 * j], s[2 * j + 1], q[2 * j], q[2 * j + 1]);
+                }
+            }
+        };
+        int f = 0;
+        for (; f + kQ4FmNB <= F; f += kQ4FmNB) fields(f, kQ4FmNB);
+        if (f < F) fields(f, F - f);
+        float part = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (valid > 4 * j)
+                part += ((s[j].x * s[j].x - q[j].x) + (s[j].y * s[j].y - q[j].y)) + ((s[j].z * s[j].z - q[j].z) + (s[j].w * s[j].w - q[j].w));
+#pragma unroll
+        for (int off = 8; off >= 1; off >>= 1) {
+            const float o = __shfl_down(part, off, 64);
+            if (sub + off < gm.lpr) part += o;
+        }
+        if (live && sub == 0) lin_fm[b] = lin + 0.5f * part;
+    }
+}
+
+// ===== the pooled (multi-hot) lookup over 4-bit records ================================================================================
+constexpr int kQ4PoolNB = 4;     // slots in flight per lane-group of the 4-bit pooled lookup
+
+// the eight codes of one dword into eight column sums, acc = fma((float)code, t, acc): q4_dequant8's two-word nibble split (two integer
+// instructions a dword), then one byte conversion and one fma a code
+__device__ __forceinline__ void q4_pool_fma8(unsigned w, float t, float4& a0, float4& a1) {
+    unsigned e = w & 0x0F0F0F0Fu, o = (w >> 4) & 0x0F0F0F0Fu;
+    asm volatile("" : "+v"(e), "+v"(o));            // (keeps the two words: the compiler otherwise extracts a bit field per code)
+    a0.x = __builtin_fmaf((float)(e & 0xFFu), t, a0.x);
+    a0.y = __builtin_fmaf((float)(o & 0xFFu), t, a0.y);
+    a0.z = __builtin_fmaf((float)((e >> 8) & 0xFFu), t, a0.z);
+    a0.w = __builtin_fmaf((float)((o >> 8) & 0xFFu), t, a0.w);
+    a1.x = __builtin_fmaf((float)((e >> 16) & 0xFFu), t, a1.x);
+    a1.y = __builtin_fmaf((float)((o >> 16) & 0xFFu), t, a1.y);
+    a1.z = __builtin_fmaf((float)(e >> 24), t, a1.z);
+    a1.w = __builtin_fmaf((float)(o >> 24), t, a1.w);
+}
+
+// eight pooled values (one code dword's columns), rounded once to the output kind: k_q4_gather's store rule (st16, `left` = the chunk's
+// valid columns from this dword on)
+template <class OT>
+__device__ __forceinline__ void q4_pool_put8(OT* __restrict__ o, const float4& y0, const float4& y1, int left, bool st16) {
+    if constexpr (sizeof(OT) == 4) {
+        if (left > 0) *(float4*)o = y0;
+        if (left > 4) *(float4*)(o + 4) = y1;
+    } else {
+        const uint2 h0 = q8_pack16((const OT*)nullptr, y0.x, y0.y, y0.z, y0.w);
+        const uint2 h1 = q8_pack16((const OT*)nullptr, y1.x, y1.y, y1.z, y1.w);
+        if (st16 && left > 4) {
+            *(uint4*)o = make_uint4(h0.x, h0.y, h1.x, h1.y);
+        } else {
+            if (left > 0) *(uint2*)o = h0;
+            if (left > 4) *(uint2*)(o + 4) = h1;
+        }
+    }
+}
+
+// ids, mask [B, Ls] contiguous.  k_q8_gather_pool_fields over the 4-bit record: gm.lpr = ceil(D / 32) + 1 lanes a sample, a code lane
+// holds acc[32].  Slot numbers, field ends and the closing of a field are the same for every lane of the wave (scalar registers, uniform
+// branches), inside which every lane of a live group-slot runs, so the ds_bpermute reads always find their source lane active.  A
+// lane-group whose sample lies past B reads sample 0's entries and stores nothing.  Every lane forms t, u and g from the first three
+// words of its own chunk; only the header lane's t, base and wsum are ever read (as are only the code lanes' acc).
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q4_gather_pool_fields(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                               const K* __restrict__ ids, const float* __restrict__ mask, int64_t B, int F,
+                                                               int Ls, int mode, OT* __restrict__ out, int64_t ldo,
+                                                               float* __restrict__ wide_out, int64_t ldw, RowGeom gm, bool st16,
+                                                               const Q8PoolFields pf) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 32;                                    // (the header lane: -32, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 32 ? D - col0 : 32);
+    const int64_t ng = (int64_t)gridDim.x * 4 * gm.G;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int slast = Ls - 1;
+    for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wave) * gm.G; b0 < B; b0 += ng) {
+        const int64_t b = b0 + grp;
+        const bool live = b < B;
+        const int64_t e0 = (live ? b : 0) * (int64_t)Ls;
+        float4 acc[8] = {zero4, zero4, zero4, zero4, zero4, zero4, zero4, zero4};
+        float base = 0.0f, wsum = 0.0f, wtot = 0.0f;
+        int f = 0;
+        unsigned fw = pf.w[0];
+        int fend = (int)(fw >> 16);                                     // one past the open field's last slot (field 0 starts at slot 0)
+        for (int s0 = 0; s0 < Ls; s0 += kQ4PoolNB) {
+            int64_t r[kQ4PoolNB];
+            float m[kQ4PoolNB];
+            uint4 x[kQ4PoolNB];
+#pragma unroll
+            for (int k = 0; k < kQ4PoolNB; ++k) {
+                const int64_t e = e0 + (s0 + k < slast ? s0 + k : slast);
+                r[k] = (int64_t)ids[e];
+                m[k] = mask ? mask[e] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4PoolNB; ++k) {
+                const bool ok = r[k] >= 0 && r[k] < V;
+                x[k] = *(const uint4*)(rec + (ok ? r[k] : 0) * row_bytes + 16 * sub);
+                if (!ok) r[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4PoolNB; ++k) {
+                asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+                if (r[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);        // header and codes zero: a +0 row, a +0 wide product
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4PoolNB; ++k) {
+                const int s = s0 + k;
+                if (s > slast) continue;                                // a spare slot of the sample's last batch: dropped
+                const float t = bperm_f(lane0, m[k] * __uint_as_float(x[k].y));
+                base = base + m[k] * __uint_as_float(x[k].x);
+                wsum = wsum + m[k] * __uint_as_float(x[k].z);
+                q4_pool_fma8(x[k].x, t, acc[0], acc[1]);
+                q4_pool_fma8(x[k].y, t, acc[2], acc[3]);
+                q4_pool_fma8(x[k].z, t, acc[4], acc[5]);
+                q4_pool_fma8(x[k].w, t, acc[6], acc[7]);
+                if (s + 1 != fend) continue;
+                // the field's last slot: y = acc + base, the mean's division by the field's own length, one rounding, one store a dword
+                const float bs = bperm_f(lane0, base);
+                const float fl = (float)(fw >> 16);
+                OT* const o = out + (b * ldo + (int64_t)f * D + col0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float4 y[2];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const float4 a = acc[2 * j + h];
+                        y[h] = make_float4(a.x + bs, a.y + bs, a.z + bs, a.w + bs);
+                        if (mode == 1) y[h] = make_float4(y[h].x / fl, y[h].y / fl, y[h].z / fl, y[h].w / fl);
+                    }
+                    if (live && sub != 0) q4_pool_put8(o + 8 * j, y[0], y[1], valid - 8 * j, st16);
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = zero4;
+                wtot = wtot + wsum;
+                base = wsum = 0.0f;
+                f = f + 1 < F ? f + 1 : f;                              // (behind the last field: its own word again, never closed twice)
+                fw = pf.w[f];
+                fend = (int)(fw & 0xFFFFu) + (int)(fw >> 16);
+            }
+        }
+        if (live && sub == 0 && wide_out) wide_out[b * ldw] = wtot;
+    }
+}
+
 int q4_check(int32_t D, int64_t row_bytes) {
     if (D <= 0) return MREC_EINVAL;
     if (D % 4 || D > 256) return MREC_EUNSUPPORTED;
@@ -754,6 +1020,67 @@ MREC_API int mrec_q4_gather_rows(const void* records, int64_t V, int64_t row_byt
         return by_out(out, out_kind, [&](auto* op) {
             k_q4_gather<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, n, row_scale, op, ldo,
                                                                             wide_prod, ldw, gm, st16);
+            MREC_LAUNCH_CHECK();
+            return (int)MREC_OK;
+        });
+    });
+}
+
+MREC_API int mrec_q4_fm_lookup(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes,
+                               const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm, void* stream) {
+    if (const int rc = q4_check(D, row_bytes)) return rc;
+    if ((id_bytes != 4 && id_bytes != 8) || rows_kind < 0 || rows_kind > 2 || B < 0 || F < 1 || V < 1) return MREC_EINVAL;
+    if (B == 0) return MREC_OK;
+    if (!records || !ids || !wts || !rows || !lin_fm) return MREC_EINVAL;
+    const int esz = rows_kind == 0 ? 4 : 2;
+    if (!al16(records) || (((uintptr_t)rows) & (esz == 4 ? 15 : 7))) return MREC_EUNSUPPORTED;
+    const bool st16 = al16(rows) && (D * esz) % 16 == 0;
+    const int lpr = (D + 31) / 32 + 1;
+    const RowGeom gm{lpr, 64 / lpr};
+    int64_t blocks = mrec_cdiv(B, (int64_t)4 * gm.G);
+    if (blocks > 2048) blocks = 2048;                                   // 256 CUs x 8 workgroups, each walking B
+    return by_key(ids, id_bytes, [&](auto* kp) {
+        return by_out(rows, rows_kind, [&](auto* op) {
+            k_q4_fm_lookup<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, wts, B, F, op,
+                                                                               lin_fm, gm, st16);
+            MREC_LAUNCH_CHECK();
+            return (int)MREC_OK;
+        });
+    });
+}
+
+MREC_API int mrec_q4_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* ids, int32_t id_bytes,
+                                        int64_t B, int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out,
+                                        int32_t out_kind, int64_t ldo, float* wide_out, int64_t ldw, void* stream) {
+    if (const int rc = q4_check(D, row_bytes)) return rc;
+    if ((id_bytes != 4 && id_bytes != 8) || out_kind < 0 || out_kind > 2 || (mode != 0 && mode != 1) || B < 0 || V < 1 || F < 1 || !field_len)
+        return MREC_EINVAL;
+    for (int f = 0; f < F; ++f)
+        if (field_len[f] < 1) return MREC_EINVAL;
+    if (ldo == 0) ldo = (int64_t)F * D;
+    if (ldo < (int64_t)F * D || (wide_out && ldw < 1)) return MREC_EINVAL;
+    if (F > MREC_POOL_MAX_FIELDS) return MREC_EUNSUPPORTED;
+    Q8PoolFields pf{};
+    int64_t Ls = 0;
+    for (int f = 0; f < F; ++f) {
+        if (Ls + field_len[f] > MREC_POOL_MAX_BAG) return MREC_EUNSUPPORTED;
+        pf.w[f] = (unsigned)Ls | ((unsigned)field_len[f] << 16);
+        Ls += field_len[f];
+    }
+    if (B * F >= (int64_t(1) << 31)) return MREC_EUNSUPPORTED;
+    if (B == 0) return MREC_OK;
+    if (!records || !ids || !out) return MREC_EINVAL;
+    const int esz = out_kind == 0 ? 4 : 2;
+    if (ldo % 4 || !al16(records) || (((uintptr_t)out) & (esz == 4 ? 15 : 7))) return MREC_EUNSUPPORTED;
+    const bool st16 = al16(out) && (ldo * esz) % 16 == 0 && (D * esz) % 16 == 0;      // (every field's column block, every row)
+    const int lpr = (D + 31) / 32 + 1;
+    const RowGeom gm{lpr, 64 / lpr};
+    int64_t blocks = mrec_cdiv(B, (int64_t)4 * gm.G);
+    if (blocks > 2048) blocks = 2048;                                   // 256 CUs x 8 workgroups, each walking B
+    return by_key(ids, id_bytes, [&](auto* kp) {
+        return by_out(out, out_kind, [&](auto* op) {
+            k_q4_gather_pool_fields<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, kp, mask, B, F,
+                                                                                        (int)Ls, mode, op, ldo, wide_out, ldw, gm, st16, pf);
             MREC_LAUNCH_CHECK();
             return (int)MREC_OK;
         });

@@ -211,13 +211,17 @@ class DeepFMEngine(_DeepFMNet):
         self._check_fused()
         return self._predict_run(self._predict_chain, ids, wts, label, capture=self.cfg.graphs != "none")
 
-    def q8_predictor(self, row_bytes=None):
+    def q8_predictor(self, row_bytes=None, bits=8):
         """Freezes the model as it stands for serving: the [V, D] table quantized to row-wise 8-bit records with the [V, 1] first-order
         weight in each record's header, one pass (ops.quantize_rows_q8), the dense parameters copied.  Returns a
         serving.DeepFMQ8Predictor, whose predict_fused has this engine's predict_fused contract (launched eagerly) and which no longer
-        depends on the engine: training on leaves it unchanged.  row_bytes: the record size (default: compact).  max_norm (the clip
+        depends on the engine: training on leaves it unchanged.  row_bytes: the record size (default: compact).  bits=4 freezes into
+        row-wise 4-bit records instead (ops.quantize_rows_q4: 64 bytes an id at data_emb_dim 80 against 96), served by the 4-bit FM
+        lookup; any other value raises ValueError.  max_norm (the clip
         is not folded into the records), a data_emb_dim outside the records' range and every case where fused_predict_supported is
         False raise ValueError."""
+        if bits not in (8, 4):
+            raise ValueError(f"q8_predictor: bits must be 8 or 4, got {bits!r}")
         D = self.cfg.data_emb_dim
         why = ("max_norm" if self._max_norm is not None
                else f"data_emb_dim={D} (data_emb_dim % 4 == 0 and 4 <= data_emb_dim <= 256)" if D % 4 or not 4 <= D <= 256
@@ -227,7 +231,7 @@ class DeepFMEngine(_DeepFMNet):
         from .serving import DeepFMQ8Predictor
         n = len(self.dims) - 1
         with torch.cuda.device(self.device):
-            q8 = ops.quantize_rows_q8(self.V_l2, self.W_l2, row_bytes=row_bytes)
+            q8 = (ops.quantize_rows_q4 if bits == 4 else ops.quantize_rows_q8)(self.V_l2, self.W_l2, row_bytes=row_bytes)
         return DeepFMQ8Predictor(q8, self.dims, [self.dense[2 * i].detach() for i in range(n)],
                                  [self.dense[2 * i + 1].detach() for i in range(n)], mlp_dtype=self._amp, mfma=self._mfma,
                                  fused_tail_eval=self._tail_eval)

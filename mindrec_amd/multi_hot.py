@@ -52,7 +52,8 @@ in the same pooled apply (ops.sparse_lazy_adam_(pool_max_norm=c)).  "lazy_adam" 
 refused at construction.
 
 Serving: MultiHotEmbedding.freeze_q8() and MultiHotWideDeep.freeze_q8() freeze the table (and the wide weights, into the record headers)
-into row-wise 8-bit records behind a serving.MultiHotQ8, whose lookup is one pooled launch over records for both sides.
+into row-wise 8-bit records (bits=4: 4-bit ones) behind a serving.MultiHotQ8, whose lookup is one pooled launch over records for both
+sides.
 
 Neither method synchronises with the host, so lookup + apply_ capture into one HIP graph on one stream.  The Adam bias-correction
 powers advance on the host with every apply_: a captured graph holds the powers of the steps it captured (replaying K captured
@@ -78,15 +79,18 @@ def _clip_arg(max_norm, optimizer, dim):
     return c
 
 
-def _freeze_q8(emb, wide, row_bytes):
-    """freeze_q8 of both classes: emb's table as records (wide: the [V, 1] header weights or None) behind a serving.MultiHotQ8"""
+def _freeze_q8(emb, wide, row_bytes, bits=8):
+    """freeze_q8 of both classes: emb's table as 8-bit or 4-bit records (wide: the [V, 1] header weights or None) behind a
+    serving.MultiHotQ8"""
     from .serving import MultiHotQ8
+    if bits not in (8, 4):
+        raise ValueError(f"freeze_q8: bits must be 8 or 4, got {bits!r}")
     if emb.max_norm is not None:
         raise ValueError("freeze_q8: max_norm is not folded into 8-bit records")
     if emb.dim % 4 != 0 or not 4 <= emb.dim <= 256:
         raise ValueError(f"freeze_q8: 8-bit records hold rows of dim % 4 == 0, 4 <= dim <= 256, got {emb.dim}")
     with torch.cuda.device(emb.device):
-        q8 = ops.quantize_rows_q8(emb.table, wide, row_bytes=row_bytes)
+        q8 = (ops.quantize_rows_q4 if bits == 4 else ops.quantize_rows_q8)(emb.table, wide, row_bytes=row_bytes)
     return MultiHotQ8(q8, emb.fields, mode=emb.mode, out_dtype=emb.out_dtype, wide=wide is not None)
 
 
@@ -196,11 +200,13 @@ class MultiHotEmbedding:
             ops.dense_adam_rows_l2_(self.table, self.m, self.v, plan, sums, 0.0, grad_scale=1.0, **akw)
         return plan
 
-    def freeze_q8(self, row_bytes=None):
+    def freeze_q8(self, row_bytes=None, bits=8):
         """The table frozen into row-wise 8-bit records (ops.quantize_rows_q8; row_bytes: the record size, default compact) behind a
-        serving.MultiHotQ8 of the same bag, mode and out_dtype: lookup only, no fp32 table, no optimizer state.  ValueError where
-        max_norm is set (the clip is not folded into records) or dim is outside the record format (dim % 4 == 0, 4 <= dim <= 256)."""
-        return _freeze_q8(self, None, row_bytes)
+        serving.MultiHotQ8 of the same bag, mode and out_dtype: lookup only, no fp32 table, no optimizer state.  bits=4: row-wise 4-bit
+        records (ops.quantize_rows_q4: 48 bytes an id at dim 64 against 80), read by the 4-bit pooled lookup.  ValueError where
+        max_norm is set (the clip is not folded into records), dim is outside the record format (dim % 4 == 0, 4 <= dim <= 256) or
+        bits is neither 8 nor 4."""
+        return _freeze_q8(self, None, row_bytes, bits)
 
 
 class MultiHotWideDeep:
@@ -252,11 +258,11 @@ class MultiHotWideDeep:
         wide._ids, wide._mask = deep._ids, deep._mask          # one copy of the ids: apply_ checks that both halves hold it
         return x, wide_out
 
-    def freeze_q8(self, row_bytes=None):
-        """Both halves frozen into ONE set of row-wise 8-bit records -- deep.table as codes, wide.table as each record's header weight --
-        behind a serving.MultiHotQ8(wide=True): its lookup(ids, mask) returns (x, w) from one launch.  ValueError as
+    def freeze_q8(self, row_bytes=None, bits=8):
+        """Both halves frozen into ONE set of row-wise 8-bit (bits=4: 4-bit) records -- deep.table as codes, wide.table as each record's
+        header weight -- behind a serving.MultiHotQ8(wide=True): its lookup(ids, mask) returns (x, w) from one launch.  ValueError as
         MultiHotEmbedding.freeze_q8."""
-        return _freeze_q8(self.deep, self.wide.table, row_bytes)
+        return _freeze_q8(self.deep, self.wide.table, row_bytes, bits)
 
     def apply_(self, dy, dwide, grad_scale=1.0):
         """The optimizer steps of both halves for dy [B, F * dim], the gradient of x, and dwide [B] (contiguous float32), the gradient

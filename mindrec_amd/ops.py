@@ -718,7 +718,7 @@ def gather_rows_wide(table, ids, row_scale, wide_col, out=None, out_dtype=torch.
 # ---- row-wise 8-bit serving records (csrc/mrec_q8.hip; the record format: include/mrec.h) --------------------------------
 class Q8Table(NamedTuple):
     """A table frozen for evaluation: records uint8 [V, row_bytes], one per row -- [lo scale wide 0 | D codes | zero padding].  bits:
-    the width of a code, 8 (a byte a column) or 4 (two columns a byte: quantize_rows_q4, gather_rows_q4)."""
+    the width of a code, 8 (a byte a column) or 4 (two columns a byte: quantize_rows_q4 and the _q4 lookups)."""
     records: torch.Tensor
     V: int
     D: int
@@ -791,7 +791,8 @@ def q4_row_bytes(D):
 def quantize_rows_q4(table, wide=None, row_bytes=None, out=None):
     """quantize_rows_q8 into row-wise 4-bit records (scale = (hi - lo) / 15, two codes a byte; csrc/mrec_q8.hip: k_q4_quantize): the
     same arguments, one pass, every byte of every record written.  row_bytes: default compact, q4_row_bytes(D) -- 64 bytes at D = 80.
-    Returns a Q8Table with bits=4, which gather_rows_q4 reads and every 8-bit lookup refuses."""
+    Returns a Q8Table with bits=4, which the _q4 lookups (gather_rows_q4, fm_lookup_q4, gather_pool_fields_q4) read and every 8-bit
+    lookup refuses."""
     _need_cuda(table, wide, out)
     V, D, ld = _table(table)
     rb = q4_row_bytes(D) if row_bytes is None else int(row_bytes)
@@ -830,6 +831,20 @@ def fm_lookup_q8(q8, ids, wts, out_dtype=torch.float16, out=None):
     bfloat16 or float16 --, gather_rows_q8(q8, ids, wts)'s bit for bit, lin_fm [B] = sum_f wide * wt + the FM term over those rows
     before rounding).  No fp32 [B, F, D] tensor in between; an id outside [0, V) gives a zero row and a zero weight.  out: dict of
     persistent output tensors "rows" and "lin_fm" (filled on first use)."""
+    return _fm_lookup_q(q8, 8, ids, wts, out_dtype, out)
+
+
+def fm_lookup_q4(q4, ids, wts, out_dtype=torch.float16, out=None):
+    """fm_lookup_q8 over a Q8Table of 4-bit records whose headers carry the FM's first-order weight (quantize_rows_q4(V, W)), one launch
+    (csrc/mrec_q8.hip: k_q4_fm_lookup): ids [B, F] int32 / int64, wts float32 [B, F] -> (rows [B, F, D] in out_dtype -- float32,
+    bfloat16 or float16 --, gather_rows_q4(q4, ids, wts)'s bit for bit, lin_fm [B] float32 = sum_f wide * wt + the FM term over those
+    rows before rounding; the same bits whatever out_dtype and the id width are).  An id outside [0, V) gives a zero row and a zero
+    weight.  out: dict of persistent output tensors "rows" and "lin_fm".  An 8-bit table is refused with TypeError."""
+    return _fm_lookup_q(q4, 4, ids, wts, out_dtype, out)
+
+
+def _fm_lookup_q(q8, bits, ids, wts, out_dtype, out):
+    op = f"fm_lookup_q{bits}"
     _need_cuda(q8.records, ids, wts)
     _suffix(ids)
     if ids.dim() != 2:
@@ -838,7 +853,7 @@ def fm_lookup_q8(q8, ids, wts, out_dtype=torch.float16, out=None):
     if wts.dtype != torch.float32 or tuple(wts.shape) != (B, F):
         raise TypeError("wts must be float32 with one value per id")
     if out_dtype not in _KIND:
-        raise TypeError("fm_lookup_q8 out_dtype must be float32, bfloat16 or float16")
+        raise TypeError(f"{op} out_dtype must be float32, bfloat16 or float16")
     dev = q8.records.device
     o = out if out is not None else {}
     res = []
@@ -847,10 +862,10 @@ def fm_lookup_q8(q8, ids, wts, out_dtype=torch.float16, out=None):
         if t is None:
             t = o[name] = torch.empty(shape, dtype=dtype, device=dev)
         elif t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise TypeError(f"fm_lookup_q8: out[{name!r}] must be a contiguous {dtype} {list(shape)} tensor on the records' device")
+            raise TypeError(f"{op}: out[{name!r}] must be a contiguous {dtype} {list(shape)} tensor on the records' device")
         res.append(t)
     rows, lin_fm = res
-    _lib.call("mrec_q8_fm_lookup", _ptr(_q8_records(q8)), q8.V, q8.row_bytes, q8.D, _ptr(ids.contiguous()), ids.element_size(),
+    _lib.call(f"mrec_q{bits}_fm_lookup", _ptr(_q8_records(q8, bits)), q8.V, q8.row_bytes, q8.D, _ptr(ids.contiguous()), ids.element_size(),
               _ptr(wts.contiguous()), B, F, _ptr(rows), _KIND[out_dtype], _ptr(lin_fm), _stream())
     return rows, lin_fm
 
@@ -864,6 +879,21 @@ def gather_pool_fields_q8(q8, ids, fields, mask=None, mode="mean", out=None, out
     w [B] float32 = the sum over all Ls slots of mask * the record's wide weight (MultiHotWideDeep's wide side, out of the same header
     loads) -- returns (out, w).  An id outside [0, V) adds nothing to either.  out: a [B, F * D] tensor or column block (unit column
     stride); wide_out: a float32 [B] tensor of any positive stride (a column of a wider matrix)."""
+    return _gather_pool_fields_q(q8, 8, ids, fields, mask, mode, out, out_dtype, wide, wide_out)
+
+
+def gather_pool_fields_q4(q4, ids, fields, mask=None, mode="mean", out=None, out_dtype=torch.float32, wide=False, wide_out=None):
+    """gather_pool_fields_q8 over a Q8Table of 4-bit records (bits=4; csrc/mrec_q8.hip: k_q4_gather_pool_fields), one launch, the same
+    arithmetic over codes 0 .. 15: ids [B, Ls] int32 / int64, Ls = sum(fields) -> out [B, F * D], field f's masked sum (mode="mean":
+    divided by L_f) of the dequantized rows, fp32 sums rounded once to out_dtype; mask: float32 [B, Ls] or None (all ones); wide=True:
+    also w [B] float32 = the sum over all slots of mask * the record's wide weight -- returns (out, w).  out: a [B, F * D] tensor or
+    column block (unit column stride); wide_out: a float32 [B] tensor of any positive stride.  An id outside [0, V) adds nothing to
+    either.  An 8-bit table is refused with TypeError."""
+    return _gather_pool_fields_q(q4, 4, ids, fields, mask, mode, out, out_dtype, wide, wide_out)
+
+
+def _gather_pool_fields_q(q8, bits, ids, fields, mask, mode, out, out_dtype, wide, wide_out):
+    op = f"gather_pool_fields_q{bits}"
     _need_cuda(q8.records, ids, mask, out, wide_out)
     lens = _fields(fields)
     _suffix(ids)
@@ -872,22 +902,22 @@ def gather_pool_fields_q8(q8, ids, fields, mask=None, mode="mean", out=None, out
     if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != tuple(ids.shape)):
         raise TypeError("mask must be float32 of the shape of ids")
     if mode not in ("sum", "mean"):
-        raise ValueError(f"gather_pool_fields_q8 mode must be 'sum' or 'mean', got {mode!r}")
+        raise ValueError(f"{op} mode must be 'sum' or 'mean', got {mode!r}")
     B, F, D, dev = ids.shape[0], len(lens), q8.D, q8.records.device
     if out is None:
         if out_dtype not in _KIND:
-            raise TypeError("gather_pool_fields_q8 out_dtype must be float32, bfloat16 or float16")
+            raise TypeError(f"{op} out_dtype must be float32, bfloat16 or float16")
         out = torch.empty((B, F * D), dtype=out_dtype, device=dev)
     elif out.dtype not in _KIND or out.dim() != 2 or tuple(out.shape) != (B, F * D) or out.stride(1) != 1:
-        raise TypeError(f"gather_pool_fields_q8 out must be a [{B}, {F * D}] float32 / bfloat16 / float16 tensor with unit column stride")
+        raise TypeError(f"{op} out must be a [{B}, {F * D}] float32 / bfloat16 / float16 tensor with unit column stride")
     if not wide:
         if wide_out is not None:
-            raise TypeError("gather_pool_fields_q8: wide_out goes with wide=True")
+            raise TypeError(f"{op}: wide_out goes with wide=True")
     elif wide_out is None:
         wide_out = torch.empty((B,), dtype=torch.float32, device=dev)
     elif wide_out.dtype != torch.float32 or wide_out.dim() != 1 or wide_out.shape[0] != B or (B > 1 and wide_out.stride(0) < 1):
-        raise TypeError(f"gather_pool_fields_q8 wide_out must be a float32 [{B}] tensor (any positive stride: a column of a wider matrix)")
-    _lib.call("mrec_q8_gather_pool_fields", _ptr(_q8_records(q8)), q8.V, q8.row_bytes, D, _ptr(ids.contiguous()), ids.element_size(), B, F,
+        raise TypeError(f"{op} wide_out must be a float32 [{B}] tensor (any positive stride: a column of a wider matrix)")
+    _lib.call(f"mrec_q{bits}_gather_pool_fields", _ptr(_q8_records(q8, bits)), q8.V, q8.row_bytes, D, _ptr(ids.contiguous()), ids.element_size(), B, F,
               (C.c_int32 * F)(*lens), _ptr(mask.contiguous() if mask is not None else None), 1 if mode == "mean" else 0, _ptr(out),
               _KIND[out.dtype], out.stride(0) if B > 1 else F * D, _ptr(wide_out), wide_out.stride(0) if wide and B > 1 else 1, _stream())
     return (out, wide_out) if wide else out

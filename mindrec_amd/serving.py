@@ -1,8 +1,9 @@
 """Serving a trained Wide&Deep model from row-wise 8-bit records (csrc/mrec_q8.hip): the evaluation forward of
 WideDeepEngine.predict_fused with the dequantizing lookup in front, holding neither the fp32 table nor any optimizer slot of it.
 Made by WideDeepEngine.q8_predictor().  DeepFMQ8Predictor: the same for DeepFMEngine.predict_fused, with the FM lookup over records
-(ops.fm_lookup_q8) in front.  MultiHotQ8: the multi-hot lookups of multi_hot.py (MultiHotEmbedding, MultiHotWideDeep) over records, one
-pooled launch (ops.gather_pool_fields_q8)."""
+(ops.fm_lookup_q8 / ops.fm_lookup_q4) in front.  MultiHotQ8: the multi-hot lookups of multi_hot.py (MultiHotEmbedding, MultiHotWideDeep)
+over records, one pooled launch (ops.gather_pool_fields_q8 / ops.gather_pool_fields_q4).  Every class takes 8-bit or 4-bit records: the
+table's `bits` picks the lookup."""
 import torch
 
 from . import ops
@@ -62,8 +63,8 @@ class WideDeepQ8Predictor:
 
 class MultiHotQ8:
     """Multi-hot fields served from a Q8Table: MultiHotEmbedding.lookup -- and, with wide=True, MultiHotWideDeep.lookup, whose wide
-    weights sit in the record headers -- as ONE pooled launch over records (ops.gather_pool_fields_q8).  It holds the records only: no
-    fp32 table, no optimizer state, no apply_.  Made by MultiHotEmbedding.freeze_q8() / MultiHotWideDeep.freeze_q8()."""
+    weights sit in the record headers -- as ONE pooled launch over records (ops.gather_pool_fields_q8, or ops.gather_pool_fields_q4
+    for a table of 4-bit records).  It holds the records only: no fp32 table, no optimizer state, no apply_.  Made by MultiHotEmbedding.freeze_q8() / MultiHotWideDeep.freeze_q8()."""
 
     def __init__(self, q8, bag, mode="mean", out_dtype=torch.float32, wide=False):
         """q8: ops.Q8Table on the GPU; bag: an int (one field) or a tuple of bag lengths, as MultiHotEmbedding takes it."""
@@ -71,8 +72,8 @@ class MultiHotQ8:
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         if q8.records.device.type != "cuda":
             raise RuntimeError("MultiHotQ8 runs on an MI355X (no CPU fallback)")
-        if q8.bits != 8:
-            raise TypeError(f"MultiHotQ8 reads 8-bit records (the pooled lookup has no 4-bit form), got bits={q8.bits}")
+        if q8.bits not in (4, 8):
+            raise TypeError(f"MultiHotQ8 reads 8-bit or 4-bit records, got bits={q8.bits}")
         self.q8, self.device = q8, q8.records.device
         self.fields = ops._fields(bag if isinstance(bag, (tuple, list)) else (bag,))
         self.bag, self.dim, self.vocab = sum(self.fields), q8.D, q8.V
@@ -94,16 +95,16 @@ class MultiHotQ8:
         elif tuple(out.shape) != (B, G * W) or (G > 1 and not out.is_contiguous()):
             raise TypeError("out must be [B, F * dim] (contiguous when ids hold more than one bag per sample)")
         with torch.cuda.device(self.device):
-            res = ops.gather_pool_fields_q8(self.q8, ids.reshape(B * G, self.bag), self.fields,
-                                            mask.reshape(B * G, self.bag) if mask is not None else None, mode=self.mode,
-                                            out=out if G == 1 else out.view(B * G, W), wide=self.wide, wide_out=wide_out)
+            pool = ops.gather_pool_fields_q4 if self.q8.bits == 4 else ops.gather_pool_fields_q8
+            res = pool(self.q8, ids.reshape(B * G, self.bag), self.fields, mask.reshape(B * G, self.bag) if mask is not None else None,
+                       mode=self.mode, out=out if G == 1 else out.view(B * G, W), wide=self.wide, wide_out=wide_out)
         return (out, res[1]) if self.wide else out
 
 
 class DeepFMQ8Predictor:
-    """DeepFM served from a Q8Table (the [V, D] rows as 8-bit codes, the [V, 1] first-order weight in each record's header) + a copy of
-    the dense parameters.  predict_fused is DeepFMEngine.predict_fused's contract over the dequantized tables; the launches are issued
-    eagerly.  Made by DeepFMEngine.q8_predictor()."""
+    """DeepFM served from a Q8Table (the [V, D] rows as 8-bit or 4-bit codes, the [V, 1] first-order weight in each record's header) + a
+    copy of the dense parameters.  predict_fused is DeepFMEngine.predict_fused's contract over the dequantized tables; the launches are
+    issued eagerly.  The table's `bits` picks the lookup (ops.fm_lookup_q8 / ops.fm_lookup_q4).  Made by DeepFMEngine.q8_predictor()."""
 
     def __init__(self, q8, dims, weights, biases, mlp_dtype=None, mfma=None, fused_tail_eval=True):
         """q8: ops.Q8Table on the GPU; dims: [F * D, hidden .., 1]; weights[i] [in_i, out_i] and biases[i] [out_i] as
@@ -112,8 +113,8 @@ class DeepFMQ8Predictor:
         self.device = q8.records.device
         if self.device.type != "cuda":
             raise RuntimeError("DeepFMQ8Predictor runs on an MI355X (no CPU fallback)")
-        if q8.bits != 8:
-            raise TypeError(f"DeepFMQ8Predictor reads 8-bit records (the FM lookup has no 4-bit form), got bits={q8.bits}")
+        if q8.bits not in (4, 8):
+            raise TypeError(f"DeepFMQ8Predictor reads 8-bit or 4-bit records, got bits={q8.bits}")
         if dims[0] % q8.D:
             raise ValueError(f"the net's input width {dims[0]} is no multiple of the table's emb_dim {q8.D}")
         mfma = (mlp_dtype is not None and DenseNetMixin.mfma_net_ok(dims)) if mfma is None else bool(mfma)
@@ -124,7 +125,8 @@ class DeepFMQ8Predictor:
 
     def _chain(self, ids, wts, label):
         B, F = ids.shape
-        rows, lin_fm = ops.fm_lookup_q8(self.q8, ids, wts, out_dtype=self._row_dtype)
+        lookup = ops.fm_lookup_q4 if self.q8.bits == 4 else ops.fm_lookup_q8
+        rows, lin_fm = lookup(self.q8, ids, wts, out_dtype=self._row_dtype)
         return self.net.mlp_predict(rows.view(B, F * self.q8.D), lin_fm, label)
 
     def predict_fused(self, ids, wts, label=None):

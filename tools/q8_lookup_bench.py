@@ -9,8 +9,9 @@ stream.  Each arm is warmed, then timed as `blocks` blocks of `calls` calls betw
 rotation; one JSON line per id distribution with the median (min, max) microseconds per call and the GB/s that implies against the
 arm's algorithmic bytes per position: the record or the 336 bytes of the fp32 row, the fp16 output row, the 8-byte wide pair, id and
 weight.  The quantize pass is timed the same way (read 4 D + 4, write row_bytes per row).  Then DeepFM's evaluation lookup over the same
-16384 x 39 ids, three arms timed the same way: ops.fm_lookup_q8 over the compact records, the composition it replaces (ops.gather_rows_q8
-into fp32 rows, then ops.fm_forward with the 16-bit copy; without the linear sum) and ops.fm_lookup over contiguous fp32 tables."""
+16384 x 39 ids, four arms timed the same way: ops.fm_lookup_q8 over the compact 8-bit records, ops.fm_lookup_q4 over the compact 4-bit
+records, the composition the former replaces (ops.gather_rows_q8 into fp32 rows, then ops.fm_forward with the 16-bit copy; without the
+linear sum) and ops.fm_lookup over contiguous fp32 tables."""
 import json
 import os
 import sys
@@ -84,26 +85,29 @@ def main():
     # DeepFM's evaluation lookup: (i) the one launch over records, (ii) the composition it replaces -- q8 gather to fp32 rows (no wide
     # pair), then the FM kernel with the 16-bit copy; its linear sum is missing, which favours it --, (iii) ops.fm_lookup over DeepFM's own
     # contiguous fp32 [V, D] and [V, 1] tables (the same values the records were made from)
-    t = q8[compact]
+    t, t4 = q8[compact], q4[ops.q4_row_bytes(D)]
     Vc, Wc = deep.contiguous(), wide.contiguous()
     rows32 = torch.empty((B, F, D), dtype=torch.float32, device=dev)
     rows16 = torch.empty((B, F, D), dtype=torch.float16, device=dev)
     lin0 = torch.zeros(B, dtype=torch.float32, device=dev)
-    o_q8, o_fm, o_f32 = {}, {}, {}
+    o_q8, o_q4, o_fm, o_f32 = {}, {}, {}, {}
     for dist in ("uniform", "zipf"):
         ids, wts, _ = synthetic_batch(cfg, dev, dist, seed=1000)
 
         def composed():
             ops.gather_rows_q8(t, ids, wts, out=rows32, wide=False)
             ops.fm_forward(rows32, add=lin0, out16=rows16, out=o_fm)
-        us = _time({"fm_q8": lambda: ops.fm_lookup_q8(t, ids, wts, out=o_q8), "q8_gather+fm_forward": composed,
+        us = _time({"fm_q8": lambda: ops.fm_lookup_q8(t, ids, wts, out=o_q8), "fm_q4": lambda: ops.fm_lookup_q4(t4, ids, wts, out=o_q4),
+                    "q8_gather+fm_forward": composed,
                     "fm_fp32": lambda: ops.fm_lookup(Vc, Wc, ids, wts, out=o_f32)}, blocks, calls)
         per = 4 + 4 + 2 * D                             # id, weight and the fp16 row of a position
-        res = {"fm_q8": _line(us["fm_q8"], n * (compact + per) + 4 * B),
+        res = {"fm_q8": _line(us["fm_q8"], n * (compact + per) + 4 * B), "fm_q4": _line(us["fm_q4"], n * (t4.row_bytes + per) + 4 * B),
                "q8_gather+fm_forward": _line(us["q8_gather+fm_forward"], n * (compact + 8 + 4 * D) + n * (4 * D + 2 * D) + B * (8 + 4 * D)),
                "fm_fp32": _line(us["fm_fp32"], n * (4 * D + 4 + per) + 4 * B)}
         same = torch.equal(o_q8["rows"].view(torch.int16), rows16.view(torch.int16))       # the two q8 arms round the same fp32 values once
-        print(json.dumps({"what": "fm_lookup", "ids": dist, "samples": B, "fields": F, "V": V, "q8_rows_equal": same, **res}), flush=True)
+        same4 = torch.equal(o_q4["rows"].view(torch.int16), ops.gather_rows_q4(t4, ids, wts, wide=False)[0].view(torch.int16))
+        print(json.dumps({"what": "fm_lookup", "ids": dist, "samples": B, "fields": F, "V": V, "q8_rows_equal": same, "q4_rows_equal": same4,
+                          **res}), flush=True)
 
 
 if __name__ == "__main__":
