@@ -1234,7 +1234,10 @@ int mrec_shard_unpack_iw_i32(const int32_t* pairs, int64_t n, int32_t* ids_out, 
  *     ([Dw words of the looked-up row | wide product, 0 | pad], W words per row) and writes emb_out[i, 0:Dw] and
  *     wprod_out[2 i] = (product, 0): what mrec_gather_rows_wide hands out on one GPU.  Dw = D / 2 (16-bit rows) or D (fp32).
  *   mrec_shard_route_grads: the gradient message, msg[slot] = [Dw words of g[pos_of_slot[slot]] | dlogit[pos / F] | pad];
- *     padding slots are left alone. */
+ *     padding slots are left alone.  pos / F is a multiply-high by 2^32 / F + 1, exact while pos * F < 2^32 and wrong just past it
+ *     (F = 4096: first at pos = 1 052 671): EVERY position in pos_of_slot must satisfy pos * F < 2^32.  The entry sees the slots and
+ *     not the positions -- it refuses n_slots * F >= 2^32 (MREC_EUNSUPPORTED), and a list of n > n_slots positions (a capacity
+ *     factor below 1, the unique-id route) is the caller's to bound: n * F < 2^32. */
 int mrec_shard_route_slots_workspace_bytes(int64_t n, int32_t n_shards, size_t* out);
 int mrec_shard_route_slots_i32(const int32_t* ids, const float* wts, int64_t n, int32_t n_shards, int64_t cap, int hashed,
                                int32_t chunk_rot, void* req, int32_t* slot_of_pos, int32_t* pos_of_slot, int64_t* overflow_dev, void* ws,

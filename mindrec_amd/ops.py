@@ -1865,11 +1865,19 @@ def shard_unroute_slots(back, slot_of_pos, D, act_dtype, out=None):
     return out.view(n, D), wprod
 
 
+def _route_grads_positions_ok(n, F):
+    """The kernel takes a position's sample as pos / F by a multiply-high that is exact while pos * F < 2^32 (include/mrec.h).  The
+    entry sees the slots, not the positions; here n bounds them."""
+    if int(n) * int(F) >= 1 << 32:
+        raise ValueError(f"shard_route_grads: n * F must stay below 2^32 (n = {int(n)}, F = {int(F)})")
+
+
 def shard_route_grads(g, dlogit, F, pos_of_slot, out=None):
     """The gradient message float32 [n_slots, W]: [row gradient of the slot's position | dlogit of its sample | pad].  out: the
-    message buffer to write (contiguous float32 [n_slots, W])."""
+    message buffer to write (contiguous float32 [n_slots, W]).  n * F < 2^32."""
     _need_cuda(g, dlogit, pos_of_slot, out)
     n, D = g.shape
+    _route_grads_positions_ok(n, F)
     Dw, W = shard_msg_words(D, g.dtype)
     if g.stride(1) != 1 or dlogit.dtype != torch.float32 or not dlogit.is_contiguous() or dlogit.numel() * F != n:
         raise TypeError("shard_route_grads: g [n, D] with unit column stride, dlogit float32 [n / F]")

@@ -270,17 +270,18 @@ def shard_capacity(n, n_shards, factor=1.25):
     return int(min(n, -(-c // 64) * 64))
 
 
-def shard_route_slots(ids, wts, n_shards, cap, hashed=False, rot=0):
+def shard_route_slots(ids, wts, n_shards, cap, hashed=False, rot=0, n_valid=None):
     """Returns (req_ids int64 [n_shards * cap] (-1: unused slot), req_wts float32, slot_of_pos int32 [n] (-1: bucket full),
     pos_of_slot int32 [n_shards * cap] (-1), dropped): position i takes slot chunk * cap + (its rank among the positions of the
-    same owner, ascending position), chunk = (owner - rot) mod n_shards."""
+    same owner, ascending position), chunk = (owner - rot) mod n_shards.  n_valid (the mrec_shard_route_slots_nv_* entries: the
+    list's length): the entries at and past it are nobody's -- slot_of_pos -1, no slot, no place in a bucket, not dropped."""
     ids = _i64(ids).ravel()
-    n = ids.size
-    w = np.ones(n, np.float32) if wts is None else _f32(wts).ravel()
+    n = ids.size if n_valid is None else min(int(n_valid), ids.size)
+    w = np.ones(ids.size, np.float32) if wts is None else _f32(wts).ravel()
     own = shard_owner(ids, n_shards, hashed)
     req_ids = np.full(n_shards * cap, -1, np.int64)
     req_wts = np.zeros(n_shards * cap, np.float32)
-    slot_of_pos = np.full(n, -1, np.int32)
+    slot_of_pos = np.full(ids.size, -1, np.int32)
     pos_of_slot = np.full(n_shards * cap, -1, np.int32)
     fill = np.zeros(n_shards, np.int64)
     dropped = 0

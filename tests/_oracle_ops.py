@@ -103,8 +103,9 @@ def shard_msg_words(D, act_dtype):
     return D, D + 4
 
 
-def shard_route_slots(ids, wts, n_shards, cap, hashed=False, overflow=None, rot=0, out=None):
-    rid, rw, sop, pos, dropped = O.shard_route_slots(_np(ids), _np(wts) if wts is not None else None, n_shards, cap, hashed, rot)
+def shard_route_slots(ids, wts, n_shards, cap, hashed=False, overflow=None, rot=0, out=None, n_valid_dev=None):
+    rid, rw, sop, pos, dropped = O.shard_route_slots(_np(ids), _np(wts) if wts is not None else None, n_shards, cap, hashed, rot,
+                                                     n_valid=int(n_valid_dev.reshape(-1)[0]) if n_valid_dev is not None else None)
     idt = _np(ids).dtype
     req = np.empty((n_shards * cap, 2), idt) if out is None else _np(out)
     req[:, 0] = rid.astype(idt)
