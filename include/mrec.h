@@ -1498,6 +1498,60 @@ int mrec_q4_gather_pool_fields(const void* records, int64_t V, int64_t row_bytes
                                int32_t F, const int32_t* field_len, const float* mask, int32_t mode, void* out, int32_t out_kind,
                                int64_t ldo, float* wide_out, int64_t ldw, void* stream);
 
+/* ---- frozen key index (mrec_kidx.hip) and the keyed FM lookups over records (mrec_q8.hip) ------------------------------------
+ * Serving a model whose tables are MapParameters keyed by raw ids: a READ-ONLY open-addressing index over n unique int64 keys, built
+ * once, never mutated, and lookups that take raw keys, resolve them in it and dequantize the records, one launch.
+ *
+ * Layout, in one caller-owned buffer `mem` of mrec_kidx_bytes(n) bytes, 256-byte aligned:
+ *   bytes 0..255        header: uint32 magic "KIDX", int32 max_probe (DEVICE-written), int64 S, int64 n, zero
+ *   then S slots        16 bytes each, {int64 key, int32 row, int32 0}: the live index's slot (MapParameter key index); row -1 = empty
+ * S = max(1024, the power of two >= 2 n); the home slot of a key is mrec_hash_key((int64)key) & (S - 1), linear probing.  max_probe is
+ * the largest displacement + 1 of any stored key (0: nothing stored).  EVERY probe loop looks at at most max_probe slots and stops
+ * early at an empty one: that cap is what makes a miss cheap, and what ends the loop whatever the buffer holds.
+ *
+ * mrec_kidx_bytes: 256 + 16 S.  n < 0 or out NULL: MREC_EINVAL; n > 2^30: MREC_EUNSUPPORTED.
+ *
+ * mrec_kidx_build: keys int64 [n]; rows int32 [n], nullable: NULL means key i maps to row i.  Keys are unique; this is NOT checked (of
+ *   two equal keys both are stored, and which one a probe meets first is not defined).  Key -1 is the reserved padding key and is
+ *   skipped, as is a key whose row is negative.  n counts the keys given, skipped ones included.  Two launches: one clears every slot
+ *   and writes the header, one inserts -- a thread claims the first empty slot from its key's home with a compare-and-swap of the
+ *   slot's row from -1, then stores the key with a plain store (nothing reads a key before the launch ends) and folds its displacement
+ *   + 1 into max_probe with an atomic maximum.  Which key sits in which slot of a cluster depends on the race; which slots are taken does
+ *   not.  No workspace, no memset, no host synchronisation, capturable.  The call also records (mem, S) on the HOST: the entries below
+ *   accept an index only at an address a build was issued for -- that record is how "a bad magic word" is refused before a launch
+ *   without reading device memory -- and take S from that record, never from the buffer; the kernels compare the header's magic and S
+ *   with it and treat every key as absent where they differ.  n == 0 builds an empty index.  Refusals, in this order: mrec_kidx_bytes';
+ *   MREC_EINVAL for a NULL mem, a NULL keys with n > 0 or mem_bytes < mrec_kidx_bytes(n); MREC_EUNSUPPORTED for mem not 256-byte aligned.
+ *
+ * mrec_kidx_release: forgets the host record of the index at mem (before the caller frees or reuses the buffer: an address that is
+ *   handed out again must not pass for a built index).  No launch, no device access; an unknown address is MREC_OK too.
+ *
+ * mrec_kidx_find: rows_out[i] = the row of keys[i], or -1; probe only, one launch.  key_bytes 4 / 8: int32 keys are widened (sign-
+ *   extended) before hashing, as the live index does.  Key -1 gives -1.  MREC_EINVAL: key_bytes not 4 or 8, n < 0; n == 0: MREC_OK;
+ *   MREC_EINVAL for a NULL pointer other than stream; MREC_EUNSUPPORTED for mem not 256-byte aligned or not built.  Capturable.
+ *
+ * mrec_q8_fm_lookup_keyed / mrec_q4_fm_lookup_keyed: keys, wts [B, F].  Let r = find(keys[b, f]) in kidx.  Everything is then
+ *   mrec_q8_fm_lookup / mrec_q4_fm_lookup with ids[b, f] = r, BIT FOR BIT: the row store rule, the field order of s, q and lin, the
+ *   column-sum tree of lin_fm, the same bits whatever rows_kind and key_bytes are.  A key that is not in the index reads as a zero
+ *   record -- a zero row (+0 * t) and a zero first-order weight --, and so do key -1 and a found row outside [0, V): the id lookups'
+ *   rule for an id out of range.  THIS DIFFERS FROM TRAINING: MapTensorGet(insert_default_value=True) would invent an N(0, sigma)
+ *   default row for the key and insert it; a frozen model does not grow, and an unseen key contributes nothing.  No max_norm.
+ *   Refusals: the unkeyed entry's, in its order (keys in the place of ids, key_bytes of id_bytes: shape and record-size codes;
+ *   MREC_EINVAL for the scalar arguments; B == 0: MREC_OK; MREC_EINVAL for a NULL records, keys, wts, rows or lin_fm; MREC_EUNSUPPORTED
+ *   for the alignment of records and rows); then MREC_EINVAL for a NULL kidx; then MREC_EUNSUPPORTED for a kidx that is not 256-byte
+ *   aligned or that no mrec_kidx_build was issued for.  Every refusal comes before the launch and leaves rows and lin_fm untouched.
+ *   One launch, persistent workgroups (at most 2048), no workspace, capturable. */
+int mrec_kidx_bytes(int64_t n, size_t* out);
+int mrec_kidx_build(void* mem, size_t mem_bytes, const int64_t* keys, const int32_t* rows, int64_t n, void* stream);
+int mrec_kidx_release(const void* mem);
+int mrec_kidx_find(const void* mem, const void* keys, int32_t key_bytes, int64_t n, int32_t* rows_out, void* stream);
+int mrec_q8_fm_lookup_keyed(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* kidx, const void* keys,
+                            int32_t key_bytes, const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm,
+                            void* stream);
+int mrec_q4_fm_lookup_keyed(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* kidx, const void* keys,
+                            int32_t key_bytes, const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,12 @@ _SIGS = {
     "mrec_q4_gather_rows": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _i64, _vp],
     "mrec_q4_fm_lookup": [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
     "mrec_q4_gather_pool_fields": [_vp, _i64, _i64, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _i64, _vp, _i64, _vp],
+    "mrec_kidx_bytes": [_i64, _szp],
+    "mrec_kidx_build": [_vp, _sz, _vp, _vp, _i64, _vp],
+    "mrec_kidx_release": [_vp],
+    "mrec_kidx_find": [_vp, _vp, _i32, _i64, _vp, _vp],
+    "mrec_q8_fm_lookup_keyed": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
+    "mrec_q4_fm_lookup_keyed": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
 }
 _RESTYPES = {"mrec_strerror": C.c_char_p, "mrec_map_counters_dev": _vp, "mrec_map_row_keys_dev": _vp}
 

@@ -98,7 +98,14 @@
 //                instructions a dword), v_cvt_f32_ubyteN and v_fma_f32; a field leaves under k_q4_gather's store rule, one 16-byte
 //                store of 16-bit values a code dword.  78-79 VGPRs, occupancy 6, no scratch (8-bit: 61-65, occupancy 7-8).
 //                Roofline bytes per sample: Ls (row_bytes + id + mask) read, F D 2 (16-bit rows) or F D 4, + 4 (wide sum) written.
+//
+// k_q8_fm_lookup_keyed, k_q4_fm_lookup_keyed  the two FM lookups over raw keys (hash-table DeepFM frozen for serving): the keys of a batch
+//                of four fields are resolved in the frozen key index (mrec_kidx.h) by the lane-group itself -- lane `sub` probes batch
+//                slot `sub`, one 16-byte slot load a step, at most max_probe steps; groups of 2 and 3 lanes take two rounds -- and
+//                four ds_bpermute reads hand the rows to every lane; behind them the unkeyed kernels' code, bit for bit.  A key the
+//                index does not hold is row -1: a zero record.  8-bit: 152-154 VGPRs, 4-bit: 157-162, occupancy 3, no scratch.
 #include "mrec_common.h"
+#include "mrec_kidx.h"
 
 namespace {
 
@@ -853,6 +860,175 @@ __global__ __launch_bounds__(256) void k_q4_gather_pool_fields(const uint8_t* __
     }
 }
 
+// ===== the keyed FM lookups: raw keys -> frozen key index -> records, one launch ========================================================
+// The rows of one batch of NB fields of a lane-group's sample, resolved in the frozen index (mrec_kidx.h).  The batch's probes are dealt
+// out over the group's lanes -- lane `sub` hashes and probes the key of batch slot `sub`, one 16-byte slot load a step -- instead of
+// every lane walking every key's chain; a group of fewer than NB lanes (lpr = 2, 3) takes a second round for slots lpr .. NB - 1.  A
+// spare slot (k >= nf) probes the batch's last field again, as the record loads do.  The probe loops' trip counts differ per lane:
+// the loops are closed -- every lane of the group back in step -- before the ds_bpermute reads that hand slot k's row to all lanes
+// (source lane and round are the same for the whole wave: lpr is a kernel argument).
+template <int NB, class K>
+__device__ __forceinline__ void q_keyed_rows(const uint8_t* __restrict__ kidx, uint32_t kmask, int cap, const K* __restrict__ keys, int64_t e,
+                                             int nf, int sub, int lane0, int lpr, int64_t (&r)[NB]) {
+    int mine[2] = {-1, -1};
+#pragma unroll
+    for (int rd = 0; rd < 2; ++rd) {
+        const int k = sub + rd * lpr;
+        if ((rd == 0 || lpr < NB) && k < NB) mine[rd] = kidx_probe(kidx, kmask, cap, (int64_t)keys[e + (k < nf ? k : nf - 1)]);
+    }
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        const bool second = k >= lpr;                                   // (uniform)
+        r[k] = (int64_t)__builtin_amdgcn_ds_bpermute((lane0 + (second ? k - lpr : k)) << 2, second ? mine[1] : mine[0]);
+    }
+}
+
+// k_q8_fm_lookup with q_keyed_rows in place of the id loads: same lane-group, same batch of kQ8FmNB fields, the same unconditional
+// record loads, q8_dequant4 and q8_fm_put in the same order, the same column-sum tree -- rows and lin_fm are k_q8_fm_lookup's over
+// ids[b, f] = find(keys[b, f]), bit for bit.  A key that is not in the index (and key -1) arrives as row -1: a zero record.
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q8_fm_lookup_keyed(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                            const uint8_t* __restrict__ kidx, uint32_t kmask, const K* __restrict__ keys,
+                                                            const float* __restrict__ wts, int64_t B, int F, OT* __restrict__ rows,
+                                                            float* __restrict__ lin_fm, RowGeom gm, bool st16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 16;                                    // (the header lane: -16, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 16 ? D - col0 : 16);
+    const int64_t ng = (int64_t)gridDim.x * 4 * gm.G;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int cap = kidx_cap(kidx, kmask);
+    for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wave) * gm.G; b0 < B; b0 += ng) {
+        const int64_t b = b0 + grp;
+        const bool live = b < B;
+        const int64_t e0 = (live ? b : 0) * (int64_t)F;
+        float4 s[4] = {zero4, zero4, zero4, zero4}, q[4] = {zero4, zero4, zero4, zero4};
+        float lin = 0.0f;
+        const auto fields = [&](const int f, const int nf) {
+            int64_t r[kQ8FmNB];
+            float t[kQ8FmNB];
+            uint4 x[kQ8FmNB];
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) t[k] = wts[e0 + f + (k < nf ? k : nf - 1)];
+            q_keyed_rows<kQ8FmNB>(kidx, kmask, cap, keys, e0 + f, nf, sub, lane0, gm.lpr, r);
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) {
+                const bool ok = r[k] >= 0 && r[k] < V;
+                x[k] = *(const uint4*)(rec + (ok ? r[k] : 0) * row_bytes + 16 * sub);
+                if (!ok) r[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) {
+                asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+                if (r[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);        // header and codes zero: a zero row, a zero linear weight
+            }
+#pragma unroll
+            for (int k = 0; k < kQ8FmNB; ++k) {
+                const float lo = bperm_f(lane0, __uint_as_float(x[k].x));
+                const float scale = bperm_f(lane0, __uint_as_float(x[k].y));
+                if (k >= nf) continue;
+                if (sub == 0) {
+                    lin = lin + __uint_as_float(x[k].z) * t[k];
+                    continue;
+                }
+                const float4 y[4] = {q8_dequant4(x[k].x, lo, scale, t[k]), q8_dequant4(x[k].y, lo, scale, t[k]),
+                                     q8_dequant4(x[k].z, lo, scale, t[k]), q8_dequant4(x[k].w, lo, scale, t[k])};
+                q8_fm_put(rows + ((b * F + f + k) * (int64_t)D + col0), y, valid, st16, live, s, q);
+            }
+        };
+        int f = 0;
+        for (; f + kQ8FmNB <= F; f += kQ8FmNB) fields(f, kQ8FmNB);
+        if (f < F) fields(f, F - f);
+        float part = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (valid > 4 * j)
+                part += ((s[j].x * s[j].x - q[j].x) + (s[j].y * s[j].y - q[j].y)) + ((s[j].z * s[j].z - q[j].z) + (s[j].w * s[j].w - q[j].w));
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) {
+            const float o = __shfl_down(part, off, 64);
+            if (sub + off < gm.lpr) part += o;
+        }
+        if (live && sub == 0) lin_fm[b] = lin + 0.5f * part;
+    }
+}
+
+// k_q4_fm_lookup with q_keyed_rows in place of the id loads (see k_q8_fm_lookup_keyed): q4_dequant8 and q4_fm_put8 in k_q4_fm_lookup's
+// order, its branch-free lane roles and its column-sum tree.
+template <class K, class OT>
+__global__ __launch_bounds__(256) void k_q4_fm_lookup_keyed(const uint8_t* __restrict__ rec, int64_t V, int64_t row_bytes, int D,
+                                                            const uint8_t* __restrict__ kidx, uint32_t kmask, const K* __restrict__ keys,
+                                                            const float* __restrict__ wts, int64_t B, int F, OT* __restrict__ rows,
+                                                            float* __restrict__ lin_fm, RowGeom gm, bool st16) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int grp = lane / gm.lpr, sub = lane - grp * gm.lpr;
+    if (grp >= gm.G) return;
+    const int lane0 = lane - sub;
+    const int col0 = (sub - 1) * 32;                                    // (the header lane: -32, never used as a column)
+    const int valid = sub == 0 ? 0 : (D - col0 < 32 ? D - col0 : 32);
+    const int64_t ng = (int64_t)gridDim.x * 4 * gm.G;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int cap = kidx_cap(kidx, kmask);
+    for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wave) * gm.G; b0 < B; b0 += ng) {
+        const int64_t b = b0 + grp;
+        const bool live = b < B;
+        const int64_t e0 = (live ? b : 0) * (int64_t)F;
+        float4 s[8] = {zero4, zero4, zero4, zero4, zero4, zero4, zero4, zero4};
+        float4 q[8] = {zero4, zero4, zero4, zero4, zero4, zero4, zero4, zero4};
+        float lin = 0.0f;
+        const auto fields = [&](const int f, const int nf) {
+            int64_t r[kQ4FmNB];
+            float t[kQ4FmNB];
+            uint4 x[kQ4FmNB];
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) t[k] = wts[e0 + f + (k < nf ? k : nf - 1)];
+            q_keyed_rows<kQ4FmNB>(kidx, kmask, cap, keys, e0 + f, nf, sub, lane0, gm.lpr, r);
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) {
+                const bool ok = r[k] >= 0 && r[k] < V;
+                x[k] = *(const uint4*)(rec + (ok ? r[k] : 0) * row_bytes + 16 * sub);
+                if (!ok) r[k] = -1;
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) {
+                asm volatile("" : "+v"(x[k].x), "+v"(x[k].y), "+v"(x[k].z), "+v"(x[k].w));
+                if (r[k] < 0) x[k] = make_uint4(0u, 0u, 0u, 0u);        // header and codes zero: a zero row, a zero linear weight
+            }
+#pragma unroll
+            for (int k = 0; k < kQ4FmNB; ++k) {
+                const float lo = bperm_f(lane0, __uint_as_float(x[k].x));
+                const float scale = bperm_f(lane0, __uint_as_float(x[k].y));
+                if (k >= nf) continue;
+                lin = lin + __uint_as_float(x[k].z) * t[k];
+                const unsigned w[4] = {x[k].x, x[k].y, x[k].z, x[k].w};
+                OT* const o = rows + ((b * F + f + k) * (int64_t)D + col0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float4 y0, y1;
+                    q4_dequant8(w[j], lo, scale, t[k], y0, y1);
+                    q4_fm_put8(o + 8 * j, y0, y1, valid - 8 * j, st16, live, s[2 * j], s[2 * j + 1], q[2 * j], q[2 * j + 1]);
+                }
+            }
+        };
+        int f = 0;
+        for (; f + kQ4FmNB <= F; f += kQ4FmNB) fields(f, kQ4FmNB);
+        if (f < F) fields(f, F - f);
+        float part = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (valid > 4 * j)
+                part += ((s[j].x * s[j].x - q[j].x) + (s[j].y * s[j].y - q[j].y)) + ((s[j].z * s[j].z - q[j].z) + (s[j].w * s[j].w - q[j].w));
+#pragma unroll
+        for (int off = 8; off >= 1; off >>= 1) {
+            const float o = __shfl_down(part, off, 64);
+            if (sub + off < gm.lpr) part += o;
+        }
+        if (live && sub == 0) lin_fm[b] = lin + 0.5f * part;
+    }
+}
+
 int q4_check(int32_t D, int64_t row_bytes) {
     if (D <= 0) return MREC_EINVAL;
     if (D % 4 || D > 256) return MREC_EUNSUPPORTED;
@@ -866,6 +1042,38 @@ int q8_check(int32_t D, int64_t row_bytes) {
     if (D % 4 || D > 256) return MREC_EUNSUPPORTED;
     if (row_bytes % 16 || row_bytes < kQ8Hdr + 16 * ((D + 15) / 16)) return MREC_EINVAL;
     return MREC_OK;
+}
+
+// The two keyed FM entries (include/mrec.h): the unkeyed entry's refusals in its order -- `rc` is the format's shape / record-size code --,
+// then the index's, all before the launch.
+int q_fm_lookup_keyed(int bits, int rc, const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* kidx, const void* keys,
+                      int32_t key_bytes, const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm, void* stream) {
+    if (rc) return rc;
+    if ((key_bytes != 4 && key_bytes != 8) || rows_kind < 0 || rows_kind > 2 || B < 0 || F < 1 || V < 1) return MREC_EINVAL;
+    if (B == 0) return MREC_OK;
+    if (!records || !keys || !wts || !rows || !lin_fm) return MREC_EINVAL;
+    const int esz = rows_kind == 0 ? 4 : 2;
+    if (!al16(records) || (((uintptr_t)rows) & (esz == 4 ? 15 : 7))) return MREC_EUNSUPPORTED;
+    if (!kidx) return MREC_EINVAL;
+    uint32_t kmask = 0;
+    if (const int krc = mrec_kidx_host_mask(kidx, &kmask)) return krc;
+    const bool st16 = al16(rows) && (D * esz) % 16 == 0;
+    const int lpr = (bits == 4 ? (D + 31) / 32 : (D + 15) / 16) + 1;
+    const RowGeom gm{lpr, 64 / lpr};
+    int64_t blocks = mrec_cdiv(B, (int64_t)4 * gm.G);
+    if (blocks > 2048) blocks = 2048;                                   // 256 CUs x 8 workgroups, each walking B
+    return by_key(keys, key_bytes, [&](auto* kp) {
+        return by_out(rows, rows_kind, [&](auto* op) {
+            if (bits == 4)
+                k_q4_fm_lookup_keyed<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, (const uint8_t*)kidx,
+                                                                                         kmask, kp, wts, B, F, op, lin_fm, gm, st16);
+            else
+                k_q8_fm_lookup_keyed<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint8_t*)records, V, row_bytes, D, (const uint8_t*)kidx,
+                                                                                         kmask, kp, wts, B, F, op, lin_fm, gm, st16);
+            MREC_LAUNCH_CHECK();
+            return (int)MREC_OK;
+        });
+    });
 }
 
 }  // namespace
@@ -1085,4 +1293,16 @@ MREC_API int mrec_q4_gather_pool_fields(const void* records, int64_t V, int64_t 
             return (int)MREC_OK;
         });
     });
+}
+
+MREC_API int mrec_q8_fm_lookup_keyed(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* kidx, const void* keys,
+                                     int32_t key_bytes, const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm,
+                                     void* stream) {
+    return q_fm_lookup_keyed(8, q8_check(D, row_bytes), records, V, row_bytes, D, kidx, keys, key_bytes, wts, B, F, rows, rows_kind, lin_fm, stream);
+}
+
+MREC_API int mrec_q4_fm_lookup_keyed(const void* records, int64_t V, int64_t row_bytes, int32_t D, const void* kidx, const void* keys,
+                                     int32_t key_bytes, const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm,
+                                     void* stream) {
+    return q_fm_lookup_keyed(4, q4_check(D, row_bytes), records, V, row_bytes, D, kidx, keys, key_bytes, wts, B, F, rows, rows_kind, lin_fm, stream);
 }

@@ -448,6 +448,39 @@ class DeepFMHashEngine(_DeepFMNet):
         _, _, pos_v, _, pos_w = self._lookup(keys, insert=True)
         return self._predict_out(self._fused_chain(self.V.values, self.W.values, pos_v.view(B, Fd), pos_w.view(B, Fd), wts, label), B)
 
+    def q8_predictor(self, row_bytes=None, bits=8):
+        """Freezes the model as it stands for serving: V's live keys are exported, the same keys resolved in W (probe only), their
+        rows of V.values and W.values quantized into row-wise 8-bit records (bits=4: 4-bit) with the first-order weight in each
+        record's header -- record i belongs to exported key i --, a read-only ops.FrozenKeyIndex built over those keys, the dense
+        parameters copied.  Returns a serving.DeepFMKeyedQ8Predictor: predict_fused(keys, wts, label=None) with this engine's
+        predict_fused contract, launched eagerly, holding no fp32 table, no optimizer slot and no reference to this engine (training
+        on leaves it unchanged).  Un-admitted keys are frozen with the row they hold.  A key the model has not seen reads as a zero
+        row and a zero weight and is not inserted -- the engine would give it a default row.  Key shards, max_norm (the clip is not
+        folded into the records), a data_emb_dim outside the records' range, bits other than 8 or 4, a model without a key and every
+        case where fused_predict_supported is False raise ValueError."""
+        D = self.cfg.data_emb_dim
+        why = (f"bits={bits!r} (8 or 4)" if bits not in (8, 4)
+               else "key shards (world > 1)" if self.world > 1
+               else "max_norm" if self._max_norm is not None
+               else f"data_emb_dim={D} (data_emb_dim % 4 == 0 and 4 <= data_emb_dim <= 256)" if D % 4 or not 4 <= D <= 256
+               else self._fused_refusal())
+        if why is not None:
+            raise ValueError(f"q8_predictor is not supported with {why}")
+        from .serving import DeepFMKeyedQ8Predictor
+        with torch.cuda.device(self.device):
+            keys, rows_v = self.V.index.export()
+            if keys.numel() == 0:
+                raise ValueError("q8_predictor is not supported with an empty model (no key has been looked up)")
+            rows_w = self.W.index.lookup(keys, insert=False)
+            v = ops.gather_rows(self.V.values, rows_v)                    # compact [n, D] and [n, 1]: record i <- exported key i
+            w = ops.gather_rows(self.W.values, rows_w)                    # (a key W does not hold: weight 0)
+            q8 = (ops.quantize_rows_q4 if bits == 4 else ops.quantize_rows_q8)(v, w, row_bytes=row_bytes)
+            kidx = ops.FrozenKeyIndex(keys)
+        n = len(self.dims) - 1
+        return DeepFMKeyedQ8Predictor(q8, kidx, self.dims, [self.dense[2 * i].detach() for i in range(n)],
+                                      [self.dense[2 * i + 1].detach() for i in range(n)], mlp_dtype=self._amp, mfma=self._mfma,
+                                      fused_tail_eval=self._tail_eval)
+
     def train_step(self, keys, wts, label):
         cfg = self.cfg
         B, Fd = keys.shape

@@ -843,18 +843,35 @@ def fm_lookup_q4(q4, ids, wts, out_dtype=torch.float16, out=None):
     return _fm_lookup_q(q4, 4, ids, wts, out_dtype, out)
 
 
-def _fm_lookup_q(q8, bits, ids, wts, out_dtype, out):
-    op = f"fm_lookup_q{bits}"
+def fm_lookup_q8_keyed(q8, kidx, keys, wts, out_dtype=torch.float16, out=None):
+    """fm_lookup_q8 over raw keys, one launch (csrc/mrec_q8.hip: k_q8_fm_lookup_keyed): keys [B, F] int32 / int64 are resolved in the
+    FrozenKeyIndex `kidx` -- record i of q8 belongs to the key the index maps to row i -- and the result is fm_lookup_q8(q8, kidx.find(keys),
+    wts) bit for bit, with no [B, F] row tensor in between.  A key the index does not hold (and key -1) gives a zero row and a zero
+    weight: nothing is inserted, unlike a MapParameter lookup."""
+    return _fm_lookup_q(q8, 8, keys, wts, out_dtype, out, kidx)
+
+
+def fm_lookup_q4_keyed(q4, kidx, keys, wts, out_dtype=torch.float16, out=None):
+    """fm_lookup_q8_keyed over a Q8Table of 4-bit records (csrc/mrec_q8.hip: k_q4_fm_lookup_keyed): fm_lookup_q4(q4, kidx.find(keys), wts)
+    bit for bit, one launch."""
+    return _fm_lookup_q(q4, 4, keys, wts, out_dtype, out, kidx)
+
+
+def _fm_lookup_q(q8, bits, ids, wts, out_dtype, out, kidx=None):
+    """the one host path of the four FM lookups over records; kidx: a FrozenKeyIndex, and `ids` are then raw keys"""
+    op = f"fm_lookup_q{bits}" + ("_keyed" if kidx is not None else "")
     _need_cuda(q8.records, ids, wts)
     _suffix(ids)
     if ids.dim() != 2:
-        raise ValueError("ids must be [B, F]")
+        raise ValueError(("keys" if kidx is not None else "ids") + " must be [B, F]")
     B, F = ids.shape
     if wts.dtype != torch.float32 or tuple(wts.shape) != (B, F):
         raise TypeError("wts must be float32 with one value per id")
     if out_dtype not in _KIND:
         raise TypeError(f"{op} out_dtype must be float32, bfloat16 or float16")
     dev = q8.records.device
+    if kidx is not None and (not isinstance(kidx, FrozenKeyIndex) or kidx.device != dev):
+        raise TypeError(f"{op}: kidx must be a FrozenKeyIndex on the records' device")
     o = out if out is not None else {}
     res = []
     for name, shape, dtype in (("rows", (B, F, q8.D), out_dtype), ("lin_fm", (B,), torch.float32)):
@@ -865,7 +882,8 @@ def _fm_lookup_q(q8, bits, ids, wts, out_dtype, out):
             raise TypeError(f"{op}: out[{name!r}] must be a contiguous {dtype} {list(shape)} tensor on the records' device")
         res.append(t)
     rows, lin_fm = res
-    _lib.call(f"mrec_q{bits}_fm_lookup", _ptr(_q8_records(q8, bits)), q8.V, q8.row_bytes, q8.D, _ptr(ids.contiguous()), ids.element_size(),
+    head = (_ptr(_q8_records(q8, bits)), q8.V, q8.row_bytes, q8.D) + ((kidx._ptr(),) if kidx is not None else ())
+    _lib.call(f"mrec_q{bits}_fm_lookup" + ("_keyed" if kidx is not None else ""), *head, _ptr(ids.contiguous()), ids.element_size(),
               _ptr(wts.contiguous()), B, F, _ptr(rows), _KIND[out_dtype], _ptr(lin_fm), _stream())
     return rows, lin_fm
 
@@ -1549,6 +1567,64 @@ class KeyIndex:
         _lib.call("mrec_map_export", self._h, _ptr(keys), _ptr(rows), _ptr(n_dev), _ptr(ws), ws.numel(), _stream())
         n = int(n_dev.item())
         return keys[:n], rows[:n]
+
+
+class FrozenKeyIndex:
+    """A read-only key -> row index for serving (csrc/mrec_kidx.hip; layout and contract: include/mrec.h "frozen key index"): built once
+    from device tensors, never mutated, probed by find() and by the keyed lookups over records (fm_lookup_q8_keyed / fm_lookup_q4_keyed).
+    keys: int32 / int64 [n], unique (not checked); rows: int32 [n] or None (key i -> row i).  Key -1, the padding key, is not stored.
+    16 bytes a slot at load <= 1/2: 32 bytes a key."""
+
+    def __init__(self, keys, rows=None):
+        _need_cuda(keys, rows)
+        keys = widen_keys(keys.reshape(-1))
+        self.device, self.n = keys.device, keys.numel()
+        if rows is not None:
+            if rows.dtype != torch.int32 or rows.numel() != self.n:
+                raise TypeError("rows must be int32 with one value per key")
+            rows = rows.reshape(-1).contiguous()
+        nb = _lib.query_bytes("mrec_kidx_bytes", self.n)
+        self._mem = torch.empty(nb + 256, dtype=torch.uint8, device=self.device)
+        self._off = (-self._mem.data_ptr()) % 256
+        self._nb = nb
+        with torch.cuda.device(self.device):
+            _lib.call("mrec_kidx_build", self._ptr(), nb, _ptr(keys), _ptr(rows), self.n, _stream())
+
+    def _ptr(self):
+        return C.c_void_p(self._mem.data_ptr() + self._off)
+
+    def __del__(self):
+        # the library accepts an index only at an address a build was issued for: withdraw this one before the allocator hands it out again
+        if getattr(self, "_mem", None) is not None and _lib is not None:          # _lib is None during interpreter shutdown
+            try:
+                _lib.lib().mrec_kidx_release(self._ptr())
+            except Exception:
+                pass
+
+    @property
+    def n_slots(self):
+        """S: max(1024, the power of two >= 2 n)."""
+        return (self._nb - 256) // 16
+
+    def slots(self):
+        """Read-only look at the slot array (tests): (key int64 [S], row int32 [S]) views of the index's own buffer; row -1 = empty."""
+        raw = self._mem[self._off + 256: self._off + self._nb]
+        return raw.view(torch.int64)[0::2], raw.view(torch.int32)[2::4]
+
+    def max_probe(self):
+        """The longest displacement + 1 of any stored key: the cap of every probe loop (host sync)."""
+        return int(self._mem[self._off + 4: self._off + 8].view(torch.int32).item())
+
+    def find(self, keys):
+        """rows int32, of the shape of keys (int32 / int64): the row of every key, -1 for a key the index does not hold.  One launch."""
+        _need_cuda(keys)
+        _suffix(keys)
+        flat = keys.reshape(-1).contiguous()
+        n = flat.numel()
+        rows = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)[:n]
+        with torch.cuda.device(self.device):
+            _lib.call("mrec_kidx_find", self._ptr(), _ptr(flat), flat.element_size(), n, _ptr(rows), _stream())
+        return rows.view(keys.shape)
 
 
 def init_rows_(table, rows, keys_i64, is_new=None, seed=0, sigma=0.01, fill=None, n_dev=None):

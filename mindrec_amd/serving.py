@@ -2,7 +2,8 @@
 WideDeepEngine.predict_fused with the dequantizing lookup in front, holding neither the fp32 table nor any optimizer slot of it.
 Made by WideDeepEngine.q8_predictor().  DeepFMQ8Predictor: the same for DeepFMEngine.predict_fused, with the FM lookup over records
 (ops.fm_lookup_q8 / ops.fm_lookup_q4) in front.  MultiHotQ8: the multi-hot lookups of multi_hot.py (MultiHotEmbedding, MultiHotWideDeep)
-over records, one pooled launch (ops.gather_pool_fields_q8 / ops.gather_pool_fields_q4).  Every class takes 8-bit or 4-bit records: the
+over records, one pooled launch (ops.gather_pool_fields_q8 / ops.gather_pool_fields_q4).  DeepFMKeyedQ8Predictor: DeepFMHashEngine's
+model -- hash tables keyed by raw ids -- served from records behind a frozen key index (ops.FrozenKeyIndex).  Every class takes 8-bit or 4-bit records: the
 table's `bits` picks the lookup."""
 import torch
 
@@ -123,10 +124,14 @@ class DeepFMQ8Predictor:
             self.net.load_dense_parameters(weights, biases)
         self._row_dtype = mlp_dtype if mfma else torch.float32
 
+    def _lookup(self, ids, wts):
+        """(rows [B, F, D] in the net's input type, lin_fm [B]) of one batch: the one thing the keyed predictor does differently"""
+        lookup = ops.fm_lookup_q4 if self.q8.bits == 4 else ops.fm_lookup_q8
+        return lookup(self.q8, ids, wts, out_dtype=self._row_dtype)
+
     def _chain(self, ids, wts, label):
         B, F = ids.shape
-        lookup = ops.fm_lookup_q4 if self.q8.bits == 4 else ops.fm_lookup_q8
-        rows, lin_fm = lookup(self.q8, ids, wts, out_dtype=self._row_dtype)
+        rows, lin_fm = self._lookup(ids, wts)
         return self.net.mlp_predict(rows.view(B, F * self.q8.D), lin_fm, label)
 
     def predict_fused(self, ids, wts, label=None):
@@ -137,3 +142,22 @@ class DeepFMQ8Predictor:
             raise ValueError(f"ids must be [B, {self.net.dims[0] // self.q8.D}], got {tuple(ids.shape)}")
         with torch.cuda.device(self.device):
             return self.net._predict_run(self._chain, ids, wts, label, capture=False)
+
+
+class DeepFMKeyedQ8Predictor(DeepFMQ8Predictor):
+    """DeepFM over MapParameter hash tables, frozen for serving: DeepFMQ8Predictor with raw keys in the place of ids.  It holds the
+    records (record i: the [D] row and the first-order weight of the i-th frozen key), an ops.FrozenKeyIndex over those keys and a copy
+    of the dense parameters -- no fp32 table, no optimizer slot, no live index.  predict_fused(keys, wts, label=None) resolves the keys
+    and dequantizes their records in ONE launch (ops.fm_lookup_q8_keyed / ops.fm_lookup_q4_keyed); a key the model was not frozen with
+    reads as a zero row and a zero weight and is NOT inserted -- where DeepFMHashEngine.predict_fused would give it a default row.
+    Made by DeepFMHashEngine.q8_predictor()."""
+
+    def __init__(self, q8, kidx, dims, weights, biases, mlp_dtype=None, mfma=None, fused_tail_eval=True):
+        super().__init__(q8, dims, weights, biases, mlp_dtype=mlp_dtype, mfma=mfma, fused_tail_eval=fused_tail_eval)
+        if not isinstance(kidx, ops.FrozenKeyIndex) or kidx.device != self.device:
+            raise TypeError("kidx must be an ops.FrozenKeyIndex on the records' device")
+        self.kidx = kidx
+
+    def _lookup(self, keys, wts):
+        lookup = ops.fm_lookup_q4_keyed if self.q8.bits == 4 else ops.fm_lookup_q8_keyed
+        return lookup(self.q8, self.kidx, keys, wts, out_dtype=self._row_dtype)

@@ -110,5 +110,60 @@ def main():
                           **res}), flush=True)
 
 
+def keyed(n, blocks, calls):
+    """python tools/q8_lookup_bench.py keyed [live keys] [blocks] [calls] -- DeepFM's evaluation lookup over HASH tables of n live int64
+    keys, 16384 x 39 positions of which ~1 % hold a key the tables have not seen, D = 80, fp16 rows; per bit width (i) the keyed one-launch
+    lookup over records, (ii) FrozenKeyIndex.find, then the unkeyed lookup over those rows, and once (iii) the key path of
+    DeepFMHashEngine.predict_fused -- Unique, the two MapParameter lookups (inserting), ops.fm_lookup over the fp32 values (the tables here
+    carry no optimizer slots, which favours it).  All arms in one rotation; one JSON line per key distribution."""
+    import numpy as np
+    from mindrec_amd import ops
+    from mindrec_amd.experimental import MapParameter
+    dev = torch.device("cuda:0")
+    D, B, F = 80, 16384, 39
+    keys_all = torch.arange(n, dtype=torch.int64, device=dev) * -7046029254386353131 + 3            # (an odd multiplier: n distinct keys)
+    table = torch.empty((n, D), dtype=torch.float32, device=dev)
+    wide = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    ops.fill_normal_(table, 1000)
+    ops.fill_normal_(wide, 1001)
+    q = {8: ops.quantize_rows_q8(table, wide), 4: ops.quantize_rows_q4(table, wide)}
+    kidx = ops.FrozenKeyIndex(keys_all)
+    del table, wide
+    mk = dict(key_dtype=torch.int64, default_value="normal", capacity=n + 2 * B * F, device=dev)
+    Vm, Wm = MapParameter(value_shape=(D,), name="V", seed=1000, **mk), MapParameter(value_shape=(1,), name="W", seed=1001, **mk)
+    for c in range(0, n, 1 << 21):
+        for m in (Vm, Wm):
+            m.lookup_rows(keys_all[c: c + (1 << 21)], insert=True)
+    torch.cuda.synchronize()
+    print(json.dumps({"what": "frozen_index", "n": n, "slots": kidx.n_slots, "bytes_per_key": round(16 * kidx.n_slots / n, 1),
+                      "max_probe": kidx.max_probe(), "record_bytes": {b: t.row_bytes for b, t in q.items()}}), flush=True)
+    rng = np.random.default_rng(1000)
+    out = {a: {} for a in ("k8", "f8", "k4", "f4")}
+    for dist in ("uniform", "zipf"):
+        pick = rng.integers(0, n, (B, F)) if dist == "uniform" else np.minimum(rng.zipf(1.05, (B, F)) + 12, n - 1)
+        kb = keys_all[torch.from_numpy(pick).to(dev)]
+        kb = torch.where(torch.from_numpy(rng.random((B, F)) < 0.01).to(dev), kb + 1, kb)
+        wts = torch.from_numpy(rng.random((B, F), dtype=np.float32)).to(dev)
+
+        def live():
+            flat = kb.view(-1)
+            d = ops.unique(flat)
+            pv, pw = (m.lookup_rows(flat, insert=True, dedup=d)[2].view(B, F) for m in (Vm, Wm))
+            ops.fm_lookup(Vm.values, Wm.values, pv, wts, ids_w=pw, out_dtype=torch.float16)
+        arms = {"live_maps": live}
+        for b, keyed_op, plain in ((8, ops.fm_lookup_q8_keyed, ops.fm_lookup_q8), (4, ops.fm_lookup_q4_keyed, ops.fm_lookup_q4)):
+            arms[f"q{b}_keyed"] = lambda b=b, f=keyed_op: f(q[b], kidx, kb, wts, out=out[f"k{b}"])
+            arms[f"q{b}_find+lookup"] = lambda b=b, f=plain: f(q[b], kidx.find(kb), wts, out=out[f"f{b}"])
+        us = _time(arms, blocks, calls)
+        same = all(torch.equal(out[f"k{b}"][k].view(torch.int16), out[f"f{b}"][k].view(torch.int16)) for b in (8, 4) for k in ("rows", "lin_fm"))
+        res = {k: {"us": round(v[len(v) // 2], 2), "min": round(v[0], 2), "max": round(v[-1], 2)} for k, v in us.items()}
+        print(json.dumps({"what": "fm_lookup_keyed", "keys": dist, "samples": B, "fields": F, "n": n, "keyed_equals_find_then_lookup": same, **res}),
+              flush=True)
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "keyed":
+        a = sys.argv[2:]
+        keyed(int(float(a[0])) if a else 20_000_000, int(a[1]) if len(a) > 1 else 9, int(a[2]) if len(a) > 2 else 20)
+    else:
+        main()
