@@ -1552,6 +1552,47 @@ int mrec_q4_fm_lookup_keyed(const void* records, int64_t V, int64_t row_bytes, i
                             int32_t key_bytes, const float* wts, int64_t B, int32_t F, void* rows, int32_t rows_kind, float* lin_fm,
                             void* stream);
 
+/* ---- FP8 hidden layers (mrec_gemm_fp8.hip; mrec_version() >= 108) -----------------------------------------------------------------
+ * The hidden DenseLayers of a frozen predictor on the 8-bit-float matrix instruction: OCP e4m3 codes (1-4-3, bias 7, largest finite
+ * value 448, no infinities; torch.float8_e4m3fn) for both operands, fp32 accumulation, no block scales.  e4m3_rne(v) below rounds a
+ * float to the nearest code, ties to even, subnormals kept; it is only ever applied to clamp(v, -448, 448).
+ *
+ * The quantization rule (weights; one row = one output channel of W^T [N, K]):
+ *     scale = amax * (1.0f / 448.0f), amax = max |src[r][c]| over the row, or 1.0f for an all-zero row;
+ *     code[r][c] = e4m3_rne(clamp(src[r][c] / scale, -448, 448)), the division correctly rounded in fp32; the source is widened to fp32
+ *     first (exactly); code[r][c] = 0x00 for C <= c < ldq.
+ * mrec_fp8_quantize_rows_{f32,f16,bf16}: src [R, C] of row stride lds (elements) -> codes [R, ldq] (bytes) and scale fp32 [R].  One
+ *   launch, no workspace, capturable.  MREC_EINVAL: R < 0, C <= 0, lds < C, ldq < C; R == 0: MREC_OK; MREC_EINVAL for a NULL src, codes
+ *   or scale, a src not aligned to its element, codes or scale not 4-byte aligned; MREC_EUNSUPPORTED for ldq % 4 != 0 or R > 2^31.
+ *
+ * mrec_dense_fwd_fp8: Y[M, N] = epi(A[M, K] . Wq[N, K]^T), kinds MREC_FP8_KIND_*:
+ *     x_kind BF16 / F16: a[m][k] = e4m3_rne(clamp(fl(x[m][k] * inv_sa), -448, 448)), converted while the rows are staged (no pass of
+ *       its own); x_kind E4M3: a = x, codes as a previous call left them (inv_sa is not read);
+ *     acc[m][n] = sum_k a[m][k] * wq[n][k] in fp32 on the matrix instruction, from +0 (every product is exact in fp32; the order of
+ *       the sum is the instruction's: the result is within K * 2^-23 * sum_k |a w| of the exact sum whatever that order is);
+ *     t = fl(sa * sw[n]); y = fmaf(acc, t, bias[n]) (bias NULL: + 0.0f); relu != 0: y = y > 0 ? y : 0;
+ *     y_kind BF16 / F16: Y = y rounded once to nearest even; y_kind E4M3: Y = e4m3_rne(clamp(fl(y * inv_so), -448, 448)).
+ *   sa, inv_sa, inv_so: per-tensor activation scales, host floats (the caller's inv_sa is its 1 / sa; inv_so the next layer's).
+ *   wq [N, ldq] codes with zero codes in columns K .. ldq - 1 (what the quantizer writes), ldq % 16 == 0 and ldq >= K rounded up to
+ *   16; sw fp32 [N].  ldx, ldy in elements.  Any M >= 0 (M == 0: MREC_OK); rows counted in 32 bits.
+ *   Refusals, before the launch, in this order: MREC_EINVAL for a kind outside 1..3, M < 0, K <= 0, N <= 0, ldx < K, ldq < K, ldy < N;
+ *   M == 0: MREC_OK; MREC_EINVAL for a NULL x, wq, sw or y, x or wq not 16-byte aligned, y not 8-byte (E4M3: 4-byte) aligned, sw or
+ *   bias not 4-byte aligned; MREC_EUNSUPPORTED for K % 8 != 0 (E4M3 x: K % 16), N % 8 != 0, ldx % 8 != 0 (E4M3 x: ldx % 16),
+ *   ldq % 16 != 0 or ldq below K rounded up to 16, ldy % 4 != 0, x or wq of 2^31 bytes or more, M > 2^30.  One launch, no
+ *   workspace, capturable, the same bits run to run.
+ *
+ * mrec_dense_fwd_fp8_tile: the output tile of that launch, rows (M side) and columns (N side). */
+#define MREC_FP8_KIND_BF16 1
+#define MREC_FP8_KIND_F16 2
+#define MREC_FP8_KIND_E4M3 3
+int mrec_fp8_quantize_rows_f32(const float* src, int64_t R, int32_t C, int64_t lds, void* codes, int64_t ldq, float* scale, void* stream);
+int mrec_fp8_quantize_rows_f16(const uint16_t* src, int64_t R, int32_t C, int64_t lds, void* codes, int64_t ldq, float* scale, void* stream);
+int mrec_fp8_quantize_rows_bf16(const uint16_t* src, int64_t R, int32_t C, int64_t lds, void* codes, int64_t ldq, float* scale, void* stream);
+int mrec_dense_fwd_fp8(const void* x, int32_t x_kind, int64_t ldx, const void* wq, int64_t ldq, const float* sw, const float* bias,
+                       int64_t M, int32_t K, int32_t N, float sa, float inv_sa, float inv_so, int relu, void* y, int32_t y_kind,
+                       int64_t ldy, void* stream);
+int mrec_dense_fwd_fp8_tile(int32_t* rows_out, int32_t* cols_out);
+
 #ifdef __cplusplus
 }
 #endif

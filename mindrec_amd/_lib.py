@@ -260,8 +260,13 @@ _SIGS = {
     "mrec_kidx_find": [_vp, _vp, _i32, _i64, _vp, _vp],
     "mrec_q8_fm_lookup_keyed": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
     "mrec_q4_fm_lookup_keyed": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp],
+    "mrec_fp8_quantize_rows_f32": [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp],
+    "mrec_fp8_quantize_rows_f16": [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp],
+    "mrec_fp8_quantize_rows_bf16": [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp],
+    "mrec_dense_fwd_fp8": [_vp, _i32, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _int, _vp, _i32, _i64, _vp],
+    "mrec_dense_fwd_fp8_tile": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
 }
-_RESTYPES = {"mrec_strerror": C.c_char_p, "mrec_map_counters_dev": _vp, "mrec_map_row_keys_dev": _vp}
+_RESTYPES ={"mrec_strerror": C.c_char_p, "mrec_map_counters_dev": _vp, "mrec_map_row_keys_dev": _vp}
 
 EXPORTED = sorted(list(_SIGS) + ["mrec_strerror"])
 

@@ -211,8 +211,9 @@ class DeepFMEngine(_DeepFMNet):
         self._check_fused()
         return self._predict_run(self._predict_chain, ids, wts, label, capture=self.cfg.graphs != "none")
 
-    def q8_predictor(self, row_bytes=None, bits=8):
-        """Freezes the model as it stands for serving: the [V, D] table quantized to row-wise 8-bit records with the [V, 1] first-order
+    def q8_predictor(self, row_bytes=None, bits=8, dense_fp8=False, calib=None, fp8_headroom=2.0):
+        """dense_fp8, calib (ids or keys, wts), fp8_headroom: the hidden layers on the 8-bit-float matrix kernel, as
+        serving.WideDeepQ8Predictor takes them.  Freezes the model as it stands for serving: the [V, D] table quantized to row-wise 8-bit records with the [V, 1] first-order
         weight in each record's header, one pass (ops.quantize_rows_q8), the dense parameters copied.  Returns a
         serving.DeepFMQ8Predictor, whose predict_fused has this engine's predict_fused contract (launched eagerly) and which no longer
         depends on the engine: training on leaves it unchanged.  row_bytes: the record size (default: compact).  bits=4 freezes into
@@ -234,7 +235,7 @@ class DeepFMEngine(_DeepFMNet):
             q8 = (ops.quantize_rows_q4 if bits == 4 else ops.quantize_rows_q8)(self.V_l2, self.W_l2, row_bytes=row_bytes)
         return DeepFMQ8Predictor(q8, self.dims, [self.dense[2 * i].detach() for i in range(n)],
                                  [self.dense[2 * i + 1].detach() for i in range(n)], mlp_dtype=self._amp, mfma=self._mfma,
-                                 fused_tail_eval=self._tail_eval)
+                                 fused_tail_eval=self._tail_eval, dense_fp8=dense_fp8, calib=calib, fp8_headroom=fp8_headroom)
 
     def release_graphs(self):
         """Drops every captured HIP graph -- the dense net's training step and the evaluation forwards (they are re-captured on demand)."""
@@ -448,8 +449,9 @@ class DeepFMHashEngine(_DeepFMNet):
         _, _, pos_v, _, pos_w = self._lookup(keys, insert=True)
         return self._predict_out(self._fused_chain(self.V.values, self.W.values, pos_v.view(B, Fd), pos_w.view(B, Fd), wts, label), B)
 
-    def q8_predictor(self, row_bytes=None, bits=8):
-        """Freezes the model as it stands for serving: V's live keys are exported, the same keys resolved in W (probe only), their
+    def q8_predictor(self, row_bytes=None, bits=8, dense_fp8=False, calib=None, fp8_headroom=2.0):
+        """dense_fp8, calib (ids or keys, wts), fp8_headroom: the hidden layers on the 8-bit-float matrix kernel, as
+        serving.WideDeepQ8Predictor takes them.  Freezes the model as it stands for serving: V's live keys are exported, the same keys resolved in W (probe only), their
         rows of V.values and W.values quantized into row-wise 8-bit records (bits=4: 4-bit) with the first-order weight in each
         record's header -- record i belongs to exported key i --, a read-only ops.FrozenKeyIndex built over those keys, the dense
         parameters copied.  Returns a serving.DeepFMKeyedQ8Predictor: predict_fused(keys, wts, label=None) with this engine's
@@ -479,7 +481,7 @@ class DeepFMHashEngine(_DeepFMNet):
         n = len(self.dims) - 1
         return DeepFMKeyedQ8Predictor(q8, kidx, self.dims, [self.dense[2 * i].detach() for i in range(n)],
                                       [self.dense[2 * i + 1].detach() for i in range(n)], mlp_dtype=self._amp, mfma=self._mfma,
-                                      fused_tail_eval=self._tail_eval)
+                                      fused_tail_eval=self._tail_eval, dense_fp8=dense_fp8, calib=calib, fp8_headroom=fp8_headroom)
 
     def train_step(self, keys, wts, label):
         cfg = self.cfg

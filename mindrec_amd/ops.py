@@ -2409,6 +2409,70 @@ def dense_fwd(x, w, bias, relu=True, out=None, drop_next=None, wt=None):
     return y
 
 
+_FP8 = torch.float8_e4m3fn
+_FP8_KIND = {torch.bfloat16: 1, torch.float16: 2, _FP8: 3}      # MREC_FP8_KIND_*
+
+
+def fp8_tile():
+    """(rows, columns) of dense_fwd_fp8's output tile."""
+    r, c = C.c_int32(0), C.c_int32(0)
+    _lib.call("mrec_dense_fwd_fp8_tile", C.byref(r), C.byref(c))
+    return int(r.value), int(c.value)
+
+
+def quantize_rows_fp8(w_t, out=None):
+    """Freezes a weight for dense_fwd_fp8 (cold path): w_t [N, K] -- W transposed, a row = an output channel -- float32, float16 or
+    bfloat16 with unit column stride -> (codes [N, K] torch.float8_e4m3fn, a view of a buffer whose rows are padded with zero codes to
+    a multiple of 16; scale float32 [N]).  The rule of include/mrec.h: scale = amax / 448 per row (1 for a zero row), code =
+    e4m3(clamp(w / scale, +-448)) rounded to nearest even.  out: a [N, ldq >= K] float8_e4m3fn buffer to write instead (all ldq
+    columns are written)."""
+    _need_cuda(w_t, out)
+    if w_t.dim() != 2 or w_t.stride(1) != 1 or w_t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError("w_t must be a float32 / float16 / bfloat16 [N, K] tensor with unit column stride")
+    N, K = w_t.shape
+    buf = out if out is not None else torch.empty((N, (K + 15) // 16 * 16), dtype=_FP8, device=w_t.device)
+    if buf.dtype != _FP8 or buf.dim() != 2 or buf.shape[0] != N or buf.shape[1] < K or not buf.is_contiguous():
+        raise TypeError("out must be a contiguous float8_e4m3fn [N, >= K] tensor")
+    scale = torch.empty(N, dtype=torch.float32, device=w_t.device)
+    name = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}[w_t.dtype]
+    _lib.call("mrec_fp8_quantize_rows_" + name, _ptr(w_t), N, K, w_t.stride(0), _ptr(buf), buf.shape[1], _ptr(scale), _stream())
+    return buf[:, :K], scale
+
+
+def dense_fwd_fp8(x, codes, scale, bias, sa, relu=True, out_scale=None, out_dtype=None, out=None):
+    """A hidden DenseLayer on the 8-bit-float matrix instruction: act((x / sa as e4m3) . codes^T * sa * scale + bias).  x [M, K] float16 /
+    bfloat16 (quantized with the static per-tensor scale `sa` while the kernel stages it: no cast pass) or float8_e4m3fn codes as a
+    previous call left them (sa: the scale they were written with); codes [N, K], scale [N]: quantize_rows_fp8's; bias float32 [N] or
+    None.  out_scale given: y = e4m3(clamp(act / out_scale, +-448)) [M, N] float8_e4m3fn, the next layer's input with sa = out_scale;
+    else y in out_dtype (float16 / bfloat16; default: x's own 16-bit type), rounded once.  One launch."""
+    _need_cuda(x, codes, scale, bias, out)
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype not in _FP8_KIND:
+        raise TypeError("x must be a float16 / bfloat16 / float8_e4m3fn [M, K] tensor with unit column stride")
+    M, K = x.shape
+    if codes.dtype != _FP8 or codes.dim() != 2 or codes.shape[1] != K or codes.stride(1) != 1:
+        raise TypeError("codes must be float8_e4m3fn [N, K] with unit column stride (quantize_rows_fp8)")
+    N = codes.shape[0]
+    if scale.dtype != torch.float32 or scale.numel() != N or not scale.is_contiguous():
+        raise TypeError("scale must be contiguous float32 [N]")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
+        raise TypeError("bias must be contiguous float32 [N]")
+    if out_scale is not None:
+        ydt = _FP8
+    else:
+        ydt = out_dtype if out_dtype is not None else (x.dtype if x.dtype != _FP8 else None)
+        if ydt not in (torch.float16, torch.bfloat16):
+            raise TypeError("out_dtype must be torch.float16 or torch.bfloat16 (or give out_scale for float8_e4m3fn output)")
+    y = out if out is not None else torch.empty((M, N), dtype=ydt, device=x.device)
+    if y.dim() != 2 or tuple(y.shape) != (M, N) or y.dtype != ydt or y.stride(1) != 1:
+        raise TypeError(f"out must be [M, N] {ydt} with unit column stride")
+    sa = float(np.float32(sa))
+    inv_sa = float(np.float32(1.0) / np.float32(sa))
+    inv_so = float(np.float32(1.0) / np.float32(out_scale)) if out_scale is not None else 0.0
+    _lib.call("mrec_dense_fwd_fp8", _ptr(x), _FP8_KIND[x.dtype], x.stride(0), _ptr(codes), codes.stride(0), _ptr(scale), _ptr(bias),
+              M, K, N, sa, inv_sa, inv_so, int(bool(relu)), _ptr(y), _FP8_KIND[ydt], y.stride(0), _stream())
+    return y
+
+
 def dense_bwd_input(dy, w, h=None, db_out=None, out=None, db_slabs=None, drop_in=None):
     """MatMul bprop with respect to the input, fused with the ReLU + BiasAdd bprops of the layer below:
     dx = (dy . w^T) * (h > 0); db_out[:] = dx.sum(0).  dy [M, N], w [K, N], h [M, K] or None, db_out fp32 [K] or None.

@@ -518,8 +518,9 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             ids, _ = self._translate_keys(ids)          # MapTensorGet inserts default rows in eval too, as predict
         return self._predict_run(self._predict_chain, ids, wts, label, capture=self._graph_level >= 1 and self.index is None)
 
-    def q8_predictor(self, row_bytes=None, bits=8):
-        """Freezes the model as it stands for serving: the deep table and the wide weights quantized to row-wise 8-bit records in one
+    def q8_predictor(self, row_bytes=None, bits=8, dense_fp8=False, calib=None, fp8_headroom=2.0):
+        """dense_fp8, calib, fp8_headroom: the hidden layers on the 8-bit-float matrix kernel, as serving.WideDeepQ8Predictor takes them.
+        Freezes the model as it stands for serving: the deep table and the wide weights quantized to row-wise 8-bit records in one
         pass (ops.quantize_rows_q8; fused rows are read in place), the dense parameters and the wide bias copied.  Returns a
         serving.WideDeepQ8Predictor, whose predict_fused has this engine's predict_fused contract and which no longer depends on the
         engine: training on leaves it unchanged.  row_bytes: the record size (default: compact).  bits=4: 4-bit records
@@ -541,7 +542,8 @@ class WideDeepEngine(DenseNetMixin, ShardStepMixin):
             q8 = (ops.quantize_rows_q4 if bits == 4 else ops.quantize_rows_q8)(self.deep, self.wide, row_bytes=row_bytes)
         return WideDeepQ8Predictor(q8, self.dims, [self.dense[2 * i].detach() for i in range(n)],
                                    [self.dense[2 * i + 1].detach() for i in range(n)], self.wide_b.detach(), mlp_dtype=self._amp,
-                                   mfma=self._mfma, fused_tail=self._tail_ok, fused_tail_eval=self._tail_eval)
+                                   mfma=self._mfma, fused_tail=self._tail_ok, fused_tail_eval=self._tail_eval, dense_fp8=dense_fp8,
+                                   calib=calib, fp8_headroom=fp8_headroom)
 
     def _map_tables(self):
         """(tensor, sigma, fill, seed) of the six tables that share the key index's row numbering, with the values a row gets
